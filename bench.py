@@ -21,6 +21,11 @@ The same JSON line also carries
     HBM-bound (config[4] shape scaled to one GPU).
 N>1 ranks (torchrun): every rank runs its own replica (the per-frame path does not shard,
 SURVEY.md §8e) -> "weak" scaling, no data-path collective; value = frames of all ranks / max time.
+A plain run (`--gpus N --steps K --warmup W`) renders the sequence, warms up (an untimed pass of it in the throughput mode, then the W steps),
+times the K steps of the headline run and prints the line
+(`value`, `ms_per_step`, the run's config); `--full` adds everything else above and below: value_deferred, the parity with the reference,
+the KITTI-0000-length and windowed-BA runs, host inputs, the batch, sharded and roofline legs, the CPU baselines.
+`--dump-outputs DIR` writes what the timed path computed in its last step (dump_outputs) for output-for-output comparisons.
 """
 from __future__ import annotations
 
@@ -305,6 +310,26 @@ def parity_check(jobs):
     return out
 
 
+def dump_outputs(out_dir, pipe):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as float64 .npy files of a few KB, so that two builds can be
+    compared output for output (the inputs of a run are fixed by --steps / --warmup and the rank):
+      camera_pose        Tcw of the last frame (4x4)
+      object_motions     the world-frame motion H of every object tracked in the last frame (n x 4 x 4), in the pipeline's order
+      object_labels      (mod_label, sem_label, n_inliers) of those objects (n x 3)
+      frame_counts       the FrameCounts of the last frame, in the order of vdo_slam_amd/pipeline.py FrameCounts
+      camera_trajectory  the camera poses the graph store kept, one per frame of the run (frames x 4 x 4)"""
+    from vdo_slam_amd.pipeline import FrameCounts
+    os.makedirs(out_dir, exist_ok=True)
+    motions = pipe.motions()
+    arrays = {"camera_pose": pipe.pose(),
+              "object_motions": np.array([m["H"] for m in motions], np.float64).reshape(-1, 4, 4),
+              "object_labels": np.array([[m["mod_label"], m["sem_label"], m["n_inliers"]] for m in motions], np.float64).reshape(-1, 3),
+              "frame_counts": np.array([getattr(pipe.counts, k) for k, _ in FrameCounts._fields_], np.float64),
+              "camera_trajectory": pipe.store_poses()}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` outside torchrun: start N ranks of this script (one process per GPU, RANK / LOCAL_RANK /
     WORLD_SIZE / MASTER_* in the environment, exactly what torchrun would set); rank 0 prints the JSON line."""
@@ -339,6 +364,11 @@ def main():
     ap.add_argument("--no-parity", action="store_true", help="skip the parity leg (the timed sequences through the whole reference, oracle/_ref/libref_full.so, and through System::TrackRGBD)")
     ap.add_argument("--no-full-sequence", action="store_true", help="do not add the KITTI-0000-length run (value_full_sequence) when --steps / --warmup ask for another window")
     ap.add_argument("--roofline-static", type=int, default=2200000, help="static landmarks of the roofline graph (default: 13.3 M edges, ~515 MB per sweep launch - twice the 256 MB Infinity Cache)")
+    ap.add_argument("--full", action="store_true", help="also run every leg beside the headline: the throughput mode (value_deferred), the parity with the reference, the "
+                    "KITTI-0000-length and windowed-BA runs, host inputs, the batch / sharded / roofline legs and the CPU baselines (the --no-* switches above "
+                    "thin that record out); without it only the headline run is set up, warmed up and timed")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR", help="after the timed steps, write what the timed path computed in its last step to "
+                    "DIR/<name>.npy (float64; see dump_outputs)")
     ap.add_argument("--cpu-worker", type=str, default="", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-worker-budget", type=float, default=8.0, help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -365,12 +395,12 @@ def main():
     atexit.register(shutil.rmtree, seq_dir, ignore_errors=True)
     spec = SQ.bench_spec(args.warmup, args.steps, seed=17 * rank)
     spec_full = SQ.bench_spec(FULL_WARMUP, KITTI0000_FRAMES - FULL_WARMUP, seed=17 * rank)
-    want_full = (not args.no_full_sequence) and spec_full != spec and world == 1
+    want_full = args.full and (not args.no_full_sequence) and spec_full != spec and world == 1
     render_workers = max(1, int(_cpu_budget() / max(1, world)))
     frames = SQ.render_bench_sequence(spec, os.path.join(seq_dir, "run"), workers=render_workers)
     frames_full = SQ.render_bench_sequence(spec_full, os.path.join(seq_dir, "full"), workers=render_workers) if want_full else None
     parity_jobs = []                # (tag, frames, settings, labels, reference child, its output)
-    if rank == 0 and world == 1 and not args.no_parity:
+    if args.full and rank == 0 and world == 1 and not args.no_parity:
         parity_jobs = parity_start(seq_dir, (("run", spec, frames),) + ((("full", spec_full, frames_full),) if want_full else ()))
 
     import torch
@@ -418,6 +448,10 @@ def main():
     from vdo_slam_amd.pipeline import FramePipeline, kitti_params
     import threading
     defer = 0 if os.environ.get("VDO_BENCH_SYNC_OBJECTS") else 1
+    R = max(1, args.replicas_per_gpu)
+    # `value` is the run with the reference's return semantics (everything of a frame done when its call returns), timed after a pass of the same
+    # sequence in the throughput mode: --full reports that pass as `value_deferred`, a plain run keeps it as an untimed warm-up of the process
+    sync_headline = R == 1 and defer == 1
 
     def defer_now():
         return defer
@@ -518,7 +552,10 @@ def main():
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         return float(tt.item()), reps
 
-    R = max(1, args.replicas_per_gpu)
+    if sync_headline and not args.full:
+        for r in run_sequences(R)[1]:
+            r.close()
+        defer = 0
     dt, reps = run_sequences(R)
     fps = world * R * args.steps / dt
     n_all = args.steps + args.warmup
@@ -593,13 +630,19 @@ def main():
     }
     if R > 1:
         out["config"]["single_sequence_latency_ms_p50"] = round(float(np.percentile(step_ms, 50)), 3)
+    if sync_headline and not args.full:
+        out["config"]["value"] = ("inputs resident in HBM, every frame complete when its call returns (object optimisations, RenewFrameInfo of the objects, tracklets, graph "
+                                  "store) - System::TrackRGBD's semantics, timed after an untimed pass of the same sequence in the throughput mode; that pass (value_deferred) and the other legs are "
+                                  "measured with --full")
+    if args.dump_outputs and rank == 0 and not (sync_headline and args.full):
+        dump_outputs(args.dump_outputs, reps[0].pipe)
     for r in reps:
         r.close()
     del reps, pipe, rep0
     # ---- the same device-resident sequence with the REFERENCE'S RETURN SEMANTICS: everything of a frame (object LMs, RenewFrameInfo of the
     # objects, tracklets) is done when Step returns - no work deferred into the next call.  (`value` defers the object stage of frame k
     # into Step k+1: same results, one frame of latency for the object motions.)
-    if not os.environ.get("VDO_BENCH_SYNC_OBJECTS") and R == 1:
+    if sync_headline and args.full:
         defer_saved = defer
         defer = 0
         dts_sync, rs_sync = run_sequences(1)
@@ -614,6 +657,8 @@ def main():
         out["config"]["value"] = ("= value_sync: inputs resident in HBM, every frame complete when its call returns (object optimisations, RenewFrameInfo of the objects, tracklets, graph "
                                   "store) - System::TrackRGBD's semantics; value_deferred = the same sequence with the object stage of frame k finished inside call k+1 (same results; "
                                   "what rounds 1-2 reported as `value`); config.step_ms_p50_p90_max, host_ms_per_section, per_frame_mean belong to the deferred run")
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, rs_sync[0].pipe)
         for r in rs_sync:
             r.close()
     out.update(out_parity)
@@ -674,7 +719,7 @@ def main():
         del rs_full
         windowed_leg(dev_full, FULL_WARMUP, steps_full)
         del dev_full
-    elif frames_full is None and args.steps + args.warmup == KITTI0000_FRAMES and "value_sync" in out:
+    elif args.full and frames_full is None and args.steps + args.warmup == KITTI0000_FRAMES and "value_sync" in out:
         out["value_full_sequence"] = out["value"]
         out["config"]["value_full_sequence"] = "= value: this run IS the KITTI-0000-length run"
         if R == 1 and not os.environ.get("VDO_BENCH_SYNC_OBJECTS"):
@@ -694,7 +739,7 @@ def main():
         out["sequences_per_gpu_sweep"] = sweep
     # ---- the same sequence through System::TrackRGBD with HOST buffers (include/System.h:45-51: the reference's real entry;
     # 7.9 MB of H2D per frame, the caller's depth converted in place, synchronous - the frame is complete when the call returns)
-    if rank == 0 and world == 1 and not args.no_host_inputs:
+    if args.full and rank == 0 and world == 1 and not args.no_host_inputs:
         import tempfile
         from vdo_slam_amd.system import System, write_settings
         with tempfile.TemporaryDirectory() as td:
@@ -732,7 +777,7 @@ def main():
                                                 "value_host_inputs: object stage deferred into the next call (as `value`), value_host_inputs_sync: everything done when TrackRGBD returns "
                                                 "(the reference's semantics); same camera pose as the device-input run: " + str(same))
 
-    if not args.no_batch:
+    if args.full and not args.no_batch:
         # ---- batch leg: LM outer iterations on the KITTI-shaped full-batch graph (configs[2] shape)
         g = synth.make_ba_graph(60, 30000, 5, 800, seed=1 + rank)
         ba = BatchBA(ctx_ba, g)
@@ -907,7 +952,7 @@ def main():
         if rank == 0 and world == 1 and not args.no_cpu_baseline:
             cb_ms, cb_sweep, cb_its = cpu_baseline_batch(g)
             out["cpu_baseline_batch"] = {"ms_per_lm_iter": cb_ms, "sweep_ms": cb_sweep, "iterations": cb_its, "cores": 1, "kind": "port"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:      # the CPU baseline is reported at N=1 only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:      # the CPU baseline is reported at N=1 only
         cfps, cn, cstage, _, cbr = cpu_baseline_frames(frames)
         out["cpu_baseline"] = {"value": cfps, "unit": "frames/s", "cores": 1, "kind": "port",
                                "sample": f"the first {cn} frames of the same sequence through the same full Track() (oracle, 1 thread)",

@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r03
 mkdir -p $O
-timeout 250 rocprofv3 --kernel-trace --stats -d $O/prof_bench -- python $R/bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-host-inputs --no-batch > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
+timeout 250 rocprofv3 --kernel-trace --stats -d $O/prof_bench -- python $R/bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-host-inputs --no-batch > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
 timeout 120 rocprofv3 --kernel-trace --stats -d $O/prof_sweep -- python $R/tools/sweep_only.py > $O/sweep.log 2>&1
 timeout 120 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_fetch -- python $R/tools/sweep_only.py > $O/pmc_fetch.log 2>&1
 timeout 120 rocprofv3 --pmc WRITE_SIZE -d $O/pmc_write -- python $R/tools/sweep_only.py > $O/pmc_write.log 2>&1
@@ -23,6 +23,6 @@ grep "^n_eb" $O/sweep.log | tail -1 >> $O/sweep_pmc_hbm_traffic.txt
 python tools/pmc_counters.py k_sweep_tile $(find $O/pmc_sq1 -name "*.db" | head -1) $(find $O/pmc_sq2 -name "*.db" | head -1) > $O/sweep_sq_counters.txt 2>&1
 DB=$(find $O/prof_bench -name "*.db" | head -1); python tools/rocprof_timeline.py $DB 40 2400 > $O/frame_timeline.txt 2>&1
 cp $O/sweep_pmc_hbm_traffic.txt profiles/r03_sweep_pmc_hbm_traffic.txt      # (bench.py quotes the counter-based traffic of this very run)
-timeout 400 python bench.py --replica-sweep 1,2,4,8 > $O/bench.json 2> $O/bench.err
+timeout 400 python bench.py --full --replica-sweep 1,2,4,8 > $O/bench.json 2> $O/bench.err
 find $O -name "*.db" -size +20M -delete
 tail -c 400 $O/bench.json

@@ -32,5 +32,5 @@ export VDO_BA_DENSE=$BEST
 ( cd /tmp && timeout 150 rocprofv3 --kernel-trace --stats -d $O/prof_probe -- env DENSE_PROBE_VERSIONS=$BEST python $R/tools/dense_probe.py > $O/dense_probe_prof.log 2>&1 )
 DB=$(find $O/prof_probe -name "*.db" | head -1); python tools/rocprof_summary.py $DB 40 > $O/dense_probe_kernel_stats.txt 2>&1; cut -c1-150 $O/dense_probe_kernel_stats.txt | head -30
 find $O -name "*.db" -size +20M -delete
-timeout 400 python bench.py --no-cpu-baseline --no-live-pmc --no-host-inputs > $O/bench.json 2> $O/bench.err; echo "bench rc $?"; cut -c1-600 $O/bench.json
+timeout 400 python bench.py --full --no-cpu-baseline --no-live-pmc --no-host-inputs > $O/bench.json 2> $O/bench.err; echo "bench rc $?"; cut -c1-600 $O/bench.json
 bash tools/gpu_suite_by_file.sh $O/suite.log --ignore=tests/test_ba_gpu.py --ignore=tests/test_dense_check_gpu.py 2>&1 | tail -40

@@ -12,7 +12,7 @@ for n in large roof; do DB=$(find $O/prof_ba_$n -name "*.db" | head -1); python 
 find $O -name "*.db" -size +20M -delete
 { for v in old base5; do echo "== $v"; VDO_HIP_LIB=$R/vdo_slam_amd/libvdo_hip_$v.so timeout 300 python tools/sweep_repeat_probe.py 2200000 2>&1 | grep -v "^edges" | tail -6; done
   echo "== default"; timeout 300 python tools/sweep_repeat_probe.py 2200000 2>&1 | grep -v "^edges" | tail -6; } > $O/sweep_ab.txt 2>&1; cat $O/sweep_ab.txt
-( time python bench.py --gpus 2 --steps 20 --no-cpu-baseline --no-host-inputs > $O/bench_gpus2_shared.json 2> $O/bench_gpus2.err ) 2> $O/bench_gpus2_time.txt; tail -3 $O/bench_gpus2_time.txt; tail -3 $O/bench_gpus2.err
+( time python bench.py --full --gpus 2 --steps 20 --no-cpu-baseline --no-host-inputs > $O/bench_gpus2_shared.json 2> $O/bench_gpus2.err ) 2> $O/bench_gpus2_time.txt; tail -3 $O/bench_gpus2_time.txt; tail -3 $O/bench_gpus2.err
 python - <<PY
 import json
 try:

@@ -1,8 +1,8 @@
 #!/bin/bash
 # round 5: the two bench lines (default = 148 steps; the driver's window) on one box.  usage (gpurun): bash tools/round5_bench_only.sh [tag]
 O=gpurun_out/r05${1:-b}; mkdir -p $O
-python bench.py > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_steps20.json 2> $O/bench_steps20.err
+python bench.py --full > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_steps20.json 2> $O/bench_steps20.err
 python - <<PY
 import json
 for f in ("bench.json", "bench_steps20.json"):

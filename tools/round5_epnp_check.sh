@@ -5,7 +5,7 @@ O=gpurun_out/r05${1:-g}; mkdir -p $O
 bash tools/gpu_suite_by_file.sh $O/suite.log > $O/suite_summary.txt 2>&1
 tail -60 $O/suite_summary.txt
 for st in 20 148; do
-  VDO_BENCH_NO_SHARDED=1 python bench.py --steps $st --no-batch > $O/bench_$st.json 2> $O/bench_$st.err || tail -5 $O/bench_$st.err
+  VDO_BENCH_NO_SHARDED=1 python bench.py --full --steps $st --no-batch > $O/bench_$st.json 2> $O/bench_$st.err || tail -5 $O/bench_$st.err
   python - <<PY
 import json
 d=json.loads(open("$O/bench_$st.json").read().strip().splitlines()[-1]); c=d["cpu_baseline"]

@@ -3,9 +3,9 @@
 # the shared GPU, kernel statistics of the LM on the roofline graph.   usage (gpurun): bash tools/round5_final.sh [tag]
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r05${1:-y}; mkdir -p $O
 bash tools/gpu_suite_by_file.sh $O/suite.log > $O/suite_summary.txt 2>&1; tail -48 $O/suite_summary.txt
-( time python bench.py > $O/bench.json 2> $O/bench.err ) 2> $O/bench_time.txt; tail -3 $O/bench_time.txt; tail -3 $O/bench.err
-( time python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_steps20.json 2> $O/bench_steps20.err ) 2> $O/bench_steps20_time.txt; tail -3 $O/bench_steps20_time.txt
-python bench.py --gpus 2 --steps 20 --no-cpu-baseline --no-host-inputs > $O/bench_gpus2_shared.json 2> $O/bench_gpus2.err; tail -2 $O/bench_gpus2.err
+( time python bench.py --full > $O/bench.json 2> $O/bench.err ) 2> $O/bench_time.txt; tail -3 $O/bench_time.txt; tail -3 $O/bench.err
+( time python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_steps20.json 2> $O/bench_steps20.err ) 2> $O/bench_steps20_time.txt; tail -3 $O/bench_steps20_time.txt
+python bench.py --full --gpus 2 --steps 20 --no-cpu-baseline --no-host-inputs > $O/bench_gpus2_shared.json 2> $O/bench_gpus2.err; tail -2 $O/bench_gpus2.err
 python - <<PY
 import json
 for f in ("bench.json", "bench_steps20.json"):

@@ -3,7 +3,7 @@
 O=gpurun_out/r05${1:-e}; mkdir -p $O
 bash tools/gpu_suite_by_file.sh $O/suite.log > $O/suite_summary.txt 2>&1
 tail -60 $O/suite_summary.txt
-( time python bench.py > $O/bench.json 2> $O/bench.err ) 2> $O/bench_time.txt
+( time python bench.py --full > $O/bench.json 2> $O/bench.err ) 2> $O/bench_time.txt
 tail -3 $O/bench_time.txt; tail -5 $O/bench.err; python - <<PY
 import json
 d=json.loads(open("$O/bench.json").read().strip().splitlines()[-1])

@@ -1,6 +1,6 @@
 #!/bin/bash
 O=gpurun_out/r06af; mkdir -p $O
-( time python bench.py --no-batch --no-host-inputs > $O/bench.json 2> $O/bench.err ) 2> $O/time.txt; tail -3 $O/time.txt; tail -2 $O/bench.err | cut -c1-300
+( time python bench.py --full --no-batch --no-host-inputs > $O/bench.json 2> $O/bench.err ) 2> $O/time.txt; tail -3 $O/time.txt; tail -2 $O/bench.err | cut -c1-300
 python - <<PY
 import json
 d=json.loads(open("$O/bench.json").read().strip().splitlines()[-1])

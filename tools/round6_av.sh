@@ -1,6 +1,6 @@
 #!/bin/bash
 O=gpurun_out/r06av; mkdir -p $O
-( time python bench.py > $O/bench.json 2> $O/bench.err ) 2> $O/bench_time.txt; tail -3 $O/bench_time.txt
+( time python bench.py --full > $O/bench.json 2> $O/bench.err ) 2> $O/bench_time.txt; tail -3 $O/bench_time.txt
 python - <<PY
 import json
 d=json.loads(open("$O/bench.json").read().strip().splitlines()[-1]); r=d["roofline"]; c=d["cpu_baseline"]

@@ -1,6 +1,6 @@
 #!/bin/bash
 cd /root/repo; O=gpurun_out/r06cg; mkdir -p $O
-( time python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err ) 2> $O/time.txt; tail -3 $O/time.txt
+( time python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err ) 2> $O/time.txt; tail -3 $O/time.txt
 python - <<PY
 import json
 d=json.loads([l for l in open("$O/bench.json") if l.startswith("{")][-1])

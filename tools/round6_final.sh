@@ -4,9 +4,9 @@
 # usage (gpurun): bash tools/round6_final.sh [tag]
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r06${1:-final}; mkdir -p $O
 bash tools/gpu_suite_by_file.sh $O/suite.log > $O/suite_summary.txt 2>&1; tail -50 $O/suite_summary.txt
-( time python bench.py > $O/bench.json 2> $O/bench.err ) 2> $O/bench_time.txt; tail -3 $O/bench_time.txt; tail -3 $O/bench.err | cut -c1-300
-( time python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_steps20.json 2> $O/bench_steps20.err ) 2> $O/bench_steps20_time.txt; tail -3 $O/bench_steps20_time.txt
-python bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline --no-host-inputs --no-parity --no-full-sequence > $O/bench_gpus2_shared.json 2> $O/bench_gpus2.err; tail -2 $O/bench_gpus2.err | cut -c1-300
+( time python bench.py --full > $O/bench.json 2> $O/bench.err ) 2> $O/bench_time.txt; tail -3 $O/bench_time.txt; tail -3 $O/bench.err | cut -c1-300
+( time python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_steps20.json 2> $O/bench_steps20.err ) 2> $O/bench_steps20_time.txt; tail -3 $O/bench_steps20_time.txt
+python bench.py --full --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline --no-host-inputs --no-parity --no-full-sequence > $O/bench_gpus2_shared.json 2> $O/bench_gpus2.err; tail -2 $O/bench_gpus2.err | cut -c1-300
 python - <<PY
 import json
 for f in ("bench.json", "bench_steps20.json"):
@@ -28,7 +28,7 @@ timeout 200 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_fetch -- python $R/tools/sweep_
 timeout 200 rocprofv3 --pmc WRITE_SIZE -d $O/pmc_write -- python $R/tools/sweep_only.py $N > $O/pmc_write.log 2>&1
 timeout 200 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES -d $O/pmc_sq1 -- python $R/tools/sweep_only.py $N > $O/pmc_sq1.log 2>&1
 timeout 200 rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS -d $O/pmc_sq2 -- python $R/tools/sweep_only.py $N > $O/pmc_sq2.log 2>&1
-timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof_frame -- python $R/bench.py --steps 60 --warmup 5 --no-parity --no-full-sequence --no-host-inputs --no-cpu-baseline --no-batch > $O/bench_frame_prof.json 2> $O/bench_frame_prof.err
+timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof_frame -- python $R/bench.py --full --steps 60 --warmup 5 --no-parity --no-full-sequence --no-host-inputs --no-cpu-baseline --no-batch > $O/bench_frame_prof.json 2> $O/bench_frame_prof.err
 timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof_ba_roof -- python $R/tools/ba_variant_probe.py roof > $O/ba_roof.log 2>&1
 cd $R
 python tools/rocprof_summary.py $(find $O/prof_sweep -name "*.db" | head -1) 40 > $O/sweep_kernel_stats.txt 2>&1

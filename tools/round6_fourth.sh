@@ -1,7 +1,7 @@
 #!/bin/bash
 O=gpurun_out/r06d; mkdir -p $O
 timeout 900 python -m pytest tests/test_bench_sequence_gpu.py tests/test_track_sequence_gpu.py -m gpu -q -x 2>&1 | tail -15 | tee $O/new_tests.log
-( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err ) 2> $O/bench_driver_time.txt
+( time timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err ) 2> $O/bench_driver_time.txt
 tail -3 $O/bench_driver_time.txt; tail -5 $O/bench_driver.err
 python - <<PY
 import json

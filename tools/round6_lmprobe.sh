@@ -4,7 +4,7 @@ timeout 900 python -m pytest tests/test_bench_sequence_gpu.py -m gpu -q -x 2>&1 
 bash tools/build_profiled_flow2.sh > $O/build_prof.log 2>&1; tail -2 $O/build_prof.log
 VDO_HIP_LIB=$PWD/vdo_slam_amd/libvdo_hip_prof.so timeout 300 python tools/flow2_phase_probe.py 1200 o800 o400 o230 o120 > $O/flow2_phase_probe.txt 2>&1; cat $O/flow2_phase_probe.txt
 rm -f vdo_slam_amd/libvdo_hip_prof.so
-( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err ) 2> $O/bench_driver_time.txt
+( time timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err ) 2> $O/bench_driver_time.txt
 tail -3 $O/bench_driver_time.txt; tail -5 $O/bench_driver.err
 python - <<PY
 import json

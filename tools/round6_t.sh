@@ -1,6 +1,6 @@
 #!/bin/bash
 O=gpurun_out/r06t; mkdir -p $O
-( time timeout 1200 python bench.py --steps 20 --warmup 5 --no-batch --no-host-inputs --no-parity > $O/bench.json 2> $O/bench.err ) 2> $O/time.txt; tail -3 $O/time.txt; tail -3 $O/bench.err | cut -c1-400
+( time timeout 1200 python bench.py --full --steps 20 --warmup 5 --no-batch --no-host-inputs --no-parity > $O/bench.json 2> $O/bench.err ) 2> $O/time.txt; tail -3 $O/time.txt; tail -3 $O/bench.err | cut -c1-400
 python - <<PY
 import json
 d=json.loads(open("$O/bench.json").read().strip().splitlines()[-1])

@@ -2,7 +2,7 @@
 # -> gpurun_out/r04h/   (run through gpurun from the repo root)
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r04h; mkdir -p $O
 cd $R
-run() { name=$1; shift; env "$@" timeout 200 python bench.py --no-cpu-baseline --no-batch --no-host-inputs > $O/bench_$name.json 2> $O/bench_$name.err; python - "$name" "$O/bench_$name.json" <<'PY'
+run() { name=$1; shift; env "$@" timeout 200 python bench.py --full --no-cpu-baseline --no-batch --no-host-inputs > $O/bench_$name.json 2> $O/bench_$name.err; python - "$name" "$O/bench_$name.json" <<'PY'
 import json, sys
 try:
     d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
