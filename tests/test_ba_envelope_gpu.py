@@ -1,0 +1,287 @@
+"""The batch solver's tile capacities (csrc/capi_ba.hip, ba_dev.hpp), each pinned on both sides: a graph exactly AT the limit against the oracle
+(every block of the linearisation, chi2, a short Levenberg run), and a graph one past it against a clean, named refusal at vdo_ba_create - or the other
+path the tile builder takes there (a hub landmark, a new tile, the PCG instead of the dense assembly).  A refused case launches nothing: its edge is
+established from the graph itself, on the host.  After a refusal the context must be as clean as before: the next graph takes its pool."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from vdo_slam_amd import _capi as K
+from vdo_slam_amd import synth
+from vdo_slam_amd.ba import BatchBA, Context
+
+from tests import ba_envelope_graphs as E
+from tests.test_ba_gpu import BLOCKS, _oracle_system, _scale, block_tol
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = Context(0)
+    yield c
+    c.close()
+
+
+def _blocks_match(ba, oracle, g):
+    ba.linearize()
+    S = ba.system()
+    R = _oracle_system(oracle, g)
+    for name in BLOCKS:
+        a, b = getattr(S, name), getattr(R, name)
+        if b.size:
+            assert np.abs(a - b).max() <= block_tol(name) * _scale(name, R) + 1e-300, (name, np.abs(a - b).max() / max(_scale(name, R), 1e-300))
+    assert abs(S.chi2 - R.chi2) <= 1e-12 * abs(R.chi2)
+    assert abs(S.robust_chi2 - R.robust_chi2) <= 1e-12 * abs(R.robust_chi2)
+
+
+def _oracle_lm(oracle, g, its):
+    gc, keep = K.graph_to_c(g)
+    opt = K.LMOptionsC(its, -1.0, 0, 0, 0.0, 0)
+    so = K.LMStatsC()
+    po = np.zeros_like(g.pose); qo = np.zeros_like(g.point)
+    assert oracle.vdo_oracle_ba_optimize(C.byref(gc), C.byref(opt), K._dp(po), K._dp(qo), C.byref(so)) == 0
+    return so, po, qo
+
+
+def _lm_matches(ba, g, ref, its, solver=0):
+    so, po, qo = ref
+    ba.set_estimates(g.pose, g.point)
+    st = ba.optimize(max_iterations=its, gain_threshold=-1.0, solver=solver)
+    assert (st.iterations, st.total_trials) == (so.iterations, so.total_trials), solver
+    assert abs(st.final_chi2 - so.final_chi2) <= 1e-6 * so.final_chi2, solver
+    pose, pt = ba.estimates()
+    np.testing.assert_allclose(pose, po, rtol=0, atol=1e-4 * max(1.0, np.abs(po).max()))
+    np.testing.assert_allclose(pt, qo, rtol=0, atol=1e-4 * max(1.0, np.abs(qo).max()))
+
+
+def _mixed_poses(g):
+    """pose vertices that carry both EdgeSE3PointXYZ and ternary edges (the sweep's partial rows are then 32 wide)"""
+    return np.intersect1d(g.eb_pose, g.et_pose)
+
+
+# ------------------------------------------------------------------ the refused side of every edge
+def _refused_cases():
+    """(graph, environment, message pattern), each established on the host"""
+    out = {}
+    # a. VDO_TILE_PTS: a dynamic track of 257 points
+    g, c = E.chain_graph(E.TILE_PTS + 1)
+    assert E.track_facts(g, c)[0] == E.TILE_PTS + 1
+    out["a_257_points"] = (g, {}, "exceeds the tile capacity")
+    # b. kHardSlots: 512 distinct pose vertices are unreachable for an accepted track - 257 cameras are 257 per-pose pieces, 255 motions at most (256
+    # points) - so the track of 512 is refused by its pieces, not by its slots; 513 by its slots
+    g, c = E.chain_graph(E.TILE_PTS, extra_cams=1)
+    assert E.track_facts(g, c)[2:] == (E.HARD_SLOTS, E.TILE_THREADS + 1)
+    out["b_512_poses"] = (g, {}, r"needs 257 per-pose pieces \(limit 256")
+    g, c = E.chain_graph(E.TILE_PTS, extra_cams=2)
+    assert E.track_facts(g, c)[2] == E.HARD_SLOTS + 1
+    out["b_513_poses"] = (g, {}, r"touches 513 distinct pose vertices \(limit 512")
+    # c. VDO_TILE_THREADS: 257 per-pose pieces (one camera with 13 observations of its point: 3 pieces, the other 127 with 7: 2 each)
+    g, c = E.repeated_chain_graph(128, [13] + [7] * 127)
+    assert E.track_facts(g, c)[3] == E.TILE_THREADS + 1 and E.track_facts(g, c)[2] <= E.HARD_SLOTS
+    out["c_257_pieces"] = (g, {}, r"needs 257 per-pose pieces \(limit 256")
+    # d. the tile kernels' LDS at 32 sums per partial row: one slot past the largest tile that fits
+    limit = E.wide_slot_limit()
+    n = (limit + 2) // 2                                       # a chain of n points: 2 n - 1 = limit + 1 slots
+    assert 2 * n - 1 == limit + 1
+    msg = rf"a tile of {limit + 1} pose slots with 32 sums per partial row needs {E.sweep_lds(limit + 1, 32)} bytes of LDS in k_sweep_tile.*more than the {E.LDS_MAX} bytes"
+    g, c = E.chain_graph(n)
+    assert E.track_facts(g, c)[2] == limit + 1 and len(_mixed_poses(g)) == 0
+    out["d_wide_env"] = (g, {"VDO_BA_WIDE_PARTIALS": "1"}, msg)
+    g = E.with_motion_observation(g, c)
+    assert E.track_facts(g, c)[2] == limit + 1 and len(_mixed_poses(g)) == 1
+    out["d_mixed_vertex"] = (g, {}, msg)
+    return out
+
+
+_REFUSED = None
+
+
+def _refused(name):
+    global _REFUSED
+    if _REFUSED is None:
+        _REFUSED = _refused_cases()
+    return _REFUSED[name]
+
+
+REFUSED_IDS = ["a_257_points", "b_512_poses", "b_513_poses", "c_257_pieces", "d_wide_env", "d_mixed_vertex"]
+
+
+def test_wide_row_slot_limit_is_where_the_sweep_lds_runs_out():
+    """(host) the edge of (d) as the size helpers put it: 400 slots fit at 32 sums per row, 401 do not - the sweep is the kernel that runs out"""
+    assert E.wide_slot_limit() == 400
+    assert E.sweep_lds(400, 32) == 163504 <= E.LDS_MAX < E.sweep_lds(401, 32) == 163880
+    assert E.precond_lds(401) <= E.LDS_MAX and E.sweep_lds(511, 16) <= E.LDS_MAX
+    assert E.dense_slot_limit() == 207
+
+
+@pytest.mark.parametrize("name", REFUSED_IDS)
+def test_one_past_the_edge_is_refused_at_create(name, monkeypatch):
+    g, env, msg = _refused(name)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    c = Context(0)
+    try:
+        with pytest.raises(K.VdoError, match=msg):
+            BatchBA(c, g)
+    finally:
+        c.close()
+
+
+@pytest.mark.parametrize("name", REFUSED_IDS)
+def test_refusal_leaves_the_context_clean(name, oracle, monkeypatch, capfd):
+    """after the refusal the next graph on the same context takes the context's pool (the VDO_BATCH_TRACE line of its create says so) and linearises like
+    the oracle"""
+    g, env, msg = _refused(name)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    c = Context(0)
+    try:
+        with pytest.raises(K.VdoError, match=msg):
+            BatchBA(c, g)
+        for k in env:
+            monkeypatch.delenv(k)
+        small = synth.make_ba_graph(6, 100, 1, 10, seed=11)
+        monkeypatch.setenv("VDO_BATCH_TRACE", "1")
+        capfd.readouterr()
+        ba = BatchBA(c, small)
+        err = capfd.readouterr().err
+        monkeypatch.delenv("VDO_BATCH_TRACE")
+        line = [l for l in err.splitlines() if l.startswith("[vdo_ba_create]")]
+        assert line and line[-1].endswith("(pooled)"), err[-500:]
+        _blocks_match(ba, oracle, small)
+        ba.close()
+    finally:
+        c.close()
+
+
+# ------------------------------------------------------------------ the accepted side (and the other paths)
+def test_a_b_dynamic_track_of_256_points_and_511_poses(ctx, oracle):
+    """a / b: a chain of VDO_TILE_PTS points touches 511 pose vertices - the most a track can (b, refused side) - in one tile of 511 slots at 16 sums per
+    row: the oracle's blocks and its Levenberg trajectory (2 iterations: the oracle's direct solve takes ~10 s per iteration at 511 poses)"""
+    g, c = E.chain_graph(E.TILE_PTS)
+    assert E.track_facts(g, c) == (256, 766, 511, 256)
+    ba = BatchBA(ctx, g)
+    d = ba.dims()
+    assert (d["max_slots"], d["ps_stride"], d["hubs"]) == (511, 16, 0)
+    _blocks_match(ba, oracle, g)
+    _lm_matches(ba, g, _oracle_lm(oracle, g, 2), 2)
+    ba.close()
+
+
+def test_c_dynamic_track_of_256_per_pose_pieces(ctx, oracle):
+    """c: 128 cameras, each seeing its point of the chain 7 times: 2 pieces of <= VDO_TILE_EPT edges each - 256 pieces, every thread of the sweep"""
+    g, c = E.repeated_chain_graph(128, [7] * 128)
+    assert E.track_facts(g, c) == (128, 128 * 7 + 2 * 127, 255, 256)
+    ba = BatchBA(ctx, g)
+    d = ba.dims()
+    assert (d["max_slots"], d["hubs"]) == (255, 0)
+    _blocks_match(ba, oracle, g)
+    _lm_matches(ba, g, _oracle_lm(oracle, g, 3), 3)
+    ba.close()
+
+
+@pytest.mark.parametrize("route", ["env", "mixed_vertex"])
+def test_d_largest_tile_at_32_sums_per_row(ctx, oracle, route, monkeypatch):
+    """d: the largest tile the tile kernels can hold with 32-wide partial rows (400 slots: a chain of 200 points seen from one more camera), the rows
+    forced by VDO_BA_WIDE_PARTIALS=1 and reached by a mixed-vertex graph: the oracle's blocks and its trajectory through the PCG"""
+    limit = E.wide_slot_limit()
+    n = (limit + 1) // 2
+    g, c = E.chain_graph(n, extra_cams=limit - (2 * n - 1))
+    if route == "env":
+        monkeypatch.setenv("VDO_BA_WIDE_PARTIALS", "1")
+    else:
+        g = E.with_motion_observation(g, c)
+        assert len(_mixed_poses(g)) == 1
+    assert E.track_facts(g, c)[2] == limit
+    ba = BatchBA(ctx, g)
+    d = ba.dims()
+    assert (d["max_slots"], d["ps_stride"], d["hubs"]) == (limit, 32, 0)
+    _blocks_match(ba, oracle, g)
+    _lm_matches(ba, g, _oracle_lm(oracle, g, 2), 2, solver=2)
+    ba.close()
+
+
+def test_e_dense_assembly_at_its_lds_limit(ctx, oracle):
+    """e: 207 slots - the largest tile of the dense assembly's workgroup (dense_tile_lds): solver 3 takes the oracle's trajectory"""
+    limit = E.dense_slot_limit()
+    n = (limit + 1) // 2
+    g, c = E.chain_graph(n)
+    assert E.track_facts(g, c)[2] == limit
+    ba = BatchBA(ctx, g)
+    assert ba.dims()["max_slots"] == limit
+    _blocks_match(ba, oracle, g)
+    _lm_matches(ba, g, _oracle_lm(oracle, g, 2), 2, solver=3)
+    ba.close()
+
+
+def test_e_one_slot_past_the_dense_assembly_goes_to_the_pcg(ctx, oracle):
+    """e: 208 slots - solver 3 is refused with a message that says dense; auto (0) and the PCG (2) take the oracle's trajectory"""
+    limit = E.dense_slot_limit()
+    n = (limit + 1) // 2
+    g, c = E.chain_graph(n, extra_cams=1)
+    assert E.track_facts(g, c)[2] == limit + 1
+    ba = BatchBA(ctx, g)
+    assert ba.dims()["max_slots"] == limit + 1
+    _blocks_match(ba, oracle, g)
+    with pytest.raises(K.VdoError, match="dense"):
+        ba.optimize(max_iterations=1, gain_threshold=-1.0, solver=3)
+    ref = _oracle_lm(oracle, g, 2)
+    for solver in (0, 2):
+        _lm_matches(ba, g, ref, 2, solver=solver)
+    ba.close()
+
+
+@pytest.mark.parametrize("cams", [E.STATIC_SLOTS, E.STATIC_SLOTS + 1])
+def test_f_static_point_seen_from_256_and_257_cameras(ctx, oracle, cams):
+    """f: a static point seen from kStaticSlots cameras is a tile of its own (256 slots); from one more it is a hub landmark - the oracle's blocks on both sides"""
+    g, l = E.hub_graph(cams)
+    n, inc, distinct, pieces = E.track_facts(g, [l])
+    assert (n, inc, distinct) == (1, cams, cams)
+    ba = BatchBA(ctx, g)
+    d = ba.dims()
+    if cams <= E.STATIC_SLOTS:
+        assert (d["hubs"], d["max_slots"]) == (0, cams)
+    else:
+        assert d["hubs"] == 1 and d["max_slots"] <= 64
+    _blocks_match(ba, oracle, g)
+    ba.close()
+
+
+@pytest.mark.parametrize("counts,hub", [([4] * 64, False), ([5] + [4] * 63, False), ([12] * 128, False), ([13] + [12] * 127, True)],
+                         ids=["256_plain", "257_not_plain", "1536_tile", "1537_hub"])
+def test_g_static_point_incidences(ctx, oracle, counts, hub):
+    """g: a static point of 256 observations is a plain tile point (no further check); of 257 it goes through the slot / piece / incidence checks and still
+    fits a tile; 1 536 observations (VDO_TILE_INC: 128 cameras x 12, 256 pieces) still fit a tile, 1 537 make it a hub - the oracle's blocks on every side"""
+    g, l = E.static_point_graph(counts)
+    n, inc, distinct, pieces = E.track_facts(g, [l])
+    assert (inc, distinct) == (sum(counts), len(counts))
+    assert (inc <= E.TILE_INC and pieces <= E.TILE_THREADS) != hub
+    ba = BatchBA(ctx, g)
+    d = ba.dims()
+    assert d["hubs"] == (1 if hub else 0)
+    if not hub:
+        assert d["max_slots"] == len(counts)
+    _blocks_match(ba, oracle, g)
+    ba.close()
+
+
+def test_h_tile_packed_to_256_points_and_256_pieces(ctx, oracle):
+    """h: 128 two-point tracks fill one tile to exactly 256 points and 256 per-pose pieces (one camera per point; beside a 511-slot track that raises the
+    dynamic tiles' slot cap; the packed tile also holds 512 incidences, the soft limit of a graph this small): accepted, the oracle's blocks; one track more opens
+    one more tile, the oracle's blocks"""
+    g0 = E.packed_chains_graph(128)
+    g1 = E.packed_chains_graph(129)
+    short0 = [c for c in E.chains(g0) if len(c) == 2]
+    assert len(short0) == 128
+    assert E.track_facts(g0, [p for c in short0 for p in c])[::3] == (256, 256)     # points, per-pose pieces
+    tiles = []
+    for g in (g0, g1):
+        ba = BatchBA(ctx, g)
+        d = ba.dims()
+        assert (d["max_slots"], d["hubs"]) == (511, 0)
+        tiles.append(d["tiles"])
+        _blocks_match(ba, oracle, g)
+        ba.close()
+    assert tiles == [2, 3]                          # the long track's tile, the packed tile (+ the one more track's)

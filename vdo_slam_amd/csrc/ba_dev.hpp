@@ -20,6 +20,9 @@
 //   part_q / part_m / part_sums   per-(tile,pose-slot) partial sums of the solver and of the sweep (NPS = total slots): pose-major rows, see below
 #pragma once
 #include <atomic>
+#include <map>
+#include <mutex>
+#include <utility>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -193,25 +196,45 @@ void launch_hub_expand_binc(const BADev& d, double* binc18, hipStream_t s);     
 void launch_publish_scalars(const BADev& d, double* h_block_dev, hipStream_t s, uint32_t ticket = 0);      // ba_solve.hip (ticket != 0: written behind the data, system-scope fence in between)
 void launch_dense_solve(const BADev& d, double* S, int64_t ld, double* Winv, double* rhs, hipStream_t s);    // MFMA Cholesky + substitutions -> xp
 
-size_t dense_tile_lds(const BADev& d);      // dynamic LDS of k_schur_dense_tile (ba_solve.hip)
+// Dynamic LDS (bytes) of the tile kernels, from the graph's largest tile (max_slots), its partial rows (ps_stride) and its longest pose chain: the launch
+// sites pass exactly these, and vdo_ba_create checks them (tile_lds_need) before it accepts a graph - one set of size expressions for both.
+size_t sweep_tile_lds(const BADev& d, bool build);   // k_sweep_tile (ba_sweep.hip): plain (error evaluation) / build (linearisation)
+size_t schur_tile_lds(const BADev& d);               // k_schur_tile (ba_solve.hip)
+size_t expand_binc_lds(const BADev& d);              // k_expand_binc
+size_t precond_tile_lds(const BADev& d);             // k_precond_tile
+size_t pcg_chain_lds(const BADev& d);                // k_pcg_chain
+size_t dense_tile_lds(const BADev& d);               // k_schur_dense_tile (the dense assembly: a graph beyond it keeps the PCG, capi_ba.hip dense_tiles_ok)
+// static __shared__ bytes of a kernel (hipFuncGetAttributes; 0 if the runtime cannot say)
+inline size_t static_lds(const void* kernel) {
+  hipFuncAttributes a{};
+  return hipFuncGetAttributes(&a, kernel) == hipSuccess ? a.sharedSizeBytes : 0;
+}
+// the largest static + dynamic LDS of one workgroup over the tile kernels every graph launches (the dense assembly excepted), and that kernel's name
+struct LdsNeed { size_t bytes; const char* kernel; };
+LdsNeed sweep_lds_need(const BADev& d);              // ba_sweep.hip
+LdsNeed tile_lds_need(const BADev& d);               // ba_solve.hip (includes sweep_lds_need)
 // A tile kernel's dynamic LDS grows with the pose slots of the graph's largest tile (a landmark seen from 150 frames needs 150 slots): past the runtime's
-// default limit the launch has to say so.  The attribute is per (kernel, device): the size already granted is remembered per kernel instantiation and device
-// (one runtime call per growth, none per launch - ADVICE r5); a refused request is reported through set_error and fails the launch's caller at its next sync_check
+// default limit the launch has to say so.  The attribute is per (kernel, device): the size already granted is remembered per kernel address and device -
+// not per template type, which instantiations such as k_schur_tile<0/1/2> share - (one runtime call per growth, none per launch - ADVICE r5); a refused request is reported through set_error and fails the launch's caller at its next sync_check
 // with that message instead of a generic asynchronous launch failure.
-template <typename Kernel>
-inline size_t raise_lds(Kernel kernel, size_t bytes) {
-  static std::atomic<size_t> granted[64];
+inline size_t raise_lds_bytes(const void* kernel, size_t bytes) {
   if (bytes > (size_t)(48 * 1024)) {
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (bytes > granted[dev].load(std::memory_order_relaxed)) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-      if (e == hipSuccess) granted[dev].store(bytes, std::memory_order_relaxed);
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0) dev = 0;
+    static std::mutex mu;
+    static std::map<std::pair<const void*, int>, size_t> granted;     // (kernel address, device) -> bytes granted
+    std::lock_guard<std::mutex> lock(mu);
+    size_t& have = granted[{kernel, dev}];
+    if (bytes > have) {
+      const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+      if (e == hipSuccess) have = bytes;
       else set_error(VDO_ERR_UNSUPPORTED, "a tile kernel needs %zu bytes of LDS per workgroup and the device refused it (%s)", bytes, hipGetErrorString(e));
     }
   }
   return bytes;
 }
+template <typename Kernel>
+inline size_t raise_lds(Kernel kernel, size_t bytes) { return raise_lds_bytes(reinterpret_cast<const void*>(kernel), bytes); }
 #define VDO_LDS_MAX_BYTES (160 * 1024)
 
 }  // namespace vdo

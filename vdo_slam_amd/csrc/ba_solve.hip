@@ -1879,10 +1879,26 @@ void launch_dense_rhs(const BADev& d, double* rhs, int64_t ld, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------ launchers
-static size_t schur_lds(const BADev& d) { return (6 * VDO_TILE_PLANE + 24 * (size_t)d.max_slots + ((size_t)d.max_slots + 1) / 2) * sizeof(double); }      // (+ the slots' row ids, int32)
+size_t schur_tile_lds(const BADev& d) { return (6 * VDO_TILE_PLANE + 24 * (size_t)d.max_slots + ((size_t)d.max_slots + 1) / 2) * sizeof(double); }      // (+ the slots' row ids, int32)
+size_t expand_binc_lds(const BADev& d) { return (12 * (size_t)d.max_slots + 3 * VDO_TILE_PTS) * sizeof(double); }
+size_t precond_tile_lds(const BADev& d) { return (33 * (size_t)d.max_slots + 3 * VDO_TILE_PLANE + ((size_t)d.max_slots + 1) / 2) * sizeof(double); }
+size_t pcg_chain_lds(const BADev& d) { return ((d.pc_lds ? 6 * (size_t)d.pc_maxlen : 0) + 96 + 24 + PC_BMAT_DOUBLES) * sizeof(double); }
+
+LdsNeed tile_lds_need(const BADev& d) {
+  // (static __shared__ bytes: asked once per process)
+  static const size_t st_schur = std::max({static_lds((const void*)k_schur_tile<0>), static_lds((const void*)k_schur_tile<1>), static_lds((const void*)k_schur_tile<2>)});
+  static const size_t st_expand = static_lds((const void*)k_expand_binc);
+  static const size_t st_precond = std::max(static_lds((const void*)k_precond_tile<true>), static_lds((const void*)k_precond_tile<false>));
+  static const size_t st_pcg = std::max(static_lds((const void*)k_pcg_chain<0>), static_lds((const void*)k_pcg_chain<1>));
+  LdsNeed need = sweep_lds_need(d);
+  const LdsNeed others[] = {{schur_tile_lds(d) + st_schur, "k_schur_tile"}, {expand_binc_lds(d) + st_expand, "k_expand_binc"},
+                            {precond_tile_lds(d) + st_precond, "k_precond_tile"}, {pcg_chain_lds(d) + st_pcg, "k_pcg_chain"}};
+  for (const LdsNeed& o : others) if (o.bytes > need.bytes) need = o;
+  return need;
+}
 
 void launch_expand_binc(const BADev& d, hipStream_t s) {
-  if (d.n_tiles) hipLaunchKernelGGL(k_expand_binc, dim3(d.n_tiles), dim3(VDO_TILE_THREADS), raise_lds(k_expand_binc, (12 * (size_t)d.max_slots + 3 * VDO_TILE_PTS) * sizeof(double)), s, d);
+  if (d.n_tiles) hipLaunchKernelGGL(k_expand_binc, dim3(d.n_tiles), dim3(VDO_TILE_THREADS), raise_lds(k_expand_binc, expand_binc_lds(d)), s, d);
 }
 
 static int red_blocks(const BADev& d) { return (int)std::min<int64_t>(256, std::max<int64_t>(1, (3 * (int64_t)d.L + 6 * (int64_t)d.P + 4095) / 4096)); }
@@ -1903,7 +1919,7 @@ void launch_factor_and_rhs(const BADev& d, double lambda, hipStream_t s, const R
   if (d.n_chains) hipLaunchKernelGGL(k_factor_chains, dim3((d.n_chains + 127) / 128), dim3(128), 0, s, d, lambda);
   precond = precond || d.sharded;          // (the dense solver needs the landmark factors and the reduced right-hand side only; a sharded run keeps its exchanges as they are)
   if (precond) {
-    const size_t lds = (33 * (size_t)d.max_slots + 3 * VDO_TILE_PLANE + ((size_t)d.max_slots + 1) / 2) * sizeof(double);
+    const size_t lds = precond_tile_lds(d);
     const int nd = d.n_tiles < 1024 ? d.n_tiles : std::min(d.n_dyn_tiles, d.n_tiles);       // tiles with dynamic tracks come first in the launch order (a graph of few tiles: one launch - a second one costs more than the registers)
     if (nd > 0) hipLaunchKernelGGL(k_precond_tile<true>, dim3(nd), dim3(VDO_TILE_THREADS), raise_lds(k_precond_tile<true>, lds), s, d, 0);
     if (d.n_tiles > nd) hipLaunchKernelGGL(k_precond_tile<false>, dim3(d.n_tiles - nd), dim3(VDO_TILE_THREADS), raise_lds(k_precond_tile<false>, lds), s, d, nd);
@@ -1916,7 +1932,7 @@ void launch_factor_and_rhs(const BADev& d, double lambda, hipStream_t s, const R
     // Sharded (round 6): the reduced right-hand side needs the landmark factors only, so its tile pass runs BEFORE the exchange and the block-Jacobi sums (21 P + 1) and
     // qs (6 P) - contiguous in memory - cross the ranks in ONE all-reduce per trial instead of two dependent ones.
     hipLaunchKernelGGL(k_precond_finalize<1>, g, b, 0, s, d, lambda);
-    if (d.n_tiles) hipLaunchKernelGGL(k_schur_tile<1>, dim3(d.n_tiles), dim3(VDO_TILE_THREADS), raise_lds(k_schur_tile<1>, schur_lds(d)), s, d, (const double*)nullptr, (const double*)nullptr);
+    if (d.n_tiles) hipLaunchKernelGGL(k_schur_tile<1>, dim3(d.n_tiles), dim3(VDO_TILE_THREADS), raise_lds(k_schur_tile<1>, schur_tile_lds(d)), s, d, (const double*)nullptr, (const double*)nullptr);
     launch_hub_schur(d, 1, nullptr, nullptr, s);
     hipLaunchKernelGGL(k_gather_q, dim3((d.P + 3) / 4), dim3(256), 0, s, d, d.qs, 0);
     // lin_pending: the linearisation in front of this trial left its exchange to us - Hpp | bp | chi2 (42 P + 4) lie right in front of msum | qs: one all-reduce of
@@ -1936,33 +1952,17 @@ void launch_factor_and_rhs(const BADev& d, double lambda, hipStream_t s, const R
     if (d.pc_lds && d.pc_nwave > 1) hipLaunchKernelGGL(k_pchain_prefix, dim3(d.n_pchains), dim3(64 * d.pc_nwave), 0, s, d);
   }
   if (!d.sharded) {
-    if (d.n_tiles) hipLaunchKernelGGL(k_schur_tile<1>, dim3(d.n_tiles), dim3(VDO_TILE_THREADS), raise_lds(k_schur_tile<1>, schur_lds(d)), sr, d, (const double*)nullptr, (const double*)nullptr);
+    if (d.n_tiles) hipLaunchKernelGGL(k_schur_tile<1>, dim3(d.n_tiles), dim3(VDO_TILE_THREADS), raise_lds(k_schur_tile<1>, schur_tile_lds(d)), sr, d, (const double*)nullptr, (const double*)nullptr);
     launch_hub_schur(d, 1, nullptr, nullptr, sr);
     hipLaunchKernelGGL(k_gather_q, dim3((d.P + 3) / 4), dim3(256), 0, sr, d, d.qs, 0);
   }
   if (two) { hipEventRecord(join, side); hipStreamWaitEvent(s, join, 0); }
 }
 
-static size_t pc_strip_bytes(const BADev& d) {
-  const size_t bytes = ((d.pc_lds ? 6 * (size_t)d.pc_maxlen : 0) + 96 + 24 + PC_BMAT_DOUBLES) * sizeof(double);
-  // more than the default 64 KB of dynamic LDS: tell the runtime.  The attribute is per DEVICE (a process may hold BA contexts on
-  // several GPUs): the size already granted is remembered per device id; the calls are idempotent.
-  static std::atomic<size_t> raised[64];
-  if (bytes > (size_t)(48 * 1024)) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (bytes > raised[dev].load(std::memory_order_relaxed)) {
-      const hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(k_pcg_chain<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-      const hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(k_pcg_chain<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-      if (e1 == hipSuccess && e2 == hipSuccess) raised[dev].store(bytes, std::memory_order_relaxed);
-    }
-  }
-  return bytes;
-}
-void launch_pcg_init(const BADev& d, hipStream_t s) { hipLaunchKernelGGL(k_pcg_chain<1>, dim3(d.n_pchains), dim3(64 * d.pc_nwave), pc_strip_bytes(d), s, d, 0.0, 0, 0); }
+void launch_pcg_init(const BADev& d, hipStream_t s) { hipLaunchKernelGGL(k_pcg_chain<1>, dim3(d.n_pchains), dim3(64 * d.pc_nwave), raise_lds(k_pcg_chain<1>, pcg_chain_lds(d)), s, d, 0.0, 0, 0); }
 
 void launch_pcg_iter(const BADev& d, double lambda, double tol2, int parity, hipStream_t s, const Reducer& R) {
-  if (d.n_tiles) hipLaunchKernelGGL(k_schur_tile<0>, dim3(d.n_tiles), dim3(VDO_TILE_THREADS), raise_lds(k_schur_tile<0>, schur_lds(d)), s, d, (const double*)d.zp, (const double*)(parity ? d.pp2 : d.pp));
+  if (d.n_tiles) hipLaunchKernelGGL(k_schur_tile<0>, dim3(d.n_tiles), dim3(VDO_TILE_THREADS), raise_lds(k_schur_tile<0>, schur_tile_lds(d)), s, d, (const double*)d.zp, (const double*)(parity ? d.pp2 : d.pp));
   launch_hub_schur(d, 0, d.zp, parity ? d.pp2 : d.pp, s);
   const int nq = (d.P + 3) / 4;
   if (d.sharded) {
@@ -1970,12 +1970,12 @@ void launch_pcg_iter(const BADev& d, double lambda, double tol2, int parity, hip
     R(d.qs, 6 * (int64_t)d.P);                     // the one exchange per CG iteration: 6P doubles
     hipLaunchKernelGGL(k_pcg_q, dim3(nq), dim3(256), 0, s, d, lambda, parity, 0);
   } else hipLaunchKernelGGL(k_pcg_q, dim3(nq), dim3(256), 0, s, d, lambda, parity, 1);
-  hipLaunchKernelGGL(k_pcg_chain<0>, dim3(d.n_pchains), dim3(64 * d.pc_nwave), pc_strip_bytes(d), s, d, tol2, parity, nq);
+  hipLaunchKernelGGL(k_pcg_chain<0>, dim3(d.n_pchains), dim3(64 * d.pc_nwave), raise_lds(k_pcg_chain<0>, pcg_chain_lds(d)), s, d, tol2, parity, nq);
 }
 
 // (profiling: the Schur mat-vec of one CG iteration alone, on whatever direction the last solve left in zp / pp; the caller clears flags[1])
 void launch_schur_matvec_only(const BADev& d, hipStream_t s) {
-  if (d.n_tiles) hipLaunchKernelGGL(k_schur_tile<0>, dim3(d.n_tiles), dim3(VDO_TILE_THREADS), raise_lds(k_schur_tile<0>, schur_lds(d)), s, d, (const double*)d.zp, (const double*)d.pp);
+  if (d.n_tiles) hipLaunchKernelGGL(k_schur_tile<0>, dim3(d.n_tiles), dim3(VDO_TILE_THREADS), raise_lds(k_schur_tile<0>, schur_tile_lds(d)), s, d, (const double*)d.zp, (const double*)d.pp);
 }
 
 // the LM scalars and flags -> the handle's mapped pinned block [S_COUNT doubles][4 int32] (visible to the host once the stream has been waited for)
@@ -1994,7 +1994,7 @@ void launch_publish_scalars(const BADev& d, double* h_block_dev, hipStream_t s, 
 }
 
 void launch_backsub_update(const BADev& d, double lambda, bool ortho, hipStream_t s) {
-  if (d.n_tiles) hipLaunchKernelGGL(k_schur_tile<2>, dim3(d.n_tiles), dim3(VDO_TILE_THREADS), raise_lds(k_schur_tile<2>, schur_lds(d)), s, d, (const double*)d.xp, (const double*)nullptr);
+  if (d.n_tiles) hipLaunchKernelGGL(k_schur_tile<2>, dim3(d.n_tiles), dim3(VDO_TILE_THREADS), raise_lds(k_schur_tile<2>, schur_tile_lds(d)), s, d, (const double*)d.xp, (const double*)nullptr);
   launch_hub_schur(d, 2, d.xp, nullptr, s);
   const int nb = red_blocks(d);
   hipLaunchKernelGGL(k_update, dim3(nb), dim3(1024), 0, s, d, lambda, ortho ? 1 : 0);

@@ -26,6 +26,7 @@
 // No global atomics.  HBM bytes of a linearisation with this layout: vdo_slam_amd/ba.py linearize_byte_model;
 // what bounds the kernel (measured): VALU issue (fp64) at 4 workgroups per CU; 109-130 us for 13.3 M edges = 510 MB by counters
 // = 0.49-0.54 of the HBM peak (round 3: 210 us - the head of every tile was a chain of four dependent loads).
+#include <algorithm>
 #include <cstdlib>
 #include "ba_dev.hpp"
 #include "ba_tile.hpp"
@@ -517,8 +518,16 @@ __global__ __launch_bounds__(256) void k_reduce_chi(BADev d, int mode) {
 // ---------------------------------------------------------------------------- launchers
 static double* ep_chi_buf(const BADev& d) { return d.part_chi + 2 * (int64_t)d.n_tiles; }
 
+size_t sweep_tile_lds(const BADev& d, bool build) { return sweep_lds_doubles(d.max_slots, build, d.ps_stride) * sizeof(double); }
+LdsNeed sweep_lds_need(const BADev& d) {
+  static const size_t st_plain = std::max(static_lds((const void*)k_sweep_tile<false, true>), static_lds((const void*)k_sweep_tile<false, false>));
+  static const size_t st_build = std::max(static_lds((const void*)k_sweep_tile<true, true>), static_lds((const void*)k_sweep_tile<true, false>));
+  const size_t plain = sweep_tile_lds(d, false) + st_plain, build = sweep_tile_lds(d, true) + st_build;
+  return build >= plain ? LdsNeed{build, "k_sweep_tile (linearisation)"} : LdsNeed{plain, "k_sweep_tile (error evaluation)"};
+}
+
 void launch_errors(const BADev& d, int which, hipStream_t s, const Reducer& R) {
-  const size_t lds = sweep_lds_doubles(d.max_slots, false, d.ps_stride) * sizeof(double);
+  const size_t lds = sweep_tile_lds(d, false);
   if (d.n_tiles) {
     if (d.eb_zf && !d.eb_w) hipLaunchKernelGGL((k_sweep_tile<false, true>), dim3(d.n_tiles), dim3(VDO_TILE_THREADS), raise_lds(k_sweep_tile<false, true>, lds), s, d, which);
     else hipLaunchKernelGGL((k_sweep_tile<false, false>), dim3(d.n_tiles), dim3(VDO_TILE_THREADS), raise_lds(k_sweep_tile<false, false>, lds), s, d, which);
@@ -535,7 +544,7 @@ void launch_errors(const BADev& d, int which, hipStream_t s, const Reducer& R) {
 void launch_linearize_finish(const BADev& d, hipStream_t s) { hipLaunchKernelGGL(k_reduce_chi, dim3(1), dim3(256), 0, s, d, 2 + 8); }
 
 void launch_sweep_only(const BADev& d, hipStream_t s, int which) {
-  const size_t lds = sweep_lds_doubles(d.max_slots, true, d.ps_stride) * sizeof(double);
+  const size_t lds = sweep_tile_lds(d, true);
   launch_hub_sweep(d, which, true, s);
   if (!d.n_tiles) return;
   if (d.eb_zf && !d.eb_w) hipLaunchKernelGGL((k_sweep_tile<true, true>), dim3(d.n_tiles), dim3(VDO_TILE_THREADS), raise_lds(k_sweep_tile<true, true>, lds), s, d, which);

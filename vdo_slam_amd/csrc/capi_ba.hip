@@ -51,7 +51,9 @@ int upload(vdo_ba* ba, T** dst, const T* src, size_t n, hipStream_t s) {
 
 constexpr int kSoftSlots = 64;     // normal tiles stay below this many pose slots
 constexpr int kHardSlots = 512;    // a single long DYNAMIC track may use up to this many (a chain of n points touches n cameras + n - 1 motion vertices: n <= 256 = VDO_TILE_PTS): the tile kernels
-                                   // stage slots in rounds of 256, and 511 slots are ~140 KB of LDS (ONE workgroup per CU - paid only by graphs that hold such a track).  Rounds 1-4: 100; round 5: 256.
+                                   // stage slots in rounds of 256.  Reachable: 511 (<= 256 cameras - one per-pose piece each - and <= 255 motions), ~140 KB of LDS at 16 sums per partial row
+                                   // (ONE workgroup per CU - paid only by graphs that hold such a track); at 32 sums per row (a pose with both edge kinds) the sweep's LDS caps a tile at
+                                   // 400 slots - vdo_ba_create checks every tile kernel's LDS (tile_lds_need) and refuses beyond.  Rounds 1-4: 100; round 5: 256.
 constexpr int kStaticSlots = 256;  // a STATIC point beyond this many pose vertices is a hub landmark (ba_hub.hip: no LDS at all) instead of a tile of its own
 
 }  // namespace
@@ -144,13 +146,6 @@ extern "C" int vdo_ba_create(vdo_ctx* ctx, const vdo_ba_graph* g, vdo_ba** out) 
   // ---- greedy tiling
   vdo_ba* ba = new vdo_ba();
   ba->ctx = ctx;
-  // a small graph takes the context's pool if nobody holds it (VDO_BA_NO_POOL: A/B switch); the slab itself is allocated on the first such graph
-  static const bool pool_off = std::getenv("VDO_BA_NO_POOL") != nullptr;
-  if (!pool_off && !ctx->ba_pool_busy && (int64_t)L + Eb + Et < 200000) {
-    if (!ctx->ba_slab && hipMalloc((void**)&ctx->ba_slab, kBaSlabBytes) == hipSuccess) ctx->ba_slab_cap = kBaSlabBytes;
-    if (ctx->ba_slab) { ctx->ba_pool_busy = true; ctx->ba_slab_used = 0; ba->pooled = true; }
-    else (void)hipGetLastError();
-  }
   std::vector<Tile> tiles;
   std::vector<int32_t> tile_pose;                  // per slot: global pose id
   std::vector<int32_t> chain_off{0};
@@ -650,6 +645,36 @@ extern "C" int vdo_ba_create(vdo_ctx* ctx, const vdo_ba_graph* g, vdo_ba** out) 
   d.P = P; d.L = L; d.Eb = Ebp; d.Et = Et; d.Ep = Ep; d.Npr = Npr; d.Ninc = Ebp + 2 * Et;
   d.n_tiles = n_tiles; d.NPS = NPS; d.n_chains = n_chains; d.max_slots = max_slots;
   if (dense_tile_lds(d) > (size_t)VDO_LDS_MAX_BYTES) ba->dense_tiles_ok = false;      // (a tile of > ~200 pose slots: the dense assembly's workgroup no longer fits the LDS; PCG does - 76 KB at 256 slots)
+  d.ps_stride = ps_stride;
+  d.n_pchains = n_pchains;
+  {   // LDS strip of a pose chain's workgroup (ba_solve.hip pchain_solve_partitioned): [len][6] doubles, <= 144 KB
+    int maxlen = 1;
+    for (int c = 0; c < n_pchains; ++c) maxlen = std::max(maxlen, (int)(pc_off[c + 1] - pc_off[c]));
+    d.pc_maxlen = maxlen;
+    d.pc_lds = 48 * (size_t)maxlen <= (size_t)(144 * 1024) ? 1 : 0;     // (up to 144 of the 160 KB of a CU: launch_pcg_* raise the kernels' dynamic-LDS limit)
+    if (std::getenv("VDO_BA_CHAIN_GLOBAL")) d.pc_lds = 0;
+    d.pc_closed = std::getenv("VDO_BA_PCHAIN_CLOSED") ? 1 : 0;
+    d.pc_nwave = d.pc_lds ? std::min(16, std::max(1, (maxlen + 7) / 8)) : 1;      // segments of >= 8 positions, one wave each
+    if (const char* e = std::getenv("VDO_BA_CHAIN_WAVES")) d.pc_nwave = std::min(16, std::max(1, std::atoi(e)));
+  }
+  {
+    // Every tile kernel's workgroup holds the largest tile's pose slots in LDS (at 32 sums per partial row the sweep passes the 160 KB of a CU above 400 slots):
+    // a graph whose tile kernels cannot be launched is refused here, with its sizes, and not at its first launch.  The same size helpers as the launch sites.
+    const LdsNeed need = tile_lds_need(d);
+    if (need.bytes > (size_t)VDO_LDS_MAX_BYTES) {
+      delete ba;
+      return set_error(VDO_ERR_UNSUPPORTED, "a tile of %d pose slots with %d sums per partial row needs %zu bytes of LDS in %s, more than the %d bytes of a workgroup "
+                       "(a landmark track touches too many pose vertices)", max_slots, ps_stride, need.bytes, need.kernel, (int)VDO_LDS_MAX_BYTES);
+    }
+  }
+  // a small graph takes the context's pool if nobody holds it (VDO_BA_NO_POOL: A/B switch); the slab itself is allocated on the first such graph.  Taken only
+  // here, once the graph has been accepted: every refusal above returns with the pool untouched (from here on vdo_ba_destroy gives it back)
+  static const bool pool_off = std::getenv("VDO_BA_NO_POOL") != nullptr;
+  if (!pool_off && !ctx->ba_pool_busy && (int64_t)L + Eb + Et < 200000) {
+    if (!ctx->ba_slab && hipMalloc((void**)&ctx->ba_slab, kBaSlabBytes) == hipSuccess) ctx->ba_slab_cap = kBaSlabBytes;
+    if (ctx->ba_slab) { ctx->ba_pool_busy = true; ctx->ba_slab_used = 0; ba->pooled = true; }
+    else (void)hipGetLastError();
+  }
   d.huber_eb = g->huber_eb; d.huber_et = g->huber_et; d.huber_ep = g->huber_ep;
   d.dsqr_eb = (double)(float)(g->huber_eb * g->huber_eb);   // float member, robust_kernel_impl.h:84
   d.dsqr_et = (double)(float)(g->huber_et * g->huber_et);
@@ -716,20 +741,8 @@ extern "C" int vdo_ba_create(vdo_ctx* ctx, const vdo_ba_graph* g, vdo_ba** out) 
     UP(hub_we, Zh, (size_t)n_hub_edges); UP(hub_chi, Zh, 2 * (size_t)n_hubs);
     ba->hub_eb_old = hub_eb_old;
   }
-  d.ps_stride = ps_stride;
   UP(pe_off, pe_off.data(), P + 1); UP(pe_idx, pe_idx.data(), pe_idx.size());
   UP(pr_off, pr_off.data(), P + 1); UP(pr_idx, pr_idx.data(), pr_idx.size());
-  d.n_pchains = n_pchains;
-  {   // LDS strip of a pose chain's workgroup (ba_solve.hip pchain_solve_partitioned): [len][6] doubles, <= 144 KB
-    int maxlen = 1;
-    for (int c = 0; c < n_pchains; ++c) maxlen = std::max(maxlen, (int)(pc_off[c + 1] - pc_off[c]));
-    d.pc_maxlen = maxlen;
-    d.pc_lds = 48 * (size_t)maxlen <= (size_t)(144 * 1024) ? 1 : 0;     // (up to 144 of the 160 KB of a CU: launch_pcg_* raise the kernels' dynamic-LDS limit)
-    if (std::getenv("VDO_BA_CHAIN_GLOBAL")) d.pc_lds = 0;
-    d.pc_closed = std::getenv("VDO_BA_PCHAIN_CLOSED") ? 1 : 0;
-    d.pc_nwave = d.pc_lds ? std::min(16, std::max(1, (maxlen + 7) / 8)) : 1;      // segments of >= 8 positions, one wave each
-    if (const char* e = std::getenv("VDO_BA_CHAIN_WAVES")) d.pc_nwave = std::min(16, std::max(1, std::atoi(e)));
-  }
   UP(pc_off, pc_off.data(), pc_off.size()); UP(pc_pose, pc_pose.data(), P); UP(pc_edge, pc_edge.data(), P);
   UP(pc_far_pos, pc_far_pos.data(), pc_far_pos.size()); UP(pc_far_edge, pc_far_edge.data(), pc_far_edge.size());
   const double* Z = nullptr;
