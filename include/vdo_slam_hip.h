@@ -539,6 +539,38 @@ int vdo_tracks_get(vdo_tracks* t, int32_t* track_off, int32_t* pair_frame, int32
  * what the windowed optimisation reads (Optimizer::PartialBatchOptimization, reference src/Optimizer.cc:42-1230, walks mpMap->TrackletSta of the window's frames). */
 int vdo_tracks_get_since(vdo_tracks* t, int first_frame, int* n_tracks, int64_t* n_pairs, int32_t* track_off, int32_t* pair_frame, int32_t* pair_feat, int32_t* obj_id);
 
+/* ---- Dataset ingest: one frame's four files decoded on the device (example/vdo_slam.cc:104-131) ------------------------------
+ * What the driver does on one host thread per frame - LoadMask's text parse, the PNG scanline un-filter (PNG spec 9.2) + pixel
+ * conversion, the .flo copy - as kernels, into the four device images FramePipeline::Step takes.  The host keeps only the file reads
+ * and zlib's inflate (vdo_slam_amd/host/DatasetIO.h: InflatePNG).  A handle is sized once per sequence (width x height of the images). */
+typedef struct vdo_ingest vdo_ingest;
+/* An inflated PNG image: `height` rows of (1 filter byte + width * channels * bit_depth / 8 bytes), host memory. */
+typedef struct vdo_png_scanlines {
+  const uint8_t* data;
+  int64_t bytes;
+  int32_t width, height, bit_depth, channels;
+} vdo_png_scanlines;
+enum { VDO_INGEST_MASK = 0, VDO_INGEST_FLO = 1, VDO_INGEST_DEPTH = 2, VDO_INGEST_COLOR = 3 };
+int vdo_ingest_create(vdo_ctx* ctx, int width, int height, vdo_ingest** out);
+int vdo_ingest_destroy(vdo_ingest* h);
+/* The handle's pinned staging buffer of one input kind (VDO_INGEST_*), grown to >= bytes (contents are not kept when it grows).  A
+ * file read or inflated straight into it goes to the device by DMA; any other host pointer is accepted by vdo_ingest_frame as well. */
+int vdo_ingest_host_buffer(vdo_ingest* h, int which, int64_t bytes, void** ptr);
+/* Device images owned by the handle (width x height: gray u8, depth_raw f32, flow 2 x f32, mask i32), for callers without their own. */
+int vdo_ingest_device_outputs(vdo_ingest* h, uint8_t** gray, float** depth_raw, float** flow, int32_t** mask);
+/* One frame, host-synchronous.  Outputs are DEVICE pointers; a part whose output is NULL is skipped (its input is not read).
+ *   mask  <- mask_text: the result of LoadMask (host/DatasetIO.cc) on these bytes, rows = height, cols = width;
+ *   flow  <- flo: a Middlebury .flo file (magic 202021.25, width / height equal to the handle's), payload copied as it is;
+ *   depth_raw <- depth: 8/16-bit grey scanlines as float (ReadPNG(.., as_float = true));
+ *   gray  <- color: 8-bit grey / RGB / RGBA scanlines as ReadPNG's image (BGR(A), like cv::imread) through vdo_rgb2gray(.., rgb_order).
+ * VDO_ERR_INVALID (the message names the file kind) for a bad .flo header, a size that is not the handle's, a filter byte > 4, an
+ * unsupported bit depth / channel count or a mask text without a row - and then nothing is written.  No CPU fallback. */
+int vdo_ingest_frame(vdo_ingest* h, const char* mask_text, int64_t mask_bytes, const void* flo, int64_t flo_bytes, const vdo_png_scanlines* depth,
+                     const vdo_png_scanlines* color, int rgb_order, uint8_t* gray, float* depth_raw, float* flow, int32_t* mask);
+/* The last vdo_ingest_frame: ms[0] wall time of the call, ms[1] device time from the first upload to the last kernel (events),
+ * ms[2] device time of the kernels alone (after the uploads). */
+int vdo_ingest_last_timing(vdo_ingest* h, double ms[3]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -68,7 +68,7 @@ bool LoadMask(const std::string& path, cv::Mat& mask) {
   return row > 0;
 }
 
-bool ReadPNG(const std::string& path, cv::Mat& img, bool as_float) {
+bool InflatePNG(const std::string& path, PngScanlines& png, unsigned char* out, size_t out_cap) {
   std::vector<unsigned char> b;
   static const unsigned char sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
   if (!read_file(path, b) || b.size() < 33 || std::memcmp(b.data(), sig, 8) != 0) return false;
@@ -92,12 +92,38 @@ bool ReadPNG(const std::string& path, cv::Mat& img, bool as_float) {
   }
   const int ch = ctype == 0 ? 1 : ctype == 2 ? 3 : ctype == 6 ? 4 : ctype == 4 ? 2 : 0;
   if (!w || !h || w > (unsigned)kMaxImageDim || h > (unsigned)kMaxImageDim || !ch || interlace || (depth != 8 && depth != 16) || ctype == 4) return false;
+  const size_t bpp = (size_t)ch * depth / 8, stride = (size_t)w * bpp, n = (stride + 1) * h;
+  if (z.empty() || n > 1032 * z.size() + 64) return false;      // deflate expands at most ~1032x: the header lies about the size
+  unsigned char* dst = out;
+  if (!out || out_cap < n) { png.raw.resize(n); dst = png.raw.data(); }
+  uLongf out_len = (uLongf)n;
+  if (uncompress(dst, &out_len, z.data(), (uLong)z.size()) != Z_OK || out_len != n) return false;
+  png.width = (int)w; png.height = (int)h; png.bit_depth = depth; png.channels = ch; png.bytes = n;
+  return true;
+}
+
+long ReadFileBytes(const std::string& path, std::vector<unsigned char>& buf, unsigned char* out, size_t out_cap) {
+  FILE* f = std::fopen(path.c_str(), "rb");
+  if (!f) return -1;
+  std::fseek(f, 0, SEEK_END);
+  const long n = std::ftell(f);
+  std::fseek(f, 0, SEEK_SET);
+  if (n < 0) { std::fclose(f); return -1; }
+  unsigned char* dst = out;
+  if (!out || out_cap < (size_t)n) { buf.resize((size_t)n); dst = buf.data(); }
+  const size_t got = n ? std::fread(dst, 1, (size_t)n, f) : 0;
+  std::fclose(f);
+  return got == (size_t)n ? n : -1;
+}
+
+bool ReadPNG(const std::string& path, cv::Mat& img, bool as_float) {
+  PngScanlines png;
+  if (!InflatePNG(path, png)) return false;
+  const unsigned w = (unsigned)png.width, h = (unsigned)png.height;
+  const int depth = png.bit_depth, ch = png.channels;
   if (depth == 16 && ch != 1 && !as_float) return false;
   const size_t bpp = (size_t)ch * depth / 8, stride = (size_t)w * bpp;
-  if (z.empty() || (stride + 1) * h > 1032 * z.size() + 64) return false;      // deflate expands at most ~1032x: the header lies about the size
-  std::vector<unsigned char> raw((stride + 1) * h);
-  uLongf out_len = (uLongf)raw.size();
-  if (uncompress(raw.data(), &out_len, z.data(), (uLong)z.size()) != Z_OK || out_len != raw.size()) return false;
+  std::vector<unsigned char>& raw = png.raw;
   // undo the scanline filters in place (PNG spec 9.2)
   std::vector<unsigned char> prev(stride, 0);
   for (unsigned y = 0; y < h; ++y) {
@@ -155,6 +181,14 @@ int host_io_read_flo(const char* path, int* dims, float* out) try {
 int host_io_load_mask(const char* path, int rows, int cols, int* out) try {
   cv::Mat m(rows, cols, cv::CV_32SC1, out);
   return VDO_SLAM::LoadMask(path, m) ? 0 : -1;
+} catch (...) { return -2; }
+// InflatePNG: dims[0..3] = height, width, bit depth, channels; the filtered scanlines go to `out` when cap allows.  Returns the scanline bytes, -1 on failure.
+long host_io_inflate_png(const char* path, int* dims, unsigned char* out, long cap) try {
+  VDO_SLAM::PngScanlines png;
+  if (!VDO_SLAM::InflatePNG(path, png)) return -1;
+  dims[0] = png.height; dims[1] = png.width; dims[2] = png.bit_depth; dims[3] = png.channels;
+  if (out && cap >= (long)png.bytes) std::memcpy(out, png.raw.data(), png.bytes);
+  return (long)png.bytes;
 } catch (...) { return -2; }
 int host_io_read_png(const char* path, int as_float, int* dims, void* out) try {
   cv::Mat m;

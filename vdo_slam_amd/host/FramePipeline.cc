@@ -822,6 +822,13 @@ int FramePipeline::StepHost(const uint8_t* gray, const float* depth, const float
   return rc;
 }
 
+int FramePipeline::StepDevice(const uint8_t* d_gray, const float* d_depth, const float* d_flow, const int32_t* d_mask, bool depth_is_metric, FrameCounts* out) {
+  depth_metric_ = depth_is_metric;
+  const int rc = Step(d_gray, d_depth, d_flow, d_mask, nullptr, nullptr, 0, 0, out);
+  depth_metric_ = false;
+  return rc;
+}
+
 int FramePipeline::DownloadMask(int32_t* mask_out) {
   VDO_TRY(vdo_frame_images_download_mask(img_[cur_ ^ 1], mask_out));      // (cur_ was flipped at the end of Step)
   return 0;

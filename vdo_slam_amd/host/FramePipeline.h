@@ -75,6 +75,9 @@ class FramePipeline {
   // Step when that read-back can run under the frame's object optimisations - DepthConvertedOnHost() tells; otherwise the caller fetches it
   // with DownloadDepth.
   int StepHost(const uint8_t* gray, const float* depth, const float* flow, const int32_t* mask, bool depth_is_metric, FrameCounts* out, float* depth_inout = nullptr);
+  // The same with DEVICE images that the pipeline may not keep beyond the call (System::TrackRGBDFromFiles: the ingest handle's outputs);
+  // depth_is_metric: K1 is not applied.
+  int StepDevice(const uint8_t* d_gray, const float* d_depth, const float* d_flow, const int32_t* d_mask, bool depth_is_metric, FrameCounts* out);
   bool DepthConvertedOnHost() const { return depth_on_host_; }
   // Objects the caller has ground truth for in the frame about to be given to Step (label = mask id).  The reference only
   // tracks an object whose label has a ground-truth row in BOTH the last and the current frame (src/Tracking.cc:791-841:

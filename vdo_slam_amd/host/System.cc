@@ -12,6 +12,7 @@
 #include <sstream>
 
 #include "Converter.h"
+#include "DatasetIO.h"
 #include "Optimizer.h"
 
 namespace VDO_SLAM {
@@ -110,6 +111,7 @@ Tracking::Tracking(System*, Map* pMap, const std::string& strSettingPath, const 
 
 Tracking::~Tracking() {
   pipe_.reset();
+  if (ingest_) vdo_ingest_destroy(ingest_);
   for (int k = 0; k < 5; ++k) if (ctx_[k]) vdo_ctx_destroy(ctx_[k]);
 }
 
@@ -167,6 +169,11 @@ cv::Mat Tracking::GrabImageRGBD(const cv::Mat& imRGB, cv::Mat& imD, const cv::Ma
   if (fc.n_recovered_masks > 0) pipe_->DownloadMask((int32_t*)maskSEM.data);      // UpdateMask writes through the shared header (Tracking.cc:3049-3068)
   if (trace_slow && since(t_call) > 5.0)
     std::fprintf(stderr, "[slow TrackRGBD f=%d] pre %.2f step %.2f depth %.2f mask(%d) %.2f ms\n", f_id, ms_pre, ms_step, ms_depth, fc.n_recovered_masks, since(t_call));
+  return FinishFrame(mTcw_gt, t_call);
+}
+
+// What GrabImageRGBD / GrabFilesRGBD do after the frame's Step: ground-truth bookkeeping, the final batch optimisation, the returned pose
+cv::Mat Tracking::FinishFrame(const cv::Mat& mTcw_gt, std::chrono::steady_clock::time_point t_call) {
   // ground-truth camera pose of the frame relative to the first one, as Map::vmCameraPose_GT keeps it (src/Tracking.cc:319-328, 1113-1115;
   // Initialization() sets the first frame's to the identity, :1255-1256) - bookkeeping for SaveResults only
   if (!mTcw_gt.empty() && mTcw_gt.rows == 4 && mTcw_gt.cols == 4 && mTcw_gt.depth() == cv::CV_32F) {
@@ -186,6 +193,62 @@ cv::Mat Tracking::GrabImageRGBD(const cv::Mat& imRGB, cv::Mat& imD, const cv::Ma
   cv::Mat Tcw(4, 4, cv::CV_32F);
   std::memcpy(Tcw.data, pipe_->Tcw_out_, 64);
   return Tcw;
+}
+
+cv::Mat Tracking::GrabFilesRGBD(const std::string& rgbPath, const std::string& depthPath, const std::string& flowPath, const std::string& maskPath, const cv::Mat& mTcw_gt,
+                                const std::vector<std::vector<float> >& vObjPose_gt, const double&, const int& nImage) {
+  StopFrame = nImage - 1;
+  if (!have_frame_) f_id = 0;
+  const auto t_call = std::chrono::steady_clock::now();
+  mLastProcessedState = mState;
+  if (mState == NO_IMAGES_YET) mState = NOT_INITIALIZED;
+  const int W = pipe_->params().width, H = pipe_->params().height;
+  if (!ingest_ && vdo_ingest_create(ctx_[0], W, H, &ingest_) != VDO_OK) { std::cerr << "VDO_SLAM::Tracking::GrabFilesRGBD: " << vdo_last_error() << std::endl; return cv::Mat(); }
+  auto fail = [](const char* what, const std::string& path) { std::cerr << "VDO_SLAM::Tracking::GrabFilesRGBD: cannot " << what << " " << path << std::endl; return cv::Mat(); };
+  // the files go straight into the handle's pinned staging buffers (the scanline buffers are sized for W x H RGBA / 16-bit grey: a larger
+  // image is inflated into a buffer of its own and then refused by the size check)
+  auto read_raw = [&](const std::string& path, int which, std::vector<unsigned char>& own, const unsigned char** data) -> long {
+    FILE* f = std::fopen(path.c_str(), "rb");
+    if (!f) return -1;
+    std::fseek(f, 0, SEEK_END);
+    const long n = std::ftell(f);
+    std::fclose(f);
+    void* pin = nullptr;
+    if (n < 0 || vdo_ingest_host_buffer(ingest_, which, n, &pin) != VDO_OK) return -1;
+    const long got = ReadFileBytes(path, own, (unsigned char*)pin, (size_t)n);      // (into `own` only if the file grew in between)
+    *data = own.empty() ? (const unsigned char*)pin : own.data();
+    return got;
+  };
+  std::vector<unsigned char> own_mask, own_flo;
+  const unsigned char *mask_text = nullptr, *flo = nullptr;
+  const long n_mask = read_raw(maskPath, VDO_INGEST_MASK, own_mask, &mask_text);
+  if (n_mask < 0) return fail("read the mask", maskPath);
+  const long n_flo = read_raw(flowPath, VDO_INGEST_FLO, own_flo, &flo);
+  if (n_flo < 0) return fail("read the flow", flowPath);
+  PngScanlines rgb, dep;
+  void *pin_rgb = nullptr, *pin_dep = nullptr;
+  const size_t cap_rgb = ((size_t)W * 4 + 1) * H, cap_dep = ((size_t)W * 2 + 1) * H;
+  if (vdo_ingest_host_buffer(ingest_, VDO_INGEST_COLOR, (int64_t)cap_rgb, &pin_rgb) != VDO_OK || vdo_ingest_host_buffer(ingest_, VDO_INGEST_DEPTH, (int64_t)cap_dep, &pin_dep) != VDO_OK) {
+    std::cerr << "VDO_SLAM::Tracking::GrabFilesRGBD: " << vdo_last_error() << std::endl; return cv::Mat();
+  }
+  if (!InflatePNG(rgbPath, rgb, (unsigned char*)pin_rgb, cap_rgb)) return fail("decode the image", rgbPath);
+  if (!InflatePNG(depthPath, dep, (unsigned char*)pin_dep, cap_dep)) return fail("decode the depth map", depthPath);
+  const vdo_png_scanlines s_rgb{rgb.raw.empty() ? (const uint8_t*)pin_rgb : rgb.raw.data(), (int64_t)rgb.bytes, rgb.width, rgb.height, rgb.bit_depth, rgb.channels};
+  const vdo_png_scanlines s_dep{dep.raw.empty() ? (const uint8_t*)pin_dep : dep.raw.data(), (int64_t)dep.bytes, dep.width, dep.height, dep.bit_depth, dep.channels};
+  uint8_t* d_gray; float *d_depth, *d_flow; int32_t* d_mask;
+  vdo_ingest_device_outputs(ingest_, &d_gray, &d_depth, &d_flow, &d_mask);
+  if (vdo_ingest_frame(ingest_, (const char*)mask_text, n_mask, flo, n_flo, &s_dep, &s_rgb, mbRGB ? 1 : 0, d_gray, d_depth, d_flow, d_mask) != VDO_OK) {
+    std::cerr << "VDO_SLAM::Tracking::GrabFilesRGBD: " << vdo_last_error() << std::endl; return cv::Mat();
+  }
+  std::vector<int> labels;
+  for (const auto& row : vObjPose_gt) if (row.size() > 1) labels.push_back((int)row[1]);
+  pipe_->SetObjectGate(labels.data(), (int)labels.size());
+  // K1 for OMD / KITTI on the device (Step's ingest); VirtualKITTI keeps the raw values with the negative ones clamped to 0 - a PNG sample
+  // is never negative, so that clamp has nothing to do here
+  const bool metric = mTestData != OMD && mTestData != KITTI;
+  FrameCounts fc{};
+  if (pipe_->StepDevice(d_gray, d_depth, d_flow, d_mask, metric, &fc) != 0) return cv::Mat();
+  return FinishFrame(mTcw_gt, t_call);
 }
 
 // The reference's per-frame containers, materialised from the pipeline's flat arrays (see System.h).  Ends a pending object stage first.
@@ -266,6 +329,12 @@ cv::Mat System::TrackRGBD(const cv::Mat& im, cv::Mat& depthmap, const cv::Mat& f
                           const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, cv::Mat& imTraj, const int& nImage) {
   if (mSensor != RGBD) { std::cerr << "ERROR: you called TrackRGBD but input sensor was not set to RGBD." << std::endl; std::exit(-1); }
   return mpTracker->GrabImageRGBD(im, depthmap, flowmap, masksem, mTcw_gt, vObjPose_gt, timestamp, imTraj, nImage);
+}
+
+cv::Mat System::TrackRGBDFromFiles(const std::string& rgbPath, const std::string& depthPath, const std::string& flowPath, const std::string& maskPath, const cv::Mat& mTcw_gt,
+                                   const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, const int& nImage) {
+  if (mSensor != RGBD) { std::cerr << "ERROR: you called TrackRGBD but input sensor was not set to RGBD." << std::endl; std::exit(-1); }
+  return mpTracker->GrabFilesRGBD(rgbPath, depthPath, flowPath, maskPath, mTcw_gt, vObjPose_gt, timestamp, nImage);
 }
 
 // The Map (reference format) is materialised from the pipeline's flat store when somebody looks at it.

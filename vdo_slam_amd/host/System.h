@@ -3,6 +3,7 @@
 // gate of the object tracker, Map bookkeeping, the batch optimisations and SaveResults' five text files (src/System.cc:75-100).  Visualisation (imTraj)
 // and metric printing are out of scope; the hot path is entirely behind FramePipeline.
 #pragma once
+#include <chrono>
 #include <map>
 #include <memory>
 #include <string>
@@ -25,6 +26,13 @@ class Tracking {
   // receives the labels UpdateMask recovered; returns mTcw.clone() (4x4 CV_32F)
   cv::Mat GrabImageRGBD(const cv::Mat& imRGB, cv::Mat& imD, const cv::Mat& imFlow, const cv::Mat& maskSEM, const cv::Mat& mTcw_gt,
                         const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, cv::Mat& imTraj, const int& nImage);
+  // The driver's frame step from files (example/vdo_slam.cc:104-131: imread -> convertTo(CV_32F) -> readOpticalFlow -> LoadMask) + the
+  // call above: the host reads the four files and inflates the two PNGs (DatasetIO's InflatePNG); the mask parse, the PNG un-filter +
+  // colour conversion and the .flo copy run on the device (vdo_ingest_frame) into the images Step takes.  The converted depth map and
+  // the repaired mask stay on the device: SyncFrameState() brings them back (mDepthMap, mSegMap).  Empty Mat + stderr on a file that
+  // cannot be read or decoded.
+  cv::Mat GrabFilesRGBD(const std::string& rgbPath, const std::string& depthPath, const std::string& flowPath, const std::string& maskPath, const cv::Mat& mTcw_gt,
+                        const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, const int& nImage);
   FramePipeline* pipeline() { return pipe_.get(); }
 
   // ---- public state of the reference class (include/Tracking.h:116-198).  Scalar configuration / progress members are kept up to date by
@@ -63,6 +71,8 @@ class Tracking {
   std::unique_ptr<FramePipeline> pipe_;
   std::vector<uint8_t> gray_;
   bool have_frame_ = false;
+  vdo_ingest* ingest_ = nullptr;       // GrabFilesRGBD: device decode of the frame's files, made on first use
+  cv::Mat FinishFrame(const cv::Mat& mTcw_gt, std::chrono::steady_clock::time_point t_call);
   cv::Mat mOriginInv;                  // ground-truth pose of the first frame (src/Tracking.cc:319-323)
 };
 
@@ -73,6 +83,10 @@ class System {
   ~System();
   cv::Mat TrackRGBD(const cv::Mat& im, cv::Mat& depthmap, const cv::Mat& flowmap, const cv::Mat& masksem, const cv::Mat& mTcw_gt,
                     const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, cv::Mat& imTraj, const int& nImage);
+  // TrackRGBD on the frame's files (Tracking::GrabFilesRGBD): rgbPath an 8-bit grey / RGB / RGBA PNG, depthPath an 8/16-bit grey disparity
+  // PNG, flowPath a .flo file, maskPath the instance-mask text - what the reference's driver reads for one frame.
+  cv::Mat TrackRGBDFromFiles(const std::string& rgbPath, const std::string& depthPath, const std::string& flowPath, const std::string& maskPath, const cv::Mat& mTcw_gt,
+                             const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, const int& nImage);
   // The reference's result files (src/System.cc:66-198), `filename` being the path PREFIX as there: initial_stereo_new.txt,
   // refined_stereo_new.txt, cam_pose_gt_stereo.txt (frame id + the 16 entries of T_wc, fixed, 9 digits) and the object motions per
   // transition in the same row format.  The reference writes the object motions in the BODY frame of the ground-truth object pose

@@ -11,6 +11,7 @@
 #include "Map.h"
 #include "ORBextractor.h"
 #include "Optimizer.h"
+#include "System.h"
 
 using namespace VDO_SLAM;
 
@@ -175,6 +176,32 @@ int host_pose_optimization_objmot(int n, const float* last_xy, const float* dept
   for (int i = 0; i < n; ++i) { inlier_flag[i] = 0; obj_label_out[i] = cur.vObjLabel[i]; }
   for (int id : inliers) inlier_flag[id] = 1;
   return (int)inliers.size();
+}
+
+// System::TrackRGBDFromFiles on one frame's four files (identity ground-truth pose; ground-truth object rows [n_rows][row_len] as in
+// host_system_track); Tcw_out 16 floats.  Returns 0, -1 when the tracker returned an empty pose, -2 on a GPU failure.
+int host_system_track_files(System* s, const char* rgb, const char* depth, const char* flow, const char* mask, const float* obj_rows, int n_rows, int row_len,
+                            int n_images, float* Tcw_out) {
+  cv::Mat gt = cv::Mat::eye(4, 4, cv::CV_32F);
+  std::vector<std::vector<float> > rows(n_rows);
+  for (int i = 0; i < n_rows; ++i) rows[i].assign(obj_rows + (size_t)i * row_len, obj_rows + (size_t)(i + 1) * row_len);
+  try {
+    cv::Mat T = s->TrackRGBDFromFiles(rgb, depth, flow, mask, gt, rows, 0.0, n_images);
+    if (T.empty()) return -1;
+    std::memcpy(Tcw_out, T.data, 64);
+  } catch (const std::exception& e) { std::fprintf(stderr, "host_system_track_files: %s\n", e.what()); return -2; }
+  return 0;
+}
+// Tracking::SyncFrameState() + its converted depth map and repaired mask (mDepthMap, mSegMap; h x w each).  0, or -1 before the first frame.
+int host_system_frame_images(System* s, float* depth, int* mask) {
+  try {
+    Tracking* T = s->tracker();
+    T->SyncFrameState();
+    if (T->mDepthMap.empty() || T->mSegMap.empty()) return -1;
+    std::memcpy(depth, T->mDepthMap.data, T->mDepthMap.step * (size_t)T->mDepthMap.rows);
+    std::memcpy(mask, T->mSegMap.data, T->mSegMap.step * (size_t)T->mSegMap.rows);
+  } catch (const std::exception& e) { std::fprintf(stderr, "host_system_frame_images: %s\n", e.what()); return -1; }
+  return 0;
 }
 
 }  // extern "C"

@@ -76,6 +76,25 @@ class System:
                                        0 if rows is None else rows.shape[1], int(n_images), _ptr(self._T))
         return None if rc != 0 else self._T.reshape(4, 4).copy()
 
+    def track_files(self, rgb_path, depth_path, flow_path, mask_path, obj_rows=None, n_images=1 << 30):
+        """One TrackRGBDFromFiles call: the frame's colour PNG, disparity PNG, .flo and mask text decoded on the device (the reference driver's
+        imread / convertTo / readOpticalFlow / LoadMask, example/vdo_slam.cc:104-131) and tracked.  Returns Tcw 4x4 float32, or None."""
+        L = self._L
+        L.host_system_track_files.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        rows = None if obj_rows is None or len(obj_rows) == 0 else np.ascontiguousarray(obj_rows, np.float32)
+        rc = L.host_system_track_files(self._h, str(rgb_path).encode(), str(depth_path).encode(), str(flow_path).encode(), str(mask_path).encode(), _ptr(rows),
+                                       0 if rows is None else rows.shape[0], 0 if rows is None else rows.shape[1], int(n_images), _ptr(self._T))
+        return None if rc != 0 else self._T.reshape(4, 4).copy()
+
+    def frame_images(self, w, h):
+        """Tracking::SyncFrameState()'s converted depth map (metres) and repaired mask of the last frame: (depth [h, w] f32, mask [h, w] i32)"""
+        L = self._L
+        L.host_system_frame_images.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        d = np.zeros((h, w), np.float32); m = np.zeros((h, w), np.int32)
+        if L.host_system_frame_images(self._h, _ptr(d), _ptr(m)) != 0:
+            raise K.VdoError("System.frame_images failed")
+        return d, m
+
     def set_defer(self, on=True):
         """Throughput mode: the object stage of a frame ends inside the next track_rgbd call (same results one frame later)."""
         self._L.host_system_set_defer.argtypes = [C.c_void_p, C.c_int]
