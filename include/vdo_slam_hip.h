@@ -335,8 +335,16 @@ typedef struct vdo_keypoints {
 } vdo_keypoints;
 
 typedef struct vdo_orb vdo_orb;
+/* Accepted: width, height >= 64, 1-16 levels, scale_factor > 1 (VDO_ERR_INVALID otherwise), every level at least 46 px on
+ * both sides (VDO_ERR_UNSUPPORTED otherwise), no upper size limit.  Also VDO_ERR_UNSUPPORTED, naming the level: a level with
+ * FAST cells whose keypoint region (the level minus 16 px on every side) is less than half as wide as it is tall -
+ * DistributeOctTree would start from round(w/h) = 0 nodes, undefined behaviour in the reference (portrait images, deep
+ * levels of tall ones). */
 int vdo_orb_create(vdo_ctx* ctx, const vdo_orb_params* prm, int width, int height, vdo_orb** out);
 int vdo_orb_destroy(vdo_orb* orb);
+/* Upper bound on the keypoints one extraction returns (sum over the levels with cells of max(4 nIni, quota + 2), see
+ * vdo_orb_create): the `capacity` of a vdo_keypoints that never fails.  It can exceed n_features - by far for small budgets. */
+int vdo_orb_max_keypoints(const vdo_orb* orb, int* n);
 /* gray: 8-bit single channel, row stride `stride` bytes; host pointer unless src_is_device. */
 int vdo_orb_extract(vdo_orb* orb, const uint8_t* gray, int stride, int src_is_device, vdo_keypoints* out);
 /* The same in two halves: _begin queues the device stage (K3, K4, K6, K7 + the copy of the candidates) on the extractor's stream

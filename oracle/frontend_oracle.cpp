@@ -217,10 +217,12 @@ void divide(const Node& n, Node& n1, Node& n2, Node& n3, Node& n4) {
   if (n4.keys.size() == 1) n4.noMore = true;
 }
 
-void distribute(const std::vector<Cand>& in, int minX, int maxX, int minY, int maxY, int N, std::vector<Cand>& out) {
+// false: nIni == 0 (a region less than half as wide as it is tall), where the reference indexes an empty vector
+bool distribute(const std::vector<Cand>& in, int minX, int maxX, int minY, int maxY, int N, std::vector<Cand>& out) {
   out.clear();
-  if (in.empty()) return;
+  if (in.empty()) return true;
   const int nIni = (int)std::round((float)(maxX - minX) / (maxY - minY));
+  if (nIni < 1) return false;
   const float hX = (float)(maxX - minX) / nIni;
   std::list<Node> nodes;
   std::vector<Node*> ini(nIni);
@@ -291,6 +293,7 @@ void distribute(const std::vector<Cand>& in, int minX, int maxX, int minY, int m
     for (size_t k = 1; k < nd.keys.size(); ++k) if (nd.keys[k].resp > mr) { best = &nd.keys[k]; mr = nd.keys[k].resp; }
     out.push_back(*best);
   }
+  return true;
 }
 
 // umax table (ORBextractor.cc:443-458)
@@ -473,7 +476,7 @@ extern "C" int vdo_oracle_orb_extract_desc(const uint8_t* gray, int w, int h, co
     std::vector<Cand> c, sel;
     level_candidates(lv[l], *p, c);
     const int minB = EDGE_THRESHOLD - 3;
-    distribute(c, minB, lv[l].w - EDGE_THRESHOLD + 3, minB, lv[l].h - EDGE_THRESHOLD + 3, nf[l], sel);
+    if (!distribute(c, minB, lv[l].w - EDGE_THRESHOLD + 3, minB, lv[l].h - EDGE_THRESHOLD + 3, nf[l], sel)) return -2;
     const int patch = (int)(PATCH_SIZE * sc[l]);
     std::vector<uint8_t> working;
     if (desc && !sel.empty()) { working.resize((size_t)lv[l].w * lv[l].h); gaussian_blur7(lv[l].d.data(), lv[l].w, lv[l].h, working.data()); }

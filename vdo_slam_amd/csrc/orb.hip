@@ -32,8 +32,8 @@ namespace vdo {
 
 constexpr int kEdge = 19, kHalfPatch = 15, kPatch = 31;
 constexpr int kSpecCand = 24576;       // candidates fetched speculatively together with the header (typ. 10-15 k per KITTI frame)
-constexpr int kCellCap = 160;          // max keypoints kept per FAST cell (NMS => <= ~(37/2)^2/2)
 constexpr int kMaxCellDim = 68;        // hCell = ceil(height/nRows) < 60, +6 overlap
+static_assert(kMaxCellDim <= 128, "k_fast_cells packs cell-local coordinates in 7 bits");
 
 struct LevelDesc { int w, h, bw, bh; int64_t off; int64_t off_inner; int64_t off_blur; };   // bordered image at img + off; blurred interior (w x h, contiguous) at blur + off_blur
 struct CellDesc { int level, x0, y0, x1, y1, addx, addy, pad; };          // ROI in level interior coords; add = j*wCell, i*hCell
@@ -221,9 +221,10 @@ __device__ __forceinline__ int fast_score_lds(const uint8_t* roi, int stride, in
   return best > t ? best - 1 : 0;
 }
 
-// One workgroup per cell.  out_cnt[cell], out_pack[cell*kCellCap + k] = x | y<<12 | score<<24 (level coords rel. (16,16))
+// One workgroup per cell.  out_cnt[cell], out_pack[cell*cell_cap + k] = x | y<<7 | score<<24 (cell-local coords, < kMaxCellDim:
+// any level size fits; k_compact_angle adds the cell's addx / addy).  cell_cap bounds the count of every cell (vdo_orb_create).
 __global__ __launch_bounds__(256) void k_fast_cells(const uint8_t* __restrict__ pyr, const LevelDesc* __restrict__ levels,
-                                                    const CellDesc* __restrict__ cells, int ini_th, int min_th,
+                                                    const CellDesc* __restrict__ cells, int ini_th, int min_th, int cell_cap,
                                                     int* __restrict__ out_cnt, uint32_t* __restrict__ out_pack) {
   __shared__ uint8_t roi[kMaxCellDim * kMaxCellDim];
   __shared__ uint8_t sc[kMaxCellDim * kMaxCellDim];
@@ -274,8 +275,8 @@ __global__ __launch_bounds__(256) void k_fast_cells(const uint8_t* __restrict__ 
         if (!(keep & (1u << k))) continue;
         const int i = tid * per + k;
         const int y = i / w, x = i - y * w;
-        if (pos < kCellCap)
-          out_pack[(size_t)blockIdx.x * kCellCap + pos] = (uint32_t)(x + C.addx) | ((uint32_t)(y + C.addy) << 12) | ((uint32_t)sc[y * kMaxCellDim + x] << 24);
+        if (pos < cell_cap)
+          out_pack[(size_t)blockIdx.x * cell_cap + pos] = (uint32_t)x | ((uint32_t)y << 7) | ((uint32_t)sc[y * kMaxCellDim + x] << 24);
         ++pos;
       }
       if (tid == 0) out_cnt[blockIdx.x] = total;
@@ -306,39 +307,42 @@ __device__ __forceinline__ float fast_atan2_dev(float y, float x) {
 // dense: x,y (float, relative to (16,16)), resp, angle, level
 __global__ __launch_bounds__(256) void k_compact_angle(const uint8_t* __restrict__ pyr, const LevelDesc* __restrict__ levels,
                                                        const CellDesc* __restrict__ cells, const int* __restrict__ cnt, const int* __restrict__ cell_level,
-                                                       int* __restrict__ level_cnt, const uint32_t* __restrict__ pack, int ncells, UMax um,
+                                                       int* __restrict__ level_cnt, const uint32_t* __restrict__ pack, int ncells, int cell_cap, UMax um,
                                                        float* __restrict__ ox, float* __restrict__ oy, float* __restrict__ oresp,
                                                        float* __restrict__ oang, int* __restrict__ olevel) {
   const int cell = blockIdx.x;
-  const int n = min(cnt[cell], kCellCap);
-  const int lvl = cells[cell].level;
+  const int n = min(cnt[cell], cell_cap);
+  const CellDesc C = cells[cell];
+  const int lvl = C.level;
   const LevelDesc L = levels[lvl];
   const uint8_t* img = pyr + L.off_inner;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   // dense offset of this cell = number of candidates in the cells before it (every workgroup sums its own prefix: ~1100 counts,
   // L2-resident - cheaper than a separate single-workgroup scan kernel in front of this one); workgroup 0 also writes the header
-  // (per-level counts + total) the host fetches next to the candidates
-  __shared__ int s_part[4], s_lvl[16];
+  // (per-level counts + total + the largest count of one cell, checked against cell_cap) the host fetches next to the candidates
+  __shared__ int s_part[4], s_lvl[17];
   int base;
   {
     int a = 0;
-    for (int c = threadIdx.x; c < cell; c += 256) a += min(cnt[c], kCellCap);
+    for (int c = threadIdx.x; c < cell; c += 256) a += min(cnt[c], cell_cap);
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) a += __shfl_down(a, off, 64);
     if (lane == 0) s_part[wv] = a;
-    if (cell == 0 && threadIdx.x < 16) s_lvl[threadIdx.x] = 0;
+    if (cell == 0 && threadIdx.x < 17) s_lvl[threadIdx.x] = 0;
     __syncthreads();
     base = s_part[0] + s_part[1] + s_part[2] + s_part[3];
     if (cell == 0) {
-      for (int c = threadIdx.x; c < ncells; c += 256) { const int v = min(cnt[c], kCellCap); if (v) atomicAdd(&s_lvl[cell_level[c]], v); }
+      int mx = 0;
+      for (int c = threadIdx.x; c < ncells; c += 256) { const int r = cnt[c], v = min(r, cell_cap); if (v) atomicAdd(&s_lvl[cell_level[c]], v); mx = max(mx, r); }
+      atomicMax(&s_lvl[16], mx);
       __syncthreads();
       if (threadIdx.x < 16) level_cnt[threadIdx.x] = s_lvl[threadIdx.x];
-      if (threadIdx.x == 0) { int t = 0; for (int q = 0; q < 16; ++q) t += s_lvl[q]; level_cnt[16] = t; }
+      if (threadIdx.x == 0) { int t = 0; for (int q = 0; q < 16; ++q) t += s_lvl[q]; level_cnt[16] = t; level_cnt[17] = s_lvl[16]; }
     }
   }
   for (int k = wv; k < n; k += 4) {
-    const uint32_t pk = pack[(size_t)cell * kCellCap + k];
-    const int x = (int)(pk & 0xfff), y = (int)((pk >> 12) & 0xfff), s = (int)(pk >> 24);
+    const uint32_t pk = pack[(size_t)cell * cell_cap + k];
+    const int x = (int)(pk & 0x7f) + C.addx, y = (int)((pk >> 7) & 0x7f) + C.addy, s = (int)(pk >> 24);     // level coords rel. (16,16)
     const int cx = x + (kEdge - 3), cy = y + (kEdge - 3);       // cvRound of integer-valued coordinates
     // rows v = -15..15 -> lanes 0..30
     int m10 = 0, m01 = 0;
@@ -485,7 +489,7 @@ class QuadTree {
     const float hX = (float)(maxX - minX) / nIni;
     // initial nodes: stable bucket sort of the candidates by column strip
     ini_cnt.assign(nIni + 1, 0);
-    for (int k = 0; k < ncand; ++k) { const int q = (int)(x[k] / hX); cls[k] = (uint8_t)q; ini_cnt[q + 1]++; }
+    for (int k = 0; k < ncand; ++k) { const int q = (int)(x[k] / hX); cls[k] = q; ini_cnt[q + 1]++; }
     for (int i = 0; i < nIni; ++i) ini_cnt[i + 1] += ini_cnt[i];
     ini_fill.assign(ini_cnt.begin(), ini_cnt.end() - 1);
     for (int k = 0; k < ncand; ++k) idx[ini_fill[cls[k]]++] = k;
@@ -543,7 +547,7 @@ class QuadTree {
  private:
   const float *x = nullptr, *y = nullptr, *resp = nullptr;
   std::vector<int> idx, tmp, ini_cnt, ini_fill;
-  std::vector<uint8_t> cls;
+  std::vector<int> cls;                                   // initial column (nIni > 255 on wide strips) or quadrant of a key
   std::vector<QNode> nodes;
   std::vector<std::pair<int, int>> sizeAndNode, prevSN;   // (size, node id); id order == creation order
   int head = -1, tail = -1, count = 0;
@@ -583,7 +587,7 @@ class QuadTree {
     for (int k = n.b; k < n.e; ++k) {
       const int ki = idx[k];
       const int q = (x[ki] < sx) ? ((y[ki] < sy) ? 0 : 2) : ((y[ki] < sy) ? 1 : 3);
-      cls[k] = (uint8_t)q; ++cnt[q];
+      cls[k] = q; ++cnt[q];
     }
     int cur[4];
     cur[0] = n.b; cur[1] = cur[0] + cnt[0]; cur[2] = cur[1] + cnt[1]; cur[3] = cur[2] + cnt[2];
@@ -610,6 +614,8 @@ struct vdo_orb {
   vdo_ctx* ctx = nullptr;
   vdo_orb_params prm{};
   int w = 0, h = 0, ncells = 0;
+  int max_kp = 0;                // vdo_orb_max_keypoints
+  int cell_cap = 1;              // candidates one FAST cell can have: row pitch of the per-cell candidate lists
   std::vector<LevelDesc> levels;
   std::vector<CellDesc> cells;
   std::vector<int> cell_level, nfeat;
@@ -629,7 +635,7 @@ struct vdo_orb {
   // K8 (on request): dense ids of the keypoints of the last extraction, device pattern / selection / descriptor rows
   std::vector<int> sel_dense;
   OrbPattern* d_pat = nullptr; int* d_sel = nullptr; uint8_t* d_desc = nullptr; int desc_cap = 0;
-  // pinned staging: [32 ints: level counts, total][5][kSpecCand] — header and candidates arrive with ONE sync
+  // pinned staging: [32 ints: level counts, total, largest cell count][5][kSpecCand] — header and candidates arrive with ONE sync
   float* h_pin = nullptr;
   float* h_over = nullptr; size_t h_over_n = 0;      // overflow staging when a frame has more than kSpecCand candidates
   // host view of the last extraction (pointers into the pinned staging)
@@ -647,6 +653,12 @@ struct vdo_orb {
 extern "C" int vdo_orb_pyramid_launches(const vdo_orb* o) {
   if (!o) return set_error(VDO_ERR_INVALID, "null handle");
   return o->pyr.n_levels ? (o->pyr2.lv1 > o->pyr2.lv0 ? 2 : 1) : (int)o->levels.size();
+}
+
+extern "C" int vdo_orb_max_keypoints(const vdo_orb* o, int* n) {
+  if (!o || !n) return set_error(VDO_ERR_INVALID, "vdo_orb_max_keypoints: null argument");
+  *n = o->max_kp;
+  return VDO_OK;
 }
 
 extern "C" int vdo_orb_destroy(vdo_orb* o) {
@@ -682,7 +694,11 @@ extern "C" int vdo_orb_create(vdo_ctx* ctx, const vdo_orb_params* prm, int w, in
     L.off = off; L.off_inner = off + (int64_t)kEdge * L.bw + kEdge; L.off_blur = boff;
     off += (int64_t)L.bw * L.bh;
     boff += (int64_t)L.w * L.h;
-    if (L.w < 2 * kEdge + 8 || L.h < 2 * kEdge + 8) { delete o; return set_error(VDO_ERR_UNSUPPORTED, "pyramid level %d too small (%dx%d)", l, L.w, L.h); }
+    if (L.w < 2 * kEdge + 8 || L.h < 2 * kEdge + 8) {        // (L lives in o: the message is formatted first)
+      const int e = set_error(VDO_ERR_UNSUPPORTED, "pyramid level %d too small (%dx%d)", l, L.w, L.h);
+      delete o;
+      return e;
+    }
   }
   o->pyr_bytes = off; o->blur_bytes = boff;
   // features per level (:424-435)
@@ -696,6 +712,7 @@ extern "C" int vdo_orb_create(vdo_ctx* ctx, const vdo_orb_params* prm, int w, in
   }
   // FAST cells (:760-796)
   for (int l = 0; l < NL; ++l) {
+    const int ncells_before = (int)o->cells.size();
     const LevelDesc& L = o->levels[l];
     const float W = 30;
     const int minBX = kEdge - 3, minBY = minBX, maxBX = L.w - kEdge + 3, maxBY = L.h - kEdge + 3;
@@ -715,10 +732,32 @@ extern "C" int vdo_orb_create(vdo_ctx* ctx, const vdo_orb_params* prm, int w, in
         if (maxX > maxBX) maxX = (float)maxBX;
         CellDesc c{l, (int)iniX, (int)iniY, (int)maxX, (int)maxY, j * wCell, i * hCell, 0};
         if (c.x1 - c.x0 > kMaxCellDim || c.y1 - c.y0 > kMaxCellDim) { delete o; return set_error(VDO_ERR_INTERNAL, "FAST cell larger than %d px", kMaxCellDim); }
+        // FAST scores pixels 3 px inside the cell, and non-maximum suppression (strict > against all 8 neighbours) never keeps
+        // two touching pixels: at most one candidate per 2x2 block of that interior (uniform noise: 184 in a 59x40 cell)
+        o->cell_cap = std::max(o->cell_cap, std::max(0, c.x1 - c.x0 - 5) / 2 * (std::max(0, c.y1 - c.y0 - 5) / 2));
         o->cells.push_back(c);
         o->cell_level.push_back(l);
       }
     }
+    if ((int)o->cells.size() == ncells_before) continue;      // no cells: no candidates, the level returns no keypoints
+    // DistributeOctTree (:535-549) starts from nIni = round(region width / region height) columns, the same float arithmetic
+    // as QuadTree::run.  nIni == 0 (a region less than half as wide as it is tall) leaves the reference indexing an empty
+    // vector, undefined behaviour: such a level is refused.
+    const int nIni = (int)std::round((float)(maxBX - minBX) / (maxBY - minBY));
+    if (nIni < 1) {
+      const int e = set_error(VDO_ERR_UNSUPPORTED, "vdo_orb_create: pyramid level %d (%dx%d): its keypoint region (%dx%d) is less than half "
+                              "as wide as it is tall, the quadtree would start with no node", l, L.w, L.h, maxBX - minBX, maxBY - minBY);
+      delete o;
+      return e;
+    }
+    // Keypoints this level can return.  Each DistributeOctTree pass divides nodes (a node with k > 1 keys becomes at most 4
+    // non-empty children: +3 at most) and stops as soon as the node count reaches N = nfeat[l]:
+    //  - the first pass divides every initial node before it tests: at most 4 nIni nodes;
+    //  - a later breadth pass runs only if count + 3 nToExpand <= N held after the pass before it, and it divides exactly
+    //    those nToExpand nodes: at most N;
+    //  - the "largest first" passes start below N and stop right after the division that reaches N: at most N - 1 + 3.
+    // Hence max(4 nIni, N + 2) per level (the reference returns one keypoint per node).
+    o->max_kp += std::max(4 * nIni, o->nfeat[l] + 2);
   }
   o->ncells = (int)o->cells.size();
   // fused pyramid: possible when there are at most 8 levels and every cascaded region fits the LDS buffers
@@ -794,7 +833,7 @@ extern "C" int vdo_orb_create(vdo_ctx* ctx, const vdo_orb_params* prm, int w, in
   }
   hipStream_t s = ctx->stream;
   auto dev = [&](size_t bytes) -> void* { void* p = nullptr; if (hipMalloc(&p, bytes ? bytes : 8) != hipSuccess) return nullptr; o->allocs.push_back(p); return p; };
-  o->dense_cap = o->ncells * kCellCap;
+  o->dense_cap = o->ncells * o->cell_cap;
   o->d_src = (uint8_t*)dev((size_t)w * h * 4);
   o->d_pyr = (uint8_t*)dev(o->pyr_bytes); o->d_blur = (uint8_t*)dev(o->blur_bytes);
   o->d_levels = (LevelDesc*)dev(sizeof(LevelDesc) * NL); o->d_cells = (CellDesc*)dev(sizeof(CellDesc) * o->ncells);
@@ -850,9 +889,9 @@ static int orb_device_stage(vdo_orb* o, const uint8_t* gray_dev, int stride) {
     }
   }
   hipLaunchKernelGGL(k_fast_cells, dim3(o->ncells), dim3(256), 0, s, (const uint8_t*)o->d_pyr, (const LevelDesc*)o->d_levels, (const CellDesc*)o->d_cells,
-                     o->prm.ini_th, o->prm.min_th, o->d_cnt, o->d_pack);
+                     o->prm.ini_th, o->prm.min_th, o->cell_cap, o->d_cnt, o->d_pack);
   hipLaunchKernelGGL(k_compact_angle, dim3(o->ncells), dim3(256), 0, s, (const uint8_t*)o->d_pyr, (const LevelDesc*)o->d_levels, (const CellDesc*)o->d_cells,
-                     (const int*)o->d_cnt, (const int*)o->d_cell_level, o->d_level_cnt, (const uint32_t*)o->d_pack, o->ncells, o->um, o->d_x, o->d_y, o->d_resp, o->d_ang, o->d_lvl);
+                     (const int*)o->d_cnt, (const int*)o->d_cell_level, o->d_level_cnt, (const uint32_t*)o->d_pack, o->ncells, o->cell_cap, o->um, o->d_x, o->d_y, o->d_resp, o->d_ang, o->d_lvl);
   return VDO_OK;
 }
 
@@ -917,6 +956,10 @@ extern "C" int vdo_orb_extract_end(vdo_orb* o, vdo_keypoints* out) {
   float* rows = o->h_pin + 32;
   const int spec = std::min(kSpecCand, o->dense_cap);
   if (hipEventSynchronize(o->ev_cand) != hipSuccess) return set_error(VDO_ERR_NO_DEVICE, "orb device stage failed: %s", hipGetErrorString(hipGetLastError()));
+  if (hdr[17] > o->cell_cap) {   // cannot happen (vdo_orb_create); k_fast_cells would have dropped the excess without a word
+    o->hlevel_cnt.clear(); o->sel_dense.clear();
+    return set_error(VDO_ERR_UNSUPPORTED, "vdo_orb_extract: a FAST cell has %d candidates, more than the %d kept per cell", hdr[17], o->cell_cap);
+  }
   const int total = hdr[16];
   o->n_cand = total;
   o->hlevel_cnt.assign(hdr, hdr + 16);

@@ -35,6 +35,7 @@ def _lib():
         ip = C.POINTER(C.c_int)
         L.vdo_orb_create.argtypes = [vp, C.POINTER(OrbParamsC), C.c_int, C.c_int, C.POINTER(vp)]
         L.vdo_orb_destroy.argtypes = [vp]
+        L.vdo_orb_max_keypoints.argtypes = [vp, ip]
         L.vdo_orb_extract.argtypes = [vp, K.c_uint8_p, C.c_int, C.c_int, C.POINTER(KeypointsC)]
         L.vdo_orb_extract_desc.argtypes = [vp, K.c_uint8_p, C.c_int, C.c_int, C.POINTER(KeypointsC), K.c_uint8_p]
         L.vdo_orb_descriptors.argtypes = [vp, K.c_uint8_p, C.c_int]
@@ -62,19 +63,27 @@ class ORBextractor:
         self.w, self.h, self.nlevels = width, height, nlevels
         self._h = C.c_void_p()
         K.check(_lib().vdo_orb_create(ctx._h, C.byref(self.params), width, height, C.byref(self._h)))
+        n = C.c_int()
+        K.check(_lib().vdo_orb_max_keypoints(self._h, C.byref(n)))
+        self.max_keypoints = n.value          # bound on the keypoints of one extraction: the default capacity
 
     def __call__(self, gray: np.ndarray, capacity=None, descriptors=False):
-        """Keypoints; with ``descriptors=True`` also ``desc`` [n, 32] uint8 (rotated BRIEF, K8)."""
-        gray = np.ascontiguousarray(gray, dtype=np.uint8)
-        cap = capacity or (self.params.n_features + 256)
+        """Keypoints; with ``descriptors=True`` also ``desc`` [n, 32] uint8 (rotated BRIEF, K8).  A uint8 view whose rows are
+        contiguous but further apart than the width (a region of a wider image) is passed with its row stride, not copied."""
+        if gray.shape != (self.h, self.w):
+            raise ValueError(f"image {gray.shape}, extractor {(self.h, self.w)}")
+        if gray.dtype != np.uint8 or gray.strides[1] != 1 or gray.strides[0] < self.w:
+            gray = np.ascontiguousarray(gray, dtype=np.uint8)
+        stride = gray.strides[0]
+        cap = capacity or self.max_keypoints
         a = {k: np.zeros(cap, np.float32) for k in ("x", "y", "response", "angle", "size")}
         octave = np.zeros(cap, np.int32)
         kp = KeypointsC(cap, 0, _fp(a["x"]), _fp(a["y"]), _fp(a["response"]), _fp(a["angle"]), _fp(a["size"]), _ip(octave))
         if descriptors:
             desc = np.zeros((cap, 32), np.uint8)
-            K.check(_lib().vdo_orb_extract_desc(self._h, _u8(gray), gray.shape[1], 0, C.byref(kp), _u8(desc)))
+            K.check(_lib().vdo_orb_extract_desc(self._h, _u8(gray), stride, 0, C.byref(kp), _u8(desc)))
         else:
-            K.check(_lib().vdo_orb_extract(self._h, _u8(gray), gray.shape[1], 0, C.byref(kp)))
+            K.check(_lib().vdo_orb_extract(self._h, _u8(gray), stride, 0, C.byref(kp)))
         n = kp.n
         out = {k: v[:n].copy() for k, v in a.items()}
         out["octave"] = octave[:n].copy()
@@ -91,7 +100,7 @@ class ORBextractor:
     def extract_device(self, gray_ptr: int, stride: int, capacity=None):
         """Like ``__call__`` but the gray image is already resident in HBM (raw device pointer).
         The returned arrays are views of buffers owned by this extractor: valid until the next call."""
-        cap = capacity or (self.params.n_features + 256)
+        cap = capacity or self.max_keypoints
         st = getattr(self, "_dev_out", None)
         if st is None or st[0] != cap:
             a = {k: np.zeros(cap, np.float32) for k in ("x", "y", "response", "angle", "size")}

@@ -84,11 +84,13 @@ FramePipeline::FramePipeline(vdo_ctx* ctx, vdo_ctx* ctx_lm, const PipelineParams
   if (vdo_orb_create(ctx_orb ? ctx_orb : ctx, &op, p.width, p.height, &orb_) != VDO_OK) return;
   for (int k = 0; k < 2; ++k) if (vdo_frame_images_create(ctx, p.width, p.height, &img_[k]) != VDO_OK) return;
   if (vdo_tracks_create(0, &tr_sta_) != VDO_OK || vdo_tracks_create(1, &tr_dyn_) != VDO_OK) return;
-  const int capk = std::max(p.n_features + 256, 3008);           // (SampleKeyPoints yields 3000)
+  int orb_cap = 0;
+  if (vdo_orb_max_keypoints(orb_, &orb_cap) != VDO_OK) return;
+  const int capk = std::max(orb_cap, 3008);                      // (SampleKeyPoints yields 3000)
   kx_.resize(capk); ky_.resize(capk); kr_.resize(capk); ka_.resize(capk); ks_.resize(capk); ko_.resize(capk);
   for (int i = 0; i < 16; ++i) Tcw_last_[i] = vel_[i] = (i % 5 == 0) ? 1.f : 0.f;
   if (p.build_lm) {
-    const int32_t ccap = std::max(p.max_track_bg + 8, p.n_features + 256);      // frame 1 tracks every filtered ORB keypoint of frame 0 (Initialization)
+    const int32_t ccap = std::max({p.max_track_bg + 8, p.n_features + 256, orb_cap});      // frame 1 tracks every filtered ORB keypoint of frame 0 (Initialization)
     if (vdo_flow2_batch_reserve(ctx_lm, 1, &ccap, &lm_cam_) != VDO_OK) return;
     std::vector<int32_t> ocap(obj_slots_, obj_cap_);
     if (vdo_flow2_batch_reserve(ctx_obj_, obj_slots_, ocap.data(), &lm_obj_) != VDO_OK) return;

@@ -39,7 +39,8 @@ void ORBextractor::operator()(cv::InputArray image, cv::InputArray /*mask*/, std
     if (vdo_orb_create(HostContext(), &p, image.cols, image.rows, &mOrb) != VDO_OK) die("vdo_orb_create");
     mW = image.cols; mH = image.rows;
   }
-  const int cap = nfeatures + 256;
+  int cap = 0;
+  if (vdo_orb_max_keypoints(mOrb, &cap) != VDO_OK) die("vdo_orb_max_keypoints");
   std::vector<float> x(cap), y(cap), r(cap), a(cap), s(cap);
   std::vector<int32_t> o(cap);
   vdo_keypoints out{cap, 0, x.data(), y.data(), r.data(), a.data(), s.data(), o.data()};
