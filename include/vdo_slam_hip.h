@@ -195,6 +195,15 @@ int vdo_ba_set_rccl(vdo_ba* ba, vdo_rccl_comm* comm /* NULL: back to single GPU 
  * edges) stay together, shards are contiguous in first-observing-frame order and balanced by
  * incidence count. */
 int vdo_ba_partition(const vdo_ba_graph* g, int world, int32_t* owner_of_point /*[n_point]*/);
+/* Host-only (no GPU, no context): the device layout vdo_ba_create decides for `g` - tiles, permutations, CSR tables, pose chains - or its refusal, for
+ * tests of the layout (csrc/ba_plan.hpp).  vdo_ba_plan_array hands out one array of the plan by its field name, read-only and valid until the plan is
+ * destroyed (an unknown name is VDO_ERR_INVALID); "tiles" / "tiles_launch" are the descriptors as 12 int32 each; "dims" is int64 [13]: tiles,
+ * (tile, pose-slot) pairs, max slots of a tile, sums per partial row, hubs, hub edges, entries of the padded edge blocks, dynamic tiles, pose chains,
+ * longest pose chain, pose graph is paths, dense assembly possible (incidences), compact edge formats (bits). */
+typedef struct vdo_ba_plan vdo_ba_plan;
+int vdo_ba_plan_create(const vdo_ba_graph* g, vdo_ba_plan** out);
+int vdo_ba_plan_array(const vdo_ba_plan* p, const char* name, const void** data, int64_t* count, int32_t* elem_bytes);
+int vdo_ba_plan_destroy(vdo_ba_plan* p);
 
 /* ---- per-frame joint pose + optical-flow optimisation ------------------------------------------
  * Replaces the g2o calls inside Optimizer::PoseOptimizationFlow2Cam (reference

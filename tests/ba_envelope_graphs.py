@@ -1,4 +1,4 @@
-"""Graphs that sit exactly on (or one past) a capacity edge of the batch solver's tile builder (csrc/capi_ba.hip, ba_dev.hpp), and the host-side
+"""Graphs that sit exactly on (or one past) a capacity edge of the batch solver's tile planner (csrc/ba_plan.hip, ba_dev.hpp; the LDS edges: csrc/capi_ba.hip), and the host-side
 facts that say where a graph sits.  Built on synth.make_ba_graph / synth.with_hub_points and dataclasses.replace; every added measurement is
 fp32-representable, like the graphs the reference builds."""
 import dataclasses
@@ -64,7 +64,7 @@ def chains(g):
 
 
 def track_facts(g, pts):
-    """(points, incidences, distinct pose vertices, per-pose pieces) of the track through `pts`: what vdo_ba_create checks a track against"""
+    """(points, incidences, distinct pose vertices, per-pose pieces) of the track through `pts`: what the planner (csrc/ba_plan.hip build_tiles) checks a track against"""
     ps = set(pts)
     eb = np.isin(g.eb_point, list(ps))
     et = np.isin(g.et_p2, list(ps)) & np.isin(g.et_p1, list(ps))

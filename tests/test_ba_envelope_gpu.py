@@ -1,7 +1,7 @@
-"""The batch solver's tile capacities (csrc/capi_ba.hip, ba_dev.hpp), each pinned on both sides: a graph exactly AT the limit against the oracle
+"""The batch solver's tile capacities (csrc/ba_plan.hip, ba_dev.hpp; the LDS check of csrc/capi_ba.hip), each pinned on both sides: a graph exactly AT the limit against the oracle
 (every block of the linearisation, chi2, a short Levenberg run), and a graph one past it against a clean, named refusal at vdo_ba_create - or the other
 path the tile builder takes there (a hub landmark, a new tile, the PCG instead of the dense assembly).  A refused case launches nothing: its edge is
-established from the graph itself, on the host.  After a refusal the context must be as clean as before: the next graph takes its pool."""
+established from the graph itself, on the host (tests/test_ba_plan.py meets the planner's refusals there too, without a device).  After a refusal the context must be as clean as before: the next graph takes its pool."""
 import ctypes as C
 
 import numpy as np

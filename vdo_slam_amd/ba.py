@@ -138,6 +138,48 @@ class BatchBA:
             pass
 
 
+PLAN_DIMS = ("tiles", "slots", "max_slots", "ps_stride", "hubs", "hub_edges", "eb_entries", "n_dyn_tiles", "n_pchains", "pc_maxlen",
+             "pose_graph_is_paths", "dense_tiles_ok", "compact_edges")
+PLAN_INT_ARRAYS = ("tiles", "tile_order", "tiles_launch", "tile_pose", "chain_off", "pt_prev_edge", "pt_single", "eb_key", "et_key", "et_slot", "inc_key",
+                   "pt_old_of_new", "pt_new_of_old", "eb_old_of_new", "et_old_of_new", "inc_of_eb", "inc1_of_et", "inc2_of_et",
+                   "ps_off", "ps_idx", "slot_dst", "pose_kind", "pe_off", "pe_idx", "pr_off", "pr_idx",
+                   "pc_off", "pc_pose", "pc_edge", "pc_far_pos", "pc_far_edge", "hub_off", "hub_point", "hub_pose", "hub_eb_old", "hub_row")
+PLAN_REAL_ARRAYS = ("point", "eb_z", "eb_w", "et_z", "et_w", "eb_zf", "hub_z", "hub_w")
+TILE_FIELDS = ("pt_begin", "pt_end", "eb_begin", "eb_end", "et_begin", "et_end", "inc_begin", "slot_begin", "slot_end", "chain_begin", "chain_end", "ept")
+
+
+def plan_graph(graph) -> dict:
+    """The device layout vdo_ba_create would decide for ``graph`` (csrc/ba_plan.hpp), on the host alone: no GPU, no context.  Returns ``dims`` (a dict
+    of the PLAN_DIMS scalars) and every array of the plan as a numpy copy (tiles / tiles_launch as [n][12] int32, columns TILE_FIELDS).  A graph that
+    vdo_ba_create refuses raises the same VdoError."""
+    L = K.lib()
+    vp = C.c_void_p
+    L.vdo_ba_plan_create.argtypes = [C.POINTER(K.BAGraphC), C.POINTER(vp)]
+    L.vdo_ba_plan_array.argtypes = [vp, C.c_char_p, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+    L.vdo_ba_plan_destroy.argtypes = [vp]
+    gc, _keep = K.graph_to_c(graph)
+    h = vp()
+    K.check(L.vdo_ba_plan_create(C.byref(gc), C.byref(h)))
+    try:
+        def array(name, dtype):
+            ptr, n, eb = vp(), C.c_int64(), C.c_int32()
+            K.check(L.vdo_ba_plan_array(h, name.encode(), C.byref(ptr), C.byref(n), C.byref(eb)))
+            assert eb.value == np.dtype(dtype).itemsize, (name, eb.value)
+            if not n.value:
+                return np.zeros(0, dtype)
+            return np.frombuffer(C.string_at(ptr.value, n.value * eb.value), dtype=dtype).copy()
+        out = {"dims": dict(zip(PLAN_DIMS, array("dims", np.int64).tolist()))}
+        for name in PLAN_INT_ARRAYS:
+            out[name] = array(name, np.uint8 if name == "pt_single" else np.int32)
+        for name in PLAN_REAL_ARRAYS:
+            out[name] = array(name, np.float32 if name == "eb_zf" else np.float64)
+        for name in ("tiles", "tiles_launch"):
+            out[name] = out[name].reshape(-1, len(TILE_FIELDS))
+        return out
+    finally:
+        L.vdo_ba_plan_destroy(h)
+
+
 def linearize_byte_model(graph, dims):
     """HBM bytes one linearisation has to move with this design - the floor the counters are compared with.
     sweep: the edge inputs of every ENTRY of the tiles' padded edge blocks (a few percent more than the edges) + every point once + 48 B of descriptor per

@@ -1,6 +1,6 @@
 // Device-resident state of one batch-BA problem + kernel launch prototypes.
 //
-// HBM layout.  The graph is re-ordered once, on the host, into TILES:
+// HBM layout.  The graph is re-ordered once, on the host, into TILES (the planner: ba_plan.hpp / ba_plan.hip; capi_ba.hip uploads its plan):
 //   tile  = up to VDO_TILE_PTS landmark points (whole tracks/chains, grouped by first observing
 //           frame) together with ALL edges incident to them (<= VDO_TILE_INC incidences).
 //   points are renumbered tile-major (chains contiguous, in chain order);
@@ -56,14 +56,14 @@ struct BADev {
   double* pose[2] = {nullptr, nullptr};
   double* point[2] = {nullptr, nullptr};
   // tiles
-  Tile* tiles = nullptr;                 // [n_tiles] in LAUNCH order (capi_ba.hip): workgroup b works on tiles[b]
+  Tile* tiles = nullptr;                 // [n_tiles] in LAUNCH order (ba_plan.hip launch_order): workgroup b works on tiles[b]
   int32_t* tile_pose = nullptr;          // [NPS] global pose id of each slot
   int32_t* chain_off = nullptr;          // [n_chains+1] point ranges (points of a chain are contiguous)
   int32_t* pt_prev_edge = nullptr;       // [L] ternary edge linking point l-1 -> l (or -1: chain head)
   // edges (tile-major)
   int32_t* eb_key = nullptr; double *eb_z = nullptr, *eb_w = nullptr;         // key = slot<<16 | local point
   int32_t *et_key = nullptr, *et_slot = nullptr; double *et_z = nullptr, *et_w = nullptr;  // key = lp1 | lp2<<16
-  // compact edge inputs, chosen at vdo_ba_create when they lose nothing:
+  // compact edge inputs, chosen by the planner (ba_plan.hip permute_data) when they lose nothing:
   //   eb_w == nullptr : every EdgeSE3PointXYZ carries the same information scalar (eb_w_uni) - true for every graph the reference
   //                     builds (one sigma per edge class, src/Optimizer.cc:1330-1335)
   //   eb_zf != nullptr: every measurement component is exactly a float (the reference's are: Get3DinCamera returns CV_32F) -
@@ -91,7 +91,7 @@ struct BADev {
   int pc_maxlen = 0, pc_lds = 0;                  // longest chain; 1: a chain's strip [len][6] fits the LDS of its workgroup (k_pcg_chain), 0: global-memory path
   int32_t *pc_off = nullptr, *pc_pose = nullptr;  // [n_pchains+1], [P]
   int32_t* pc_edge = nullptr;                     // [P] edge<<1|side linking position k-1 -> k (side 0: previous pose is the edge's i), -1 at a chain head
-  // TWISTED chains (capi_ba.hip): first half of the path, second half backwards (its first position carries pc_edge = -1), the middle pose last.  The last
+  // TWISTED chains (ba_plan.hip pose_chains): first half of the path, second half backwards (its first position carries pc_edge = -1), the middle pose last.  The last
   // position - the joint - has its ordinary link to the position before it and ONE far link to position pc_far_pos[c] (the end of the first half).
   int32_t *pc_far_pos = nullptr, *pc_far_edge = nullptr;   // [n_pchains] global chain position of the far predecessor / its link (edge<<1|side); -1: not twisted
   // linear system
@@ -203,7 +203,7 @@ size_t schur_tile_lds(const BADev& d);               // k_schur_tile (ba_solve.h
 size_t expand_binc_lds(const BADev& d);              // k_expand_binc
 size_t precond_tile_lds(const BADev& d);             // k_precond_tile
 size_t pcg_chain_lds(const BADev& d);                // k_pcg_chain
-size_t dense_tile_lds(const BADev& d);               // k_schur_dense_tile (the dense assembly: a graph beyond it keeps the PCG, capi_ba.hip dense_tiles_ok)
+size_t dense_tile_lds(const BADev& d);               // k_schur_dense_tile (the dense assembly: a graph beyond it keeps the PCG: dense_tiles_ok, its incidence half in ba_plan.hip, this half in capi_ba.hip)
 // static __shared__ bytes of a kernel (hipFuncGetAttributes; 0 if the runtime cannot say)
 inline size_t static_lds(const void* kernel) {
   hipFuncAttributes a{};

@@ -1,4 +1,5 @@
-// Host-side handle of one batch-BA problem (shared by capi_ba.hip and ba_lm.hip).
+// Host-side handle of one batch-BA problem (shared by capi_ba.hip and ba_lm.hip).  vdo_ba_create fills it from a BaPlan (ba_plan.hpp): the device arrays are
+// uploaded from the plan, the permutations below are moved out of it.
 #pragma once
 #include <vector>
 

@@ -4,7 +4,7 @@
 //   k_hub_sweep<BUILD>   = k_sweep_tile     errors, Huber, the edge's `we`, the landmark's Hll / bl (fixed-order block sums), ONE pose-major partial row per edge
 //   k_hub_precond        = k_precond_tile   the 21 sums of  B Hll^-1 B^T  of every edge -> its row of part_m / part_m8
 //   k_hub_schur<MODE>    = k_schur_tile     0: part_q = B Hll^-1 B^T p     1: part_q = B Hll^-1 bl     2: xl = Hll^-1 (bl - B^T x_p)
-// Every hub edge owns a row of the pose-major partial arrays (capi_ba.hip appends one slot per hub edge to tile_pose / slot_dst / ps_off), so k_finalize_pose, k_gather_q /
+// Every hub edge owns a row of the pose-major partial arrays (ba_plan.hip appends one slot per hub edge to tile_pose / slot_dst / ps_off), so k_finalize_pose, k_gather_q /
 // k_pcg_q and k_precond_finalize pick the hub's contributions up with the rows of the (tile, slot) pairs - no change on the pose side.  The landmark side is the scalar
 // Hll[l] (the block is Hll * I3: J_point^T J_point = R R^T) and bl[l], x_l of the hub's device point; k_factor_chains gives it dscal like any single point.
 // Same arithmetic as the tile kernels (se3_dev.hpp: cam_point, chi2_w3, huber_dev; the 16 running sums of ba_sweep.hip acc_terms); sums over a hub's edges in a fixed

@@ -6,7 +6,7 @@
 // — and the reduced pose/motion system S = Hpp - Hpl Hll^-1 Hlp is solved matrix-free with
 // conjugate gradients preconditioned by the block-tridiagonal matrix M = blockdiag(S) + EdgeSE3
 // off-diagonal blocks along every pose chain (block LDL^T, k_pchain_factor; round 5: long chains in TWISTED order - two half-depth
-// recurrences on two waves that meet in a joint with one far link, capi_ba.hip).  x equals the direct solve up to the PCG tolerance.
+// recurrences on two waves that meet in a joint with one far link, ba_plan.hip).  x equals the direct solve up to the PCG tolerance.
 //
 // One workgroup per TILE for everything that touches landmarks (ba_dev.hpp): each thread keeps
 // its <= VDO_TILE_EPT incidences of ONE pose slot in registers (the Huber-weighted information scalar from HBM, the 6x3 block
@@ -536,7 +536,7 @@ __device__ __forceinline__ double chain_inv6(double a, int ln, int r, int q, dou
   return sm[ln];
 }
 
-// Two waves per chain (round 5).  An untwisted chain: wave 0 walks it, wave 1 has nothing to do.  A TWISTED chain (capi_ba.hip): wave 0 factorises the first
+// Two waves per chain (round 5).  An untwisted chain: wave 0 walks it, wave 1 has nothing to do.  A TWISTED chain (ba_plan.hip): wave 0 factorises the first
 // half [b, far], wave 1 the second half - stored backwards, its first position has no link - [far + 1, e - 2]; then wave 1 does the joint (position e - 1), which
 // takes Delta^-1 of BOTH halves' last positions:  Delta_joint = A - L E - L_far E_far.  Half the depth of the one recurrence that cannot be partitioned.
 template <int INV>
@@ -885,7 +885,7 @@ __device__ void pchain_solve_partitioned(const BADev& d, int c, int bgn, int len
   }
   __syncthreads();
   PCG_TICK(5);
-  // A TWISTED chain (capi_ba.hip; uniform over the workgroup): its last position - the joint - also hangs on position far_l, the end of the first half.  The
+  // A TWISTED chain (ba_plan.hip; uniform over the workgroup): its last position - the joint - also hangs on position far_l, the end of the first half.  The
   // second half starts with L = 0, so the recurrences above and below run over the whole strip unchanged; what the far link adds is one block product on the
   // way down (y_last -= L_far y_far, once y_far is final) and one on the way up (w_far -= L_far^T z_last, z_last = w_last, before the backward recurrences start).
   const int far_l = d.pc_far_pos[c] < 0 ? -1 : d.pc_far_pos[c] - bgn;
@@ -1766,7 +1766,7 @@ __global__ __launch_bounds__(VDO_TILE_THREADS) void k_schur_dense_tile(BADev d, 
     AP_TICK(5);
     // pass C: block (r, s) += B_r w_b for every incidence (r, l) on a touched point - of the slots r >= s only: block (s, r) is the transpose
     // (threads and ternary incidences are in slot order, so about half of the waves have nothing to do; S comes out exactly symmetric).  The EdgeSE3PointXYZ entries of a thread (rows j < T.ept of
-    // the tile's edge block) belong to ONE pose slot (capi_ba.hip): their 36 sums add up in registers and go through ONE segmented DPP
+    // the tile's edge block) belong to ONE pose slot (ba_plan.hip): their 36 sums add up in registers and go through ONE segmented DPP
     // reduction per thread (threads are in slot order; many lanes share a slot: plain LDS atomics would serialise); the ternary incidences
     // (rows behind the block, slot-sorted) one reduction each.
     {

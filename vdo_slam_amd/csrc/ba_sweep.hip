@@ -19,7 +19,7 @@
 //   4. the pose 6x6+6 contribution of an edge depends on 16 running sums only
 //      (J_pose = [-I | 2[zc]x]  resp. [I | -[v]x]): Σw, Σw·zc, Σw·zc zcᵀ, Σw·e, Σw·zc×e.
 //      Every thread sums them in registers over its <= VDO_TILE_EPT consecutive EdgeSE3PointXYZ edges, which belong to ONE pose slot (edges are
-//      pose-sorted inside the tile; the tile builder - capi_ba.hip close_tile - cuts every slot's run into pieces of <= VDO_TILE_EPT, one per thread), the
+//      pose-sorted inside the tile; the tile planner - ba_plan.hip OpenTile::close - cuts every slot's run into pieces of <= VDO_TILE_EPT, one per thread), the
 //      threads' totals go through a segmented DPP scan into per-slot LDS accumulators and leave as one 128-byte row per
 //      (tile, slot) of the POSE-MAJOR partial array; k_finalize_pose streams a pose's rows, expands them to the 6x6 block + rhs
 //      and adds the blocks of the pose's EdgeSE3 / prior edges (k_posepose), all in fixed order.
@@ -215,7 +215,7 @@ __global__ __launch_bounds__(VDO_TILE_THREADS, 4) void k_sweep_tile(BADev d, int
       if (BUILD) sdst[sidx] = d.slot_dst[T.slot_begin + sidx];
     }
     // points -> LDS as three planes x | y | z of VDO_TILE_PTS: a coordinate of the 64 points of an edge row is ONE ds_read_b64 (2 LDS cycles, banks by
-    // point id mod 32 - what the tile builder's placement keeps apart, capi_ba.hip close_tile) instead of a ds_read2_b64 + ds_read_b64 over 24-byte records (10)
+    // point id mod 32 - what the tile planner's placement keeps apart, ba_plan.hip place_edges) instead of a ds_read2_b64 + ds_read_b64 over 24-byte records (10)
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       const int i = tid + k * VDO_TILE_THREADS;             // flat index into the tile's [npts][3] block (coalesced request), < 768
