@@ -10,9 +10,10 @@
 // These problems are tiny (<=~1.2k correspondences, 6 unknowns after Schur) and latency-bound
 // (SURVEY.md H4), so the WHOLE LM loop runs inside ONE persistent workgroup per problem —
 // one launch for the camera problem, one launch for all objects of a frame (grid = #objects).
-// Correspondences are strided over the 256 threads, per-landmark data stays in L2-resident
-// scratch, pose-side sums use wave shuffles + one LDS stage, the 6x6 pivoted LDLT and the SE(3)
-// update run on lane 0.  ref_quirks=1 reproduces the BlockSolver_6_3 / 2-DoF aliasing (F3)
+// A thread that owns one correspondence (every problem of the pipeline) keeps its per-landmark data
+// in registers for the whole loop; otherwise correspondences are strided over the 256 threads and
+// the data stays in L2-resident scratch.  Pose-side sums use a register butterfly + one LDS stage,
+// the 6x6 pivoted LDLT runs on wave 0 and the SE(3) update on lane 0.  ref_quirks=1 reproduces the BlockSolver_6_3 / 2-DoF aliasing (F3)
 // exactly as analysed in oracle/flow_oracle.cpp (product code does not use the oracle).
 #include <algorithm>
 #include <cmath>
@@ -46,6 +47,7 @@ struct Flow2Arrays {
   struct Flow2Comm* comm;   // [n_problems]: exchange area of the workgroup cluster of every problem
   unsigned int tag_base;    // launch number << 16: exchange tags of earlier launches never match, the area needs no clearing
   int max_cluster;          // workgroups per problem in this launch (<= F2_CLUSTER): lowered by the launch for very large batches
+  int force_general;        // VDO_LM_GENERAL=1: every problem takes the general (scratch-array) path of k_flow2_lm - the A/B switch of the register path
 };
 
 // One problem is spread over a CLUSTER of up to F2_CLUSTER workgroups (one CU each; a single wave needs ~8k cycles per
@@ -148,8 +150,13 @@ __global__ __launch_bounds__(F2_THREADS) void k_flow2_lm(const Flow2Dev* __restr
   }
   const double fx = P.K[0], fy = P.K[1], cx = P.K[2], cy = P.K[3];
   const bool Q = P.ref_quirks != 0;
+  // One correspondence per thread (every problem the pipeline builds: N <= 2048 on a full cluster): the per-correspondence state of
+  // the whole Levenberg loop stays in the registers of the thread that owns it - the REGISTER path below; everything else
+  // (N > 2048, a lowered cluster, VDO_LM_GENERAL=1) takes the general path over the scratch arrays.  Workgroup-uniform, chosen
+  // per problem; both paths evaluate the same expressions on the same values in the same order: same bits.
+  const bool REG = chunk <= F2_THREADS && !A.force_general;
   // ---- setup: Xw, flows, initial pose (Converter::toSE3Quat)
-  for (int i = first; i < c_hi; i += stride) {
+  if (!REG) for (int i = first; i < c_hi; i += stride) {
     const double dz = depth[i];
     const double o0 = in_obs[i], o1 = in_obs[N + i], m0 = in_meas[i], m1 = in_meas[N + i];
     obs[i] = o0; obs[N + i] = o1; meas[i] = m0; meas[N + i] = m1;
@@ -238,6 +245,326 @@ __global__ __launch_bounds__(F2_THREADS) void k_flow2_lm(const Flow2Dev* __restr
     const double id = 1.0 / (a0 * a3 - a1 * a2);
     Di[0] = a3 * id; Di[1] = -a1 * id; Di[2] = 0; Di[3] = -a2 * id; Di[4] = a0 * id; Di[5] = 0; Di[6] = 0; Di[7] = 0; Di[8] = 0;
   };
+
+  // ---- (2) of a trial, shared by both paths: reduced 6x6 system, SE3 update, pose part of computeScale.  Leaves x_p in s_xp, the
+  // trial pose in s_Ttry, s_rho, and s_ctrl[1] (trial skipped) / s_ctrl[2] (ok2) - valid for every thread on return.
+  auto solve_pose = [&](const double lambda, const int qmax, const double currentChi) __attribute__((always_inline)) {
+    // reduced system: lower triangle Hpp - (Schur sums) + lambda I, rhs bp - (Schur sums); one thread per entry
+    if (tid < 36) {
+      const int a = tid / 6, c2 = tid - 6 * a;
+      if (c2 <= a) {
+        const int k = a * (a + 1) / 2 + c2;
+        double v = s_Hc[k] - s_red[k];
+        if (c2 == a) v += lambda;
+        s_Hs[tid] = v;
+      } else {
+        s_Hs[tid] = s_Hc[c2 * (c2 + 1) / 2 + a];
+      }
+    } else if (tid < 42) {
+      const int j = tid - 36;
+      s_bs[j] = s_Hc[21 + j] - s_red[21 + j];
+    }
+    __syncthreads();
+    F2_TICK(5);
+    bool ok2w = false;
+    if (tid < 64) ok2w = ldlt6_solve_lanes(s_Hs, s_bs, s_xs);      // wave 0: one row of the 6x6 system per lane
+    if (tid == 0) {
+      const bool ok2 = ok2w;
+      F2_TICK(6);
+      s_ctrl[2] = ok2 ? 1 : 0;
+      if (ok2) {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) s_xp[j] = s_xs[j];
+      }
+      // (failed LDLT leaves x untouched in the reference; the trial is rejected anyway)
+      double s = 0;
+      for (int j = 0; j < 6; ++j) s += s_xp[j] * (lambda * s_xp[j] + s_Hc[21 + j]);
+      s_rho = s;    // pose part of computeScale
+      // A failed solve rejects the trial whatever its errors are (tempChi = DBL_MAX) as long as computeScale - known here: the
+      // stale x against the current gradient - is positive, and everything the evaluation would leave behind (errors, chi2,
+      // the trial linearisation) is overwritten by the trial that follows: skip the SE3 update and the sweep.  Not for the
+      // last trial of an iteration (its errors are the ones classified).
+      bool skip = false;
+      if (!ok2 && qmax + 1 < 10) skip = (currentChi - 1.7976931348623157e308) / ((s + s_red[27]) + 1e-3) < 0;
+      s_ctrl[1] = skip ? 1 : 0;
+      if (!skip) s_Ttry = se3_exp_compose(s_xp, s_T);
+      F2_TICK(7);
+    }
+    __syncthreads();
+    F2_TICK(1);
+  };
+
+  if (REG) {
+    // ================= register path: thread tid owns correspondence i = c_lo + tid (idle for the whole loop if i >= c_hi)
+    const int i = first;
+    const bool active = i < c_hi;
+    __shared__ double s_h[F2_THREADS];      // Hll diagonals of the linearisation just made: the F3 aliasing needs the left neighbour's
+    double o0 = 0, o1 = 0, m0 = 0, m1 = 0, xw[3] = {0, 0, 0};
+    double fc0 = 0, fc1 = 0, ft0 = 0, ft1 = 0, xl0 = 0, xl1 = 0, er0 = 0, er1 = 0;
+    double Bc[12], Bt[12], hc = 0, ht = 0, bc0 = 0, bc1 = 0, bt0 = 0, bt1 = 0;      // current / trial linearisation
+    double hpc = 0, hpt = 0;                // Hll diagonal of landmark i - 1 in the current / trial linearisation
+#pragma unroll
+    for (int a = 0; a < 12; ++a) { Bc[a] = 0; Bt[a] = 0; }
+    if (active) {
+      const double dz = depth[i];
+      o0 = in_obs[i]; o1 = in_obs[N + i]; m0 = in_meas[i]; m1 = in_meas[N + i];
+      const double x = (o0 - cx) * dz / fx, y = (o1 - cy) * dz / fy;
+      const double* W = P.Twl;
+      xw[0] = W[0] * x + W[1] * y + W[2] * dz + W[3];
+      xw[1] = W[4] * x + W[5] * y + W[6] * dz + W[7];
+      xw[2] = W[8] * x + W[9] * y + W[10] * dz + W[11];
+      fc0 = m0; fc1 = m1;
+    }
+    // what the Schur sums of a trial leave for the back-substitution of the same trial (same lambda, same divisions)
+    double q0 = 0, q1 = 0, q2 = 0, qp2 = 0;
+
+    // Sweep (3) over registers: TRIAL -> back-substitution against the current linearisation, flow update into (fo0, fo1); then
+    // errors + linearisation at (T, f) into (Bw, hw, bw0, bw1).  Sums and return value as in the general sweep below.
+    auto sweep_r = [&](auto trial_c, const double lam, const bool ok2, double (&Bw)[12], double& hw, double& bw0, double& bw1,
+                       const double fin0, const double fin1, double& fo0, double& fo1) -> double {
+      constexpr bool TRIAL = decltype(trial_c)::value;
+      const SE3d T = TRIAL ? s_Ttry : s_T;
+      double xp[6];
+#pragma unroll
+      for (int j = 0; j < 6; ++j) xp[j] = s_xp[j];
+      double acc[29];
+#pragma unroll
+      for (int k = 0; k < 29; ++k) acc[k] = 0.0;
+      double hmax = 0.0;
+      if (active) {
+        double f0v, f1v;
+        if (TRIAL) {
+          const double b0 = bc0, b1 = bc1;
+          double t0 = 0, t1 = 0;
+#pragma unroll
+          for (int a = 0; a < 6; ++a) { t0 += Bc[2 * a] * (-xp[a]); t1 += Bc[2 * a + 1] * (-xp[a]); }
+          const double c0 = b0 + t0, c1 = b1 + t1;
+          double x0, x1;
+          if (Q) {
+            x0 = q0 * c0 + q1 * c1;
+            x1 = q2 * c1;
+            if (i > 0) x0 = qp2 * c0 + x0;
+          } else {
+            double Di[9];
+            dinv_of(hc, lam, Di);
+            x0 = (Di[0] * c0 + Di[1] * c1) + Di[2] * 0.0;
+            x1 = (Di[3] * c0 + Di[4] * c1) + Di[5] * 0.0;
+          }
+          F2_TICK(8);
+          if (!ok2) x0 = xl0;           // failed LDLT: stale x (the reference keeps the previous content); the trial is rejected anyway
+          const double x1e = ok2 ? x1 : xl1;
+          xl0 = x0; xl1 = x1e;
+          f0v = fin0 + x0; f1v = fin1 + x1e;
+          fo0 = f0v; fo1 = f1v;
+          acc[28] += x0 * (lam * x0 + b0) + x1e * (lam * x1e + b1);
+        } else {
+          f0v = fin0; f1v = fin1;
+        }
+        // computeActiveErrors at (T, f)
+        double pc[3];
+        q_rotate(T.r, xw, pc);
+        const double X = pc[0] + T.t[0], Y = pc[1] + T.t[1], Z = pc[2] + T.t[2], Z2 = Z * Z;
+        const double u = X / Z * fx + cx, v = Y / Z * fy + cy;
+        const double e0 = (o0 + f0v) - u, e1 = (o1 + f1v) - v;
+        er0 = e0; er1 = e1;
+        if (TRIAL) F2_TICK(9);
+        const double c = e0 * (P.info_flow * e0) + e1 * (P.info_flow * e1);
+        double r0, r1;
+        huber_f2(c, P.huber_delta, P.huber_dsqr, r0, r1);
+        const double p0 = f0v - m0, p1 = f1v - m1;
+        acc[27] += r0 + (p0 * (P.info_prior * p0) + p1 * (P.info_prior * p1));
+        // buildSystem at the same point
+        double J[12];
+        J[0] = X * Y / Z2 * fx; J[1] = -(1 + (X * X / Z2)) * fx; J[2] = Y / Z * fx; J[3] = -1. / Z * fx; J[4] = 0; J[5] = X / Z2 * fx;
+        J[6] = (1 + Y * Y / Z2) * fy; J[7] = -X * Y / Z2 * fy; J[8] = -X / Z * fy; J[9] = 0; J[10] = -1. / Z * fy; J[11] = Y / Z2 * fy;
+        const double wo = r1 * P.info_flow;
+        const double or0 = -(P.info_flow * e0) * r1, or1 = -(P.info_flow * e1) * r1;
+#pragma unroll
+        for (int a = 0; a < 6; ++a) { Bw[2 * a] = J[a] * wo; Bw[2 * a + 1] = J[6 + a] * wo; }
+        int k = 0;
+#pragma unroll
+        for (int a = 0; a < 6; ++a) {
+          acc[21 + a] += J[a] * or0 + J[6 + a] * or1;
+#pragma unroll
+          for (int c2 = 0; c2 <= a; ++c2) acc[k++] += J[a] * wo * J[c2] + J[6 + a] * wo * J[6 + c2];   // lower triangle
+        }
+        const double h = wo + P.info_prior;
+        hw = h;                   // Hll block = h * I2 (off-diagonals are exact zeros)
+        bw0 = or0 - P.info_prior * p0;
+        bw1 = or1 - P.info_prior * p1;
+        hmax = fmax(hmax, h);
+        s_h[tid] = h;
+        if (i == c_hi - 1) s_hlast = h;
+        if (TRIAL) F2_TICK(10);
+      }
+      block_reduce_bfly<29>(acc, s_wpart, s_red);
+      if (TRIAL) F2_TICK(11);
+      return hmax;
+    };
+    // h of landmark i - 1 after a sweep and its exchange: the left neighbour's, or - first thread - the previous chunk's last
+    auto h_prev = [&](const double hb) -> double { return tid > 0 ? s_h[tid - 1] : hb; };
+
+    double lambda = -1, ni = 2;
+    int nBad = 0, it = 0, total_trials = 0, stop_reason = 0;
+    const double tau = 1e-5, upper = 2. / 3., lower = 1. / 3.;
+    double chi2_check = 0;
+    // initial computeActiveErrors + buildSystem
+    double hmax = sweep_r(std::false_type{}, 0.0, true, Bc, hc, bc0, bc1, fc0, fc1, fc0, fc1);
+#pragma unroll
+    for (int off2 = 32; off2 > 0; off2 >>= 1) hmax = fmax(hmax, __shfl_down(hmax, off2, 64));
+    if ((tid & 63) == 0) s_scr[tid >> 6] = hmax;
+    __syncthreads();
+    double hmx = s_scr[0];
+    for (int w = 1; w < F2_WAVES; ++w) hmx = fmax(hmx, s_scr[w]);
+    double hb_cur = s_hlast, hb_try = 0.0;
+    F2_CLUSTER_SUM(29, hmx, hb_cur);
+    hpc = h_prev(hb_cur);
+    double last_err_chi = s_red[27];
+    const double initial_chi2 = last_err_chi;
+    if (tid < 27) s_Hc[tid] = s_red[tid];
+    __syncthreads();
+    {
+      // computeLambdaInit: max |H(j,j)| over pose and flow vertices
+      double mm = hmx;
+      for (int j = 0; j < 6; ++j) mm = fmax(mm, fabs(s_Hc[j * (j + 3) / 2]));
+      lambda = tau * mm; ni = 2; nBad = 0;
+    }
+    F2_TICK(4);
+    bool built = true;
+    bool ok = true;
+    for (; it < P.max_iterations && ok; ++it) {
+      // re-linearisation at the current estimate after a rejected trial that did not end the iteration loop (non-finite chi2)
+      if (!built) {
+        sweep_r(std::false_type{}, 0.0, true, Bc, hc, bc0, bc1, fc0, fc1, fc0, fc1);
+        { double d_ = 0; hb_cur = s_hlast; F2_CLUSTER_SUM(29, d_, hb_cur); }
+        hpc = h_prev(hb_cur);
+        last_err_chi = s_red[27];
+        if (tid < 27) s_Hc[tid] = s_red[tid];
+        __syncthreads();
+        built = true;
+      }
+      double currentChi = last_err_chi, tempChi = currentChi;
+      const double iniChi = currentChi;
+      double rho = 0;
+      int qmax = 0;
+      do {
+        // ---- (1) Schur sums for this lambda (with the F3 aliasing)
+        {
+          double acc[28];      // 27 Schur sums + [27] the landmark part of computeScale for the STALE x (what a failed solve leaves behind)
+#pragma unroll
+          for (int k = 0; k < 28; ++k) acc[k] = 0.0;
+          if (active) {
+            const double bl0 = bc0, bl1 = bc1;
+            acc[27] += xl0 * (lambda * xl0 + bl0) + xl1 * (lambda * xl1 + bl1);
+            if (Q) {
+              double d0, d1, d2;
+              dinv_q(hc, lambda, d0, d1, d2);
+              const double db0 = d0 * bl0 + d1 * bl1, db1 = d2 * bl1;      // (the aliased third row/column only ever meets exact zeros)
+              q0 = d0; q1 = d1; q2 = d2; qp2 = 0.0;
+              if (i > 0) { double p0_, p1_; dinv_q(hpc, lambda, p0_, p1_, qp2); }
+              int k = 0;
+#pragma unroll
+              for (int a = 0; a < 6; ++a) {
+                acc[21 + a] += Bc[2 * a] * db0 + Bc[2 * a + 1] * db1;
+                const double bd0 = Bc[2 * a] * d0;
+                const double bd1 = Bc[2 * a] * d1 + Bc[2 * a + 1] * d2;
+#pragma unroll
+                for (int c2 = 0; c2 <= a; ++c2) acc[k++] += bd0 * Bc[2 * c2] + bd1 * Bc[2 * c2 + 1];   // lower triangle (LDLT reads only it)
+              }
+            } else {
+              double Di[9];
+              dinv_of(hc, lambda, Di);
+              const double db0 = Di[0] * bl0 + Di[1] * bl1, db1 = Di[3] * bl0 + Di[4] * bl1;
+              int k = 0;
+#pragma unroll
+              for (int a = 0; a < 6; ++a) {
+                acc[21 + a] += Bc[2 * a] * db0 + Bc[2 * a + 1] * db1;
+                const double bd0 = Bc[2 * a] * Di[0] + Bc[2 * a + 1] * Di[3];
+                const double bd1 = Bc[2 * a] * Di[1] + Bc[2 * a + 1] * Di[4];
+#pragma unroll
+                for (int c2 = 0; c2 <= a; ++c2) acc[k++] += bd0 * Bc[2 * c2] + bd1 * Bc[2 * c2 + 1];
+              }
+            }
+          }
+          F2_TICK(12);
+          block_reduce_bfly<28>(acc, s_wpart, s_red);
+          F2_TICK(13);
+          { double d_ = 0, e_ = 0; F2_CLUSTER_SUM(28, d_, e_); }
+        }
+        F2_TICK(0);
+        solve_pose(lambda, qmax, currentChi);
+        const bool ok2 = s_ctrl[2] != 0;
+        if (s_ctrl[1]) {
+          rho = (currentChi - 1.7976931348623157e308) / ((s_rho + s_red[27]) + 1e-3);
+          lambda *= ni; ni *= 2; built = false;
+          ++qmax; ++total_trials;
+          continue;
+        }
+        // ---- (3) finish the solve per correspondence, errors + speculative linearisation at the trial point
+        sweep_r(std::true_type{}, lambda, ok2, Bt, ht, bt0, bt1, fc0, fc1, ft0, ft1);
+        { double d_ = 0; hb_try = s_hlast; F2_CLUSTER_SUM(29, d_, hb_try); }
+        hpt = h_prev(hb_try);
+        last_err_chi = tempChi = s_red[27];
+        const double scale = (s_rho + s_red[28]) + 1e-3;
+        F2_TICK(2);
+        if (!ok2) tempChi = 1.7976931348623157e308;
+        rho = (currentChi - tempChi) / scale;
+        if (rho > 0 && isfinite(tempChi)) {
+          double alpha = 1. - cube_rn(2 * rho - 1);
+          alpha = fmin(alpha, upper);
+          lambda *= fmax(lower, alpha); ni = 2; currentChi = tempChi; built = true;
+          fc0 = ft0; fc1 = ft1;                                                 // discardTop(): accept - the trial registers become the current ones
+#pragma unroll
+          for (int a = 0; a < 12; ++a) Bc[a] = Bt[a];
+          hc = ht; bc0 = bt0; bc1 = bt1; hpc = hpt; hb_cur = hb_try;
+          if (tid < 27) s_Hc[tid] = s_red[tid];
+          if (tid == 32) s_T = s_Ttry;
+        } else {
+          lambda *= ni; ni *= 2; built = false;                               // pop(): keep (s_T, fc) and their linearisation
+        }
+        __syncthreads();
+        F2_TICK(3);
+        ++qmax; ++total_trials;
+      } while (rho < 0 && qmax < 10);
+      int result;
+      if (qmax == 10 || rho == 0) result = 1;
+      else {
+        if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;
+        result = nBad >= 3 ? 1 : 0;
+      }
+      ok = (result == 0);
+      if (!ok) stop_reason = 1;
+      if (chi2_check < last_err_chi && it > 0) { ok = false; stop_reason = 2; }
+      chi2_check = last_err_chi;
+    }
+    // ---- classification on the errors of the last evaluated trial (Optimizer.cc:2470-2508)
+    double cnt[1] = {0.0};
+    const float gate = (float)P.chi2_gate;
+    if (active) {
+      const float chi2 = (float)(er0 * (P.info_flow * er0) + er1 * (P.info_flow * er1));
+      const bool outl = chi2 > gate;
+      inlier_out[i] = outl ? 0 : 1;
+      cnt[0] += outl ? 0.0 : 1.0;
+      flow_out[2 * i] = fc0;
+      flow_out[2 * i + 1] = fc1;
+    }
+    block_reduce<1>(cnt, s_scr, s_red);
+    { double d_ = 0, e_ = 0; F2_CLUSTER_SUM(1, d_, e_); }
+    if (tid == 0 && wg == 0) {
+      se3_to_matrix(s_T, res->T);
+      res->n_inliers = (int)(s_red[0] + 0.5);
+      res->iterations = it; res->trials = total_trials; res->stop_reason = stop_reason;
+      res->initial_chi2 = initial_chi2; res->final_chi2 = last_err_chi; res->final_lambda = lambda;
+#ifdef F2_PROFILE
+      for (int k = 0; k < 14; ++k) res->T[k] = (double)s_prof[k];     // cycles per phase instead of the pose (debug build only)
+#endif
+    }
+#ifdef F2_PROFILE
+    __syncthreads();
+    if (tid == 0 && wg < 2) res->T[14 + wg] = (double)(__builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 20) & 0xf) + 100.0 * blockIdx.x;
+#endif
+    return;
+  }
 
   // Sweep (3): TRIAL -> finish the solve for every correspondence (reads the current linearisation Br/hr/br and x_p),
   // then evaluate + linearise the edges at (T, f) into Bw/hw/bw.  Block sums -> s_red[0..26] (Hpp lower, bp), [27] robust chi2,
@@ -443,50 +770,7 @@ __global__ __launch_bounds__(F2_THREADS) void k_flow2_lm(const Flow2Dev* __restr
         { double d_ = 0, e_ = 0; F2_CLUSTER_SUM(28, d_, e_); }
       }
       F2_TICK(0);
-      // ---- (2) reduced 6x6 system, SE3 update, pose part of computeScale
-      // reduced system: lower triangle Hpp - (Schur sums) + lambda I, rhs bp - (Schur sums); one thread per entry
-      if (tid < 36) {
-        const int a = tid / 6, c2 = tid - 6 * a;
-        if (c2 <= a) {
-          const int k = a * (a + 1) / 2 + c2;
-          double v = s_Hc[k] - s_red[k];
-          if (c2 == a) v += lambda;
-          s_Hs[tid] = v;
-        } else {
-          s_Hs[tid] = s_Hc[c2 * (c2 + 1) / 2 + a];
-        }
-      } else if (tid < 42) {
-        const int j = tid - 36;
-        s_bs[j] = s_Hc[21 + j] - s_red[21 + j];
-      }
-      __syncthreads();
-      F2_TICK(5);
-      bool ok2w = false;
-      if (tid < 64) ok2w = ldlt6_solve_lanes(s_Hs, s_bs, s_xs);      // wave 0: one row of the 6x6 system per lane
-      if (tid == 0) {
-        const bool ok2 = ok2w;
-        F2_TICK(6);
-        s_ctrl[2] = ok2 ? 1 : 0;
-        if (ok2) {
-#pragma unroll
-          for (int j = 0; j < 6; ++j) s_xp[j] = s_xs[j];
-        }
-        // (failed LDLT leaves x untouched in the reference; the trial is rejected anyway)
-        double s = 0;
-        for (int j = 0; j < 6; ++j) s += s_xp[j] * (lambda * s_xp[j] + s_Hc[21 + j]);
-        s_rho = s;    // pose part of computeScale
-        // A failed solve rejects the trial whatever its errors are (tempChi = DBL_MAX) as long as computeScale - known here: the
-        // stale x against the current gradient - is positive, and everything the evaluation would leave behind (errors, chi2,
-        // the trial linearisation) is overwritten by the trial that follows: skip the SE3 update and the sweep.  Not for the
-        // last trial of an iteration (its errors are the ones classified).
-        bool skip = false;
-        if (!ok2 && qmax + 1 < 10) skip = (currentChi - 1.7976931348623157e308) / ((s + s_red[27]) + 1e-3) < 0;
-        s_ctrl[1] = skip ? 1 : 0;
-        if (!skip) s_Ttry = se3_exp_compose(s_xp, s_T);
-        F2_TICK(7);
-      }
-      __syncthreads();
-      F2_TICK(1);
+      solve_pose(lambda, qmax, currentChi);
       const bool ok2 = s_ctrl[2] != 0;
       if (s_ctrl[1]) {
         rho = (currentChi - 1.7976931348623157e308) / ((s_rho + s_red[27]) + 1e-3);
@@ -742,6 +1026,8 @@ extern "C" int vdo_flow2_batch_run(vdo_flow2_batch* b) {
     }
     b->A.max_cluster = mc;
   }
+  // A/B switch of the register path (read on every call, like the budget above): 1 = every problem on the general path
+  { const char* e = std::getenv("VDO_LM_GENERAL"); b->A.force_general = (e && std::atoi(e) != 0) ? 1 : 0; }
   hipLaunchKernelGGL(k_flow2_lm, dim3(((b->n_problems + 7) / 8) * 8 * F2_CLUSTER), dim3(F2_THREADS), 0, b->ctx->stream, b->d_probs_run ? b->d_probs_run : (const Flow2Dev*)b->d_probs, b->A);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_error(VDO_ERR_NO_DEVICE, "k_flow2_lm launch: %s", hipGetErrorString(e));
