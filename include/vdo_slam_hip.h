@@ -476,6 +476,8 @@ int vdo_frame_images_download_mask(vdo_frame_images* f, int32_t* mask_out);
 /* The resident depth image after K1 (metres): GrabImageRGBD converts the caller's imD in place (src/Tracking.cc:180-204); a host
  * caller that uploaded the raw map gets the converted one back with this. */
 int vdo_frame_images_download_depth(vdo_frame_images* f, float* depth_out);
+/* The resident flow image, [h][w][2] floats. */
+int vdo_frame_images_download_flow(vdo_frame_images* f, float* flow_out);
 
 /* ---- Tracking bookkeeping around the gathers ------------------------------------ */
 

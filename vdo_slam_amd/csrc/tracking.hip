@@ -202,6 +202,18 @@ extern "C" int vdo_frame_images_download_depth(vdo_frame_images* f, float* depth
   return VDO_OK;
 }
 
+// the resident flow image ([h][w][2], as uploaded / ingested)
+extern "C" int vdo_frame_images_download_flow(vdo_frame_images* f, float* flow_out) {
+  if (!f || !flow_out) return set_error(VDO_ERR_INVALID, "bad argument");
+  int rc = ctx_bind(f->ctx);
+  if (rc != VDO_OK) return rc;
+  hipMemcpyAsync(flow_out, f->d_flow, 8 * (size_t)f->w * f->h, hipMemcpyDeviceToHost, f->ctx->stream);
+  hipError_t e = hipStreamSynchronize(f->ctx->stream);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e != hipSuccess) return set_error(VDO_ERR_NO_DEVICE, "vdo_frame_images_download_flow: %s", hipGetErrorString(e));
+  return VDO_OK;
+}
+
 extern "C" int vdo_get3d_world(vdo_ctx* ctx, int n, const float* kx, const float* ky, const float* depth, const float K4[4], const float Twc[16], float* xyz_out) {
   if (!ctx || n < 0) return set_error(VDO_ERR_INVALID, "bad argument");
   if (n == 0) return VDO_OK;

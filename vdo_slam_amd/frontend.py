@@ -49,6 +49,7 @@ def _lib():
         L.vdo_frame_images_upload.argtypes = [vp, K.c_float_p, K.c_float_p, K.c_int32_p]
         L.vdo_frame_images_destroy.argtypes = [vp]
         L.vdo_frame_static_filter.argtypes = [vp, C.c_int, K.c_float_p, K.c_float_p, C.c_float, K.c_int32_p] + [K.c_float_p] * 5 + [ip]
+        L.vdo_frame_static_filter_sampled.argtypes = L.vdo_frame_static_filter.argtypes
         L.vdo_frame_object_sample.argtypes = [vp, C.c_float, C.c_int, C.c_int] + [K.c_float_p] * 7 + [K.c_int32_p, ip]
         _declared = True
     return L
@@ -194,13 +195,34 @@ class FrameImages:
         L.vdo_frame_images_upload_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         K.check(L.vdo_frame_images_upload_device(self._h, C.c_void_p(depth_ptr), C.c_void_p(flow_ptr), C.c_void_p(mask_ptr)))
 
+    def ingest_device(self, depth_ptr: int, flow_ptr: int, mask_ptr: int, bf: float, factor: float, convert: bool):
+        """``upload_device`` + K1 on the way (``convert``): one launch for 16-byte aligned sources, else the copies + K1.
+        Stream-ordered on the library's stream: synchronise the producer of the sources first."""
+        L = _lib()
+        L.vdo_frame_images_ingest_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int]
+        K.check(L.vdo_frame_images_ingest_device(self._h, C.c_void_p(depth_ptr), C.c_void_p(flow_ptr), C.c_void_p(mask_ptr), bf, factor, int(bool(convert))))
+
+    def download_depth(self) -> np.ndarray:
+        out = np.zeros((self.h, self.w), np.float32)
+        L = _lib()
+        L.vdo_frame_images_download_depth.argtypes = [C.c_void_p, K.c_float_p]
+        K.check(L.vdo_frame_images_download_depth(self._h, _fp(out)))
+        return out
+
+    def download_flow(self) -> np.ndarray:
+        out = np.zeros((self.h, self.w, 2), np.float32)
+        L = _lib()
+        L.vdo_frame_images_download_flow.argtypes = [C.c_void_p, K.c_float_p]
+        K.check(L.vdo_frame_images_download_flow(self._h, _fp(out)))
+        return out
+
     def depth_preprocess(self, bf, factor):
         L = _lib()
         L.vdo_frame_images_depth_preprocess.argtypes = [C.c_void_p, C.c_float, C.c_float]
         K.check(L.vdo_frame_images_depth_preprocess(self._h, bf, factor))
 
-    def static_filter(self, kx, ky, th_depth):
-        """Outputs are views of buffers owned by this object: valid until the next call."""
+    def static_filter(self, kx, ky, th_depth, sampled=False):
+        """Outputs are views of buffers owned by this object: valid until the next call.  ``sampled``: the UseSampleFeature branch."""
         kx = np.ascontiguousarray(kx, dtype=np.float32); ky = np.ascontiguousarray(ky, dtype=np.float32)
         n = kx.size
         st = getattr(self, "_sf", None)
@@ -210,17 +232,20 @@ class FrameImages:
             m = C.c_int()
             st = self._sf = (cap, idx, f, m, [_ip(idx)] + [_fp(a) for a in f] + [C.byref(m)], _lib().vdo_frame_static_filter)
         _, idx, f, m, args, fn = st
+        if sampled:
+            fn = _lib().vdo_frame_static_filter_sampled
         K.check(fn(self._h, n, _fp(kx), _fp(ky), th_depth, *args))
         m = m.value
         return dict(keep_idx=idx[:m], corr_x=f[0][:m], corr_y=f[1][:m], flow_x=f[2][:m], flow_y=f[3][:m], depth=f[4][:m])
 
-    def object_sample(self, th_depth_obj, step=4):
-        """Outputs are views of buffers owned by this object: valid until the next call."""
-        cap = ((self.w + step - 1) // step) * ((self.h + step - 1) // step)
+    def object_sample(self, th_depth_obj, step=4, cap=None):
+        """Outputs are views of buffers owned by this object: valid until the next call.  ``cap``: output capacity (default: every probe)."""
+        if cap is None:
+            cap = ((self.w + step - 1) // step) * ((self.h + step - 1) // step)
         st = getattr(self, "_os", None)
         if st is None or st[0] != cap:
-            f = [np.zeros(cap, np.float32) for _ in range(7)]
-            lab = np.zeros(cap, np.int32)
+            f = [np.zeros(max(cap, 1), np.float32) for _ in range(7)]
+            lab = np.zeros(max(cap, 1), np.int32)
             m = C.c_int()
             st = self._os = (cap, f, lab, m, [_fp(a) for a in f] + [_ip(lab), C.byref(m)], _lib().vdo_frame_object_sample)
         _, f, lab, m, args, fn = st
