@@ -10,21 +10,21 @@
 // These problems are tiny (<=~1.2k correspondences, 6 unknowns after Schur) and latency-bound
 // (SURVEY.md H4), so the WHOLE LM loop runs inside ONE persistent workgroup per problem —
 // one launch for the camera problem, one launch for all objects of a frame (grid = #objects).
-// A thread that owns one correspondence (every problem of the pipeline) keeps its per-landmark data
-// in registers for the whole loop; otherwise correspondences are strided over the 256 threads and
-// the data stays in L2-resident scratch.  Pose-side sums use a register butterfly + one LDS stage,
+// The loop body is written once over a per-correspondence store: a thread that owns one correspondence
+// (every problem of the pipeline) keeps its per-landmark data in registers for the whole loop (F2RegStore);
+// otherwise correspondences are strided over the 256 threads and the data stays in L2-resident scratch
+// (F2MemStore).  Pose-side sums use a register butterfly + one LDS stage,
 // the 6x6 pivoted LDLT runs on wave 0 and the SE(3) update on lane 0.  ref_quirks=1 reproduces the BlockSolver_6_3 / 2-DoF aliasing (F3)
 // exactly as analysed in oracle/flow_oracle.cpp (product code does not use the oracle).
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <type_traits>
 #include <vector>
 
 #include "../../include/vdo_slam_hip.h"
 #include "ctx.hpp"
-#include <cstdlib>
-
 #include "lm_dev.hpp"
 
 namespace vdo {
@@ -88,6 +88,96 @@ __device__ __forceinline__ f2_u32x4 f2_slot_load(const Flow2Slot* p) {
 // what the Schur sums of a trial leave in registers for the solve sweep of the same trial (first correspondence of a thread)
 struct F2Pre { double B[12], b0, b1, d0, d1, d2, p2; int i; };
 
+// one correspondence's linearisation: B = its 6x2 pose-flow block ([2a], [2a+1] = row a), h = Hll diagonal, (b0, b1) = b_l
+struct F2Lin { double B[12], h, b0, b1; };
+
+// Where the per-correspondence state of the Levenberg loop lives.  k_flow2_lm's loop body is written once against this interface:
+//   for_each(f)                 f(i) for every correspondence i of this thread
+//   set_point / point           the setup results (key point, measured flow, Xw); set_point also starts the flow at the measured one, x_l at 0
+//   flow_cur / set_flow_try     current flow (read), trial flow (written);  get_xl / set_xl, get_err / set_err: last x_l, last edge errors
+//   lin_cur / set_lin<TRIAL>    current linearisation (read), current or trial linearisation (written, before the block reduction's barrier)
+//   h_prev(i, hb)               Hll diagonal of landmark i - 1 in the current linearisation (hb: the previous chunk's last, from the exchange)
+//   after_exchange<TRIAL>(hb)   after the sweep's exchange;  accept(): the trial flow and linearisation become the current ones
+// F2RegStore: thread tid owns correspondence i = c_lo + tid (idle for the whole loop if i >= c_hi) and keeps everything in registers.
+// Current and trial are separate members picked at compile time, accept is a copy (a runtime index would send them to scratch);
+// s_h (LDS) passes the Hll diagonals of the linearisation just made to the right neighbour (F3 aliasing).
+struct F2RegStore {
+  static constexpr bool kReg = true;
+  const int i, tid;
+  const bool active;
+  double* const s_h;
+  double o0 = 0, o1 = 0, m0 = 0, m1 = 0, xw[3] = {0, 0, 0};
+  double fc0 = 0, fc1 = 0, ft0 = 0, ft1 = 0, xl0 = 0, xl1 = 0, er0 = 0, er1 = 0;
+  F2Lin cur{}, trial{};
+  double hpc = 0, hpt = 0;                // Hll diagonal of landmark i - 1 in the current / trial linearisation
+  template <class F> __device__ __forceinline__ void for_each(F&& f) { if (active) f(i); }
+  __device__ __forceinline__ void set_point(int, double a0, double a1, double b0, double b1, const double (&x)[3]) {
+    o0 = a0; o1 = a1; m0 = b0; m1 = b1; xw[0] = x[0]; xw[1] = x[1]; xw[2] = x[2]; fc0 = b0; fc1 = b1; xl0 = 0; xl1 = 0;
+  }
+  __device__ __forceinline__ void point(int, double& a0, double& a1, double& b0, double& b1, double (&x)[3]) const {
+    a0 = o0; a1 = o1; b0 = m0; b1 = m1; x[0] = xw[0]; x[1] = xw[1]; x[2] = xw[2];
+  }
+  __device__ __forceinline__ void flow_cur(int, double& f0, double& f1) const { f0 = fc0; f1 = fc1; }
+  __device__ __forceinline__ void set_flow_try(int, double f0, double f1) { ft0 = f0; ft1 = f1; }
+  __device__ __forceinline__ void get_xl(int, double& x0, double& x1) const { x0 = xl0; x1 = xl1; }
+  __device__ __forceinline__ void set_xl(int, double x0, double x1) { xl0 = x0; xl1 = x1; }
+  __device__ __forceinline__ void get_err(int, double& e0, double& e1) const { e0 = er0; e1 = er1; }
+  __device__ __forceinline__ void set_err(int, double e0, double e1) { er0 = e0; er1 = e1; }
+  __device__ __forceinline__ void lin_cur(int, F2Lin& L) const { L = cur; }
+  template <bool TRIAL> __device__ __forceinline__ void set_lin(int, const F2Lin& L) {
+    if constexpr (TRIAL) trial = L; else cur = L;
+    s_h[tid] = L.h;
+  }
+  __device__ __forceinline__ double h_prev(int, double) const { return hpc; }
+  template <bool TRIAL> __device__ __forceinline__ void after_exchange(double hb) {      // the left neighbour's, or - first thread - the previous chunk's last
+    const double h = tid > 0 ? s_h[tid - 1] : hb;
+    if constexpr (TRIAL) hpt = h; else hpc = h;
+  }
+  __device__ __forceinline__ void accept() { fc0 = ft0; fc1 = ft1; cur = trial; hpc = hpt; }
+};
+
+// F2MemStore: correspondences first, first + F2_THREADS, ... < c_hi of a problem of N, in the SoA planes of the batch's L2-resident
+// scratch arrays; current and trial are pointer pairs, accept swaps them (workgroup-uniform).
+struct F2MemStore {
+  static constexpr bool kReg = false;
+  const int N, first, c_lo, c_hi;
+  double *obs, *meas, *Xw, *fcur, *ftry, *err, *xl;
+  double *Bc, *Bt, *hc, *ht, *bc, *bt;      // current / trial linearisation
+  template <class F> __device__ __forceinline__ void for_each(F&& f) { for (int i = first; i < c_hi; i += F2_THREADS) f(i); }
+  __device__ __forceinline__ void set_point(int i, double o0, double o1, double m0, double m1, const double (&x)[3]) {
+    obs[i] = o0; obs[N + i] = o1; meas[i] = m0; meas[N + i] = m1;
+    Xw[i] = x[0]; Xw[N + i] = x[1]; Xw[2 * N + i] = x[2];
+    fcur[i] = m0; fcur[N + i] = m1;
+    xl[i] = 0.0; xl[N + i] = 0.0;
+  }
+  __device__ __forceinline__ void point(int i, double& o0, double& o1, double& m0, double& m1, double (&x)[3]) const {
+    o0 = obs[i]; o1 = obs[N + i]; m0 = meas[i]; m1 = meas[N + i]; x[0] = Xw[i]; x[1] = Xw[N + i]; x[2] = Xw[2 * N + i];
+  }
+  __device__ __forceinline__ void flow_cur(int i, double& f0, double& f1) const { f0 = fcur[i]; f1 = fcur[N + i]; }
+  __device__ __forceinline__ void set_flow_try(int i, double f0, double f1) { ftry[i] = f0; ftry[N + i] = f1; }
+  __device__ __forceinline__ void get_xl(int i, double& x0, double& x1) const { x0 = xl[i]; x1 = xl[N + i]; }
+  __device__ __forceinline__ void set_xl(int i, double x0, double x1) { xl[i] = x0; xl[N + i] = x1; }
+  __device__ __forceinline__ void get_err(int i, double& e0, double& e1) const { e0 = err[i]; e1 = err[N + i]; }
+  __device__ __forceinline__ void set_err(int i, double e0, double e1) { err[i] = e0; err[N + i] = e1; }
+  __device__ __forceinline__ void lin_cur(int i, F2Lin& L) const {
+#pragma unroll
+    for (int a = 0; a < 12; ++a) L.B[a] = Bc[a * N + i];
+    L.h = hc[i]; L.b0 = bc[i]; L.b1 = bc[N + i];
+  }
+  template <bool TRIAL> __device__ __forceinline__ void set_lin(int i, const F2Lin& L) {
+    double* const B = TRIAL ? Bt : Bc; double* const h = TRIAL ? ht : hc; double* const b = TRIAL ? bt : bc;
+#pragma unroll
+    for (int a = 0; a < 12; ++a) B[a * N + i] = L.B[a];
+    h[i] = L.h; b[i] = L.b0; b[N + i] = L.b1;
+  }
+  __device__ __forceinline__ double h_prev(int i, double hb) const { return i > c_lo ? hc[i - 1] : hb; }      // (the previous chunk's last landmark belongs to another workgroup)
+  template <bool TRIAL> __device__ __forceinline__ void after_exchange(double) {}
+  __device__ __forceinline__ void accept() {
+    double* t_ = fcur; fcur = ftry; ftry = t_;
+    t_ = Bc; Bc = Bt; Bt = t_; t_ = hc; hc = ht; ht = t_; t_ = bc; bc = bt; bt = t_;
+  }
+};
+
 #ifdef F2_PROFILE
 #define F2_TICK(slot) do { if (tid == 0) { const long long t_ = clock64(); s_prof[slot] += t_ - s_tprev; s_tprev = t_; } } while (0)
 #else
@@ -117,14 +207,10 @@ __global__ __launch_bounds__(F2_THREADS) void k_flow2_lm(const Flow2Dev* __restr
   if (wg >= Gp) return;
   __builtin_amdgcn_s_setprio(3);        // latency-bound persistent workgroups: issue ahead of the throughput kernels sharing the CU
   const int chunk = (N + Gp - 1) / Gp, c_lo = wg * chunk, c_hi = min(N, c_lo + chunk);   // this workgroup's correspondences [c_lo, c_hi): nothing but
-  const int first = c_lo + tid, stride = F2_THREADS;                                      // the block sums (and one Hll entry) crosses workgroups
+  const int first = c_lo + tid;                                                           // the block sums (and one Hll entry) crosses workgroups
   Flow2Comm* comm = A.comm + prob;
   const int64_t off = P.off;
   const double* __restrict__ in_obs = A.in + 5 * off; const double* __restrict__ in_meas = in_obs + 2 * (size_t)N; const double* __restrict__ depth = in_obs + 4 * (size_t)N;
-  double* __restrict__ obs = A.om + 4 * off; double* __restrict__ meas = obs + 2 * (size_t)N;
-  double* __restrict__ Xw = A.Xw + 3 * off; double* fcur = A.f0 + 2 * off; double* ftry = A.f1 + 2 * off;
-  double* __restrict__ err = A.err + 2 * off; double* __restrict__ xl = A.xl + 2 * off;
-  double *Bc = A.B2a + 12 * off, *Bt = A.B2b + 12 * off, *hc = A.hla + off, *ht = A.hlb + off, *bc = A.bla + 2 * off, *bt = A.blb + 2 * off;   // current / trial linearisation
   vdo_flow2_result* res = (vdo_flow2_result*)A.out + prob;
   double* __restrict__ flow_out = (double*)(A.out + sizeof(vdo_flow2_result) * (size_t)A.n_problems) + 2 * P.out_off;
   unsigned char* __restrict__ inlier_out = (unsigned char*)((double*)(A.out + sizeof(vdo_flow2_result) * (size_t)A.n_problems) + 2 * P.out_total) + P.out_off;
@@ -150,24 +236,7 @@ __global__ __launch_bounds__(F2_THREADS) void k_flow2_lm(const Flow2Dev* __restr
   }
   const double fx = P.K[0], fy = P.K[1], cx = P.K[2], cy = P.K[3];
   const bool Q = P.ref_quirks != 0;
-  // One correspondence per thread (every problem the pipeline builds: N <= 2048 on a full cluster): the per-correspondence state of
-  // the whole Levenberg loop stays in the registers of the thread that owns it - the REGISTER path below; everything else
-  // (N > 2048, a lowered cluster, VDO_LM_GENERAL=1) takes the general path over the scratch arrays.  Workgroup-uniform, chosen
-  // per problem; both paths evaluate the same expressions on the same values in the same order: same bits.
-  const bool REG = chunk <= F2_THREADS && !A.force_general;
-  // ---- setup: Xw, flows, initial pose (Converter::toSE3Quat)
-  if (!REG) for (int i = first; i < c_hi; i += stride) {
-    const double dz = depth[i];
-    const double o0 = in_obs[i], o1 = in_obs[N + i], m0 = in_meas[i], m1 = in_meas[N + i];
-    obs[i] = o0; obs[N + i] = o1; meas[i] = m0; meas[N + i] = m1;
-    const double x = (o0 - cx) * dz / fx, y = (o1 - cy) * dz / fy;
-    const double* W = P.Twl;
-    Xw[i] = W[0] * x + W[1] * y + W[2] * dz + W[3];
-    Xw[N + i] = W[4] * x + W[5] * y + W[6] * dz + W[7];
-    Xw[2 * N + i] = W[8] * x + W[9] * y + W[10] * dz + W[11];
-    fcur[i] = m0; fcur[N + i] = m1;
-    xl[i] = 0.0; xl[N + i] = 0.0;
-  }
+  // ---- setup: initial pose (Converter::toSE3Quat)
   if (tid < 6) s_xp[tid] = 0.0;
   if (tid == 0) {
     const double R[9] = {P.T0[0], P.T0[1], P.T0[2], P.T0[4], P.T0[5], P.T0[6], P.T0[8], P.T0[9], P.T0[10]};
@@ -246,7 +315,7 @@ __global__ __launch_bounds__(F2_THREADS) void k_flow2_lm(const Flow2Dev* __restr
     Di[0] = a3 * id; Di[1] = -a1 * id; Di[2] = 0; Di[3] = -a2 * id; Di[4] = a0 * id; Di[5] = 0; Di[6] = 0; Di[7] = 0; Di[8] = 0;
   };
 
-  // ---- (2) of a trial, shared by both paths: reduced 6x6 system, SE3 update, pose part of computeScale.  Leaves x_p in s_xp, the
+  // ---- (2) of a trial: reduced 6x6 system, SE3 update, pose part of computeScale.  Leaves x_p in s_xp, the
   // trial pose in s_Ttry, s_rho, and s_ctrl[1] (trial skipped) / s_ctrl[2] (ok2) - valid for every thread on return.
   auto solve_pose = [&](const double lambda, const int qmax, const double currentChi) __attribute__((always_inline)) {
     // reduced system: lower triangle Hpp - (Schur sums) + lambda I, rhs bp - (Schur sums); one thread per entry
@@ -294,34 +363,25 @@ __global__ __launch_bounds__(F2_THREADS) void k_flow2_lm(const Flow2Dev* __restr
     F2_TICK(1);
   };
 
-  if (REG) {
-    // ================= register path: thread tid owns correspondence i = c_lo + tid (idle for the whole loop if i >= c_hi)
-    const int i = first;
-    const bool active = i < c_hi;
-    __shared__ double s_h[F2_THREADS];      // Hll diagonals of the linearisation just made: the F3 aliasing needs the left neighbour's
-    double o0 = 0, o1 = 0, m0 = 0, m1 = 0, xw[3] = {0, 0, 0};
-    double fc0 = 0, fc1 = 0, ft0 = 0, ft1 = 0, xl0 = 0, xl1 = 0, er0 = 0, er1 = 0;
-    double Bc[12], Bt[12], hc = 0, ht = 0, bc0 = 0, bc1 = 0, bt0 = 0, bt1 = 0;      // current / trial linearisation
-    double hpc = 0, hpt = 0;                // Hll diagonal of landmark i - 1 in the current / trial linearisation
-#pragma unroll
-    for (int a = 0; a < 12; ++a) { Bc[a] = 0; Bt[a] = 0; }
-    if (active) {
+  // ---- the Levenberg loop, written once: S (F2RegStore / F2MemStore above) is where a correspondence's values live.  Both stores
+  // see the same expressions on the same values in the same order - same bits - and the same barriers and exchanges.
+  auto lm_body = [&](auto& S) __attribute__((always_inline)) {
+    constexpr bool kReg = std::remove_reference_t<decltype(S)>::kReg;
+    // ---- setup: Xw, flows (only the owning thread reads these values before the next barrier)
+    S.for_each([&](const int i) {
       const double dz = depth[i];
-      o0 = in_obs[i]; o1 = in_obs[N + i]; m0 = in_meas[i]; m1 = in_meas[N + i];
+      const double o0 = in_obs[i], o1 = in_obs[N + i], m0 = in_meas[i], m1 = in_meas[N + i];
       const double x = (o0 - cx) * dz / fx, y = (o1 - cy) * dz / fy;
       const double* W = P.Twl;
-      xw[0] = W[0] * x + W[1] * y + W[2] * dz + W[3];
-      xw[1] = W[4] * x + W[5] * y + W[6] * dz + W[7];
-      xw[2] = W[8] * x + W[9] * y + W[10] * dz + W[11];
-      fc0 = m0; fc1 = m1;
-    }
-    // what the Schur sums of a trial leave for the back-substitution of the same trial (same lambda, same divisions)
-    double q0 = 0, q1 = 0, q2 = 0, qp2 = 0;
+      const double xw[3] = {W[0] * x + W[1] * y + W[2] * dz + W[3], W[4] * x + W[5] * y + W[6] * dz + W[7], W[8] * x + W[9] * y + W[10] * dz + W[11]};
+      S.set_point(i, o0, o1, m0, m1, xw);
+    });
 
-    // Sweep (3) over registers: TRIAL -> back-substitution against the current linearisation, flow update into (fo0, fo1); then
-    // errors + linearisation at (T, f) into (Bw, hw, bw0, bw1).  Sums and return value as in the general sweep below.
-    auto sweep_r = [&](auto trial_c, const double lam, const bool ok2, double (&Bw)[12], double& hw, double& bw0, double& bw1,
-                       const double fin0, const double fin1, double& fo0, double& fo1) -> double {
+    // Sweep (3): TRIAL -> finish the solve for every correspondence (reads the current linearisation and x_p; the thread's first
+    // correspondence takes what the Schur sums of this trial left in pre), flow update into the trial flow; then evaluate +
+    // linearise the edges at (T, f) into the current (!TRIAL) or the trial linearisation.  Block sums -> s_red[0..26] (Hpp lower,
+    // bp), [27] robust chi2, [28] landmark part of computeScale; returns the per-thread max of the Hll diagonal (computeLambdaInit).
+    auto sweep = [&](auto trial_c, const double lam, const bool ok2, const double hb_prev, const F2Pre& pre) -> double {
       constexpr bool TRIAL = decltype(trial_c)::value;
       const SE3d T = TRIAL ? s_Ttry : s_T;
       double xp[6];
@@ -331,42 +391,60 @@ __global__ __launch_bounds__(F2_THREADS) void k_flow2_lm(const Flow2Dev* __restr
 #pragma unroll
       for (int k = 0; k < 29; ++k) acc[k] = 0.0;
       double hmax = 0.0;
-      if (active) {
+      S.for_each([&](const int i) {
         double f0v, f1v;
+        S.flow_cur(i, f0v, f1v);
         if (TRIAL) {
-          const double b0 = bc0, b1 = bc1;
+          // back-substitution c = b_l - B^T x_p for this landmark (hp: D^-1 - memory store: and B, b_l - are still in registers
+          // from the Schur sums of this trial - same loads, same lambda, same divisions)
+          const bool hp = kReg || (Q && i == pre.i);
+          F2Lin L;
+          if (!kReg && hp) {
+#pragma unroll
+            for (int a = 0; a < 12; ++a) L.B[a] = pre.B[a];
+            L.b0 = pre.b0; L.b1 = pre.b1;
+          } else {
+            S.lin_cur(i, L);
+          }
+          const double b0 = L.b0, b1 = L.b1;
           double t0 = 0, t1 = 0;
 #pragma unroll
-          for (int a = 0; a < 6; ++a) { t0 += Bc[2 * a] * (-xp[a]); t1 += Bc[2 * a + 1] * (-xp[a]); }
+          for (int a = 0; a < 6; ++a) { t0 += L.B[2 * a] * (-xp[a]); t1 += L.B[2 * a + 1] * (-xp[a]); }
           const double c0 = b0 + t0, c1 = b1 + t1;
           double x0, x1;
           if (Q) {
-            x0 = q0 * c0 + q1 * c1;
-            x1 = q2 * c1;
-            if (i > 0) x0 = qp2 * c0 + x0;
+            // x[2i..2i+2] = D_i^-1 c_i with the aliased 3x3 block (dinv_q): rows 0/1 give this landmark's flow update, row 2 of
+            // landmark i-1 (= its d2 * c0 of THIS landmark: the aliased third component) was written into slot 2i first
+            double d0, d1, d2, p2_ = 0;
+            if (hp) { d0 = pre.d0; d1 = pre.d1; d2 = pre.d2; p2_ = pre.p2; }
+            else if constexpr (!kReg) {
+              dinv_q(L.h, lam, d0, d1, d2);
+              if (i > 0) { double p0_, p1_; dinv_q(S.h_prev(i, hb_prev), lam, p0_, p1_, p2_); }
+            }
+            x0 = d0 * c0 + d1 * c1;
+            x1 = d2 * c1;
+            if (i > 0) x0 = p2_ * c0 + x0;
           } else {
             double Di[9];
-            dinv_of(hc, lam, Di);
+            dinv_of(L.h, lam, Di);
             x0 = (Di[0] * c0 + Di[1] * c1) + Di[2] * 0.0;
             x1 = (Di[3] * c0 + Di[4] * c1) + Di[5] * 0.0;
           }
           F2_TICK(8);
-          if (!ok2) x0 = xl0;           // failed LDLT: stale x (the reference keeps the previous content); the trial is rejected anyway
-          const double x1e = ok2 ? x1 : xl1;
-          xl0 = x0; xl1 = x1e;
-          f0v = fin0 + x0; f1v = fin1 + x1e;
-          fo0 = f0v; fo1 = f1v;
-          acc[28] += x0 * (lam * x0 + b0) + x1e * (lam * x1e + b1);
-        } else {
-          f0v = fin0; f1v = fin1;
+          if (!ok2) S.get_xl(i, x0, x1);      // failed LDLT: stale x (the reference keeps the previous content); the trial is rejected anyway
+          S.set_xl(i, x0, x1);
+          f0v = f0v + x0; f1v = f1v + x1;
+          S.set_flow_try(i, f0v, f1v);
+          acc[28] += x0 * (lam * x0 + b0) + x1 * (lam * x1 + b1);
         }
         // computeActiveErrors at (T, f)
-        double pc[3];
+        double o0, o1, m0, m1, xw[3], pc[3];
+        S.point(i, o0, o1, m0, m1, xw);
         q_rotate(T.r, xw, pc);
         const double X = pc[0] + T.t[0], Y = pc[1] + T.t[1], Z = pc[2] + T.t[2], Z2 = Z * Z;
         const double u = X / Z * fx + cx, v = Y / Z * fy + cy;
         const double e0 = (o0 + f0v) - u, e1 = (o1 + f1v) - v;
-        er0 = e0; er1 = e1;
+        S.set_err(i, e0, e1);
         if (TRIAL) F2_TICK(9);
         const double c = e0 * (P.info_flow * e0) + e1 * (P.info_flow * e1);
         double r0, r1;
@@ -379,8 +457,9 @@ __global__ __launch_bounds__(F2_THREADS) void k_flow2_lm(const Flow2Dev* __restr
         J[6] = (1 + Y * Y / Z2) * fy; J[7] = -X * Y / Z2 * fy; J[8] = -X / Z * fy; J[9] = 0; J[10] = -1. / Z * fy; J[11] = Y / Z2 * fy;
         const double wo = r1 * P.info_flow;
         const double or0 = -(P.info_flow * e0) * r1, or1 = -(P.info_flow * e1) * r1;
+        F2Lin Lw;
 #pragma unroll
-        for (int a = 0; a < 6; ++a) { Bw[2 * a] = J[a] * wo; Bw[2 * a + 1] = J[6 + a] * wo; }
+        for (int a = 0; a < 6; ++a) { Lw.B[2 * a] = J[a] * wo; Lw.B[2 * a + 1] = J[6 + a] * wo; }
         int k = 0;
 #pragma unroll
         for (int a = 0; a < 6; ++a) {
@@ -389,36 +468,34 @@ __global__ __launch_bounds__(F2_THREADS) void k_flow2_lm(const Flow2Dev* __restr
           for (int c2 = 0; c2 <= a; ++c2) acc[k++] += J[a] * wo * J[c2] + J[6 + a] * wo * J[6 + c2];   // lower triangle
         }
         const double h = wo + P.info_prior;
-        hw = h;                   // Hll block = h * I2 (off-diagonals are exact zeros)
-        bw0 = or0 - P.info_prior * p0;
-        bw1 = or1 - P.info_prior * p1;
+        Lw.h = h;                 // Hll block = h * I2 (off-diagonals are exact zeros)
+        Lw.b0 = or0 - P.info_prior * p0;
+        Lw.b1 = or1 - P.info_prior * p1;
+        S.template set_lin<TRIAL>(i, Lw);
         hmax = fmax(hmax, h);
-        s_h[tid] = h;
         if (i == c_hi - 1) s_hlast = h;
         if (TRIAL) F2_TICK(10);
-      }
+      });
       block_reduce_bfly<29>(acc, s_wpart, s_red);
       if (TRIAL) F2_TICK(11);
       return hmax;
     };
-    // h of landmark i - 1 after a sweep and its exchange: the left neighbour's, or - first thread - the previous chunk's last
-    auto h_prev = [&](const double hb) -> double { return tid > 0 ? s_h[tid - 1] : hb; };
 
     double lambda = -1, ni = 2;
     int nBad = 0, it = 0, total_trials = 0, stop_reason = 0;
     const double tau = 1e-5, upper = 2. / 3., lower = 1. / 3.;
     double chi2_check = 0;
     // initial computeActiveErrors + buildSystem
-    double hmax = sweep_r(std::false_type{}, 0.0, true, Bc, hc, bc0, bc1, fc0, fc1, fc0, fc1);
+    double hmax = sweep(std::false_type{}, 0.0, true, 0.0, F2Pre{});
 #pragma unroll
     for (int off2 = 32; off2 > 0; off2 >>= 1) hmax = fmax(hmax, __shfl_down(hmax, off2, 64));
     if ((tid & 63) == 0) s_scr[tid >> 6] = hmax;
     __syncthreads();
     double hmx = s_scr[0];
     for (int w = 1; w < F2_WAVES; ++w) hmx = fmax(hmx, s_scr[w]);
-    double hb_cur = s_hlast, hb_try = 0.0;
+    double hb_cur = s_hlast, hb_try = 0.0;     // -> Hll diagonal of the landmark just before this chunk (current / trial linearisation)
     F2_CLUSTER_SUM(29, hmx, hb_cur);
-    hpc = h_prev(hb_cur);
+    S.template after_exchange<false>(hb_cur);
     double last_err_chi = s_red[27];
     const double initial_chi2 = last_err_chi;
     if (tid < 27) s_Hc[tid] = s_red[tid];
@@ -433,11 +510,12 @@ __global__ __launch_bounds__(F2_THREADS) void k_flow2_lm(const Flow2Dev* __restr
     bool built = true;
     bool ok = true;
     for (; it < P.max_iterations && ok; ++it) {
-      // re-linearisation at the current estimate after a rejected trial that did not end the iteration loop (non-finite chi2)
+      // computeActiveErrors + buildSystem at the current estimate: already there after an accepted trial; repeated
+      // only when the previous trial was rejected without ending the iteration loop (non-finite chi2)
       if (!built) {
-        sweep_r(std::false_type{}, 0.0, true, Bc, hc, bc0, bc1, fc0, fc1, fc0, fc1);
+        sweep(std::false_type{}, 0.0, true, 0.0, F2Pre{});
         { double d_ = 0; hb_cur = s_hlast; F2_CLUSTER_SUM(29, d_, hb_cur); }
-        hpc = h_prev(hb_cur);
+        S.template after_exchange<false>(hb_cur);
         last_err_chi = s_red[27];
         if (tid < 27) s_Hc[tid] = s_red[tid];
         __syncthreads();
@@ -449,43 +527,55 @@ __global__ __launch_bounds__(F2_THREADS) void k_flow2_lm(const Flow2Dev* __restr
       int qmax = 0;
       do {
         // ---- (1) Schur sums for this lambda (with the F3 aliasing)
+        F2Pre pre;      // hand-over to the sweep of this trial: D^-1 of the thread's first correspondence (memory store: B and b_l too)
+        pre.i = -1;
         {
           double acc[28];      // 27 Schur sums + [27] the landmark part of computeScale for the STALE x (what a failed solve leaves behind)
 #pragma unroll
           for (int k = 0; k < 28; ++k) acc[k] = 0.0;
-          if (active) {
-            const double bl0 = bc0, bl1 = bc1;
-            acc[27] += xl0 * (lambda * xl0 + bl0) + xl1 * (lambda * xl1 + bl1);
+          S.for_each([&](const int i) {
+            F2Lin L;
+            S.lin_cur(i, L);
+            const double bl0 = L.b0, bl1 = L.b1;
+            { double xs0, xs1; S.get_xl(i, xs0, xs1); acc[27] += xs0 * (lambda * xs0 + bl0) + xs1 * (lambda * xs1 + bl1); }
+            const double (&Bv)[12] = L.B;
             if (Q) {
               double d0, d1, d2;
-              dinv_q(hc, lambda, d0, d1, d2);
+              dinv_q(L.h, lambda, d0, d1, d2);
               const double db0 = d0 * bl0 + d1 * bl1, db1 = d2 * bl1;      // (the aliased third row/column only ever meets exact zeros)
-              q0 = d0; q1 = d1; q2 = d2; qp2 = 0.0;
-              if (i > 0) { double p0_, p1_; dinv_q(hpc, lambda, p0_, p1_, qp2); }
+              if (kReg || i == first) {
+                if constexpr (!kReg) {
+#pragma unroll
+                  for (int a = 0; a < 12; ++a) pre.B[a] = Bv[a];
+                  pre.b0 = bl0; pre.b1 = bl1;
+                }
+                pre.d0 = d0; pre.d1 = d1; pre.d2 = d2; pre.p2 = 0.0; pre.i = i;
+                if (i > 0) { double p0_, p1_; dinv_q(S.h_prev(i, hb_cur), lambda, p0_, p1_, pre.p2); }
+              }
               int k = 0;
 #pragma unroll
               for (int a = 0; a < 6; ++a) {
-                acc[21 + a] += Bc[2 * a] * db0 + Bc[2 * a + 1] * db1;
-                const double bd0 = Bc[2 * a] * d0;
-                const double bd1 = Bc[2 * a] * d1 + Bc[2 * a + 1] * d2;
+                acc[21 + a] += Bv[2 * a] * db0 + Bv[2 * a + 1] * db1;
+                const double bd0 = Bv[2 * a] * d0;
+                const double bd1 = Bv[2 * a] * d1 + Bv[2 * a + 1] * d2;
 #pragma unroll
-                for (int c2 = 0; c2 <= a; ++c2) acc[k++] += bd0 * Bc[2 * c2] + bd1 * Bc[2 * c2 + 1];   // lower triangle (LDLT reads only it)
+                for (int c2 = 0; c2 <= a; ++c2) acc[k++] += bd0 * Bv[2 * c2] + bd1 * Bv[2 * c2 + 1];   // lower triangle (LDLT reads only it)
               }
             } else {
               double Di[9];
-              dinv_of(hc, lambda, Di);
+              dinv_of(L.h, lambda, Di);
               const double db0 = Di[0] * bl0 + Di[1] * bl1, db1 = Di[3] * bl0 + Di[4] * bl1;
               int k = 0;
 #pragma unroll
               for (int a = 0; a < 6; ++a) {
-                acc[21 + a] += Bc[2 * a] * db0 + Bc[2 * a + 1] * db1;
-                const double bd0 = Bc[2 * a] * Di[0] + Bc[2 * a + 1] * Di[3];
-                const double bd1 = Bc[2 * a] * Di[1] + Bc[2 * a + 1] * Di[4];
+                acc[21 + a] += Bv[2 * a] * db0 + Bv[2 * a + 1] * db1;
+                const double bd0 = Bv[2 * a] * Di[0] + Bv[2 * a + 1] * Di[3];
+                const double bd1 = Bv[2 * a] * Di[1] + Bv[2 * a + 1] * Di[4];
 #pragma unroll
-                for (int c2 = 0; c2 <= a; ++c2) acc[k++] += bd0 * Bc[2 * c2] + bd1 * Bc[2 * c2 + 1];
+                for (int c2 = 0; c2 <= a; ++c2) acc[k++] += bd0 * Bv[2 * c2] + bd1 * Bv[2 * c2 + 1];
               }
             }
-          }
+          });
           F2_TICK(12);
           block_reduce_bfly<28>(acc, s_wpart, s_red);
           F2_TICK(13);
@@ -501,9 +591,9 @@ __global__ __launch_bounds__(F2_THREADS) void k_flow2_lm(const Flow2Dev* __restr
           continue;
         }
         // ---- (3) finish the solve per correspondence, errors + speculative linearisation at the trial point
-        sweep_r(std::true_type{}, lambda, ok2, Bt, ht, bt0, bt1, fc0, fc1, ft0, ft1);
+        sweep(std::true_type{}, lambda, ok2, hb_cur, pre);
         { double d_ = 0; hb_try = s_hlast; F2_CLUSTER_SUM(29, d_, hb_try); }
-        hpt = h_prev(hb_try);
+        S.template after_exchange<true>(hb_try);
         last_err_chi = tempChi = s_red[27];
         const double scale = (s_rho + s_red[28]) + 1e-3;
         F2_TICK(2);
@@ -513,14 +603,12 @@ __global__ __launch_bounds__(F2_THREADS) void k_flow2_lm(const Flow2Dev* __restr
           double alpha = 1. - cube_rn(2 * rho - 1);
           alpha = fmin(alpha, upper);
           lambda *= fmax(lower, alpha); ni = 2; currentChi = tempChi; built = true;
-          fc0 = ft0; fc1 = ft1;                                                 // discardTop(): accept - the trial registers become the current ones
-#pragma unroll
-          for (int a = 0; a < 12; ++a) Bc[a] = Bt[a];
-          hc = ht; bc0 = bt0; bc1 = bt1; hpc = hpt; hb_cur = hb_try;
+          S.accept();                                                         // discardTop(): the trial flow and linearisation become the current ones
+          hb_cur = hb_try;
           if (tid < 27) s_Hc[tid] = s_red[tid];
           if (tid == 32) s_T = s_Ttry;
         } else {
-          lambda *= ni; ni *= 2; built = false;                               // pop(): keep (s_T, fc) and their linearisation
+          lambda *= ni; ni *= 2; built = false;                               // pop(): keep (s_T, current flow) and their linearisation
         }
         __syncthreads();
         F2_TICK(3);
@@ -540,14 +628,17 @@ __global__ __launch_bounds__(F2_THREADS) void k_flow2_lm(const Flow2Dev* __restr
     // ---- classification on the errors of the last evaluated trial (Optimizer.cc:2470-2508)
     double cnt[1] = {0.0};
     const float gate = (float)P.chi2_gate;
-    if (active) {
-      const float chi2 = (float)(er0 * (P.info_flow * er0) + er1 * (P.info_flow * er1));
+    S.for_each([&](const int i) {
+      double e0, e1, f0, f1;
+      S.get_err(i, e0, e1);
+      S.flow_cur(i, f0, f1);
+      const float chi2 = (float)(e0 * (P.info_flow * e0) + e1 * (P.info_flow * e1));
       const bool outl = chi2 > gate;
       inlier_out[i] = outl ? 0 : 1;
       cnt[0] += outl ? 0.0 : 1.0;
-      flow_out[2 * i] = fc0;
-      flow_out[2 * i + 1] = fc1;
-    }
+      flow_out[2 * i] = f0;
+      flow_out[2 * i + 1] = f1;
+    });
     block_reduce<1>(cnt, s_scr, s_red);
     { double d_ = 0, e_ = 0; F2_CLUSTER_SUM(1, d_, e_); }
     if (tid == 0 && wg == 0) {
@@ -561,284 +652,24 @@ __global__ __launch_bounds__(F2_THREADS) void k_flow2_lm(const Flow2Dev* __restr
     }
 #ifdef F2_PROFILE
     __syncthreads();
-    if (tid == 0 && wg < 2) res->T[14 + wg] = (double)(__builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 20) & 0xf) + 100.0 * blockIdx.x;
+    if (tid == 0 && wg < 2) res->T[14 + wg] = (double)(__builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 20) & 0xf) + 100.0 * blockIdx.x;   // XCC_ID of workgroups 0 / 1 (+ 100 x block id)
 #endif
-    return;
-  }
-
-  // Sweep (3): TRIAL -> finish the solve for every correspondence (reads the current linearisation Br/hr/br and x_p),
-  // then evaluate + linearise the edges at (T, f) into Bw/hw/bw.  Block sums -> s_red[0..26] (Hpp lower, bp), [27] robust chi2,
-  // [28] landmark part of computeScale; returns the per-thread max of the Hll diagonal (computeLambdaInit).
-  auto sweep = [&](auto trial_c, const double lam, const bool ok2, const double* __restrict__ Br, const double* __restrict__ hr, const double* __restrict__ br,
-                   double* __restrict__ Bw, double* __restrict__ hw, double* __restrict__ bw, const double* fin, double* fout, const double hb_prev, const F2Pre& pre) -> double {
-    constexpr bool TRIAL = decltype(trial_c)::value;
-    const SE3d T = TRIAL ? s_Ttry : s_T;
-    double xp[6];
-#pragma unroll
-    for (int j = 0; j < 6; ++j) xp[j] = s_xp[j];
-    double acc[29];
-#pragma unroll
-    for (int i = 0; i < 29; ++i) acc[i] = 0.0;
-    double hmax = 0.0;
-    for (int i = first; i < c_hi; i += stride) {
-      double f0v, f1v;
-      if (TRIAL) {
-        // back-substitution c = b_l - B^T x_p for this landmark (first correspondence of the thread: B, b_l and D^-1 are
-        // still in registers from the Schur sums of this trial - same loads, same lambda, same divisions)
-        const bool hp = Q && i == pre.i;
-        double Bl[12], b0, b1;
-        if (hp) {
-#pragma unroll
-          for (int a = 0; a < 12; ++a) Bl[a] = pre.B[a];
-          b0 = pre.b0; b1 = pre.b1;
-        } else {
-          const double* B = Br + i;
-#pragma unroll
-          for (int a = 0; a < 12; ++a) Bl[a] = B[a * N];
-          b0 = br[i]; b1 = br[N + i];
-        }
-        double t0 = 0, t1 = 0;
-#pragma unroll
-        for (int a = 0; a < 6; ++a) { t0 += Bl[2 * a] * (-xp[a]); t1 += Bl[2 * a + 1] * (-xp[a]); }
-        const double c0 = b0 + t0, c1 = b1 + t1;
-        double x0, x1;
-        if (Q) {
-          // x[2i..2i+2] = D_i^-1 c_i with the aliased 3x3 block (dinv_q): rows 0/1 give this landmark's flow update, row 2 of
-          // landmark i-1 (= its d2 * c0 of THIS landmark: the aliased third component) was written into slot 2i first
-          double d0, d1, d2, p2_ = 0;
-          if (hp) { d0 = pre.d0; d1 = pre.d1; d2 = pre.d2; p2_ = pre.p2; }
-          else {
-            dinv_q(hr[i], lam, d0, d1, d2);
-            if (i > 0) { double p0_, p1_; dinv_q(i > c_lo ? hr[i - 1] : hb_prev, lam, p0_, p1_, p2_); }      // (the previous chunk's last landmark belongs to another workgroup)
-          }
-          x0 = d0 * c0 + d1 * c1;
-          x1 = d2 * c1;
-          if (i > 0) x0 = p2_ * c0 + x0;
-        } else {
-          double Di[9];
-          dinv_of(hr[i], lam, Di);
-          x0 = (Di[0] * c0 + Di[1] * c1) + Di[2] * 0.0;
-          x1 = (Di[3] * c0 + Di[4] * c1) + Di[5] * 0.0;
-        }
-        F2_TICK(8);
-        if (!ok2) x0 = xl[i];         // failed LDLT: stale x (the reference keeps the previous content); the trial is rejected anyway
-        const double x1e = ok2 ? x1 : xl[N + i];
-        xl[i] = x0; xl[N + i] = x1e;
-        f0v = fin[i] + x0; f1v = fin[N + i] + x1e;
-        fout[i] = f0v; fout[N + i] = f1v;
-        acc[28] += x0 * (lam * x0 + b0) + x1e * (lam * x1e + b1);
-      } else {
-        f0v = fin[i]; f1v = fin[N + i];
-      }
-      // computeActiveErrors at (T, f)
-      double pc[3];
-      const double xw[3] = {Xw[i], Xw[N + i], Xw[2 * N + i]};
-      q_rotate(T.r, xw, pc);
-      const double X = pc[0] + T.t[0], Y = pc[1] + T.t[1], Z = pc[2] + T.t[2], Z2 = Z * Z;
-      const double u = X / Z * fx + cx, v = Y / Z * fy + cy;
-      const double e0 = (obs[i] + f0v) - u, e1 = (obs[N + i] + f1v) - v;
-      err[i] = e0; err[N + i] = e1;
-      if (TRIAL) F2_TICK(9);
-      const double c = e0 * (P.info_flow * e0) + e1 * (P.info_flow * e1);
-      double r0, r1;
-      huber_f2(c, P.huber_delta, P.huber_dsqr, r0, r1);
-      const double p0 = f0v - meas[i], p1 = f1v - meas[N + i];
-      acc[27] += r0 + (p0 * (P.info_prior * p0) + p1 * (P.info_prior * p1));
-      // buildSystem at the same point
-      double J[12];
-      J[0] = X * Y / Z2 * fx; J[1] = -(1 + (X * X / Z2)) * fx; J[2] = Y / Z * fx; J[3] = -1. / Z * fx; J[4] = 0; J[5] = X / Z2 * fx;
-      J[6] = (1 + Y * Y / Z2) * fy; J[7] = -X * Y / Z2 * fy; J[8] = -X / Z * fy; J[9] = 0; J[10] = -1. / Z * fy; J[11] = Y / Z2 * fy;
-      const double wo = r1 * P.info_flow;
-      const double or0 = -(P.info_flow * e0) * r1, or1 = -(P.info_flow * e1) * r1;
-#pragma unroll
-      for (int a = 0; a < 6; ++a) { Bw[(2 * a) * N + i] = J[a] * wo; Bw[(2 * a + 1) * N + i] = J[6 + a] * wo; }
-      int k = 0;
-#pragma unroll
-      for (int a = 0; a < 6; ++a) {
-        acc[21 + a] += J[a] * or0 + J[6 + a] * or1;
-#pragma unroll
-        for (int c2 = 0; c2 <= a; ++c2) acc[k++] += J[a] * wo * J[c2] + J[6 + a] * wo * J[6 + c2];   // lower triangle
-      }
-      const double h = wo + P.info_prior;
-      hw[i] = h;                // Hll block = h * I2 (off-diagonals are exact zeros)
-      bw[i] = or0 - P.info_prior * p0;
-      bw[N + i] = or1 - P.info_prior * p1;
-      hmax = fmax(hmax, h);
-      if (i == c_hi - 1) s_hlast = h;
-      if (TRIAL) F2_TICK(10);
-    }
-    block_reduce_bfly<29>(acc, s_wpart, s_red);
-    if (TRIAL) F2_TICK(11);
-    return hmax;
   };
 
-  double lambda = -1, ni = 2;
-  int nBad = 0, it = 0, total_trials = 0, stop_reason = 0;
-  const double tau = 1e-5, upper = 2. / 3., lower = 1. / 3.;
-  double chi2_check = 0;
-  // initial computeActiveErrors + buildSystem
-  double hmax = sweep(std::false_type{}, 0.0, true, nullptr, nullptr, nullptr, Bc, hc, bc, fcur, nullptr, 0.0, F2Pre{});
-#pragma unroll
-  for (int off2 = 32; off2 > 0; off2 >>= 1) hmax = fmax(hmax, __shfl_down(hmax, off2, 64));
-  if ((tid & 63) == 0) s_scr[tid >> 6] = hmax;
-  __syncthreads();
-  double hmx = s_scr[0];
-  for (int w = 1; w < F2_WAVES; ++w) hmx = fmax(hmx, s_scr[w]);
-  double hb_cur = s_hlast, hb_try = 0.0;     // -> Hll diagonal of the landmark just before this chunk (current / trial linearisation)
-  F2_CLUSTER_SUM(29, hmx, hb_cur);
-  double last_err_chi = s_red[27];
-  const double initial_chi2 = last_err_chi;
-  if (tid < 27) s_Hc[tid] = s_red[tid];
-  __syncthreads();
-  {
-    // computeLambdaInit: max |H(j,j)| over pose and flow vertices
-    double mm = hmx;
-    for (int j = 0; j < 6; ++j) mm = fmax(mm, fabs(s_Hc[j * (j + 3) / 2]));
-    lambda = tau * mm; ni = 2; nBad = 0;
+  // One correspondence per thread (every problem the pipeline builds: N <= 2048 on a full cluster): the register store; everything
+  // else (N > 2048, a lowered cluster, VDO_LM_GENERAL=1) the memory store.  Workgroup-uniform, chosen per problem - and the only
+  // place that knows which store is used.
+  const bool REG = chunk <= F2_THREADS && !A.force_general;
+  if (REG) {
+    __shared__ double s_h[F2_THREADS];
+    F2RegStore S{first, tid, first < c_hi, s_h};
+    lm_body(S);
+  } else {
+    double* const om = A.om + 4 * off;
+    F2MemStore S{N, first, c_lo, c_hi, om, om + 2 * (size_t)N, A.Xw + 3 * off, A.f0 + 2 * off, A.f1 + 2 * off, A.err + 2 * off, A.xl + 2 * off,
+                 A.B2a + 12 * off, A.B2b + 12 * off, A.hla + off, A.hlb + off, A.bla + 2 * off, A.blb + 2 * off};
+    lm_body(S);
   }
-  F2_TICK(4);
-  bool built = true;
-  bool ok = true;
-  for (; it < P.max_iterations && ok; ++it) {
-    // computeActiveErrors + buildSystem at the current estimate: already there after an accepted trial; repeated
-    // only when the previous trial was rejected without ending the iteration loop (non-finite chi2)
-    if (!built) {
-      sweep(std::false_type{}, 0.0, true, nullptr, nullptr, nullptr, Bc, hc, bc, fcur, nullptr, 0.0, F2Pre{});
-      { double d_ = 0; hb_cur = s_hlast; F2_CLUSTER_SUM(29, d_, hb_cur); }
-      last_err_chi = s_red[27];
-      if (tid < 27) s_Hc[tid] = s_red[tid];
-      __syncthreads();
-      built = true;
-    }
-    double currentChi = last_err_chi, tempChi = currentChi;
-    const double iniChi = currentChi;
-    double rho = 0;
-    int qmax = 0;
-    do {
-      // ---- (1) Schur sums for this lambda (with the F3 aliasing)
-      F2Pre pre;
-      pre.i = -1;
-      {
-        double acc[28];      // 27 Schur sums + [27] the landmark part of computeScale for the STALE x (what a failed solve leaves behind)
-#pragma unroll
-        for (int i = 0; i < 28; ++i) acc[i] = 0.0;
-        const double* __restrict__ Br = Bc; const double* __restrict__ hr = hc; const double* __restrict__ br = bc;
-        for (int i = first; i < c_hi; i += stride) {
-          const double bl0 = br[i], bl1 = br[N + i];
-          { const double xs0 = xl[i], xs1 = xl[N + i]; acc[27] += xs0 * (lambda * xs0 + bl0) + xs1 * (lambda * xs1 + bl1); }
-          const double* B = Br + i;
-          double Bv[12];
-#pragma unroll
-          for (int a = 0; a < 12; ++a) Bv[a] = B[a * N];
-          if (Q) {
-            double d0, d1, d2;
-            dinv_q(hr[i], lambda, d0, d1, d2);
-            const double db0 = d0 * bl0 + d1 * bl1, db1 = d2 * bl1;      // (the aliased third row/column only ever meets exact zeros)
-            if (i == first) {
-#pragma unroll
-              for (int a = 0; a < 12; ++a) pre.B[a] = Bv[a];
-              pre.b0 = bl0; pre.b1 = bl1; pre.d0 = d0; pre.d1 = d1; pre.d2 = d2; pre.p2 = 0.0; pre.i = i;
-              if (i > 0) { double p0_, p1_; dinv_q(i > c_lo ? hr[i - 1] : hb_cur, lambda, p0_, p1_, pre.p2); }
-            }
-            int k = 0;
-#pragma unroll
-            for (int a = 0; a < 6; ++a) {
-              acc[21 + a] += Bv[2 * a] * db0 + Bv[2 * a + 1] * db1;
-              const double bd0 = Bv[2 * a] * d0;
-              const double bd1 = Bv[2 * a] * d1 + Bv[2 * a + 1] * d2;
-#pragma unroll
-              for (int c2 = 0; c2 <= a; ++c2) acc[k++] += bd0 * Bv[2 * c2] + bd1 * Bv[2 * c2 + 1];   // lower triangle (LDLT reads only it)
-            }
-          } else {
-            double Di[9];
-            dinv_of(hr[i], lambda, Di);
-            const double db0 = Di[0] * bl0 + Di[1] * bl1, db1 = Di[3] * bl0 + Di[4] * bl1;
-            int k = 0;
-#pragma unroll
-            for (int a = 0; a < 6; ++a) {
-              acc[21 + a] += Bv[2 * a] * db0 + Bv[2 * a + 1] * db1;
-              const double bd0 = Bv[2 * a] * Di[0] + Bv[2 * a + 1] * Di[3];
-              const double bd1 = Bv[2 * a] * Di[1] + Bv[2 * a + 1] * Di[4];
-#pragma unroll
-              for (int c2 = 0; c2 <= a; ++c2) acc[k++] += bd0 * Bv[2 * c2] + bd1 * Bv[2 * c2 + 1];
-            }
-          }
-        }
-        F2_TICK(12);
-        block_reduce_bfly<28>(acc, s_wpart, s_red);
-        F2_TICK(13);
-        { double d_ = 0, e_ = 0; F2_CLUSTER_SUM(28, d_, e_); }
-      }
-      F2_TICK(0);
-      solve_pose(lambda, qmax, currentChi);
-      const bool ok2 = s_ctrl[2] != 0;
-      if (s_ctrl[1]) {
-        rho = (currentChi - 1.7976931348623157e308) / ((s_rho + s_red[27]) + 1e-3);
-        lambda *= ni; ni *= 2; built = false;
-        ++qmax; ++total_trials;
-        continue;
-      }
-      // ---- (3) finish the solve per correspondence, errors + speculative linearisation at the trial point
-      sweep(std::true_type{}, lambda, ok2, Bc, hc, bc, Bt, ht, bt, fcur, ftry, hb_cur, pre);
-      { double d_ = 0; hb_try = s_hlast; F2_CLUSTER_SUM(29, d_, hb_try); }
-      last_err_chi = tempChi = s_red[27];
-      const double scale = (s_rho + s_red[28]) + 1e-3;
-      F2_TICK(2);
-      if (!ok2) tempChi = 1.7976931348623157e308;
-      rho = (currentChi - tempChi) / scale;
-      if (rho > 0 && isfinite(tempChi)) {
-        double alpha = 1. - cube_rn(2 * rho - 1);
-        alpha = fmin(alpha, upper);
-        lambda *= fmax(lower, alpha); ni = 2; currentChi = tempChi; built = true;
-        { double* t_ = fcur; fcur = ftry; ftry = t_; }                       // discardTop(): accept (uniform pointer swaps)
-        { double* t_ = Bc; Bc = Bt; Bt = t_; t_ = hc; hc = ht; ht = t_; t_ = bc; bc = bt; bt = t_; hb_cur = hb_try; }
-        if (tid < 27) s_Hc[tid] = s_red[tid];
-        if (tid == 32) s_T = s_Ttry;
-      } else {
-        lambda *= ni; ni *= 2; built = false;                               // pop(): keep (s_T, fcur) and their linearisation
-      }
-      __syncthreads();
-      F2_TICK(3);
-      ++qmax; ++total_trials;
-    } while (rho < 0 && qmax < 10);
-    int result;
-    if (qmax == 10 || rho == 0) result = 1;
-    else {
-      if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;
-      result = nBad >= 3 ? 1 : 0;
-    }
-    ok = (result == 0);
-    if (!ok) stop_reason = 1;
-    if (chi2_check < last_err_chi && it > 0) { ok = false; stop_reason = 2; }
-    chi2_check = last_err_chi;
-  }
-  // ---- classification on the stored errors of the last evaluated trial (Optimizer.cc:2470-2508)
-  double cnt[1] = {0.0};
-  const float gate = (float)P.chi2_gate;
-  for (int i = first; i < c_hi; i += stride) {
-    const double e0 = err[i], e1 = err[N + i];
-    const float chi2 = (float)(e0 * (P.info_flow * e0) + e1 * (P.info_flow * e1));
-    const bool outl = chi2 > gate;
-    inlier_out[i] = outl ? 0 : 1;
-    cnt[0] += outl ? 0.0 : 1.0;
-    flow_out[2 * i] = fcur[i];
-    flow_out[2 * i + 1] = fcur[N + i];
-  }
-  block_reduce<1>(cnt, s_scr, s_red);
-  { double d_ = 0, e_ = 0; F2_CLUSTER_SUM(1, d_, e_); }
-  if (tid == 0 && wg == 0) {
-    se3_to_matrix(s_T, res->T);
-    res->n_inliers = (int)(s_red[0] + 0.5);
-    res->iterations = it; res->trials = total_trials; res->stop_reason = stop_reason;
-    res->initial_chi2 = initial_chi2; res->final_chi2 = last_err_chi; res->final_lambda = lambda;
-#ifdef F2_PROFILE
-    for (int i = 0; i < 14; ++i) res->T[i] = (double)s_prof[i];     // cycles per phase instead of the pose (debug build only)
-#endif
-  }
-#ifdef F2_PROFILE
-  __syncthreads();
-  if (tid == 0 && wg < 2) res->T[14 + wg] = (double)(__builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 20) & 0xf) + 100.0 * blockIdx.x;   // XCC_ID of workgroups 0 / 1 (+ 100 x block id)
-#endif
 }
 
 }  // namespace vdo
@@ -873,6 +704,23 @@ extern "C" int vdo_flow2_batch_destroy(vdo_flow2_batch* b) {
   return VDO_OK;
 }
 
+// What a problem's descriptor takes over from the caller's struct (its size and offsets are the batch's business).
+static void fill_descriptor(Flow2Dev& d, const vdo_flow2_problem& p) {
+  d.max_iterations = p.max_iterations; d.ref_quirks = p.ref_quirks;
+  std::memcpy(d.K, p.K, sizeof(d.K)); std::memcpy(d.Twl, p.Twl, sizeof(d.Twl)); std::memcpy(d.T0, p.T0, sizeof(d.T0));
+  d.info_flow = p.info_flow; d.info_prior = p.info_prior; d.huber_delta = p.huber_delta;
+  d.huber_dsqr = (double)(float)(p.huber_delta * p.huber_delta);     // float member, robust_kernel_impl.h:84
+  d.chi2_gate = p.chi2_gate;
+}
+
+// A problem's inputs as SoA planes at st: key points [2][n], measured flow [2][n], depth [n]: consecutive lanes read consecutive doubles.
+static void pack_planes(double* st, const vdo_flow2_problem& p) {
+  const size_t n = (size_t)p.n;
+  double *po = st, *pm = st + 2 * n;
+  for (size_t i = 0; i < n; ++i) { po[i] = p.obs[2 * i]; po[n + i] = p.obs[2 * i + 1]; pm[i] = p.flow[2 * i]; pm[n + i] = p.flow[2 * i + 1]; }
+  std::memcpy(st + 4 * n, p.depth, sizeof(double) * n);
+}
+
 extern "C" int vdo_flow2_batch_create(vdo_ctx* ctx, int n_problems, const vdo_flow2_problem* probs, vdo_flow2_batch** out) {
   if (!ctx || !probs || !out || n_problems <= 0) return set_error(VDO_ERR_INVALID, "vdo_flow2_batch_create: bad argument");
   int rc = ctx_bind(ctx);
@@ -885,12 +733,8 @@ extern "C" int vdo_flow2_batch_create(vdo_ctx* ctx, int n_problems, const vdo_fl
     const vdo_flow2_problem& p = probs[k];
     if (p.n < 0 || (p.n > 0 && (!p.obs || !p.flow || !p.depth))) { delete b; return set_error(VDO_ERR_INVALID, "flow2 problem %d: null input", k); }
     Flow2Dev& d = hp[k];
-    d.n = p.n; d.max_iterations = p.max_iterations; d.ref_quirks = p.ref_quirks; d.pad = 0; d.off = total;
-    std::memcpy(d.K, p.K, sizeof(d.K)); std::memcpy(d.Twl, p.Twl, sizeof(d.Twl)); std::memcpy(d.T0, p.T0, sizeof(d.T0));
-    d.info_flow = p.info_flow; d.info_prior = p.info_prior; d.huber_delta = p.huber_delta;
-    d.huber_dsqr = (double)(float)(p.huber_delta * p.huber_delta);     // float member, robust_kernel_impl.h:84
-    d.chi2_gate = p.chi2_gate;
-    d.out_off = total;
+    fill_descriptor(d, p);
+    d.n = p.n; d.pad = 0; d.off = total; d.out_off = total;
     b->offs.push_back(total); b->ns.push_back(p.n);
     total += p.n;
   }
@@ -906,14 +750,7 @@ extern "C" int vdo_flow2_batch_create(vdo_ctx* ctx, int n_problems, const vdo_fl
   };
   const size_t T = (size_t)total, NP = (size_t)n_problems;
   std::vector<double> in(5 * T);
-  for (int k = 0; k < n_problems; ++k) {
-    const vdo_flow2_problem& p = probs[k];
-    if (p.n == 0) continue;
-    // per-problem SoA planes: key points [2][n], measured flow [2][n], depth [n]: consecutive lanes read consecutive doubles
-    double* po = in.data() + 5 * b->offs[k]; double* pm = po + 2 * (size_t)p.n;
-    for (int i = 0; i < p.n; ++i) { po[i] = p.obs[2 * i]; po[p.n + i] = p.obs[2 * i + 1]; pm[i] = p.flow[2 * i]; pm[p.n + i] = p.flow[2 * i + 1]; }
-    std::memcpy(po + 4 * (size_t)p.n, p.depth, sizeof(double) * p.n);
-  }
+  for (int k = 0; k < n_problems; ++k) if (probs[k].n) pack_planes(in.data() + 5 * b->offs[k], probs[k]);
   double* d_in = (double*)dev(40 * T);
   b->d_probs = (Flow2Dev*)dev(sizeof(Flow2Dev) * NP);
   Flow2Arrays& A = b->A;
@@ -979,21 +816,12 @@ extern "C" int vdo_flow2_batch_set(vdo_flow2_batch* b, int k, const vdo_flow2_pr
   if (!b || k < 0 || k >= b->n_problems || !b->h_up) return set_error(VDO_ERR_INVALID, "vdo_flow2_batch_set: bad argument / batch not created by vdo_flow2_batch_reserve");
   int rc = ctx_bind(b->ctx);
   if (rc != VDO_OK) return rc;
-  hipStream_t s = b->ctx->stream;
   Flow2Dev& d = b->hp[k];
   const int n = p ? p->n : 0;
   if (n < 0 || n > b->caps[k] || (n > 0 && (!p->obs || !p->flow || !p->depth))) return set_error(VDO_ERR_INVALID, "vdo_flow2_batch_set: %d points do not fit slot %d (capacity %d)", n, k, b->caps[k]);
   if (n) {
-    const int64_t off = b->offs[k];
-    double* st = b->h_up + 5 * off;
-    double *po = st, *pm = st + 2 * (size_t)n, *pd = st + 4 * (size_t)n;
-    for (int i = 0; i < n; ++i) { po[i] = p->obs[2 * i]; po[n + i] = p->obs[2 * i + 1]; pm[i] = p->flow[2 * i]; pm[n + i] = p->flow[2 * i + 1]; pd[i] = p->depth[i]; }
-    (void)s;                               // (the kernel reads the slot through the mapping)
-    d.max_iterations = p->max_iterations; d.ref_quirks = p->ref_quirks;
-    std::memcpy(d.K, p->K, sizeof(d.K)); std::memcpy(d.Twl, p->Twl, sizeof(d.Twl)); std::memcpy(d.T0, p->T0, sizeof(d.T0));
-    d.info_flow = p->info_flow; d.info_prior = p->info_prior; d.huber_delta = p->huber_delta;
-    d.huber_dsqr = (double)(float)(p->huber_delta * p->huber_delta);
-    d.chi2_gate = p->chi2_gate;
+    pack_planes(b->h_up + 5 * b->offs[k], *p);      // (the kernel reads the slot through the mapping)
+    fill_descriptor(d, *p);
   }
   d.n = n; b->ns[k] = n;
   b->probs_dirty = true;                 // the descriptors go up in one copy at the next run
@@ -1038,15 +866,12 @@ extern "C" int vdo_flow2_batch_fetch(vdo_flow2_batch* b, vdo_flow2_result* resul
   if (!b || !results) return set_error(VDO_ERR_INVALID, "null argument");
   int rc = ctx_bind(b->ctx);
   if (rc != VDO_OK) return rc;
-  hipStream_t s = b->ctx->stream;
   // results, refined flows and inlier flags are packed by the actual problem sizes in the pinned block the kernel wrote
+  // (already in host memory: the kernel wrote through the mapping)
   const size_t NP = (size_t)b->n_problems;
   size_t used = 0;
   for (int k = 0; k < b->n_problems; ++k) used += (size_t)b->ns[k];
-  const bool want_pts = (flow_out || inlier_out) && used;
-  const size_t bytes = sizeof(vdo_flow2_result) * NP + (want_pts ? 17 * used : 0);
-  (void)bytes;                                             // (already in host memory: the kernel wrote through the mapping)
-  hipError_t e = hipStreamSynchronize(s);
+  hipError_t e = hipStreamSynchronize(b->ctx->stream);
   if (e != hipSuccess) return set_error(VDO_ERR_NO_DEVICE, "flow2 fetch: %s", hipGetErrorString(e));
   const vdo_flow2_result* pr = (const vdo_flow2_result*)b->h_pin;
   const double* pf = (const double*)(b->h_pin + sizeof(vdo_flow2_result) * NP);
