@@ -273,8 +273,10 @@ struct Flow2 {
 
 }  // namespace
 
-extern "C" int vdo_oracle_flow2_optimize(const vdo_flow2_problem* p, double T_out[16], double* flow_out,
-                                         uint8_t* inlier_out, vdo_lm_stats* st) {
+// The optimisation itself; log (may be null): one record per Levenberg trial, at most cap of them, *n_log counts every trial.
+// The log only copies values the loop has computed anyway: results are the same bits with and without it.
+static int flow2_optimize(const vdo_flow2_problem* p, double T_out[16], double* flow_out, uint8_t* inlier_out, vdo_lm_stats* st,
+                          vdo_flow2_trial* log, int32_t cap, int32_t* n_log) {
   vdo_lm_stats local;
   if (!st) st = &local;
   std::memset(st, 0, sizeof(*st));
@@ -316,6 +318,15 @@ extern "C" int vdo_oracle_flow2_optimize(const vdo_flow2_problem* p, double T_ou
       scale += 1e-3;
       rho /= scale;
       if (trace_rho) std::fprintf(stderr, "[lm n=%d it=%d q=%d] rho %.6g lambda %.4g chi %.9g -> %.9g\n", N, it, qmax, rho, lambda, currentChi, tempChi);
+      const bool accepted = rho > 0 && std::isfinite(tempChi);
+      if (log) {
+        if (*n_log < cap) {
+          vdo_flow2_trial& r = log[*n_log];
+          r.iteration = it; r.trial = qmax; r.solved = ok2 ? 1 : 0; r.accepted = accepted ? 1 : 0;
+          r.lambda = lambda; r.chi2 = last_err_chi; r.rho = rho;
+        }
+        ++*n_log;
+      }
       if (rho > 0 && std::isfinite(tempChi)) {
         double alpha = 1. - std::pow((2 * rho - 1), 3);
         alpha = std::min(alpha, upper);
@@ -355,6 +366,19 @@ extern "C" int vdo_oracle_flow2_optimize(const vdo_flow2_problem* p, double T_ou
   }
   S.T.toMatrix4(T_out);
   return N - nbad;
+}
+
+extern "C" int vdo_oracle_flow2_optimize(const vdo_flow2_problem* p, double T_out[16], double* flow_out,
+                                         uint8_t* inlier_out, vdo_lm_stats* st) {
+  return flow2_optimize(p, T_out, flow_out, inlier_out, st, nullptr, 0, nullptr);
+}
+
+extern "C" int vdo_oracle_flow2_optimize_log(const vdo_flow2_problem* p, double T_out[16], double* flow_out, uint8_t* inlier_out,
+                                             vdo_lm_stats* st, vdo_flow2_trial* log, int32_t capacity, int32_t* n_trials) {
+  int32_t n = 0;
+  const int r = flow2_optimize(p, T_out, flow_out, inlier_out, st, log, log ? capacity : 0, &n);
+  if (n_trials) *n_trials = n;
+  return r;
 }
 
 // ------------------------------------------------------------------------------------------------

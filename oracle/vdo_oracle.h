@@ -130,6 +130,21 @@ typedef struct vdo_flow2_problem {
 int vdo_oracle_flow2_optimize(const vdo_flow2_problem* p, double T_out[16], double* flow_out,
                               uint8_t* inlier_out, vdo_lm_stats* stats);
 
+/* One Levenberg trial of vdo_oracle_flow2_optimize, for tests that assert WHICH branch an input takes. */
+typedef struct vdo_flow2_trial {
+  int32_t iteration;      /* outer iteration                                             */
+  int32_t trial;          /* trial inside the iteration, 0..9                            */
+  int32_t solved;         /* 1: the reduced 6x6 LDLT was positive                        */
+  int32_t accepted;       /* 1: rho > 0 and the trial chi2 finite                        */
+  double lambda;          /* damping the trial was solved with                           */
+  double chi2;            /* robust chi2 at the trial point, as evaluated                */
+  double rho;             /* gain ratio (a failed solve counts chi2 as DBL_MAX)          */
+} vdo_flow2_trial;
+/* vdo_oracle_flow2_optimize (same results, bit for bit) that also writes the first `capacity` trials to log[] and the number of
+ * trials run to *n_trials (log and n_trials may be NULL). */
+int vdo_oracle_flow2_optimize_log(const vdo_flow2_problem* p, double T_out[16], double* flow_out, uint8_t* inlier_out,
+                                  vdo_lm_stats* stats, vdo_flow2_trial* log, int32_t capacity, int32_t* n_trials);
+
 /* Non-joint per-frame pose refinement (Optimizer::PoseOptimizationNew src/Optimizer.cc:2177-2331,
  * Optimizer::PoseOptimizationObjMot :2544-2753): one VertexSE3Expmap, n unary reprojection edges,
  * information I2.  Same layout as include/vdo_slam_hip.h. */

@@ -202,22 +202,29 @@ def _declare(L):
     pp_d = C.POINTER(c_double_p)
     pp_u8 = C.POINTER(c_uint8_p)
     L.vdo_flow2_batch_create.argtypes = [vp, C.c_int, C.POINTER(Flow2ProblemC), C.POINTER(vp)]
+    L.vdo_flow2_batch_reserve.argtypes = [vp, C.c_int, c_int32_p, C.POINTER(vp)]
+    L.vdo_flow2_batch_set.argtypes = [vp, C.c_int, C.POINTER(Flow2ProblemC)]
     L.vdo_flow2_batch_run.argtypes = [vp]
     L.vdo_flow2_batch_fetch.argtypes = [vp, C.POINTER(Flow2ResultC), pp_d, pp_u8]
     L.vdo_flow2_batch_destroy.argtypes = [vp]
     L.vdo_flow2_optimize.argtypes = [vp, C.POINTER(Flow2ProblemC), C.POINTER(Flow2ResultC), c_double_p, c_uint8_p]
     for f in ("vdo_ctx_create", "vdo_ctx_destroy", "vdo_ctx_synchronize", "vdo_ba_create", "vdo_ba_destroy",
               "vdo_ba_linearize", "vdo_ba_download_system", "vdo_ba_optimize", "vdo_ba_get_estimates",
-              "vdo_ba_set_estimates", "vdo_flow2_batch_create", "vdo_flow2_batch_run", "vdo_flow2_batch_fetch",
+              "vdo_ba_set_estimates", "vdo_flow2_batch_create", "vdo_flow2_batch_reserve", "vdo_flow2_batch_set", "vdo_flow2_batch_run", "vdo_flow2_batch_fetch",
               "vdo_flow2_batch_destroy", "vdo_flow2_optimize"):
         getattr(L, f).restype = C.c_int
 
 
 class VdoError(RuntimeError):
-    pass
+    code = None        # the library's return code (VDO_ERR_* of include/vdo_slam_hip.h)
+
+
+VDO_ERR_INVALID = -1
 
 
 def check(rc: int):
     if rc != 0:
         msg = lib().vdo_last_error()
-        raise VdoError(f"libvdo_hip error {rc}: {msg.decode() if msg else ''}")
+        err = VdoError(f"libvdo_hip error {rc}: {msg.decode() if msg else ''}")
+        err.code = rc
+        raise err

@@ -504,7 +504,8 @@ __global__ __launch_bounds__(F2_THREADS) void k_flow2_lm(const Flow2Dev* __restr
       // computeLambdaInit: max |H(j,j)| over pose and flow vertices
       double mm = hmx;
       for (int j = 0; j < 6; ++j) mm = fmax(mm, fabs(s_Hc[j * (j + 3) / 2]));
-      lambda = tau * mm; ni = 2; nBad = 0;
+      if (P.max_iterations > 0) lambda = tau * mm;      // (iteration 0 computes it: with no iteration at all it stays g2o's initial -1)
+      ni = 2; nBad = 0;
     }
     F2_TICK(4);
     bool built = true;

@@ -3,6 +3,9 @@
 ``Flow2Batch`` corresponds to one call of ``Optimizer::PoseOptimizationFlow2Cam`` (camera) or
 to the per-object loop over ``Optimizer::PoseOptimizationFlow2`` in ``Tracking::Track``
 (reference src/Tracking.cc:697, 785-1001): all problems of a batch run in ONE kernel launch.
+
+``Flow2Batch.reserve`` + ``set`` are the slots the frame pipeline uses (``vdo_flow2_batch_reserve`` / ``vdo_flow2_batch_set``):
+capacities fixed once, every slot (re)defined or emptied before each run, results packed by the current sizes.
 """
 from __future__ import annotations
 
@@ -27,14 +30,36 @@ class Flow2Batch:
         self._h = C.c_void_p()
         K.check(K.lib().vdo_flow2_batch_create(ctx._h, len(self.problems), arr, C.byref(self._h)))
 
+    @classmethod
+    def reserve(cls, ctx, capacities):
+        """A batch of ``len(capacities)`` empty slots of at most ``capacities[k]`` correspondences each: define them with :meth:`set`."""
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        self.problems = [None] * len(capacities)      # None: an empty slot (0 correspondences)
+        self._keep = [None] * len(capacities)
+        self._h = C.c_void_p()
+        caps = np.ascontiguousarray(capacities, dtype=np.int32)
+        K.check(K.lib().vdo_flow2_batch_reserve(ctx._h, len(caps), K._ip(caps), C.byref(self._h)))
+        return self
+
+    def set(self, k, problem):
+        """(Re)define slot ``k`` of a reserved batch; ``None`` empties it.  A refused call (:class:`VdoError`) leaves the slot as it was."""
+        if problem is None:
+            K.check(K.lib().vdo_flow2_batch_set(self._h, k, None))
+        else:
+            s, keep = K.flow2_to_c(problem)
+            K.check(K.lib().vdo_flow2_batch_set(self._h, k, C.byref(s)))      # (the library copies the inputs into the slot)
+        self.problems[k] = problem
+
     def run(self):
         K.check(K.lib().vdo_flow2_batch_run(self._h))
 
     def fetch(self):
         n = len(self.problems)
         res = (K.Flow2ResultC * n)()
-        flows = [np.zeros((p.n, 2)) for p in self.problems]
-        inl = [np.zeros(p.n, np.uint8) for p in self.problems]
+        sizes = [p.n if p is not None else 0 for p in self.problems]
+        flows = [np.zeros((m, 2)) for m in sizes]
+        inl = [np.zeros(m, np.uint8) for m in sizes]
         fp = (K.c_double_p * n)(*[K._dp(f) for f in flows])
         ip = (K.c_uint8_p * n)(*[a.ctypes.data_as(K.c_uint8_p) for a in inl])
         K.check(K.lib().vdo_flow2_batch_fetch(self._h, res, fp, ip))
