@@ -246,6 +246,9 @@ int vdo_flow2_batch_create(vdo_ctx* ctx, int n_problems, const vdo_flow2_problem
  * stream-ordered, no sync; problem == NULL empties a slot) -> run -> fetch. */
 int vdo_flow2_batch_reserve(vdo_ctx* ctx, int n_problems, const int32_t* capacity, vdo_flow2_batch** out);
 int vdo_flow2_batch_set(vdo_flow2_batch* batch, int k, const vdo_flow2_problem* problem);
+/* Rewrites the initial pose (4x4 row-major) of a slot vdo_flow2_batch_set has filled - for a caller that packs the correspondences before it knows the pose.
+ * The next run starts from it, exactly as if the slot had been set with that pose. */
+int vdo_flow2_batch_set_T0(vdo_flow2_batch* batch, int k, const double T0[16]);
 /* One kernel launch: every problem is optimised from its initial estimate (stream-ordered, no sync). */
 int vdo_flow2_batch_run(vdo_flow2_batch* batch);
 /* results[n_problems]; flow_out[k] -> [n_k][2] refined flows; inlier_out[k] -> [n_k] (1 = inlier). Synchronises. */
@@ -320,6 +323,17 @@ int vdo_pnp_ransac_batch(vdo_ctx* ctx, int n_problems, const vdo_pnp_problem* pr
  * caller that does not depend on the result (GetInitModelObj's motion-model inlier count, src/Tracking.cc:1767-1800, depends on neither).  NULL: no hook. */
 int vdo_pnp_ransac_batch_overlap(vdo_ctx* ctx, int n_problems, const vdo_pnp_problem* probs, vdo_pnp_result* results, uint8_t** inlier_out,
                                  void (*host_work)(void*), void* host_arg);
+/* The same for a caller that uses the re-estimated model of a problem only if its vote beats a count of the caller's own (GetInitModelCam / GetInitModelObj
+ * seed the optimisation with the RANSAC model only if it has MORE inliers than the motion model, src/Tracking.cc:1690-1712, 1803-1825), and that has work to do
+ * on the inlier flags which does not need the model:
+ *   refit_above  [n_problems] or NULL (no gate).  Read after host_work has returned, so host_work may fill it.  Problem k is re-estimated by EPnP only if
+ *                results[k].n_inliers > refit_above[k] (and its refit bit is set, as ever); otherwise T stays the winning hypothesis, exactly as with the bit
+ *                off.  -1 therefore means "always".  Votes, flags, iterations_run and best_iteration never depend on the gate.
+ *   after_replay (nullable) is called once, on the calling thread, when the inlier flags and results[].n_inliers / iterations_run / best_iteration are final
+ *                and results[].T is NOT yet: the refits - a single one too - run on the pool threads meanwhile.  The call joins them before it returns.
+ * VDO_PNP_NO_GATE in the environment (read on every call): refit_above is ignored and after_replay runs behind the refits. */
+int vdo_pnp_ransac_batch_gated(vdo_ctx* ctx, int n_problems, const vdo_pnp_problem* probs, vdo_pnp_result* results, uint8_t** inlier_out,
+                               const int32_t* refit_above, void (*host_work)(void*), void* host_arg, void (*after_replay)(void*), void* after_arg);
 int vdo_pnp_ransac(vdo_ctx* ctx, const vdo_pnp_problem* p, vdo_pnp_result* result, uint8_t* inlier_out);
 
 /* ---- ORB front-end ------------------------------------------------------------------------------
@@ -468,6 +482,17 @@ int vdo_renew_static_world(vdo_frame_images* f, int n_tm, const int32_t* tm_sta,
                            int n_orb, const float* orb_x, const float* orb_y, int max_num_sta, const float K4[4], const float Twc[16],
                            float* key_x, float* key_y, float* corr_x, float* corr_y, float* flow_x, float* flow_y,
                            int32_t* inlier_id, float* depth_out, float* xyz_out, int* n_out);
+/* New (no counterpart in the reference): K9 of the ORB keypoints (vdo_frame_static_filter) and vdo_renew_static_world topping up from the SAME keypoints, as one
+ * round trip - K9 is queued in front of the renewal kernels on the keypoints the renewal sends and writes its rows where the host reads them, one
+ * synchronisation delivers both.  Returns exactly what the two calls
+ * return one after the other: first K9's outputs (capacity n_orb each, *n_static = count), then the renewal's.  For the ORB mode once a last frame exists; where
+ * the renewal tops up from K9's own output (UseSampleFeature, Initialization) the two calls stay two.  VDO_ERR_INVALID as vdo_frame_static_filter when the
+ * keypoints exceed the image set's staging (10 * n_orb > 8 * capacity). */
+int vdo_static_stage(vdo_frame_images* f, int n_orb, const float* orb_x, const float* orb_y, float th_depth,
+                     int32_t* keep_idx, float* s_corr_x, float* s_corr_y, float* s_flow_x, float* s_flow_y, float* s_depth, int* n_static,
+                     int n_tm, const int32_t* tm_sta, const float* stat_x, const float* stat_y, int max_num_sta, const float K4[4], const float Twc[16],
+                     float* key_x, float* key_y, float* corr_x, float* corr_y, float* flow_x, float* flow_y,
+                     int32_t* inlier_id, float* depth_out, float* xyz_out, int* n_out);
 /* Tracking::UpdateMask (src/Tracking.cc:3015-3065): labels of this frame's mask at n positions
  * (-1 outside), and the warp of label `label` from `last`'s mask into `cur`'s mask by `last`'s flow. */
 int vdo_mask_at(vdo_frame_images* f, int n, const float* cx, const float* cy, int32_t* label_out);
@@ -539,6 +564,19 @@ int vdo_update_mask(vdo_frame_images* cur, vdo_frame_images* last, int n, const 
 int vdo_object_chain(vdo_frame_images* cur, vdo_frame_images* last, int n, const int32_t* last_sem_label, const float* last_corr_x, const float* last_corr_y,
                      float th_depth_obj, const float Tcw_cur[16], const float* last_x, const float* last_y, const float* last_d, const float Tcw_last[16],
                      const float K4[4], int* n_recovered, float* depth_out, int32_t* sem_out, float* flow3d_out, int32_t* obj_label_out);
+/* vdo_object_chain in two halves, for a caller that does not know the current camera pose yet: of the chain only the scene flow reads Tcw_cur.
+ *   begin: stages the last frame's inputs (or finds them prestaged, as vdo_object_chain does), queues UpdateMask (K15) on the stream of cur's context and
+ *          returns WITHOUT waiting.  The arrays must stay valid and unchanged until the end has returned.
+ *   end:   queues K11 (objects) + K13 with Tcw_cur, synchronises once, checks the flags and delivers what vdo_object_chain delivers.
+ * vdo_object_chain is the begin followed by the end.  One chain can be open per context; between its begin and its end no other call may use that context's
+ * scratch (every vdo_frame_images call on a set of that context, vdo_pnp_ransac*, vdo_get3d_world, vdo_scene_flow on it: they fail with VDO_ERR_OOM), and
+ * nothing else may touch the two image sets.  A begin that fails leaves no chain open (a second begin on a context fails and leaves the first open); an end
+ * closes the chain whether it succeeds or not - also when it reports a mask label outside the vote's histogram.  n == 0: the begin queues nothing and opens
+ * nothing; an end with no chain open returns VDO_OK and writes only *n_recovered = 0. */
+int vdo_object_chain_begin(vdo_frame_images* cur, vdo_frame_images* last, int n, const int32_t* last_sem_label, const float* last_corr_x, const float* last_corr_y,
+                           const float* last_x, const float* last_y, const float* last_d);
+int vdo_object_chain_end(vdo_frame_images* cur, float th_depth_obj, const float Tcw_cur[16], const float Tcw_last[16], const float K4[4],
+                         int* n_recovered, float* depth_out, int32_t* sem_out, float* flow3d_out, int32_t* obj_label_out);
 /* Optional, new (no counterpart in the reference): the inputs of vdo_object_chain that belong to the LAST frame (mLastFrame's object set: vSemObjLabel, mvObjCorres,
  * mvObjKeys, mvObjDepth - src/Tracking.cc:1040-1063 leaves them final at the end of Track()) sent to the device a frame ahead, asynchronously on `ctx`'s stream.  The
  * next vdo_object_chain on a frame of that context uses them if - compared value by value - they are what it is called with, and otherwise stages its inputs itself. */

@@ -26,6 +26,7 @@ class Arena {
   // Make room for `bytes` of device scratch and as much pinned staging (called once, before any up/alloc:
   // growing re-allocates the blocks).
   bool reserve(size_t bytes) {
+    if (c_->arena_held) return false;                             // (an open object chain owns the blocks until its end)
     bytes = (bytes + 4095) & ~size_t(4095);
     if (bytes > c_->d_cap) {
       hipStreamSynchronize(s_);
@@ -73,7 +74,7 @@ class Arena {
   // between the last kernel and the synchronisation.  down() of such a pointer only hands the data over after finish().  Falls back to a device buffer.
   template <class T>
   T* out(size_t n) {
-    static const bool off = std::getenv("VDO_ARENA_NO_MAPPED_OUT") != nullptr;
+    const bool off = std::getenv("VDO_ARENA_NO_MAPPED_OUT") != nullptr;      // (read on every call: one process can run both paths)
     if (off || !c_->h_arena_dev) return up<T>(nullptr, n);
     const size_t a = (off_ + 255) & ~size_t(255), bytes = n * sizeof(T);
     if (!c_->d_arena || !c_->h_arena || a + bytes > c_->d_cap || a + bytes > c_->h_cap) return nullptr;
@@ -101,6 +102,13 @@ class Arena {
     if ((const char*)dev < c_->d_arena || o + n * sizeof(T) > c_->d_cap) { failed_ = true; return nullptr; }
     if (n) pend_.push_back({nullptr, o, n * sizeof(T), false});
     return (const T*)(c_->h_arena + o);
+  }
+  // Where the n elements at `dev` - an out() buffer or a device buffer - will be on the host once finish() has returned (valid until the context's arena is
+  // used again): for an output of which the caller hands over a part whose size it learns from another output
+  template <class T>
+  const T* view(const T* dev, size_t n) {
+    if (c_->h_arena_dev && (const char*)dev >= c_->h_arena_dev && (const char*)dev + n * sizeof(T) <= c_->h_arena_dev + c_->h_cap) return (const T*)(c_->h_arena + ((const char*)dev - c_->h_arena_dev));
+    return down_view(dev, n);
   }
   // the outputs come back (one copy of their span, or one per buffer when the span is mostly something else), one
   // synchronisation, then they reach the caller's arrays

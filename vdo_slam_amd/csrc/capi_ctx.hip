@@ -52,6 +52,10 @@ extern "C" int vdo_ctx_create(int device, void* hip_stream, vdo_ctx** out) {
 extern "C" int vdo_ctx_destroy(vdo_ctx* ctx) {
   if (!ctx) return VDO_OK;
   hipSetDevice(ctx->device);
+  if (ctx->chain_open) {                                 // (an object chain begun and never ended: its kernels may still be reading the arena)
+    hipStreamSynchronize(ctx->stream);
+    ctx->chain_open_free(ctx->chain_open);
+  }
   if (ctx->d_arena) hipFree(ctx->d_arena);
   if (ctx->h_arena) hipHostFree(ctx->h_arena);
   if (ctx->ba_slab) hipFree(ctx->ba_slab);

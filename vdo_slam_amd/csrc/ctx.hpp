@@ -13,6 +13,9 @@ struct vdo_ctx {
   char* d_arena = nullptr; size_t d_cap = 0;
   char* h_arena = nullptr; size_t h_cap = 0;
   char* h_arena_dev = nullptr;                    // the pinned block as the DEVICE sees it (mapped): kernels write small outputs straight into it (Arena::out)
+  // an object chain between its begin and its end (vdo_object_chain_begin, tracking_logic.hip): its state, how to free it, and the arena held for it -
+  // no other call reserves the arena meanwhile (Arena::reserve refuses)
+  void* chain_open = nullptr; void (*chain_open_free)(void*) = nullptr; bool arena_held = false;
   // inputs of the NEXT frame's object chain, staged ahead (vdo_object_chain_prestage, tracking_logic.hip): device block + pinned mirror + what the host
   // worked out while staging (label slots); n < 0: nothing staged
   char* d_stage = nullptr; char* h_stage = nullptr; size_t stage_cap = 0;

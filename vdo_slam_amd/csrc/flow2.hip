@@ -829,6 +829,14 @@ extern "C" int vdo_flow2_batch_set(vdo_flow2_batch* b, int k, const vdo_flow2_pr
   return VDO_OK;
 }
 
+// The initial pose of a slot that vdo_flow2_batch_set has filled, rewritten: for a caller that packs the correspondences before it knows the pose.
+extern "C" int vdo_flow2_batch_set_T0(vdo_flow2_batch* b, int k, const double T0[16]) {
+  if (!b || k < 0 || k >= b->n_problems || !b->h_up || !T0) return set_error(VDO_ERR_INVALID, "vdo_flow2_batch_set_T0: bad argument / batch not created by vdo_flow2_batch_reserve");
+  std::memcpy(b->hp[k].T0, T0, sizeof(b->hp[k].T0));
+  b->probs_dirty = true;                 // the descriptors go up in one copy at the next run
+  return VDO_OK;
+}
+
 extern "C" int vdo_flow2_batch_run(vdo_flow2_batch* b) {
   if (!b) return set_error(VDO_ERR_INVALID, "null handle");
   int rc = ctx_bind(b->ctx);

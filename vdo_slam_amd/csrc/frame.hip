@@ -322,6 +322,11 @@ extern "C" int vdo_sample_keypoints(int rows, int cols, uint64_t seed, int capac
   return VDO_OK;
 }
 
+void vdo::static_filter_launch(vdo_frame_images* f, hipStream_t s, int n, const float* d_kx, const float* d_ky, float th_depth, int sampled,
+                               int32_t* keep_idx, float* corr_x, float* corr_y, float* flow_x, float* flow_y, float* depth_out, int* n_out) {
+  hipLaunchKernelGGL(k_static_filter, dim3(1), dim3(1024), 0, s, n, d_kx, d_ky, (const int32_t*)f->d_mask, (const float*)f->d_depth, (const float*)f->d_flow, f->w, f->h, th_depth,
+                     keep_idx, corr_x, corr_y, flow_x, flow_y, depth_out, n_out, sampled);
+}
 static int static_filter_enqueue(vdo_frame_images* f, hipStream_t s, int n, const float* kx, const float* ky, float th_depth, int sampled) {
   // inputs: kx|ky -> pinned -> rows 8,9 in one strided H2D; outputs: rows 0..7 (5 float rows, 2 unused, idx) x n in one
   // strided D2H next to the count (m <= n is only known after the kernel): 1 sync, no pageable copies.

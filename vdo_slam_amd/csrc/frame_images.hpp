@@ -23,3 +23,10 @@ struct vdo_frame_images {
   float* d_rows2 = nullptr; int* d_cnt2 = nullptr; float* h_pin2 = nullptr;
   std::vector<void*> allocs;
 };
+
+namespace vdo {
+// The K9 kernel (frame.hip) alone, on keypoints and outputs of the caller's own (device pointers; the outputs n elements each + one count): no copy, no wait -
+// for a caller that queues more work on the stream and synchronises once (vdo_static_stage).  n > 0 is the caller's to check.
+void static_filter_launch(vdo_frame_images* f, hipStream_t s, int n, const float* d_kx, const float* d_ky, float th_depth, int sampled,
+                          int32_t* keep_idx, float* corr_x, float* corr_y, float* flow_x, float* flow_y, float* depth_out, int* n_out);
+}  // namespace vdo

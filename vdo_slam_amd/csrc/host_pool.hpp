@@ -42,6 +42,23 @@ class LevelPool {
     { std::lock_guard<std::mutex> g(mu_); cur_ = nullptr; }                       // from here on no worker can pick the batch up ...
     while (b.active.load(std::memory_order_acquire) != 0) std::this_thread::yield();   // ... and those that did have left it
   }
+  // The same, with work of the caller's own beside the batch: `mine` runs once on the calling thread as soon as the batch is published - the workers take the
+  // tasks meanwhile, whatever their number - and the caller then helps with what is left.
+  template <class F, class G>
+  void run_beside(int n_tasks, F&& fn, G&& mine) {
+    if (n_tasks <= 0) { mine(); return; }
+    std::lock_guard<std::mutex> serial(run_mu_);
+    Batch b;
+    b.fn = [&fn](int i) { fn(i); };
+    b.n = n_tasks;
+    { std::lock_guard<std::mutex> g(mu_); cur_ = &b; ++gen_; }
+    cv_.notify_all();
+    mine();
+    drain(b);
+    while (b.done.load(std::memory_order_acquire) < b.n) std::this_thread::yield();
+    { std::lock_guard<std::mutex> g(mu_); cur_ = nullptr; }
+    while (b.active.load(std::memory_order_acquire) != 0) std::this_thread::yield();
+  }
 
  private:
   struct Batch {

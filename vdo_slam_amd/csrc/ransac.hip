@@ -468,14 +468,21 @@ using namespace vdo;
 namespace {
 struct PnpTrace {            // (VDO_PNP_TRACE=1, debug; the pipelines of several sequences call in concurrently: updated under a mutex)
   std::mutex mu;
-  double t[5] = {0, 0, 0, 0, 0}; long n = 0; bool on = std::getenv("VDO_PNP_TRACE") != nullptr;
-  ~PnpTrace() { if (on && n) std::fprintf(stderr, "[pnp trace] calls %ld: setup %.1f us, gpu %.1f us, replay %.1f us, refit %.1f us (per call)\n", n, t[0] / n, t[1] / n, t[2] / n, t[3] / n); }
+  // [0]: calls of one problem (the camera), [1]: batches (the objects of a frame); refits = problems re-estimated by EPnP, of all that asked for it
+  double t[2][5] = {{0, 0, 0, 0, 0}, {0, 0, 0, 0, 0}}; long n[2] = {0, 0}, refits[2] = {0, 0}, asked[2] = {0, 0}; bool on = std::getenv("VDO_PNP_TRACE") != nullptr;
+  ~PnpTrace() {
+    for (int q = 0; q < 2; ++q)
+      if (on && n[q]) std::fprintf(stderr, "[pnp trace%s] calls %ld: setup %.1f us, gpu %.1f us, replay %.1f us, refit (+ the caller's work beside it) %.1f us (per call); EPnP refits %ld of %ld\n",
+                                   q ? "" : " single", n[q], t[q][0] / n[q], t[q][1] / n[q], t[q][2] / n[q], t[q][3] / n[q], refits[q], asked[q]);
+  }
 } g_pnp_trace;
 inline double pnp_now_us() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 }  // namespace
 
-extern "C" int vdo_pnp_ransac_batch_overlap(vdo_ctx* ctx, int n_problems, const vdo_pnp_problem* probs, vdo_pnp_result* results, uint8_t** inlier_out,
-                                            void (*host_work)(void*), void* host_arg) {
+// The batched call behind every entry point.  refit_above (nullable, read after host_work has returned): problem k is re-estimated only if its vote exceeds
+// refit_above[k]; after_replay (nullable): the caller's work on the final inlier flags and votes, on the calling thread, beside the refits on the pool threads.
+static int pnp_ransac_impl(vdo_ctx* ctx, int n_problems, const vdo_pnp_problem* probs, vdo_pnp_result* results, uint8_t** inlier_out, const int32_t* refit_above,
+                           void (*host_work)(void*), void* host_arg, void (*after_replay)(void*), void* after_arg, bool beside) {
   if (!ctx || !probs || !results || n_problems <= 0) return set_error(VDO_ERR_INVALID, "vdo_pnp_ransac_batch: bad argument");
   const double tr0 = g_pnp_trace.on ? pnp_now_us() : 0.0;
   int rc = ctx_bind(ctx);
@@ -503,7 +510,7 @@ extern "C" int vdo_pnp_ransac_batch_overlap(vdo_ctx* ctx, int n_problems, const 
     r.n_inliers = 0; r.iterations_run = 0; r.best_iteration = -1;
     if (inlier_out && inlier_out[k] && probs[k].n) std::memset(inlier_out[k], 0, (size_t)probs[k].n);
   }
-  if (tot_hyp == 0) { if (host_work) host_work(host_arg); return VDO_OK; }
+  if (tot_hyp == 0) { if (host_work) host_work(host_arg); if (after_replay) after_replay(after_arg); return VDO_OK; }
   // the subsets the sequential loop would draw (getSubset: 4 distinct indices by rejection, RNG seeded with (uint64)-1 per call):
   // a function of (point count, hypotheses) alone - the draws of a frame's problems cost ~30 us of the object chain, and the same
   // counts come back every few frames, so the tables are kept (8 KB per distinct count)
@@ -593,7 +600,13 @@ extern "C" int vdo_pnp_ransac_batch_overlap(vdo_ctx* ctx, int n_problems, const 
   // independent: one per pool task (the objects of a frame in parallel)
   const double tr3 = g_pnp_trace.on ? pnp_now_us() : 0.0;
   std::vector<int> todo;
-  for (int k = 0; k < n_problems; ++k) if ((probs[k].refit & 1) && results[k].n_inliers >= 4 && results[k].best_iteration >= 0) todo.push_back(k);
+  int asked = 0;
+  for (int k = 0; k < n_problems; ++k)
+    if ((probs[k].refit & 1) && results[k].n_inliers >= 4 && results[k].best_iteration >= 0) {
+      ++asked;
+      if (!refit_above || results[k].n_inliers > refit_above[k]) todo.push_back(k);      // (gated out: T stays the winning hypothesis, as with the refit bit off)
+    }
+  bool after_done = false;
   if (!todo.empty()) {
     const PnpDev* hp_main = hp.data();               // (hp is thread_local: a pool thread naming it would see ITS OWN, empty, vector)
     auto refit_one = [&, hp_main](int q) {
@@ -618,19 +631,36 @@ extern "C" int vdo_pnp_ransac_batch_overlap(vdo_ctx* ctx, int n_problems, const 
       return nw > 0 ? new LevelPool(std::min(nw, 15)) : nullptr;
     }();
     static std::mutex pool_mu;                       // (one batch at a time through the shared helpers; a second caller refits inline)
-    if (todo.size() > 1 && pool && pool_mu.try_lock()) {
-      pool->run((int)todo.size(), refit_one);
+    const bool mine = after_replay && beside;        // (the caller's work runs beside the refits - a single refit too goes to a pool thread then)
+    if ((todo.size() > 1 || mine) && pool && pool_mu.try_lock()) {
+      if (mine) { pool->run_beside((int)todo.size(), refit_one, [&] { after_replay(after_arg); }); after_done = true; }
+      else pool->run((int)todo.size(), refit_one);
       pool_mu.unlock();
     } else {
       for (int q = 0; q < (int)todo.size(); ++q) refit_one(q);
     }
   }
-  if (g_pnp_trace.on && n_problems > 1) {
+  if (after_replay && !after_done) after_replay(after_arg);
+  if (g_pnp_trace.on) {
     const double tr4 = pnp_now_us();
+    const int q = n_problems > 1 ? 1 : 0;
     std::lock_guard<std::mutex> lock(g_pnp_trace.mu);
-    g_pnp_trace.t[0] += tr1 - tr0; g_pnp_trace.t[1] += tr2 - tr1; g_pnp_trace.t[2] += tr3 - tr2; g_pnp_trace.t[3] += tr4 - tr3; ++g_pnp_trace.n;
+    g_pnp_trace.t[q][0] += tr1 - tr0; g_pnp_trace.t[q][1] += tr2 - tr1; g_pnp_trace.t[q][2] += tr3 - tr2; g_pnp_trace.t[q][3] += tr4 - tr3; ++g_pnp_trace.n[q];
+    g_pnp_trace.refits[q] += (long)todo.size(); g_pnp_trace.asked[q] += asked;
   }
   return VDO_OK;
+}
+
+extern "C" int vdo_pnp_ransac_batch_overlap(vdo_ctx* ctx, int n_problems, const vdo_pnp_problem* probs, vdo_pnp_result* results, uint8_t** inlier_out,
+                                            void (*host_work)(void*), void* host_arg) {
+  return pnp_ransac_impl(ctx, n_problems, probs, results, inlier_out, nullptr, host_work, host_arg, nullptr, nullptr, false);
+}
+
+extern "C" int vdo_pnp_ransac_batch_gated(vdo_ctx* ctx, int n_problems, const vdo_pnp_problem* probs, vdo_pnp_result* results, uint8_t** inlier_out,
+                                          const int32_t* refit_above, void (*host_work)(void*), void* host_arg, void (*after_replay)(void*), void* after_arg) {
+  // VDO_PNP_NO_GATE (A/B switch, read on every call): every problem that asks for it is re-estimated, and after_replay runs behind the refits
+  const bool gate = std::getenv("VDO_PNP_NO_GATE") == nullptr;
+  return pnp_ransac_impl(ctx, n_problems, probs, results, inlier_out, gate ? refit_above : nullptr, host_work, host_arg, after_replay, after_arg, gate);
 }
 
 extern "C" int vdo_pnp_ransac_batch(vdo_ctx* ctx, int n_problems, const vdo_pnp_problem* probs, vdo_pnp_result* results, uint8_t** inlier_out) {

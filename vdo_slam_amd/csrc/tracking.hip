@@ -253,15 +253,24 @@ extern "C" int vdo_scene_flow(vdo_ctx* ctx, int n, const float* cur_x, const flo
 // top-up keypoints) are judged, the carry-over truncation is a device-side selection, the "within 1 px of a carried key"
 // test runs against that selection, every candidate is back-projected - one copy back, one synchronisation; the
 // ORDER-dependent part (first-come, stride-20 interleave) stays on the host.  xyz_out may be NULL (K4 / Twc unused then).
-extern "C" int vdo_renew_static_world(vdo_frame_images* f, int n_tm, const int32_t* tm_sta, const float* stat_x, const float* stat_y,
-                                      int n_orb, const float* orb_x, const float* orb_y, int max_num_sta, const float K4[4], const float Twc[16],
-                                      float* key_x, float* key_y, float* corr_x, float* corr_y, float* flow_x, float* flow_y,
-                                      int32_t* inlier_id, float* depth_out, float* xyz_out, int* n_out) {
+// k9 != null: K9 of the same keypoints (vdo_frame_static_filter) is queued on the stream in front of the renewal kernels and collected behind the ONE
+// synchronisation (vdo_static_stage).  It reads the keypoints the renewal has sent and writes its rows and its count - each written once, by that kernel alone -
+// into the pinned block (Arena::out): K9 adds its kernel to the round trip and no copy operation.
+namespace {
+struct K9Args { float th_depth; int32_t* keep_idx; float *corr_x, *corr_y, *flow_x, *flow_y, *depth; int* n_out; };
+}
+static int renew_static_world_impl(vdo_frame_images* f, int n_tm, const int32_t* tm_sta, const float* stat_x, const float* stat_y,
+                                   int n_orb, const float* orb_x, const float* orb_y, int max_num_sta, const float K4[4], const float Twc[16],
+                                   float* key_x, float* key_y, float* corr_x, float* corr_y, float* flow_x, float* flow_y,
+                                   int32_t* inlier_id, float* depth_out, float* xyz_out, int* n_out, const K9Args* k9) {
   if (!f || !n_out || n_tm < 0 || n_orb < 0 || (xyz_out && (!K4 || !Twc))) return set_error(VDO_ERR_INVALID, "bad argument");
+  if (k9 && (!k9->n_out || 10 * (size_t)n_orb > 8 * (size_t)f->cap)) return set_error(VDO_ERR_INVALID, "bad argument / too many keypoints for the staging buffer");
+  if (k9) *k9->n_out = 0;
+  if (k9 && n_orb == 0) k9 = nullptr;                        // (K9 of no keypoints: nothing to launch, as in vdo_frame_static_filter)
   int rc = ctx_bind(f->ctx);
   if (rc != VDO_OK) return rc;
   Arena S(f->ctx);
-  if (!S.reserve(Arena::bytes_for(24 * ((size_t)n_tm + (size_t)n_orb) + 4 * (size_t)max_num_sta))) return set_error(VDO_ERR_OOM, "scratch arena: allocation failed");
+  if (!S.reserve(Arena::bytes_for(24 * ((size_t)n_tm + (size_t)n_orb) + 4 * (size_t)max_num_sta + (k9 ? 6 * (size_t)n_orb + 512 : 0)))) return set_error(VDO_ERR_OOM, "scratch arena: allocation failed");
   // phase 1 candidates: the inlier static keys, in TM_sta order
   std::vector<float> cx1, cy1; std::vector<int32_t> id1;
   for (int i = 0; i < n_tm; ++i) if (tm_sta[i] != -1) { cx1.push_back(stat_x[tm_sta[i]]); cy1.push_back(stat_y[tm_sta[i]]); id1.push_back(tm_sta[i]); }
@@ -276,6 +285,17 @@ extern "C" int vdo_renew_static_world(vdo_frame_images* f, int n_tm, const int32
   float *dfx2 = S.up<float>(nullptr, n_orb), *dfy2 = S.up<float>(nullptr, n_orb), *dd2 = S.up<float>(nullptr, n_orb), *dxyz2 = S.up<float>(nullptr, xyz_out ? 3 * (size_t)n_orb : 0);
   if (!dxyz2 || !dxyz1 || !dd2 || !dd1) return set_error(VDO_ERR_OOM, "scratch arena: allocation failed");
   hipStream_t s = S.stream();
+  const int32_t* k9_idx = nullptr; const float* k9_row[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; const int* k9_cnt = nullptr;
+  if (k9) {
+    int32_t* oi = S.out<int32_t>(n_orb);
+    float* orow[5];
+    for (float*& r : orow) r = S.out<float>(n_orb);
+    int* oc = S.out<int>(1);
+    if (!oi || !orow[0] || !orow[1] || !orow[2] || !orow[3] || !orow[4] || !oc) return set_error(VDO_ERR_OOM, "scratch arena: allocation failed");
+    static_filter_launch(f, s, n_orb, dx2, dy2, k9->th_depth, 0, oi, orow[0], orow[1], orow[2], orow[3], orow[4], oc);
+    k9_idx = S.view(oi, n_orb); k9_cnt = S.view(oc, 1);
+    for (int k = 0; k < 5; ++k) k9_row[k] = S.view(orow[k], n_orb);
+  }
   const Cam cam = xyz_out ? make_cam_Twc(K4, Twc) : Cam{};
   if (n1) {
     hipLaunchKernelGGL(k_renew_pred, dim3((n1 + 255) / 256), dim3(256), 0, s, n1, (const float*)dx1, (const float*)dy1, (const int32_t*)f->d_mask, (const float*)f->d_depth, (const float*)f->d_flow, f->w, f->h, dok1, dfx1, dfy1, dd1);
@@ -292,6 +312,16 @@ extern "C" int vdo_renew_static_world(vdo_frame_images* f, int n_tm, const int32
   if (xyz_out) { S.down(xyz1.data(), dxyz1, 3 * (size_t)n1); S.down(xyz2.data(), dxyz2, 3 * (size_t)n_orb); }
   rc = S.finish("vdo_renew_static");
   if (rc != VDO_OK) return rc;
+  if (k9) {
+    if (!k9_idx || !k9_cnt || !k9_row[4]) return set_error(VDO_ERR_OOM, "scratch arena: allocation failed");
+    const int m9 = *k9_cnt;
+    *k9->n_out = m9;
+    if (m9) {
+      float* dst[5] = {k9->corr_x, k9->corr_y, k9->flow_x, k9->flow_y, k9->depth};
+      for (int k = 0; k < 5; ++k) std::memcpy(dst[k], k9_row[k], 4 * (size_t)m9);
+      std::memcpy(k9->keep_idx, k9_idx, 4 * (size_t)m9);
+    }
+  }
   // carry-over: first-come, stop once size > max (the reference checks after every element, :2703-2709)
   int m = 0;
   for (int i = 0; i < n1; ++i) {
@@ -323,6 +353,28 @@ extern "C" int vdo_renew_static_world(vdo_frame_images* f, int n_tm, const int32
   }
   *n_out = m;
   return VDO_OK;
+}
+
+extern "C" int vdo_renew_static_world(vdo_frame_images* f, int n_tm, const int32_t* tm_sta, const float* stat_x, const float* stat_y,
+                                      int n_orb, const float* orb_x, const float* orb_y, int max_num_sta, const float K4[4], const float Twc[16],
+                                      float* key_x, float* key_y, float* corr_x, float* corr_y, float* flow_x, float* flow_y,
+                                      int32_t* inlier_id, float* depth_out, float* xyz_out, int* n_out) {
+  return renew_static_world_impl(f, n_tm, tm_sta, stat_x, stat_y, n_orb, orb_x, orb_y, max_num_sta, K4, Twc, key_x, key_y, corr_x, corr_y, flow_x, flow_y,
+                                 inlier_id, depth_out, xyz_out, n_out, nullptr);
+}
+
+// K9 of the ORB keypoints + RenewFrameInfo (static) + Get3DinWorld in ONE round trip: what vdo_frame_static_filter followed by vdo_renew_static_world return,
+// for a caller whose renewal tops up from the keypoints themselves (not from K9's set: the ORB mode once a last frame exists), so that K9's outputs need not
+// be on the host before the renewal is queued.
+extern "C" int vdo_static_stage(vdo_frame_images* f, int n_orb, const float* orb_x, const float* orb_y, float th_depth,
+                                int32_t* keep_idx, float* s_corr_x, float* s_corr_y, float* s_flow_x, float* s_flow_y, float* s_depth, int* n_static,
+                                int n_tm, const int32_t* tm_sta, const float* stat_x, const float* stat_y, int max_num_sta, const float K4[4], const float Twc[16],
+                                float* key_x, float* key_y, float* corr_x, float* corr_y, float* flow_x, float* flow_y,
+                                int32_t* inlier_id, float* depth_out, float* xyz_out, int* n_out) {
+  if (!n_static) return set_error(VDO_ERR_INVALID, "vdo_static_stage: bad argument");
+  const K9Args k9{th_depth, keep_idx, s_corr_x, s_corr_y, s_flow_x, s_flow_y, s_depth, n_static};
+  return renew_static_world_impl(f, n_tm, tm_sta, stat_x, stat_y, n_orb, orb_x, orb_y, max_num_sta, K4, Twc, key_x, key_y, corr_x, corr_y, flow_x, flow_y,
+                                 inlier_id, depth_out, xyz_out, n_out, &k9);
 }
 
 extern "C" int vdo_renew_static(vdo_frame_images* f, int n_tm, const int32_t* tm_sta, const float* stat_x, const float* stat_y,

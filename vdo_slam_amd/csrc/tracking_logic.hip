@@ -678,27 +678,50 @@ extern "C" int vdo_object_chain_prestage(vdo_ctx* ctx, int n, const int32_t* las
   return VDO_OK;
 }
 
-extern "C" int vdo_object_chain(vdo_frame_images* cur, vdo_frame_images* last, int n, const int32_t* last_sem_label, const float* last_corr_x, const float* last_corr_y,
-                                float th_depth_obj, const float Tcw_cur[16], const float* last_x, const float* last_y, const float* last_d, const float Tcw_last[16],
-                                const float K4[4], int* n_recovered, float* depth_out, int32_t* sem_out, float* flow3d_out, int32_t* obj_label_out) {
+// The chain in two halves (vdo_object_chain_begin / _end): UpdateMask needs the two image sets and the last frame's object set, only the scene flow needs the
+// current camera pose - a caller that is still waiting for that pose queues UpdateMask first.  What is open between the halves lives in the context: the arena
+// (held: nothing else may reserve it meanwhile) and where the inputs are on the device.
+namespace {
+struct ChainOpen {
+  Arena S;
+  vdo_frame_images* cur = nullptr;
+  int n = 0, L = 0;
+  bool staged = false;
+  const float *dcx = nullptr, *dcy = nullptr, *dlx = nullptr, *dly = nullptr, *dld = nullptr;
+  const int32_t* dll = nullptr;
+  int32_t* dflag = nullptr;
+  double tr_prep = 0, tr_launch = 0, tr_begin_end = 0;
+  explicit ChainOpen(vdo_ctx* c) : S(c) {}
+};
+void chain_open_free(void* p) { delete static_cast<ChainOpen*>(p); }
+double chain_now() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+void chain_close(vdo_ctx* ctx) {
+  if (ctx->chain_open) { chain_open_free(ctx->chain_open); ctx->chain_open = nullptr; }
+  ctx->arena_held = false;
+}
+}  // namespace
+
+extern "C" int vdo_object_chain_begin(vdo_frame_images* cur, vdo_frame_images* last, int n, const int32_t* last_sem_label, const float* last_corr_x, const float* last_corr_y,
+                                      const float* last_x, const float* last_y, const float* last_d) {
   if (!cur || !last || cur->w != last->w || cur->h != last->h || n < 0) return set_error(VDO_ERR_INVALID, "vdo_object_chain: bad argument");
-  if (n_recovered) *n_recovered = 0;
-  if (n == 0) return VDO_OK;
-  int rc = ctx_bind(cur->ctx);
-  if (rc != VDO_OK) return rc;
   vdo_ctx* ctx = cur->ctx;
-  // VDO_CHAIN_TRACE=1 (debugging): where the wall time of this call goes, every 20 calls on stderr
-  static const bool tr_on = std::getenv("VDO_CHAIN_TRACE") != nullptr;
-  static thread_local double tr_acc[6] = {0, 0, 0, 0, 0, 0}; static thread_local int tr_n = 0;
-  auto tr_now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double tr0 = tr_on ? tr_now() : 0.0;
-  Arena S(ctx);
-  if (!S.reserve(Arena::bytes_for(16 * (size_t)n + 512))) return set_error(VDO_ERR_OOM, "scratch arena: allocation failed");
-  static thread_local std::vector<int32_t> uni, flag;       // (per-thread scratch: no allocation in steady state)
+  if (ctx->chain_open) return set_error(VDO_ERR_INVALID, "vdo_object_chain_begin: a chain is already open on this context");
+  if (n == 0) return VDO_OK;
+  int rc = ctx_bind(ctx);
+  if (rc != VDO_OK) return rc;
+  // VDO_CHAIN_TRACE=1 (debugging): where the wall time of the two halves goes, every 20 chains on stderr
+  const bool tr_on = std::getenv("VDO_CHAIN_TRACE") != nullptr;
+  const double tr0 = tr_on ? chain_now() : 0.0;
+  ChainOpen* C = new ChainOpen(ctx);
+  ctx->chain_open = C; ctx->chain_open_free = &chain_open_free;
+  Arena& S = C->S;
+  if (!S.reserve(Arena::bytes_for(16 * (size_t)n + 512))) { chain_close(ctx); return set_error(VDO_ERR_OOM, "scratch arena: allocation failed"); }
+  ctx->arena_held = true;
+  static thread_local std::vector<int32_t> uni;             // (per-thread scratch: no allocation in steady state)
   static thread_local std::vector<int> off;
   static thread_local std::vector<float> gx, gy;
-  const float *dgx, *dgy, *dcx, *dcy, *dlx, *dly, *dld;
-  const int32_t *dll, *doff;
+  const float *dgx, *dgy;
+  const int32_t* doff;
   int L;
   // ---- the last frame's half of the inputs: staged ahead (and still what the caller passes), or staged now
   const ChainLayout q = chain_layout(n);
@@ -711,8 +734,8 @@ extern "C" int vdo_object_chain(vdo_frame_images* cur, vdo_frame_images* last, i
   ctx->stage_n = -1;                                       // (one use)
   if (staged) {
     const char* dv = ctx->d_stage;
-    dgx = (const float*)(dv + q.gx); dgy = (const float*)(dv + q.gy); dcx = (const float*)(dv + q.cx); dcy = (const float*)(dv + q.cy);
-    dlx = (const float*)(dv + q.lx); dly = (const float*)(dv + q.ly); dld = (const float*)(dv + q.ld); dll = (const int32_t*)(dv + q.ll); doff = (const int32_t*)(dv + q.off);
+    dgx = (const float*)(dv + q.gx); dgy = (const float*)(dv + q.gy); C->dcx = (const float*)(dv + q.cx); C->dcy = (const float*)(dv + q.cy);
+    C->dlx = (const float*)(dv + q.lx); C->dly = (const float*)(dv + q.ly); C->dld = (const float*)(dv + q.ld); C->dll = (const int32_t*)(dv + q.ll); doff = (const int32_t*)(dv + q.off);
     L = ctx->stage_L;
     uni.assign(ctx->stage_uni, ctx->stage_uni + L); off.assign(ctx->stage_off, ctx->stage_off + L + 1);
   } else {
@@ -722,35 +745,59 @@ extern "C" int vdo_object_chain(vdo_frame_images* cur, vdo_frame_images* last, i
     static thread_local std::vector<int32_t> off32;
     off32.assign(off.begin(), off.end());
     dgx = S.up(gx.data(), n); dgy = S.up(gy.data(), n);
-    dcx = S.up(last_corr_x, n); dcy = S.up(last_corr_y, n);
-    dlx = S.up(last_x, n); dly = S.up(last_y, n); dld = S.up(last_d, n);
-    dll = S.up(last_sem_label, n);
+    C->dcx = S.up(last_corr_x, n); C->dcy = S.up(last_corr_y, n);
+    C->dlx = S.up(last_x, n); C->dly = S.up(last_y, n); C->dld = S.up(last_d, n);
+    C->dll = S.up(last_sem_label, n);
     doff = S.up(off32.data(), off32.size());
-    if (!dgx || !dgy || !dcx || !dcy || !dlx || !dly || !dld || !dll || !doff) return set_error(VDO_ERR_OOM, "scratch arena exhausted");
+    if (!dgx || !dgy || !C->dcx || !C->dcy || !C->dlx || !C->dly || !C->dld || !C->dll || !doff) { chain_close(ctx); return set_error(VDO_ERR_OOM, "scratch arena exhausted"); }
   }
   unsigned long long* drec = S.up<unsigned long long>(nullptr, 1);
-  int32_t* dflag = S.up<int32_t>(nullptr, 2 * (size_t)L);  // (read by other workgroups of the votes: device memory; the last kernel copies it out)
+  C->dflag = S.up<int32_t>(nullptr, 2 * (size_t)L);        // (read by other workgroups of the votes: device memory; the last kernel copies it out)
+  if (!drec || !C->dflag) { chain_close(ctx); return set_error(VDO_ERR_OOM, "scratch arena exhausted"); }
+  C->cur = cur; C->n = n; C->L = L; C->staged = staged;
+  const double tr1 = tr_on ? chain_now() : 0.0;
+  launch_update_mask(cur, last, uni, off, dgx, dgy, doff, C->dflag, drec, S.stream());
+  if (tr_on) { const double tr2 = chain_now(); C->tr_prep = tr1 - tr0; C->tr_launch = tr2 - tr1; C->tr_begin_end = tr2; }
+  return VDO_OK;
+}
+
+extern "C" int vdo_object_chain_end(vdo_frame_images* cur, float th_depth_obj, const float Tcw_cur[16], const float Tcw_last[16], const float K4[4],
+                                    int* n_recovered, float* depth_out, int32_t* sem_out, float* flow3d_out, int32_t* obj_label_out) {
+  if (!cur || !Tcw_cur || !Tcw_last || !K4) return set_error(VDO_ERR_INVALID, "vdo_object_chain: bad argument");
+  if (n_recovered) *n_recovered = 0;
+  vdo_ctx* ctx = cur->ctx;
+  ChainOpen* C = static_cast<ChainOpen*>(ctx->chain_open);
+  if (!C) return VDO_OK;                                    // (a begin of no samples queued nothing)
+  if (C->cur != cur) return set_error(VDO_ERR_INVALID, "vdo_object_chain_end: the open chain belongs to another image set");
+  int rc = ctx_bind(ctx);
+  if (rc != VDO_OK) { chain_close(ctx); return rc; }
+  const bool tr_on = std::getenv("VDO_CHAIN_TRACE") != nullptr;
+  static thread_local double tr_acc[6] = {0, 0, 0, 0, 0, 0}; static thread_local int tr_n = 0;
+  const double tr0 = tr_on ? chain_now() : 0.0;
+  Arena& S = C->S;
+  const int n = C->n, L = C->L;
+  static thread_local std::vector<int32_t> flag;
   // outputs: written once by the last kernel, straight into the pinned block (Arena::out) - no device -> host copy
   int32_t* oflag = S.out<int32_t>(2 * (size_t)L);
   float* ddep = S.out<float>(n);
   int32_t* dsem = S.out<int32_t>(n);
   float* dfl = S.out<float>(3 * (size_t)n);
   int32_t* dol = S.out<int32_t>(n);
-  if (!drec || !dflag || !oflag || !ddep || !dsem || !dfl || !dol) return set_error(VDO_ERR_OOM, "scratch arena exhausted");
-  const double tr1 = tr_on ? tr_now() : 0.0;
-  launch_update_mask(cur, last, uni, off, dgx, dgy, doff, dflag, drec, S.stream());
+  if (!oflag || !ddep || !dsem || !dfl || !dol) { chain_close(ctx); return set_error(VDO_ERR_OOM, "scratch arena exhausted"); }
   // K11 (objects) on the updated mask, K13 on its outputs
   const int nth = std::max(n, 2 * L);
-  hipLaunchKernelGGL(k_gather_scene_flow, dim3((nth + 255) / 256), dim3(256), 0, S.stream(), n, dcx, dcy, (const float*)cur->d_depth, (const int32_t*)cur->d_mask,
+  hipLaunchKernelGGL(k_gather_scene_flow, dim3((nth + 255) / 256), dim3(256), 0, S.stream(), n, C->dcx, C->dcy, (const float*)cur->d_depth, (const int32_t*)cur->d_mask,
                      cur->w, cur->h, th_depth_obj, ddep, dsem, make_cam_Tcw(K4, Tcw_cur),
-                     dlx, dly, dld, dll, make_cam_Tcw(K4, Tcw_last), dfl, dol, (const int32_t*)nullptr, (const int32_t*)dflag, oflag, 2 * L);
+                     C->dlx, C->dly, C->dld, C->dll, make_cam_Tcw(K4, Tcw_last), dfl, dol, (const int32_t*)nullptr, (const int32_t*)C->dflag, oflag, 2 * L);
   flag.assign(2 * (size_t)L, 0);
   double tr2 = 0.0, tr3 = 0.0;
-  if (tr_on) { tr2 = tr_now(); hipStreamSynchronize(ctx->stream); tr3 = tr_now(); }
+  if (tr_on) { tr2 = chain_now(); hipStreamSynchronize(ctx->stream); tr3 = chain_now(); }
   S.down(flag.data(), oflag, flag.size()); S.down(depth_out, ddep, n); S.down(sem_out, dsem, n); S.down(flow3d_out, dfl, 3 * (size_t)n); S.down(obj_label_out, dol, n);
   rc = S.finish("vdo_object_chain");
-  if (tr_on) { const double tr4 = tr_now(); tr_acc[0] += tr1 - tr0; tr_acc[1] += tr2 - tr1; tr_acc[2] += tr3 - tr2; tr_acc[3] += tr4 - tr3; tr_acc[4] += staged ? 1 : 0;
-    if (++tr_n % 20 == 0) { std::fprintf(stderr, "vdo_object_chain: n %d L %d staged %.0f%% | prep %.1f us, launches enqueued %.1f, wait for the kernels %.1f, copy out %.1f\n", n, L, 100 * tr_acc[4] / 20, tr_acc[0] / 20, tr_acc[1] / 20, tr_acc[2] / 20, tr_acc[3] / 20); for (double& a : tr_acc) a = 0; } }
+  if (tr_on) { const double tr4 = chain_now(); tr_acc[0] += C->tr_prep; tr_acc[1] += C->tr_launch + (tr2 - tr0); tr_acc[2] += tr3 - tr2; tr_acc[3] += tr4 - tr3; tr_acc[4] += C->staged ? 1 : 0;
+    tr_acc[5] += tr0 - C->tr_begin_end;
+    if (++tr_n % 20 == 0) { std::fprintf(stderr, "vdo_object_chain: n %d L %d staged %.0f%% | prep %.1f us, launches enqueued %.1f, wait for the kernels %.1f, copy out %.1f, between begin and end %.1f\n", n, L, 100 * tr_acc[4] / 20, tr_acc[0] / 20, tr_acc[1] / 20, tr_acc[2] / 20, tr_acc[3] / 20, tr_acc[5] / 20); for (double& a : tr_acc) a = 0; } }
+  chain_close(ctx);
   if (rc != VDO_OK) return rc;
   int rec = 0;
   for (int s = 0; s < L; ++s) {
@@ -759,6 +806,15 @@ extern "C" int vdo_object_chain(vdo_frame_images* cur, vdo_frame_images* last, i
   }
   if (n_recovered) *n_recovered = rec;
   return VDO_OK;
+}
+
+extern "C" int vdo_object_chain(vdo_frame_images* cur, vdo_frame_images* last, int n, const int32_t* last_sem_label, const float* last_corr_x, const float* last_corr_y,
+                                float th_depth_obj, const float Tcw_cur[16], const float* last_x, const float* last_y, const float* last_d, const float Tcw_last[16],
+                                const float K4[4], int* n_recovered, float* depth_out, int32_t* sem_out, float* flow3d_out, int32_t* obj_label_out) {
+  if (n_recovered) *n_recovered = 0;
+  const int rc = vdo_object_chain_begin(cur, last, n, last_sem_label, last_corr_x, last_corr_y, last_x, last_y, last_d);
+  if (rc != VDO_OK || n == 0) return rc;
+  return vdo_object_chain_end(cur, th_depth_obj, Tcw_cur, Tcw_last, K4, n_recovered, depth_out, sem_out, flow3d_out, obj_label_out);
 }
 
 // ---- tracklets, incrementally: each frame only looks at its own association vector --------------------

@@ -51,6 +51,13 @@ class Flow2Batch:
             K.check(K.lib().vdo_flow2_batch_set(self._h, k, C.byref(s)))      # (the library copies the inputs into the slot)
         self.problems[k] = problem
 
+    def set_T0(self, k, T0):
+        """Rewrites the initial pose of slot ``k`` (vdo_flow2_batch_set_T0): the next run starts from it."""
+        T = np.ascontiguousarray(T0, dtype=np.float64).reshape(16)
+        L = K.lib()
+        L.vdo_flow2_batch_set_T0.argtypes = [C.c_void_p, C.c_int, K.c_double_p]
+        K.check(L.vdo_flow2_batch_set_T0(self._h, k, K._dp(T)))
+
     def run(self):
         K.check(K.lib().vdo_flow2_batch_run(self._h))
 

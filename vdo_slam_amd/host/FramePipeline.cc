@@ -9,6 +9,7 @@
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <thread>
 #include <stdexcept>
 
@@ -148,25 +149,30 @@ int FramePipeline::CameraStage() {
     vdo_pnp_problem pp{n_s, X.data(), uvd.data(), {p_.K4[0], p_.K4[1], p_.K4[2], p_.K4[3]}, 500, 0.4, 0.98, p_.pnp_refit};
     vdo_pnp_result pr;
     inl_ransac_cam_.assign(n_s, 0);
-    VDO_TRY(vdo_pnp_ransac(ctx_, &pp, &pr, inl_ransac_cam_.data()));
-    // motion-model inliers (mVelocity * last pose), same 0.4 px gate; the larger set seeds the optimisation
+    // One gated call (vdo_pnp_ransac_batch_gated).  Under its kernels: the motion-model inliers (mVelocity * last pose), same 0.4 px gate; the larger set seeds
+    // the optimisation, so the RANSAC model is re-estimated only if its vote beats that count.  Beside the re-estimation: TemperalMatch_subset and the packing of
+    // the LM problem, which need the inlier flags and not the model.
     float MM[16];
-    for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) { float a = 0; for (int k = 0; k < 4; ++k) a += vel_[4 * i + k] * Tcw_last_[4 * k + j]; MM[4 * i + j] = a; }
-    int mm = 0;
-    inl_mm_cam_.assign(n_s, 0);
-    for (int i = 0; i < n_s; ++i) {
-      const float x = sta_.xyz[3 * i], y = sta_.xyz[3 * i + 1], z = sta_.xyz[3 * i + 2];
-      const float xc = MM[0] * x + MM[1] * y + MM[2] * z + MM[3], yc = MM[4] * x + MM[5] * y + MM[6] * z + MM[7], invz = 1.0f / (MM[8] * x + MM[9] * y + MM[10] * z + MM[11]);
-      const float u_ = sta_.cx[i] - (p_.K4[0] * xc * invz + p_.K4[2]), v_ = sta_.cy[i] - (p_.K4[1] * yc * invz + p_.K4[3]);
-      if (std::sqrt(u_ * u_ + v_ * v_) < 0.4f) { inl_mm_cam_[i] = 1; ++mm; }
-    }
-    cam_n_ransac_ = pr.n_inliers; cam_n_mm_ = mm;
-    if (lm_cam_) {
+    int32_t mm = 0;
+    bool use_ransac = false;
+    int rc_set = VDO_OK;
+    std::function<void()> count_mm = [&] {
+      for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) { float a = 0; for (int k = 0; k < 4; ++k) a += vel_[4 * i + k] * Tcw_last_[4 * k + j]; MM[4 * i + j] = a; }
+      inl_mm_cam_.assign(n_s, 0);
+      for (int i = 0; i < n_s; ++i) {
+        const float x = sta_.xyz[3 * i], y = sta_.xyz[3 * i + 1], z = sta_.xyz[3 * i + 2];
+        const float xc = MM[0] * x + MM[1] * y + MM[2] * z + MM[3], yc = MM[4] * x + MM[5] * y + MM[6] * z + MM[7], invz = 1.0f / (MM[8] * x + MM[9] * y + MM[10] * z + MM[11]);
+        const float u_ = sta_.cx[i] - (p_.K4[0] * xc * invz + p_.K4[2]), v_ = sta_.cy[i] - (p_.K4[1] * yc * invz + p_.K4[3]);
+        if (std::sqrt(u_ * u_ + v_ * v_) < 0.4f) { inl_mm_cam_[i] = 1; ++mm; }
+      }
+    };
+    std::function<void()> pack_lm = [&] {
+      if (!lm_cam_) return;
       // TemperalMatch_subset + initial pose: RANSAC model if it has more inliers than the motion model (Tracking.cc:1690-1712)
-      const bool use_ransac = pr.n_inliers > mm;
+      use_ransac = pr.n_inliers > mm;
       const std::vector<uint8_t>& flag = use_ransac ? inl_ransac_cam_ : inl_mm_cam_;
       double T0[16];
-      for (int i = 0; i < 16; ++i) T0[i] = use_ransac ? (double)(float)pr.T[i] : (double)MM[i];     // iniTcw is a CV_32F Mat
+      for (int i = 0; i < 16; ++i) T0[i] = (double)MM[i];       // (the RANSAC model, where it wins, replaces it once it is final: below)
       cam_subset_.clear();
       std::vector<double>&ob = dcam_[2], &fl = dcam_[3], &dp = dcam_[4];
       ob.clear(); fl.clear(); dp.clear();
@@ -177,8 +183,19 @@ int FramePipeline::CameraStage() {
       }
       vdo_flow2_problem fp;
       fill_flow2(fp, (int)cam_subset_.size(), ob.data(), fl.data(), dp.data(), p_.K4, Tcw_last_, T0, 0.3, 100);
-      VDO_TRY(vdo_flow2_batch_set(lm_cam_, 0, &fp));        // (copied into the batch's pinned block: dcam_ is free again)
+      rc_set = vdo_flow2_batch_set(lm_cam_, 0, &fp);        // (copied into the batch's pinned block: dcam_ is free again)
       cam_run_ = lm_cam_; cam_n_pts_ = fp.n;
+      for (int i = 0; i < 16; ++i) Tcw_init_[i] = (float)T0[i];
+    };
+    auto call = [](void* f) { (*static_cast<std::function<void()>*>(f))(); };
+    uint8_t* rip = inl_ransac_cam_.data();
+    VDO_TRY(vdo_pnp_ransac_batch_gated(ctx_, 1, &pp, &pr, &rip, &mm, +call, &count_mm, +call, &pack_lm));
+    cam_n_ransac_ = pr.n_inliers; cam_n_mm_ = mm;
+    if (rc_set != VDO_OK) { std::fprintf(stderr, "FramePipeline: %s\n", vdo_last_error()); return -1; }
+    if (lm_cam_ && use_ransac) {
+      double T0[16];
+      for (int i = 0; i < 16; ++i) T0[i] = (double)(float)pr.T[i];     // iniTcw is a CV_32F Mat
+      VDO_TRY(vdo_flow2_batch_set_T0(lm_cam_, 0, T0));
       for (int i = 0; i < 16; ++i) Tcw_init_[i] = (float)T0[i];
     }
   } else if (lm_cam_) {
@@ -359,6 +376,21 @@ int FramePipeline::Step(const uint8_t* d_gray, const float* d_depth_raw, const f
     return 0;
   };
   tick(2);
+  // ---- UpdateMask (K15) ahead of the camera pose: of the object chain only the scene flow reads the pose this thread is about to wait for; UpdateMask needs the
+  // two image sets and the last frame's object set, final once that frame's object stage is over - which it is here unless that stage is still pending (deferred
+  // mode: the begin then follows FinishObjects below, the order it always had).  Its kernels run while the camera optimisation finishes (vdo_object_chain_begin).
+  struct ChainGuard {                                    // (never leave Step with a chain open on ctx_: its end closes it, whatever it returns)
+    vdo_frame_images* cur = nullptr; const float* K4 = nullptr;
+    ~ChainGuard() { if (cur) { const float I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}; vdo_object_chain_end(cur, 0.f, I4, I4, K4, nullptr, nullptr, nullptr, nullptr, nullptr); } }
+  } chain_guard;
+  const bool chain_split = std::getenv("VDO_PIPE_NO_CHAIN_SPLIT") == nullptr;      // (A/B switch, read every Step)
+  auto chain_begin = [&]() -> int {
+    VDO_TRY(vdo_object_chain_begin(cur, last, (int)obj_.cx.size(), obj_.sem.data(), obj_.cx.data(), obj_.cy.data(), obj_.x.data(), obj_.y.data(), obj_.d.data()));
+    chain_guard.cur = cur; chain_guard.K4 = p_.K4;
+    return 0;
+  };
+  if (chain_split && have_last_ && !pending_ && chain_begin() != 0) return -1;
+  mark(kEvChainBegun);
   // ---- consume the camera result
   float Tcw[16];
   for (int i = 0; i < 16; ++i) Tcw[i] = Tcw_last_[i];
@@ -417,8 +449,14 @@ int FramePipeline::Step(const uint8_t* d_gray, const float* d_depth_raw, const f
     int rec = 0;
     flow3d.resize(3 * (size_t)std::max(n_o, 1));
     olab.assign(n_o, -2);
-    VDO_TRY(vdo_object_chain(cur, last, n_o, obj_.sem.data(), obj_.cx.data(), obj_.cy.data(), p_.th_depth_obj, Tcw, obj_.x.data(), obj_.y.data(), obj_.d.data(),
-                             Tcw_last_, p_.K4, &rec, obj_depth.data(), obj_sem.data(), flow3d.data(), olab.data()));
+    if (!chain_split) {
+      VDO_TRY(vdo_object_chain(cur, last, n_o, obj_.sem.data(), obj_.cx.data(), obj_.cy.data(), p_.th_depth_obj, Tcw, obj_.x.data(), obj_.y.data(), obj_.d.data(),
+                               Tcw_last_, p_.K4, &rec, obj_depth.data(), obj_sem.data(), flow3d.data(), olab.data()));
+    } else {
+      if (!chain_guard.cur && chain_begin() != 0) return -1;     // (the last frame's object stage was pending at the top: its object set is final only now)
+      chain_guard.cur = nullptr;                                 // (the end closes the chain, whatever it returns)
+      VDO_TRY(vdo_object_chain_end(cur, p_.th_depth_obj, Tcw, Tcw_last_, p_.K4, &rec, obj_depth.data(), obj_sem.data(), flow3d.data(), olab.data()));
+    }
     fc.n_recovered_masks = rec;
   }
   // vdo_object_chain returns without a synchronisation when there are no object samples (n_o == 0): the asynchronous ingest of this frame's images
@@ -436,8 +474,12 @@ int FramePipeline::Step(const uint8_t* d_gray, const float* d_depth_raw, const f
     auto tp = std::chrono::steady_clock::now();
     auto tk = [&](int slot) { const auto t = std::chrono::steady_clock::now(); ms_[slot] += std::chrono::duration<double, std::milli>(t - tp).count(); tp = t; };
     VDO_TRY(vdo_propagate_static(cur, n_s, sta_.cx.data(), sta_.cy.data(), stat_depth.data()));      // K11 (static), see above
-    if (frame_filters() != 0) return -1;
-    tk(2); mark(kEvFilters);
+    // K9 and the renewal as ONE round trip (vdo_static_stage): the renewal tops up from the ORB keypoints themselves, K9's outputs feed only fc.n_static_new
+    // here - nothing is worth a synchronisation of its own.  Not where the renewal reads K9's set (UseSampleFeature) or where K10 shares K9's round trip.
+    const bool fused = !p_.use_sample_feature && k10_via_orb && std::getenv("VDO_PIPE_NO_FUSED_STATIC") == nullptr;      // (A/B switch, read every Step)
+    if (fused) { if (orb_join() != 0) return -1; size_filter_outputs(); }
+    else if (frame_filters() != 0) return -1;
+    tk(2); if (!fused) mark(kEvFilters);
     const int cs = p_.max_track_bg + 2;
     nsta.x.resize(cs); nsta.y.resize(cs); nsta.cx.resize(cs); nsta.cy.resize(cs); nsta.fx.resize(cs); nsta.fy.resize(cs); nsta.d.resize(cs);
     sta_asso.resize(cs);
@@ -454,6 +496,13 @@ int FramePipeline::Step(const uint8_t* d_gray, const float* d_depth_raw, const f
     inv_rigid(Tcw, Twc);
     nsta.xyz.resize(3 * (size_t)cs);
     // RenewFrameInfo (static) + Get3DinWorld (mvStat3DPointTmp) in one pass, one synchronisation
+    if (fused) {
+      VDO_TRY(vdo_static_stage(cur, kp.n, kx_.data(), ky_.data(), p_.th_depth_bg, keep.data(), f_[2].data(), f_[3].data(), f_[4].data(), f_[5].data(), f_[6].data(), &n_new_s,
+                               n_s, tm.data(), cur_sx.data(), cur_sy.data(), p_.max_track_bg, p_.K4, Twc,
+                               nsta.x.data(), nsta.y.data(), nsta.cx.data(), nsta.cy.data(), nsta.fx.data(), nsta.fy.data(), sta_asso.data(), nsta.d.data(), nsta.xyz.data(), &m));
+      fc.n_static_new = n_new_s;
+      mark(kEvFilters);
+    } else
     VDO_TRY(vdo_renew_static_world(cur, n_s, tm.data(), cur_sx.data(), cur_sy.data(), n_src, src_x, src_y, p_.max_track_bg, p_.K4, Twc,
                                    nsta.x.data(), nsta.y.data(), nsta.cx.data(), nsta.cy.data(), nsta.fx.data(), nsta.fy.data(), sta_asso.data(), nsta.d.data(), nsta.xyz.data(), &m));
     for (auto* v : {&nsta.x, &nsta.y, &nsta.cx, &nsta.cy, &nsta.fx, &nsta.fy, &nsta.d}) v->resize(m);
@@ -554,50 +603,69 @@ int FramePipeline::Step(const uint8_t* d_gray, const float* d_depth_raw, const f
           (*c.cnt)[a] = mm;
         }
       };
+      // One gated call (vdo_pnp_ransac_batch_gated): the motion-model count runs under its kernels and is the gate - an object whose motion model has at least
+      // as many inliers is seeded by it, its RANSAC model would not be read and is not re-estimated (-1, no motion of the last frame: always).  Beside the
+      // re-estimations, on this thread: the choice per object, the subsets, the slots and the packing of the LM problems, which need the inlier flags and the
+      // votes but no model; the RANSAC-seeded problems get their initial pose once the call has returned.
+      int rc_pack = 0;
+      std::function<void()> pack_lms = [&] {
+        for (int a = 0; a < n_objects; ++a) if (mm_cnt[a] >= 0 && !(pr[a].n_inliers > mm_cnt[a])) obj_use_mm_[a] = 1;
+        if (lm_obj_) {
+          // per object: ObjIdTest_in = inliers of the chosen model; fewer than 50 -> the object is not tracked this frame (Tracking.cc:879)
+          if ((int)obj_subsets_.size() < n_objects) obj_subsets_.resize(n_objects);      // (inner vectors keep their capacity from frame to frame)
+          for (int a = 0; a < n_objects; ++a) obj_subsets_[a].clear();
+          obj_stat_.assign(n_objects, 1);
+          obj_buf_.resize(n_objects);
+          int need_pts = 0;
+          for (int a = 0; a < n_objects; ++a) {
+            std::vector<int32_t>& sub = obj_subsets_[a];
+            const std::vector<uint8_t>& flag = obj_use_mm_[a] ? min_ : rin;
+            for (int q = off[a]; q < off[a + 1]; ++q) if (flag[q]) sub.push_back(idx[q]);
+            // (the reference also sets vObjLabel = -1 outside the chosen set, Tracking.cc:1841-1846: RenewFrameInfo only reads the labels of LM
+            // inliers, a subset of the chosen set, and then replaces vObjLabel, :2862,2991 - nothing observes it)
+            bool gated = true;                                                            // ground truth in both frames (Tracking.cc:791-841)
+            if (gate_on_) {
+              gated = std::find(gate_cur_.begin(), gate_cur_.end(), osem[a]) != gate_cur_.end() && std::find(gate_last_.begin(), gate_last_.end(), osem[a]) != gate_last_.end();
+              if (!gated) { sub.clear(); for (int q = off[a]; q < off[a + 1]; ++q) sub.push_back(idx[q]); }   // vnObjInlierID = ObjIdNew
+            }
+            if (!gated || (int)sub.size() < 50) obj_stat_[a] = 0;
+            else need_pts = std::max(need_pts, (int)sub.size());
+          }
+          if (ReserveObjectSlots(n_objects, need_pts) != 0) { rc_pack = -1; return; }    // every object gets a slot, whatever its size
+          for (int a = 0; a < n_objects; ++a) {
+            const std::vector<int32_t>& sub = obj_subsets_[a];
+            if (!obj_stat_[a]) { if (vdo_flow2_batch_set(lm_obj_, a, nullptr) != VDO_OK) rc_pack = -2; continue; }
+            ObjBuf& B = obj_buf_[a];
+            B.ob.clear(); B.fl.clear(); B.dp.clear();
+            for (int id : sub) { B.ob.push_back(obj_.x[id]); B.ob.push_back(obj_.y[id]); B.fl.push_back(obj_.fx[id]); B.fl.push_back(obj_.fy[id]); B.dp.push_back(obj_.d[id]); }
+            double T0[16];
+            for (int i = 0; i < 16; ++i) T0[i] = obj_use_mm_[a] ? (double)obj_mm_[16 * (size_t)a + i] : (i % 5 == 0 ? 1.0 : 0.0);   // (the RANSAC model, where it wins, is set once it is final: below)
+            vdo_flow2_problem fp;
+            fill_flow2(fp, (int)sub.size(), B.ob.data(), B.fl.data(), B.dp.data(), p_.K4, Tcw_last_, T0, 0.5, 200);
+            if (vdo_flow2_batch_set(lm_obj_, a, &fp) != VDO_OK) rc_pack = -2;
+          }
+          for (int a = n_objects; a < obj_slots_; ++a) if (vdo_flow2_batch_set(lm_obj_, a, nullptr) != VDO_OK) rc_pack = -2;
+        }
+      };
+      std::function<void()> count_mm = [&] { mm_work(&mmc); };
+      auto call = [](void* f) { (*static_cast<std::function<void()>*>(f))(); };
       static const bool mm_overlap = std::getenv("VDO_PIPE_NO_MM_OVERLAP") == nullptr;      // (A/B switch)
-      if (mm_overlap) VDO_TRY(vdo_pnp_ransac_batch_overlap(ctx_, n_objects, pp.data(), pr.data(), rip.data(), +mm_work, &mmc));
-      else { VDO_TRY(vdo_pnp_ransac_batch(ctx_, n_objects, pp.data(), pr.data(), rip.data())); mm_work(&mmc); }
+      if (mm_overlap) VDO_TRY(vdo_pnp_ransac_batch_gated(ctx_, n_objects, pp.data(), pr.data(), rip.data(), mm_cnt.data(), +call, &count_mm, +call, &pack_lms));
+      else { VDO_TRY(vdo_pnp_ransac_batch(ctx_, n_objects, pp.data(), pr.data(), rip.data())); mm_work(&mmc); pack_lms(); }
+      if (rc_pack != 0) { if (rc_pack == -2) std::fprintf(stderr, "FramePipeline: %s\n", vdo_last_error()); return -1; }
       for (int a = 0; a < n_objects; ++a) fc.n_ransac_obj += pr[a].n_inliers;
       for (int a = 0; a < n_objects; ++a) {
         if (mm_cnt[a] < 0) continue;
         fc.n_mm_inliers_obj += mm_cnt[a];
-        if (!(pr[a].n_inliers > mm_cnt[a])) { obj_use_mm_[a] = 1; ++fc.n_motion_model_obj; }
+        if (obj_use_mm_[a]) ++fc.n_motion_model_obj;
       }
       if (lm_obj_) {
-        // per object: ObjIdTest_in = inliers of the chosen model; fewer than 50 -> the object is not tracked this frame (Tracking.cc:879)
-        if ((int)obj_subsets_.size() < n_objects) obj_subsets_.resize(n_objects);      // (inner vectors keep their capacity from frame to frame)
-        for (int a = 0; a < n_objects; ++a) obj_subsets_[a].clear();
-        obj_stat_.assign(n_objects, 1);
-        obj_buf_.resize(n_objects);
-        int need_pts = 0;
         for (int a = 0; a < n_objects; ++a) {
-          std::vector<int32_t>& sub = obj_subsets_[a];
-          const std::vector<uint8_t>& flag = obj_use_mm_[a] ? min_ : rin;
-          for (int q = off[a]; q < off[a + 1]; ++q) if (flag[q]) sub.push_back(idx[q]);
-          // (the reference also sets vObjLabel = -1 outside the chosen set, Tracking.cc:1841-1846: RenewFrameInfo only reads the labels of LM
-          // inliers, a subset of the chosen set, and then replaces vObjLabel, :2862,2991 - nothing observes it)
-          bool gated = true;                                                            // ground truth in both frames (Tracking.cc:791-841)
-          if (gate_on_) {
-            gated = std::find(gate_cur_.begin(), gate_cur_.end(), osem[a]) != gate_cur_.end() && std::find(gate_last_.begin(), gate_last_.end(), osem[a]) != gate_last_.end();
-            if (!gated) { sub.clear(); for (int q = off[a]; q < off[a + 1]; ++q) sub.push_back(idx[q]); }   // vnObjInlierID = ObjIdNew
-          }
-          if (!gated || (int)sub.size() < 50) obj_stat_[a] = 0;
-          else need_pts = std::max(need_pts, (int)sub.size());
-        }
-        if (ReserveObjectSlots(n_objects, need_pts) != 0) return -1;                    // every object gets a slot, whatever its size
-        for (int a = 0; a < n_objects; ++a) {
-          const std::vector<int32_t>& sub = obj_subsets_[a];
-          if (!obj_stat_[a]) { VDO_TRY(vdo_flow2_batch_set(lm_obj_, a, nullptr)); continue; }
-          ObjBuf& B = obj_buf_[a];
-          B.ob.clear(); B.fl.clear(); B.dp.clear();
-          for (int id : sub) { B.ob.push_back(obj_.x[id]); B.ob.push_back(obj_.y[id]); B.fl.push_back(obj_.fx[id]); B.fl.push_back(obj_.fy[id]); B.dp.push_back(obj_.d[id]); }
+          if (!obj_stat_[a] || obj_use_mm_[a]) continue;
           double T0[16];
-          for (int i = 0; i < 16; ++i) T0[i] = obj_use_mm_[a] ? (double)obj_mm_[16 * (size_t)a + i] : (double)(float)pr[a].T[i];   // mInitModel (CV_32F)
-          vdo_flow2_problem fp;
-          fill_flow2(fp, (int)sub.size(), B.ob.data(), B.fl.data(), B.dp.data(), p_.K4, Tcw_last_, T0, 0.5, 200);
-          VDO_TRY(vdo_flow2_batch_set(lm_obj_, a, &fp));
+          for (int i = 0; i < 16; ++i) T0[i] = (double)(float)pr[a].T[i];                  // mInitModel (CV_32F)
+          VDO_TRY(vdo_flow2_batch_set_T0(lm_obj_, a, T0));
         }
-        for (int a = n_objects; a < obj_slots_; ++a) VDO_TRY(vdo_flow2_batch_set(lm_obj_, a, nullptr));
         obj = lm_obj_; n_obj_problems = obj_slots_;
       }
     } else if (lm_obj_) {

@@ -114,7 +114,7 @@ class FramePipeline {
   // VDO_PIPE_EVENTS=1 (debug / bench): when, relative to the start of its Step, each milestone of a frame was reached - summed over the
   // Steps since the last reset (host_pipeline_events).  Slots: kEv* below.
   enum { kEvInputs = 0, kEvCamFetched, kEvObjChain, kEvDynObj, kEvObjLmBuilt, kEvObjLmLaunched, kEvOrbDevice, kEvOrbDone, kEvFilters, kEvStaticDone,
-         kEvStaticJoined, kEvCamStageDone, kEvObjLmFetched, kEvObjRenewed, kEvObjDone, kEvStepEnd, kEvCount };
+         kEvStaticJoined, kEvCamStageDone, kEvObjLmFetched, kEvObjRenewed, kEvObjDone, kEvStepEnd, kEvChainBegun, kEvCount };
   double ev_ms_[kEvCount] = {0}; long ev_n_[kEvCount] = {0};
   bool ev_on_ = false;
   std::chrono::steady_clock::time_point ev_t0_;

@@ -93,6 +93,34 @@ def renew_static(images, tm_sta, stat_x, stat_y, orb_x, orb_y, max_num_sta, worl
     return out
 
 
+def static_stage(images, orb_x, orb_y, th_depth, tm_sta, stat_x, stat_y, max_num_sta, world=None):
+    """vdo_static_stage: K9 of the ORB keypoints and RenewFrameInfo (static) topping up from the same keypoints, one round trip.
+    Returns (k9, renewed): ``k9`` as FrameImages.static_filter (keep_idx, corr_x, corr_y, flow_x, flow_y, depth), ``renewed`` as renew_static."""
+    tm, sx, sy, ox, oy = _i(tm_sta), _f(stat_x), _f(stat_y), _f(orb_x), _f(orb_y)
+    cap = max_num_sta + 2
+    f = [np.zeros(cap, np.float32) for _ in range(6)]
+    ids = np.zeros(cap, np.int32); d = np.zeros(cap, np.float32)
+    xyz = np.zeros((cap, 3), np.float32) if world is not None else None
+    K4, Twc = (_f(world[0]), _f(world[1])) if world is not None else (None, None)
+    kc = max(ox.size, 1)
+    kidx = np.zeros(kc, np.int32); kf = [np.zeros(kc, np.float32) for _ in range(5)]
+    n, m = C.c_int(), C.c_int()
+    L = K.lib()
+    fp, ip = K.c_float_p, K.c_int32_p
+    L.vdo_static_stage.argtypes = [C.c_void_p, C.c_int, fp, fp, C.c_float, ip, fp, fp, fp, fp, fp, C.POINTER(C.c_int),
+                                   C.c_int, ip, fp, fp, C.c_int, fp, fp, fp, fp, fp, fp, fp, fp, ip, fp, fp, C.POINTER(C.c_int)]
+    K.check(L.vdo_static_stage(images._h, ox.size, _fp(ox), _fp(oy), th_depth, _ip(kidx), *[_fp(a) for a in kf], C.byref(m),
+                               tm.size, _ip(tm), _fp(sx), _fp(sy), max_num_sta, _fp(K4) if world is not None else None, _fp(Twc) if world is not None else None,
+                               *[_fp(a) for a in f], _ip(ids), _fp(d), _fp(xyz) if world is not None else None, C.byref(n)))
+    n, m = n.value, m.value
+    k9 = dict(keep_idx=kidx[:m], corr_x=kf[0][:m], corr_y=kf[1][:m], flow_x=kf[2][:m], flow_y=kf[3][:m], depth=kf[4][:m])
+    out = {k: a[:n] for k, a in zip(("key_x", "key_y", "corr_x", "corr_y", "flow_x", "flow_y"), f)}
+    out["inlier_id"] = ids[:n]; out["depth"] = d[:n]
+    if world is not None:
+        out["xyz"] = xyz[:n]
+    return k9, out
+
+
 def mask_at(images, cx, cy):
     cx, cy = _f(cx), _f(cy)
     out = np.zeros(cx.size, np.int32)
@@ -199,6 +227,30 @@ def object_chain(cur_images, last_images, last_sem_label, last_corr_x, last_corr
     K.check(L.vdo_object_chain(cur_images._h, last_images._h, n, _ip(sl), _fp(cx), _fp(cy), th_depth_obj, _fp(Tc), _fp(lx), _fp(ly), _fp(ld), _fp(Tl), _fp(K4),
                                C.byref(rec), _fp(d), _ip(sem), _fp(fl), _ip(ol)))
     return rec.value, d, sem, fl, ol
+
+
+class ObjectChain:
+    """vdo_object_chain in two halves: ``ObjectChain(cur, last, ...)`` queues UpdateMask and returns without waiting (vdo_object_chain_begin);
+    ``end(th_depth_obj, Tcw_cur, Tcw_last, K4)`` queues the rest with the pose, waits and returns what object_chain returns.  The object keeps the
+    input arrays alive in between."""
+
+    def __init__(self, cur_images, last_images, last_sem_label, last_corr_x, last_corr_y, last_x, last_y, last_d):
+        self._cur = cur_images
+        self._in = (_i(last_sem_label), _f(last_corr_x), _f(last_corr_y), _f(last_x), _f(last_y), _f(last_d))
+        sl, cx, cy, lx, ly, ld = self._in
+        L = K.lib()
+        L.vdo_object_chain_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_int, K.c_int32_p] + [K.c_float_p] * 5
+        K.check(L.vdo_object_chain_begin(cur_images._h, last_images._h, sl.size, _ip(sl), _fp(cx), _fp(cy), _fp(lx), _fp(ly), _fp(ld)))
+
+    def end(self, th_depth_obj, Tcw_cur, Tcw_last, K4):
+        Tc, Tl, K4 = _f(Tcw_cur), _f(Tcw_last), _f(K4)
+        n = self._in[0].size
+        rec = C.c_int()
+        d = np.zeros(n, np.float32); sem = np.zeros(n, np.int32); fl = np.zeros((n, 3), np.float32); ol = np.zeros(n, np.int32)
+        L = K.lib()
+        L.vdo_object_chain_end.argtypes = [C.c_void_p, C.c_float, K.c_float_p, K.c_float_p, K.c_float_p, C.POINTER(C.c_int), K.c_float_p, K.c_int32_p, K.c_float_p, K.c_int32_p]
+        K.check(L.vdo_object_chain_end(self._cur._h, th_depth_obj, _fp(Tc), _fp(Tl), _fp(K4), C.byref(rec), _fp(d), _ip(sem), _fp(fl), _ip(ol)))
+        return rec.value, d, sem, fl, ol
 
 
 def object_chain_prestage(ctx, last_sem_label, last_corr_x, last_corr_y, last_x, last_y, last_d):
