@@ -73,7 +73,19 @@ def load():
     return L
 
 
-_prod_epnp = None
+_helpers = {}
+
+
+def _load_helper(name, header):
+    """tests/helpers/<name>.cpp (a C entry point in front of a plain-C++ header of the product) -> tests/helpers/lib<name>.so, rebuilt when either is newer."""
+    if name not in _helpers:
+        here = os.path.join(ROOT, "tests", "helpers")
+        src, out = os.path.join(here, name + ".cpp"), os.path.join(here, "lib" + name + ".so")
+        hdr = os.path.join(ROOT, "vdo_slam_amd", *header)
+        if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
+            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-shared", "-o", out, src], check=True)
+        _helpers[name] = C.CDLL(out)
+    return _helpers[name]
 
 
 def load_product_epnp():
@@ -81,18 +93,23 @@ def load_product_epnp():
     (tests/helpers/product_host_epnp.cpp).  Two uses: tests/test_epnp_independent.py compares it with the oracle's independent EPnP;
     the sequence tests hand it to OraclePipeline(seed_refit="product") so that both sides start every LM from the same float seed
     (see tests/pipeline_ref.py for why that is needed)."""
-    global _prod_epnp
-    if _prod_epnp is not None:
-        return _prod_epnp
-    here = os.path.join(ROOT, "tests", "helpers")
-    src, out = os.path.join(here, "product_host_epnp.cpp"), os.path.join(here, "libproduct_host_epnp.so")
-    hdr = os.path.join(ROOT, "vdo_slam_amd", "csrc", "epnp_refit.hpp")
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-shared", "-o", out, src], check=True)
-    L = C.CDLL(out)
+    L = _load_helper("product_host_epnp", ("csrc", "epnp_refit.hpp"))
     L.product_host_epnp.restype = C.c_double
     L.product_host_epnp.argtypes = [C.c_int] + [K.c_double_p] * 4
-    _prod_epnp = L
+    return L
+
+
+def load_product_frame_math():
+    """The PRODUCT's per-frame float arithmetic (vdo_slam_amd/host/frame_math.h - plain C++, no GPU) behind C entry points
+    (tests/helpers/product_frame_math.cpp), for tests/test_frame_math.py."""
+    L = _load_helper("product_frame_math", ("host", "frame_math.h"))
+    fp = K.c_float_p
+    L.product_fm_identity.argtypes = [fp]
+    L.product_fm_inv_rigid.argtypes = [fp, fp]
+    L.product_fm_mul44.argtypes = [fp, fp, fp]
+    L.product_fm_count_mm_inliers.restype = C.c_int
+    L.product_fm_count_mm_inliers.argtypes = [fp, fp, C.c_int, K.c_int32_p, fp, fp, fp, K.c_uint8_p]
+    L.product_fm_key_plus_flow.argtypes = [C.c_int, fp, K.c_double_p, fp]
     return L
 
 

@@ -1,4 +1,4 @@
-"""The four round-trip switches of FramePipeline (VDO_PIPE_NO_FUSED_STATIC, VDO_PIPE_NO_CHAIN_SPLIT, VDO_PNP_NO_GATE, VDO_ARENA_NO_MAPPED_OUT): each restores
+"""The round-trip switches of FramePipeline (VDO_PIPE_NO_FUSED_STATIC, VDO_PIPE_NO_CHAIN_SPLIT, VDO_PNP_NO_GATE, VDO_ARENA_NO_MAPPED_OUT, VDO_PIPE_NO_MM_OVERLAP): each restores
 an older schedule of the same work, none may change a result.  A synchronous pipeline with its helper and ORB threads (the configuration in which every new
 path is taken) runs a sequence with two moving objects and a mask that goes missing; all switches off against all on and each alone: poses, motions, every
 FrameCounts field of every frame, and the renewed static / object sets with their tracklets (the Map) are equal."""
@@ -12,7 +12,7 @@ from vdo_slam_amd.pipeline import FramePipeline, kitti_params
 pytestmark = pytest.mark.gpu
 
 W, H = synth.KITTI_W, synth.KITTI_H          # (the size every sequence test runs at)
-SWITCHES = ("VDO_PIPE_NO_FUSED_STATIC", "VDO_PIPE_NO_CHAIN_SPLIT", "VDO_PNP_NO_GATE", "VDO_ARENA_NO_MAPPED_OUT")
+SWITCHES = ("VDO_PIPE_NO_FUSED_STATIC", "VDO_PIPE_NO_CHAIN_SPLIT", "VDO_PNP_NO_GATE", "VDO_ARENA_NO_MAPPED_OUT", "VDO_PIPE_NO_MM_OVERLAP")      # (each is read when a pipeline is built)
 N_FRAMES = 7
 
 

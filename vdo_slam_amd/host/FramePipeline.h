@@ -18,7 +18,6 @@
 #include <functional>
 #include <memory>
 #include <atomic>
-#include <cstdlib>
 #include <vector>
 
 #include "../../include/vdo_slam_hip.h"
@@ -110,7 +109,10 @@ class FramePipeline {
   struct ObjectMotion { int mod_label, sem_label, n_inliers; float H[16]; };   // H: world-frame motion of the object from the last to this frame
   std::vector<ObjectMotion> motions_;   // objects tracked in the last Step (build_lm mode)
   float Tcw_out_[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-  double ms_[12] = {0};              // accumulated wall time per section (see host_pipeline_timing)
+  // accumulated wall time per section: the slots of pipeline.py's SECTIONS (host_pipeline_timing returns those 11), then K10 where the ORB thread runs it
+  enum { kSecK1K11RansacCam = 0, kSecOrb, kSecK9K10, kSecWaitCamLm, kSecK13DynObj, kSecRenewStatic, kSecWaitObjLm, kSecRenewObject, kSecTracklets, kSecRansacObj,
+         kSecK15K11Objects, kSecK10OnOrb, kSecCount };
+  double ms_[kSecCount] = {0};
   // VDO_PIPE_EVENTS=1 (debug / bench): when, relative to the start of its Step, each milestone of a frame was reached - summed over the
   // Steps since the last reset (host_pipeline_events).  Slots: kEv* below.
   enum { kEvInputs = 0, kEvCamFetched, kEvObjChain, kEvDynObj, kEvObjLmBuilt, kEvObjLmLaunched, kEvOrbDevice, kEvOrbDone, kEvFilters, kEvStaticDone,
@@ -123,12 +125,12 @@ class FramePipeline {
   // ---- the per-frame state the reference keeps in Tracking::mCurrentFrame / mLastFrame after Track() (RenewFrameInfo,
   // src/Tracking.cc:2780-2812, 2984-2991; per-object vectors :836-933), as views of the pipeline's own flat arrays.  Valid between
   // Steps, after Flush() in deferred mode; Tracking::SyncFrameState() turns them into the reference's containers.
-  struct ObjSet { std::vector<float> x, y, cx, cy, fx, fy, d, xyz; std::vector<int32_t> sem, label; };   // mvObjKeys, mvObjCorres, mvObjFlowNext, mvObjDepth, mvObj3DPoint, vSemObjLabel, vObjLabel
   struct StaSet { std::vector<float> x, y, cx, cy, fx, fy, d, xyz; };                                      // mvStatKeysTmp, mvCorres, mvFlowNext, mvStatDepthTmp, mvStat3DPointTmp
+  struct ObjSet : StaSet { std::vector<int32_t> sem, label; };                                            // mvObjKeys, mvObjCorres, mvObjFlowNext, mvObjDepth, mvObj3DPoint + vSemObjLabel, vObjLabel
   const StaSet& StaticSet() const { return sta_; }
   const ObjSet& ObjectSet() const { return obj_; }
-  const ObjSet& ObjectSamples() const { return tmpb_[tmp_idx_obj_]; }        // mvTmpObjKeys / Corres / FlowNext / Depth / SemObjLabel of the last frame (first n_object_samples entries)
-  int NumObjectSamples() const { return n_tmp_; }
+  const ObjSet& ObjectSamples() const { return tmpb_[ho_.tmp_idx]; }        // mvTmpObjKeys / Corres / FlowNext / Depth / SemObjLabel of the last frame (first n_object_samples entries)
+  int NumObjectSamples() const { return ho_.n_tmp; }
   const std::vector<int32_t>& ObjSemPosition() const { return last_sem_pos_; }   // nSemPosition
   const std::vector<int32_t>& ObjModLabel() const { return last_mod_label_; }    // nModLabel
   const std::vector<uint8_t>& ObjStat() const { return last_obj_stat_; }          // bObjStat
@@ -136,11 +138,33 @@ class FramePipeline {
   int MaxId() const { return max_id_; }                                           // max_id
 
  private:
+  // The environment switches of FramePipeline.cc, all read in one place, when the pipeline is built (ReadSwitches)
+  struct Switches { bool events, trace_slow, trace_obj, trace_batch, sync_upload, async_upload, chain_split, fused_static, mm_overlap, cam_ahead; };
+  static Switches ReadSwitches();
+  const Switches sw_ = ReadSwitches();
+  // Step() is these stages, in this order, over one StepState (FramePipeline.cc): what a Step owns and shares with the helper and ORB threads
+  struct StepState;
+  int StartOrb(StepState& s), OrbJob(StepState& s), SampleObjectsOnOrb(StepState& s), JoinOrb(StepState& s);      //  1. ORB on its own thread (OrbJob: extraction, then the
+                                            //     last frame's tail, then K10) or its device stage queued.  (2. the last frame's object stage starts: in Step)
+  int IngestImages(StepState& s);           //  3. images, K1
+  int CameraAndLateUpload(StepState& s);    //  4. CameraStage unless it ran ahead; flow + mask of host inputs; keypoints where this thread makes them
+  int BeginChain(StepState& s);             //  5. UpdateMask's front half, ahead of the camera pose
+  int ConsumeCamera(StepState& s);          //  6. camera pose, current static keys
+  int JoinLastObjects(StepState& s);        //  7. the last frame's object set is final; its tail goes on behind
+  int EndChain(StepState& s);               //  8. UpdateMask, K11 (objects), scene flow
+  int FrameFilters(StepState& s), StaticStage(StepState& s);      //  9. K9 (+ K10), RenewFrameInfo (static), static tracklets - on the helper thread if there is one
+  int InitFirstFrame(StepState& s);         // 10. Initialization()
+  int ObjectProblems(StepState& s);         // 11. DynObjTracking, batched RANSAC under the motion-model gate, LM packing
+  void CommitFrame(StepState& s);           // 13. store, sta_, mVelocity, pose, ids.  (12. launch, joins, hand-over and 14. camera stage ahead, FinishObjects: in Step)
   int CameraStage();                        // GetInitModelCam + launch of the camera optimisation for the frame after the last one
   int FinishObjects(FrameCounts* fc, bool defer_tail = false);
   int FinishObjectsTail(FrameCounts* fc);   // dynamic tracklets, Map, windowed optimisation: nothing the next frame's object chain waits for
-  bool tail_pending_ = false, tail_has_lm_ = false;
-  std::vector<int32_t> dyn_asso_tail_;
+  void CountObjectMotionModels(const float* Tcw, int n_objects, int* cnt);
+  int PackObjectLms(int n_objects, const vdo_pnp_result* pr, const int* mm_cnt);
+  int SampleCap() const { return ((p_.width + 3) / 4) * ((p_.height + 3) / 4); }      // K10 samples every 4th pixel
+  void SizeFilterOutputs(int n);
+  void SizeSampleOutputs(ObjSet& tmp);
+  bool tail_pending_ = false;
   GraphStore store_;
   TrackList tl_sta_, tl_dyn_;
   bool keep_graph_ = false;
@@ -149,7 +173,6 @@ class FramePipeline {
   bool depth_on_host_ = false;
   std::vector<int> gate_cur_, gate_last_;
   Map* map_ = nullptr;
-  int f_id_obj_ = 0;                  // frame id of the pending object stage
   float cam_motion_[16];              // Converter::toInvMatrix(mVelocity) of the frame whose object stage is pending
   class Worker;
   std::unique_ptr<Worker> worker_;
@@ -157,12 +180,21 @@ class FramePipeline {
   std::atomic<bool> tail_done_{true};
   bool orb_split_ = false;
   vdo_ctx *ctx_, *ctx_lm_, *ctx_obj_, *ctx_w_, *ctx_orb_ = nullptr;
-  // object stage handed from Step() to FinishObjects()
+  // The object stage of a frame, handed from Step() to FinishObjects() / FinishObjectsTail().  WRITTEN by Step on the main thread: olab by EndChain; off, idx,
+  // osem, omod (DynObjTracking's objects) and subsets, stat, use_mm (PackObjectLms) by ObjectProblems; the rest by LaunchJoinHandOver, which sets pending_
+  // (frame 0: n_tmp, tmp_idx by InitFirstFrame).  READ by FinishObjects, which writes dyn_asso_tail / tail_has_lm for FinishObjectsTail (that reads f_id too).
+  // Synchronous mode: both run at the end of the same Step, on the main thread.  Deferred mode: inside the NEXT Step (or Flush) - FinishObjects on the helper
+  // thread from stage 2 to stage 7, or on the main thread in stage 7; the tail behind it on the ORB or the helper thread, joined before stage 12 / stage 9.
+  // That Step writes none of this before those joins: its first write is EndChain's (stage 8), and the tail's fields are next written by stage 14 or later.
+  struct ObjHandOver {
+    std::vector<int32_t> olab, off, idx, osem, omod;      // label per object sample; per object: its samples (CSR), semantic and motion label
+    int n_objects = 0, n_obj_problems = 0, n_tmp = 0, f_id = 0, tmp_idx = 0;      // ...; frame id of the stage; which of tmpb_ it reads
+    vdo_flow2_batch* obj_run = nullptr; vdo_frame_images* img = nullptr; float Tcw[16];      // the launched object LMs (NULL: none), the frame's images and pose
+    std::vector<std::vector<int32_t>> subsets;            // per object: the correspondences in its LM
+    std::vector<uint8_t> stat, use_mm;                     // bObjStat; use_mm[a]: the motion model seeds object a's LM
+    std::vector<int32_t> dyn_asso_tail; bool tail_has_lm = false;
+  } ho_;
   bool pending_ = false;
-  int n_objects_ = 0, n_obj_problems_ = 0, n_tmp_ = 0;
-  vdo_flow2_batch* obj_run_ = nullptr;
-  vdo_frame_images* img_obj_ = nullptr;
-  float Tcw_obj_[16];
   PipelineParams p_;
   vdo_orb* orb_ = nullptr;
   vdo_frame_images* img_[2] = {nullptr, nullptr};
@@ -172,7 +204,6 @@ class FramePipeline {
   int32_t max_id_ = 1;
   StaSet sta_;                        // last frame: static keys + their correspondences in the next image
   ObjSet tmpb_[2];                    // K10 output of a frame, by image-set index (the object stage of frame k-1 reads [k-1] while frame k fills [k])
-  int tmp_idx_obj_ = 0;               // which of the two the pending object stage reads
   std::atomic<int> orb_ready_{0};     // +-(frame id + 1): keypoints and speculative K9 / K10 of that frame are there (negative: failed)
   std::atomic<int> objects_done_{0};  // +-(frame id + 1): the object stage the ORB thread's tail waits for is over (negative: no tail)
   std::atomic<int> mask_final_{0};    // +-(frame id + 1): UpdateMask of that frame is through (K10 on the ORB thread waits for it; negative: skip)
@@ -180,11 +211,14 @@ class FramePipeline {
   std::vector<int32_t> last_sem_pos_, last_mod_label_; std::vector<uint8_t> last_obj_stat_;
   std::vector<float> last_obj_mod_;   // mLastFrame.vObjMod: 16 floats per object of the last frame (identity for an object that was not tracked, Tracking.cc:836,884)
   float Tcw_last_[16], vel_[16];      // last pose, mVelocity
-  // scratch reused across frames
-  std::vector<float> kx_, ky_, kr_, ka_, ks_; std::vector<int32_t> ko_;
-  std::vector<float> f_[16]; std::vector<int32_t> i_[8];
+  // scratch reused across frames (the buffers keep their capacity)
+  std::vector<float> kx_, ky_, kr_, ka_, ks_; std::vector<int32_t> ko_;      // keypoints
+  std::vector<float> stat_depth_, obj_depth_, flow3d_;                        // K11 (static / objects), K13
+  std::vector<int32_t> obj_sem_, keep_, tm_;                                  // K11 (objects); K9's kept keypoints; TemperalMatch
+  std::vector<float> flt_cx_, flt_cy_, flt_fx_, flt_fy_, flt_d_;              // K9: correspondence, flow, depth of the kept keypoints
+  std::vector<float> cur_sx_, cur_sy_, cur_ox_, cur_oy_, src_x_, src_y_;      // current static / object keys; top-up source of UseSampleFeature
   std::vector<double> flow_out_; std::vector<uint8_t> inl_out_, inl_ransac_;
-  std::vector<double> d_[5];
+  std::vector<double> obj_X_, obj_uvd_, cam_X_, cam_uvd_;                     // RANSAC inputs of the objects / the camera
   // build_lm mode
   // object-LM slots: one per accepted object of a frame, each with room for obj_cap_ correspondences.  The reference has no
   // limit on either (src/Tracking.cc:785-1001 loops over all objects, an untracked label carries all its step-4 samples), so
@@ -192,21 +226,20 @@ class FramePipeline {
   int obj_slots_ = 8, obj_cap_ = 6000;
   int ReserveObjectSlots(int n_objects, int max_points);
   struct ObjBuf { std::vector<double> ob, fl, dp; };
+  int PackLm(vdo_flow2_batch* b, int slot, const std::vector<int32_t>& sub, const StaSet& S, ObjBuf& B, const double* T0, double info_prior, int max_it);
+  int SeedRansac(vdo_flow2_batch* b, int slot, const double* T, float* init);
   vdo_flow2_batch *lm_cam_ = nullptr, *lm_obj_ = nullptr;
   std::vector<int32_t> cam_subset_, inl_off_, inl_idx_;
-  std::vector<std::vector<int32_t>> obj_subsets_;
   std::vector<vdo_flow2_result> lm_rs_; std::vector<std::vector<double>> lm_fo_; std::vector<std::vector<uint8_t>> lm_io_;   // fetch buffers of the object LMs
   std::vector<double*> lm_fop_; std::vector<uint8_t*> lm_iop_;
-  std::vector<uint8_t> inl_mm_, obj_stat_, obj_use_mm_;   // obj_use_mm_[a]: the motion model seeds object a's LM
+  std::vector<uint8_t> inl_mm_;
   std::vector<float> obj_mm_;                             // MotionModel of the frame's objects (16 floats each)
-  std::vector<ObjBuf> obj_buf_;
+  std::vector<ObjBuf> obj_buf_; ObjBuf cam_buf_;
   float Tcw_init_[16];
   // camera stage (CameraStage): launched ahead of its frame or at the start of its Step
   bool cam_ahead_ = false;
-  bool cam_ahead_on_ = std::getenv("VDO_PIPE_NO_CAM_AHEAD") == nullptr;      // (read when the pipeline is built)
   vdo_flow2_batch* cam_run_ = nullptr;
   int cam_n_pts_ = 0, cam_n_ransac_ = 0, cam_n_mm_ = 0;
-  std::vector<double> dcam_[5];
   std::vector<uint8_t> inl_ransac_cam_, inl_mm_cam_;
 };
 
