@@ -340,8 +340,9 @@ int vdo_pnp_ransac(vdo_ctx* ctx, const vdo_pnp_problem* p, vdo_pnp_result* resul
  * Replaces ORBextractor::ORBextractor (reference src/ORBextractor.cc:399-459) and
  * ORBextractor::operator() (:1035-1110): ComputePyramid (:1112-1137), ComputeKeyPointsOctTree
  * (:754-842: per-cell cv::FAST with threshold fallback, DistributeOctTree :528-752, IC_Angle
- * :66-93) and the per-level 7x7 GaussianBlur (:1083-1084).  Descriptors are NOT produced: the
- * reference never computes them (call commented out at :1091). */
+ * :66-93) and the per-level 7x7 GaussianBlur (:1083-1084).  vdo_orb_extract produces no descriptors, as the
+ * reference does not (its computeDescriptors call is commented out at :1091); the rotated-BRIEF rows that call
+ * would have written come from vdo_orb_descriptors / vdo_orb_extract_desc (K8) on request, and vdo_orb_match* consume them. */
 typedef struct vdo_orb_params {
   int32_t n_features;     /* ORBextractor.nFeatures  2500 */
   float scale_factor;     /* ORBextractor.scaleFactor 1.2 */
@@ -368,6 +369,8 @@ int vdo_orb_destroy(vdo_orb* orb);
 /* Upper bound on the keypoints one extraction returns (sum over the levels with cells of max(4 nIni, quota + 2), see
  * vdo_orb_create): the `capacity` of a vdo_keypoints that never fails.  It can exceed n_features - by far for small budgets. */
 int vdo_orb_max_keypoints(const vdo_orb* orb, int* n);
+/* Keypoints the last vdo_orb_extract / _end returned (0 before the first): the rows vdo_orb_descriptors and vdo_orb_match_extractors work on. */
+int vdo_orb_last_keypoints(const vdo_orb* orb, int* n);
 /* gray: 8-bit single channel, row stride `stride` bytes; host pointer unless src_is_device. */
 int vdo_orb_extract(vdo_orb* orb, const uint8_t* gray, int stride, int src_is_device, vdo_keypoints* out);
 /* The same in two halves: _begin queues the device stage (K3, K4, K6, K7 + the copy of the candidates) on the extractor's stream
@@ -391,6 +394,62 @@ int vdo_orb_last_timing(vdo_orb* orb, double ms[2]);
  * 1 with <= 5 levels) - possible with <= 8 levels whose cascaded source windows fit the LDS buffers - or n_levels (level by
  * level; also forced by the environment variable VDO_ORB_PYRAMID_LAUNCHES). */
 int vdo_orb_pyramid_launches(const vdo_orb* orb);
+
+/* ---- ORB descriptor matcher ---------------------------------------------------------------------
+ * New (the reference keeps ORB-SLAM2's mDescriptors / mvKeysUn / feature grid but has no matcher): gated brute-force Hamming
+ * search between two sets of 32-byte rotated-BRIEF rows.  For query row i, train row j is a CANDIDATE iff every gate that is
+ * switched on passes:
+ *   window gate (window >= 0):           fabsf(tx[j] - qx[i]) <= window && fabsf(ty[j] - qy[i]) <= window  - one fp32 subtraction,
+ *                                        fabsf and compare per axis, nothing fused; a NaN position is never a candidate;
+ *   octave gate (max_octave_diff >= 0):  |toct[j] - qoct[i]| <= max_octave_diff.
+ * d(i, j) = popcount of the XOR of the two rows, 0..256.  Per query row:
+ *   best_dist    the smallest d over the candidates, -1 without a candidate;
+ *   second_dist  the second-smallest value of the MULTISET of candidate distances (== best_dist when two candidates tie), -1 with
+ *                fewer than two candidates;
+ *   train_idx    the lowest j that attains best_dist (what a sequential scan with strict < keeps) if every filter passes, else -1:
+ *     distance     best_dist <= max_distance;
+ *     ratio        only when 0 < ratio < 1 and a second candidate exists: (float)best_dist < ratio * (float)second_dist - one fp32
+ *                  multiply, strict compare;
+ *     cross-check  (cross_check != 0) the reverse best of train row j is i: over all query rows under the same gates, smallest
+ *                  distance, lowest query index on ties, whatever the distance and ratio filters say.
+ * *n_matches = rows with train_idx >= 0.  No result depends on chunk_rows or on any other tiling of the work. */
+
+/* One side of a match.  desc: n rows of 32 bytes.  x, y (fp32) and octave are nullable: x and y are read only with the window gate on,
+ * octave only with the octave gate on.  is_device: every pointer is a device pointer (desc 8-byte aligned), else a host pointer. */
+typedef struct vdo_match_set {
+  int32_t n;                        /* rows, 0 .. 1 << 24 */
+  const uint8_t* desc;              /* [n][32] */
+  const float *x, *y;               /* nullable */
+  const int32_t* octave;            /* nullable */
+  int32_t is_device;
+} vdo_match_set;
+
+/* Gates, filters and tiling of a match (see above). */
+typedef struct vdo_match_params {
+  int32_t max_distance;             /* 0..256; 256 accepts every best */
+  float ratio;                      /* ratio test for 0 < ratio < 1, off otherwise; not NaN */
+  float window;                     /* window gate half-width in pixels for >= 0, off for < 0; not NaN */
+  int32_t max_octave_diff;          /* octave gate for >= 0, off for < 0 */
+  int32_t cross_check;              /* != 0: keep mutual bests only */
+  int32_t chunk_rows;               /* train rows per workgroup: >= 1 is honoured exactly, 0 picks it (about two workgroups per CU at 2 500 x 2 500) */
+} vdo_match_params;
+
+/* Matches `query` against `train` on the context's stream and returns when the outputs - host arrays of query->n entries each, and
+ * *n_matches - are written.  With query->n == 0 or train->n == 0 nothing is launched and the outputs are -1.  Scratch comes from
+ * the context (grown on demand, freed with it).  VDO_ERR_INVALID, the message naming the argument: a null struct, descriptor or
+ * output pointer; window >= 0 without x and y on both sets; max_octave_diff >= 0 without octave on both sets; max_distance outside
+ * 0..256; NaN ratio or window; n < 0 or n > 1 << 24; chunk_rows < 0.  VDO_ERR_UNSUPPORTED: a caller-given chunk_rows so small that
+ * the partial results would take more than 65535 chunks or 1 GiB. */
+int vdo_orb_match(vdo_ctx* ctx, const vdo_match_set* query, const vdo_match_set* train, const vdo_match_params* prm, int32_t* train_idx,
+                  int32_t* best_dist, int32_t* second_dist, int32_t* n_matches);
+/* The same between the keypoints of the LAST EXTRACTION of two extractors, in the order vdo_orb_extract returned them, with no host
+ * round trip of descriptors or keypoints: K8 is queued for an extractor whose descriptors have not been asked for since, positions are
+ * the returned level-0 x, y (bit for bit), octaves the returned octaves.  A later vdo_orb_descriptors returns the same bytes as ever.
+ * The match runs on the query extractor's stream, ordered behind the train extractor's by an event; both must live on one device
+ * (VDO_ERR_INVALID otherwise) and may be one object.  Outputs: host, the query extractor's keypoint count entries each; VDO_ERR_INVALID
+ * when `capacity` is smaller than that, between vdo_orb_extract_begin and _end of either, and as for vdo_orb_match. */
+int vdo_orb_match_extractors(vdo_orb* query, vdo_orb* train, const vdo_match_params* prm, int32_t* train_idx, int32_t* best_dist,
+                             int32_t* second_dist, int32_t* n_matches, int32_t capacity);
 
 /* K1: Tracking::GrabImageRGBD depth preprocessing (src/Tracking.cc:180-204), in place. */
 int vdo_depth_preprocess(vdo_ctx* ctx, float* depth, int64_t n, float bf, float depth_map_factor, int is_device);

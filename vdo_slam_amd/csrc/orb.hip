@@ -26,6 +26,7 @@
 #include "../../include/vdo_slam_hip.h"
 #include "ctx.hpp"
 #include "host_pool.hpp"
+#include "orb_match.hpp"
 #include "orb_pattern.hpp"
 
 namespace vdo {
@@ -423,6 +424,20 @@ __global__ __launch_bounds__(256) void k_orb_desc(const uint8_t* __restrict__ bl
   if ((lane & 1) == 0) desc[(size_t)kp * 32 + (lane >> 1)] = (uint8_t)(nib | (hi << 4));
 }
 
+// The keypoints of the last extraction as vdo_orb_extract_end returns them, written on the device for the matcher: x, y of level 0 (the host's
+// arithmetic: candidate + 13 as one fp32 add, then - above level 0 - one fp32 multiply by the level's scale) and the octave, in output order.
+struct OrbScales { float v[16]; };
+__global__ __launch_bounds__(256) void k_orb_match_pos(const int* __restrict__ sel, int n, const float* __restrict__ dx, const float* __restrict__ dy,
+                                                       const int* __restrict__ dlvl, OrbScales sc, float* __restrict__ ox, float* __restrict__ oy,
+                                                       int32_t* __restrict__ ooct) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int id = sel[i], l = dlvl[id];
+  float x = dx[id] + (float)(kEdge - 3), y = dy[id] + (float)(kEdge - 3);
+  if (l != 0) { x = x * sc.v[l]; y = y * sc.v[l]; }
+  ox[i] = x; oy[i] = y; ooct[i] = l;
+}
+
 // all pyramid levels in ONE launch: blockIdx.x -> (level, tile) through the per-level tile offsets
 struct BlurTiles { int off[17]; int tiles_x[16]; };
 __global__ __launch_bounds__(256) void k_blur7_all(const uint8_t* __restrict__ pyr, const LevelDesc* __restrict__ levels, int n_levels, BlurTiles bt, Blur7 K,
@@ -635,6 +650,10 @@ struct vdo_orb {
   // K8 (on request): dense ids of the keypoints of the last extraction, device pattern / selection / descriptor rows
   std::vector<int> sel_dense;
   OrbPattern* d_pat = nullptr; int* d_sel = nullptr; uint8_t* d_desc = nullptr; int desc_cap = 0;
+  // what the matcher reads of the last extraction (orb_match_view): d_desc holds its descriptors (desc_ready), m_x / m_y / m_oct its level-0 positions
+  // and octaves in output order (pos_ready).  A new extraction clears both flags.
+  bool desc_ready = false, pos_ready = false;
+  float *m_x = nullptr, *m_y = nullptr; int32_t* m_oct = nullptr; int match_cap = 0;
   // pinned staging: [32 ints: level counts, total, largest cell count][5][kSpecCand] — header and candidates arrive with ONE sync
   float* h_pin = nullptr;
   float* h_over = nullptr; size_t h_over_n = 0;      // overflow staging when a frame has more than kSpecCand candidates
@@ -658,6 +677,12 @@ extern "C" int vdo_orb_pyramid_launches(const vdo_orb* o) {
 extern "C" int vdo_orb_max_keypoints(const vdo_orb* o, int* n) {
   if (!o || !n) return set_error(VDO_ERR_INVALID, "vdo_orb_max_keypoints: null argument");
   *n = o->max_kp;
+  return VDO_OK;
+}
+
+extern "C" int vdo_orb_last_keypoints(const vdo_orb* o, int* n) {
+  if (!o || !n) return set_error(VDO_ERR_INVALID, "vdo_orb_last_keypoints: null argument");
+  *n = (int)o->sel_dense.size();
   return VDO_OK;
 }
 
@@ -926,6 +951,7 @@ extern "C" int vdo_orb_extract_begin(vdo_orb* o, const uint8_t* gray, int stride
     src = o->d_src; sstride = o->w;
   }
   o->t_begin = std::chrono::steady_clock::now();
+  o->desc_ready = o->pos_ready = false;             // (the dense candidate arrays are overwritten from here on)
   orb_device_stage(o, src, sstride);
   // candidates -> host: header (level counts + total) and the first kSpecCand columns of the 5 candidate rows
   int* hdr = (int*)o->h_pin;
@@ -1013,14 +1039,8 @@ extern "C" int vdo_orb_extract_end(vdo_orb* o, vdo_keypoints* out) {
   return VDO_OK;
 }
 
-// K8: descriptors of the keypoints of the last extraction, in their output order.  desc32: host, [n][32].
-extern "C" int vdo_orb_descriptors(vdo_orb* o, uint8_t* desc32, int capacity_rows) {
-  if (!o || !desc32) return set_error(VDO_ERR_INVALID, "vdo_orb_descriptors: null argument");
-  const int n = (int)o->sel_dense.size();
-  if (n > capacity_rows) return set_error(VDO_ERR_INVALID, "vdo_orb_descriptors: %d keypoints, room for %d", n, capacity_rows);
-  if (n == 0) return VDO_OK;
-  int rc = ctx_bind(o->ctx);
-  if (rc != VDO_OK) return rc;
+// Queues K8 for the n keypoints of the last extraction on the extractor's stream: o->d_desc holds their descriptors once the stream gets there.
+static int orb_queue_descriptors(vdo_orb* o, int n) {
   hipStream_t s = o->ctx->stream;
   if (n > o->desc_cap) {
     const int cap = std::max(n, 4096);
@@ -1036,6 +1056,21 @@ extern "C" int vdo_orb_descriptors(vdo_orb* o, uint8_t* desc32, int capacity_row
   hipMemcpyAsync(o->d_sel, o->sel_dense.data(), 4 * (size_t)n, hipMemcpyHostToDevice, s);
   hipLaunchKernelGGL(k_orb_desc, dim3((n + 3) / 4), dim3(256), 0, s, (const uint8_t*)o->d_blur, (const LevelDesc*)o->d_levels, (const int*)o->d_sel, n,
                      (const float*)o->d_x, (const float*)o->d_y, (const float*)o->d_ang, (const int*)o->d_lvl, (const OrbPattern*)o->d_pat, o->d_desc);
+  o->desc_ready = true;
+  return VDO_OK;
+}
+
+// K8: descriptors of the keypoints of the last extraction, in their output order.  desc32: host, [n][32].
+extern "C" int vdo_orb_descriptors(vdo_orb* o, uint8_t* desc32, int capacity_rows) {
+  if (!o || !desc32) return set_error(VDO_ERR_INVALID, "vdo_orb_descriptors: null argument");
+  const int n = (int)o->sel_dense.size();
+  if (n > capacity_rows) return set_error(VDO_ERR_INVALID, "vdo_orb_descriptors: %d keypoints, room for %d", n, capacity_rows);
+  if (n == 0) return VDO_OK;
+  int rc = ctx_bind(o->ctx);
+  if (rc != VDO_OK) return rc;
+  rc = orb_queue_descriptors(o, n);
+  if (rc != VDO_OK) return rc;
+  hipStream_t s = o->ctx->stream;
   hipMemcpyAsync(desc32, o->d_desc, 32 * (size_t)n, hipMemcpyDeviceToHost, s);
   if (hipStreamSynchronize(s) != hipSuccess) return set_error(VDO_ERR_NO_DEVICE, "orb descriptors: %s", hipGetErrorString(hipGetLastError()));
   return VDO_OK;
@@ -1046,6 +1081,40 @@ extern "C" int vdo_orb_extract_desc(vdo_orb* o, const uint8_t* gray, int stride,
   int rc = vdo_orb_extract(o, gray, stride, src_is_device, out);
   if (rc != VDO_OK || !desc32) return rc;
   return vdo_orb_descriptors(o, desc32, out->capacity);
+}
+
+// What vdo_orb_match_extractors reads (orb_match.hpp): descriptors, level-0 positions and octaves of the last extraction, resident and in output order.
+// Everything is queued on the extractor's stream; nothing comes back to the host.
+int vdo::orb_match_view(vdo_orb* o, OrbMatchView* v) {
+  if (o->begun) return set_error(VDO_ERR_INVALID, "vdo_orb_match_extractors: an extraction is in flight (vdo_orb_extract_begin without _end)");
+  int rc = ctx_bind(o->ctx);
+  if (rc != VDO_OK) return rc;
+  const int n = (int)o->sel_dense.size();
+  v->ctx = o->ctx; v->n = n; v->desc = nullptr; v->x = v->y = nullptr; v->octave = nullptr;
+  if (n == 0) return VDO_OK;
+  hipStream_t s = o->ctx->stream;
+  if (!o->desc_ready) {
+    rc = orb_queue_descriptors(o, n);          // (also uploads d_sel, which the positions below go through)
+    if (rc != VDO_OK) return rc;
+  }
+  if (!o->pos_ready) {
+    if (n > o->match_cap) {
+      const int cap = std::max(n, 4096);
+      float* nx = nullptr;
+      if (hipMalloc((void**)&nx, 12 * (size_t)cap) != hipSuccess) return set_error(VDO_ERR_OOM, "hipMalloc failed");
+      hipStreamSynchronize(s);
+      if (o->m_x) { hipFree(o->m_x); o->allocs.erase(std::remove(o->allocs.begin(), o->allocs.end(), (void*)o->m_x), o->allocs.end()); }
+      o->m_x = nx; o->m_y = nx + cap; o->m_oct = (int32_t*)(nx + 2 * (size_t)cap); o->match_cap = cap;
+      o->allocs.push_back(nx);
+    }
+    OrbScales sc{};
+    for (int l = 0; l < o->prm.n_levels; ++l) sc.v[l] = o->scale[l];
+    hipLaunchKernelGGL(k_orb_match_pos, dim3((n + 255) / 256), dim3(256), 0, s, (const int*)o->d_sel, n, (const float*)o->d_x, (const float*)o->d_y,
+                       (const int*)o->d_lvl, sc, o->m_x, o->m_y, o->m_oct);
+    o->pos_ready = true;
+  }
+  v->desc = o->d_desc; v->x = o->m_x; v->y = o->m_y; v->octave = o->m_oct;
+  return VDO_OK;
 }
 
 // Wall time of the last vdo_orb_extract: [0] launch of the device stage .. candidates on the host, [1] host quadtree (K5)

@@ -26,6 +26,8 @@ class ORBextractor {
   // rotated BRIEF (computeOrbDescriptor, src/ORBextractor.cc:97-136): off = the reference as shipped (call commented out,
   // rows uninitialised); on = `descriptors` holds the 32-byte rows the commented-out call would have produced
   bool mbComputeDescriptors = false;
+  // the device extractor behind this object (null before the first image): what ORBmatcher matches two extractors through
+  vdo_orb* handle() const { return mOrb; }
 
  protected:
   int nfeatures;

@@ -10,6 +10,7 @@
 #include "Frame.h"
 #include "Map.h"
 #include "ORBextractor.h"
+#include "ORBmatcher.h"
 #include "Optimizer.h"
 #include "System.h"
 
@@ -176,6 +177,47 @@ int host_pose_optimization_objmot(int n, const float* last_xy, const float* dept
   for (int i = 0; i < n; ++i) { inlier_flag[i] = 0; obj_label_out[i] = cur.vObjLabel[i]; }
   for (int id : inliers) inlier_flag[id] = 1;
   return (int)inliers.size();
+}
+
+// ORBmatcher::DescriptorDistance of two 32-byte rows (host only: no device call)
+int host_descriptor_distance(const unsigned char* a, const unsigned char* b) {
+  cv::Mat A(1, 32, cv::CV_8UC1, (void*)a), B(1, 32, cv::CV_8UC1, (void*)b);
+  return ORBmatcher::DescriptorDistance(A, B);
+}
+
+// ORBmatcher::Match over flat keypoint arrays.  desc: [n][32]; matches / dist: [nq].  Returns the number of matches, -1 on a failure.
+int host_orb_match(int nq, const float* qx, const float* qy, const int* qoct, const unsigned char* qdesc, int nt, const float* tx, const float* ty, const int* toct,
+                   const unsigned char* tdesc, float nnratio, int cross_check, float window, int max_octave_diff, int max_distance, int* matches, int* dist) {
+  try {
+    std::vector<cv::KeyPoint> kq, kt;
+    for (int i = 0; i < nq; ++i) kq.push_back(cv::KeyPoint(qx[i], qy[i], 31.f, -1, 0, qoct[i]));
+    for (int i = 0; i < nt; ++i) kt.push_back(cv::KeyPoint(tx[i], ty[i], 31.f, -1, 0, toct[i]));
+    cv::Mat dq(nq, 32, cv::CV_8UC1, (void*)qdesc), dt(nt, 32, cv::CV_8UC1, (void*)tdesc);
+    ORBmatcher matcher(nnratio, cross_check != 0);
+    std::vector<int> m, d;
+    const int n = matcher.Match(kq, dq, kt, dt, window, max_octave_diff, max_distance, m, &d);
+    for (int i = 0; i < nq; ++i) { matches[i] = m[i]; dist[i] = d[i]; }
+    return n;
+  } catch (const std::exception& e) { std::fprintf(stderr, "host_orb_match: %s\n", e.what()); return -1; }
+}
+
+// Two ORBextractor objects (2500, 1.2, 8, 20, 7) on two gray images of one size, then ORBmatcher::Match(extractor, extractor): the device-resident
+// path.  *nq_out = keypoints of the first image; matches / dist: [cap].  Returns the number of matches, -1 on a failure (a too small cap included).
+int host_orb_match_extractors(const unsigned char* gray_q, const unsigned char* gray_t, int w, int h, float nnratio, int cross_check, float window,
+                              int max_octave_diff, int max_distance, int* matches, int* dist, int cap, int* nq_out) {
+  try {
+    ORBextractor eq(2500, 1.2f, 8, 20, 7), et(2500, 1.2f, 8, 20, 7);
+    cv::Mat Gq(h, w, cv::CV_8UC1, (void*)gray_q), Gt(h, w, cv::CV_8UC1, (void*)gray_t), none, dq, dt;
+    std::vector<cv::KeyPoint> kq, kt;
+    eq(Gq, none, kq, dq); et(Gt, none, kt, dt);
+    ORBmatcher matcher(nnratio, cross_check != 0);
+    std::vector<int> m, d;
+    const int n = matcher.Match(eq, et, window, max_octave_diff, max_distance, m, &d);
+    *nq_out = (int)m.size();
+    if ((int)m.size() > cap || m.size() != kq.size()) return -1;
+    for (size_t i = 0; i < m.size(); ++i) { matches[i] = m[i]; dist[i] = d[i]; }
+    return n;
+  } catch (const std::exception& e) { std::fprintf(stderr, "host_orb_match_extractors: %s\n", e.what()); return -1; }
 }
 
 // System::TrackRGBDFromFiles on one frame's four files (identity ground-truth pose; ground-truth object rows [n_rows][row_len] as in
