@@ -687,6 +687,69 @@ int vdo_ingest_frame(vdo_ingest* h, const char* mask_text, int64_t mask_bytes, c
  * ms[2] device time of the kernels alone (after the uploads). */
 int vdo_ingest_last_timing(vdo_ingest* h, double ms[3]);
 
+/* ---- Stereo matcher: census + semi-global matching -------------------------------------------------------------------------------
+ * New (the reference consumes a stereo disparity map x 256 as its depth input, src/Tracking.cc:180-204, and leaves making it to an offline
+ * matcher): from a rectified pair of 8-bit grey images to disparity in 1/256 px, float - the `depth_raw` image that
+ * vdo_frame_images_ingest_device(.., bf, 256, convert_depth = 1) and FramePipeline::Step take.  Integer arithmetic in every stage; the
+ * result does not depend on the order in which directions or workgroups run.  With W x H images, D = max_disparity, candidates d = 0 .. D-1:
+ *
+ * 1. Census, 9 wide x 7 high, 62 bits in a uint64.  For pixel (x, y), bit k is 1 iff I(clamp(x+dx, 0, W-1), clamp(y+dy, 0, H-1)) < I(x, y);
+ *    k counts the window offsets in raster order - dy = -3 .. 3 outer, dx = -4 .. 4 inner, the centre skipped - and bit k sits at bit position k.
+ * 2. Cost, 0 .. 62.  C(x, y, d) = popcount(cL(x, y) ^ cR(x-d, y)) when x - d >= 0, else 62.
+ * 3. Aggregation.  The directions r = (dx, dy) are the first `paths` of (1,0), (-1,0), (0,1), (0,-1), (1,1), (-1,1), (1,-1), (-1,-1); the
+ *    predecessor of p is p - r.  If p - r lies outside the image, L_r(p, d) = C(p, d); otherwise
+ *      L_r(p, d) = C(p, d) + min(L_r(p-r, d), L_r(p-r, d-1) + P1, L_r(p-r, d+1) + P1, m + P2) - m,   m = min_k L_r(p-r, k),
+ *    where a d-1 or d+1 outside [0, D) takes no part.  S = sum over r of L_r.  P1, P2 are constants.  L_r <= 62 + P2, so S <= 8 * (62 + P2) < 2^16.
+ * 4. Selection, per pixel; the output is 0 (invalid) as soon as one rule fails.  d* = argmin_d S(x, y, d), the lowest d on ties; s0 = its value.
+ *      (a) d* >= 1 (disparity 0 is infinite depth; K1 and the depth gates read 0 as "no depth");
+ *      (b) x - d* >= 0;
+ *      (c) uniqueness, if uniqueness > 0: 100 * s0 < (100 - uniqueness) * s2, s2 = the minimum of S over |d - d*| > 1 (+infinity, hence passed, if
+ *          there is no such d);
+ *      (d) left-right check, if lr_max_diff >= 0: dR(x', y) = argmin over d with x' + d < W of S(x'+d, y, d), lowest d on ties - the right image's
+ *          disparity read from the same volume; require |dR(x - d*, y) - d*| <= lr_max_diff.
+ *    Sub-pixel, if subpixel != 0, 1 <= d* <= D-2 and den = S(d*-1) + S(d*+1) - 2 * s0 > 0: num = 128 * (S(d*-1) - S(d*+1)),
+ *    off = sign(num) * ((2 * |num| + den) / (2 * den)) in integer division; otherwise off = 0.
+ *    Output: (float)(256 * d* + off) - an integer below 2^17, exact in fp32.  *n_valid = the number of non-zero outputs. */
+typedef struct vdo_stereo vdo_stereo;
+typedef struct vdo_stereo_params {
+  int32_t max_disparity;            /* D: a multiple of 16 in 16..256 */
+  int32_t p1, p2;                   /* 1 <= p1 <= p2 <= 1000 */
+  int32_t paths;                    /* 4 or 8 */
+  int32_t uniqueness;               /* 0..99; 0 switches rule (c) off */
+  int32_t lr_max_diff;              /* >= -1; -1 switches rule (d) off */
+  int32_t subpixel;                 /* != 0: sub-pixel offset */
+} vdo_stereo_params;
+/* A matcher for width x height images.  ALL device memory is taken here (two staged images, two census images, the uint8 cost volume
+ * [y][x][d], the uint16 volume of sums in the same layout, one float image): 3 bytes per volume entry + 22 per pixel; vdo_stereo_compute
+ * allocates nothing.  VDO_ERR_INVALID, the message naming the argument: width or height < 1; max_disparity not a multiple of 16 in 16..256;
+ * paths not 4 or 8; not 1 <= p1 <= p2 <= 1000; uniqueness outside 0..99; lr_max_diff < -1; a null pointer.  VDO_ERR_UNSUPPORTED when
+ * width * height * max_disparity > 2^28.  VDO_ERR_OOM when the device has no room. */
+int vdo_stereo_create(vdo_ctx* ctx, int width, int height, const vdo_stereo_params* params, vdo_stereo** out);
+int vdo_stereo_destroy(vdo_stereo* h);
+/* One pair, host-synchronous, on the context's stream.  left / right: rows of `width` bytes, *_stride bytes apart (>= width); host pointers, or
+ * device pointers when src_is_device != 0 (read where they are).  disparity256: width x height floats, packed, a device pointer when
+ * out_is_device != 0; n_valid: host.  VDO_ERR_INVALID, the message naming the argument, for a null image, output or count and a stride < width -
+ * and then NOTHING is written.  No state of an earlier compute on the handle enters the result. */
+int vdo_stereo_compute(vdo_stereo* h, const uint8_t* left, int64_t left_stride, const uint8_t* right, int64_t right_stride, int src_is_device,
+                       float* disparity256, int out_is_device, int32_t* n_valid);
+/* The output is multiplied by `scale` (fp32, one multiply fused into the selection; 1 by default, which changes no bit): a pipeline whose
+ * DepthMapFactor is f takes scale = f / 256, so that K1's d / f is the disparity in pixels again.  Only a power of two keeps that composition
+ * exact.  VDO_ERR_INVALID outside (0, 65536]. */
+int vdo_stereo_set_output_scale(vdo_stereo* h, float scale);
+/* Inspection of the LAST compute (VDO_ERR_INVALID before the first), host outputs: the census image of the left (which = 0) or right (1)
+ * image [H][W]; the cost volume [H][W][D]; the volume of sums S [H][W][D]. */
+int vdo_stereo_get_census(vdo_stereo* h, int which, uint64_t* out);
+int vdo_stereo_get_cost(vdo_stereo* h, uint8_t* out);
+int vdo_stereo_get_aggregated(vdo_stereo* h, uint16_t* out);
+/* The last compute: ms[0] wall time of the call, ms[1] device time from the first upload to the end of the selection kernel (events). */
+int vdo_stereo_last_timing(vdo_stereo* h, double ms[2]);
+/* Device images owned by the handle, for callers without their own: the packed width x height staging images a HOST pair is uploaded to (after
+ * such a compute `left` is the left image on the device) and a float image to pass as a device disparity256.  Any of the three may be NULL. */
+int vdo_stereo_device_images(vdo_stereo* h, uint8_t** left, uint8_t** right, float** disparity256);
+/* Brings the frame's other two host images (flow 2 x f32, mask i32, width x height, packed) to device images owned by the handle (made on the
+ * first call), for a caller that hands the whole frame to a device-input step (Tracking::GrabImageStereo).  Host-synchronous. */
+int vdo_stereo_stage_frame(vdo_stereo* h, const float* flow, const int32_t* mask, float** flow_dev, int32_t** mask_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -69,7 +69,8 @@ bool read_tracking_settings(const std::string& path, TrackingSettings& t, std::m
 }
 }  // namespace
 
-Tracking::Tracking(System*, Map* pMap, const std::string& strSettingPath, const int) : mpMap(pMap) {
+Tracking::Tracking(System*, Map* pMap, const std::string& strSettingPath, const int sensor) : mpMap(pMap) {
+  mSensor = sensor;
   TrackingSettings t{};
   if (!read_tracking_settings(strSettingPath, t, &cfg_)) { std::cerr << "Failed to open settings file at: " << strSettingPath << std::endl; std::exit(-1); }
   mK = cv::Mat::eye(3, 3, cv::CV_32F);
@@ -107,10 +108,20 @@ Tracking::Tracking(System*, Map* pMap, const std::string& strSettingPath, const 
   pipe_.reset(new FramePipeline(ctx_[0], ctx_[1], p, ctx_[2], ctx_[3], ctx_[4]));
   if (!pipe_->ok()) throw std::runtime_error(std::string("VDO_SLAM::Tracking: FramePipeline: ") + vdo_last_error());
   pipe_->AttachMap(mpMap);
+  if (mSensor == System::STEREO) {
+    const vdo_stereo_params d = StereoMatcher::DefaultParams();
+    const vdo_stereo_params sp{(int)get(cfg_, "Stereo.MaxDisparity", d.max_disparity), (int)get(cfg_, "Stereo.P1", d.p1), (int)get(cfg_, "Stereo.P2", d.p2),
+                               (int)get(cfg_, "Stereo.Paths", d.paths), (int)get(cfg_, "Stereo.Uniqueness", d.uniqueness), (int)get(cfg_, "Stereo.LRMaxDiff", d.lr_max_diff),
+                               (int)get(cfg_, "Stereo.SubPixel", d.subpixel)};
+    stereo_.reset(new StereoMatcher(ctx_[0], p.width, p.height, sp));
+    // depth_raw = disparity x DepthMapFactor: the matcher's 1/256 px scaled by factor / 256 (one fp32 multiply in its selection kernel)
+    if (vdo_stereo_set_output_scale(stereo_->handle(), mDepthMapFactor / 256.f) != VDO_OK) throw std::runtime_error(std::string("VDO_SLAM::Tracking: DepthMapFactor: ") + vdo_last_error());
+  }
 }
 
 Tracking::~Tracking() {
   pipe_.reset();
+  stereo_.reset();
   if (ingest_) vdo_ingest_destroy(ingest_);
   for (int k = 0; k < 5; ++k) if (ctx_[k]) vdo_ctx_destroy(ctx_[k]);
 }
@@ -169,6 +180,54 @@ cv::Mat Tracking::GrabImageRGBD(const cv::Mat& imRGB, cv::Mat& imD, const cv::Ma
   if (fc.n_recovered_masks > 0) pipe_->DownloadMask((int32_t*)maskSEM.data);      // UpdateMask writes through the shared header (Tracking.cc:3049-3068)
   if (trace_slow && since(t_call) > 5.0)
     std::fprintf(stderr, "[slow TrackRGBD f=%d] pre %.2f step %.2f depth %.2f mask(%d) %.2f ms\n", f_id, ms_pre, ms_step, ms_depth, fc.n_recovered_masks, since(t_call));
+  return FinishFrame(mTcw_gt, t_call);
+}
+
+cv::Mat Tracking::GrabImageStereo(const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat& imFlow, const cv::Mat& maskSEM, const cv::Mat& mTcw_gt,
+                                  const std::vector<std::vector<float> >& vObjPose_gt, const double&, cv::Mat&, const int& nImage) {
+  if (!stereo_) { std::cerr << "VDO_SLAM::Tracking::GrabImageStereo: the sensor is not STEREO" << std::endl; return cv::Mat(); }
+  StopFrame = nImage - 1;
+  if (!have_frame_) f_id = 0;
+  const auto t_call = std::chrono::steady_clock::now();
+  mLastProcessedState = mState;
+  if (mState == NO_IMAGES_YET) mState = NOT_INITIALIZED;
+  const int W = pipe_->params().width, H = pipe_->params().height;
+  {
+    auto bad = [&](const cv::Mat& m, const char* name, int depth, int ch_lo, int ch_hi) {
+      const bool ok = !m.empty() && m.rows == H && m.cols == W && m.depth() == depth && m.channels() >= ch_lo && m.channels() <= ch_hi &&
+                      m.step == (size_t)m.cols * m.elemSize();
+      if (!ok) std::cerr << "VDO_SLAM::Tracking::GrabImageStereo: " << name << " is " << m.cols << "x" << m.rows << " (type " << m.type() << ", step " << m.step
+                         << "), expected a continuous " << W << "x" << H << " image of the settings file's Camera.width/height" << std::endl;
+      return !ok;
+    };
+    if (bad(imLeft, "imLeft", cv::CV_8U, 1, 4) || imLeft.channels() == 2 || bad(imRight, "imRight", cv::CV_8U, 1, 4) || imRight.channels() == 2 ||
+        bad(imFlow, "imFlow", cv::CV_32F, 2, 2) || bad(maskSEM, "maskSEM", cv::CV_32S, 1, 1))
+      return cv::Mat();
+  }
+  const int64_t n = (int64_t)W * H;
+  auto to_gray = [&](const cv::Mat& im, std::vector<uint8_t>& buf) -> const uint8_t* {      // (cvtColor as in GrabImageRGBD; the caller's image is not touched)
+    if (im.channels() < 3) return im.data;
+    buf.resize((size_t)n);
+    if (vdo_rgb2gray(ctx_[0], im.data, n, im.channels(), mbRGB ? 1 : 0, buf.data()) != VDO_OK) { std::cerr << vdo_last_error() << std::endl; return nullptr; }
+    return buf.data();
+  };
+  const uint8_t *gl = to_gray(imLeft, gray_), *gr = to_gray(imRight, gray_right_);
+  if (!gl || !gr) return cv::Mat();
+  // the pair goes up into the matcher's staging images (its left one is the frame's grey image on the device from then on), the disparity
+  // into its device float image; the flow and the mask go up beside them
+  vdo_stereo* sh = stereo_->handle();
+  uint8_t* d_gray = nullptr; float *d_disp = nullptr, *d_flow = nullptr; int32_t* d_mask = nullptr;
+  int32_t n_valid = 0;
+  if (vdo_stereo_device_images(sh, &d_gray, nullptr, &d_disp) != VDO_OK || vdo_stereo_compute(sh, gl, W, gr, W, 0, d_disp, 1, &n_valid) != VDO_OK ||
+      vdo_stereo_stage_frame(sh, (const float*)imFlow.data, (const int32_t*)maskSEM.data, &d_flow, &d_mask) != VDO_OK) {
+    std::cerr << "VDO_SLAM::Tracking::GrabImageStereo: " << vdo_last_error() << std::endl; return cv::Mat();
+  }
+  std::vector<int> labels;
+  for (const auto& row : vObjPose_gt) if (row.size() > 1) labels.push_back((int)row[1]);
+  pipe_->SetObjectGate(labels.data(), (int)labels.size());
+  FrameCounts fc{};
+  if (pipe_->StepDevice(d_gray, d_disp, d_flow, d_mask, false, &fc) != 0) return cv::Mat();
+  if (fc.n_recovered_masks > 0) pipe_->DownloadMask((int32_t*)maskSEM.data);      // UpdateMask writes through the shared header, as in GrabImageRGBD
   return FinishFrame(mTcw_gt, t_call);
 }
 
@@ -337,6 +396,12 @@ cv::Mat System::TrackRGBDFromFiles(const std::string& rgbPath, const std::string
   return mpTracker->GrabFilesRGBD(rgbPath, depthPath, flowPath, maskPath, mTcw_gt, vObjPose_gt, timestamp, nImage);
 }
 
+cv::Mat System::TrackStereo(const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat& flowmap, const cv::Mat& masksem, const cv::Mat& mTcw_gt,
+                            const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, cv::Mat& imTraj, const int& nImage) {
+  if (mSensor != STEREO) { std::cerr << "ERROR: you called TrackStereo but input sensor was not set to STEREO." << std::endl; std::exit(-1); }
+  return mpTracker->GrabImageStereo(imLeft, imRight, flowmap, masksem, mTcw_gt, vObjPose_gt, timestamp, imTraj, nImage);
+}
+
 // The Map (reference format) is materialised from the pipeline's flat store when somebody looks at it.
 Map* System::map() { mpTracker->pipeline()->SyncMap(); return mpMap; }
 
@@ -381,7 +446,7 @@ int host_settings_read(const char* path, double* out31) {
 }
 // (the C++ classes keep the reference's behaviour - exit(-1) on an unreadable settings file, no error channel; these hooks are
 // reached through ctypes, so they check first and turn failures into return codes instead of ending the host process)
-VDO_SLAM::System* host_system_create(const char* settings) {
+static VDO_SLAM::System* host_system_create_sensor(const char* settings, VDO_SLAM::System::eSensor sensor) {
   {
     std::ifstream f(settings);
     if (!f.is_open()) { std::fprintf(stderr, "host_system_create: cannot open %s\n", settings); return nullptr; }
@@ -401,9 +466,12 @@ VDO_SLAM::System* host_system_create(const char* settings) {
     if (vdo_ctx_create(dev ? std::atoi(dev) : 0, nullptr, &probe) != VDO_OK) { std::fprintf(stderr, "host_system_create: %s\n", vdo_last_error()); return nullptr; }
     vdo_ctx_destroy(probe);
   }
-  try { return new VDO_SLAM::System(settings, VDO_SLAM::System::RGBD); }
+  try { return new VDO_SLAM::System(settings, sensor); }
   catch (const std::exception& e) { std::fprintf(stderr, "host_system_create: %s\n", e.what()); return nullptr; }
 }
+VDO_SLAM::System* host_system_create(const char* settings) { return host_system_create_sensor(settings, VDO_SLAM::System::RGBD); }
+// System(settings, System::STEREO): the same checks; a Stereo.* key the matcher refuses comes back as nullptr with its message on stderr
+VDO_SLAM::System* host_system_create_stereo(const char* settings) { return host_system_create_sensor(settings, VDO_SLAM::System::STEREO); }
 void host_system_destroy(VDO_SLAM::System* s) { delete s; }
 // one TrackRGBD call on host images: im (h x w x channels u8), depth (in/out f32), flow (f32 x2), mask (in/out i32), ground-truth
 // object rows [n_rows][row_len]; Tcw_out 16 floats.  Returns 0, -1 when the tracker returned an empty pose, -2 on a GPU failure.

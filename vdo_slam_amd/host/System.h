@@ -12,6 +12,7 @@
 #include "Frame.h"
 #include "FramePipeline.h"
 #include "Map.h"
+#include "StereoMatcher.h"
 #include "minicv.h"
 
 namespace VDO_SLAM {
@@ -33,7 +34,14 @@ class Tracking {
   // cannot be read or decoded.
   cv::Mat GrabFilesRGBD(const std::string& rgbPath, const std::string& depthPath, const std::string& flowPath, const std::string& maskPath, const cv::Mat& mTcw_gt,
                         const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, const int& nImage);
+  // A rectified pair instead of a depth map (System::STEREO): both images to grey, the disparity x 256 x DepthMapFactor / 256 computed on the
+  // device (StereoMatcher, settings keys Stereo.*) into a device depth_raw image, the flow and the mask brought up beside it, then the same
+  // device-input Step as GrabFilesRGBD - the disparity never passes through the host.  K1 always converts it (whatever ChooseData says: a
+  // disparity is not metric); only a power-of-two DepthMapFactor keeps that composition exact.  Inputs as GrabImageRGBD's.
+  cv::Mat GrabImageStereo(const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat& imFlow, const cv::Mat& maskSEM, const cv::Mat& mTcw_gt,
+                          const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, cv::Mat& imTraj, const int& nImage);
   FramePipeline* pipeline() { return pipe_.get(); }
+  StereoMatcher* stereo() { return stereo_.get(); }      // null unless the sensor is System::STEREO
 
   // ---- public state of the reference class (include/Tracking.h:116-198).  Scalar configuration / progress members are kept up to date by
   // every call.  The per-frame containers live in HBM / in FramePipeline's flat arrays; SyncFrameState() materialises them in the reference's
@@ -69,7 +77,8 @@ class Tracking {
   bool mbRGB = true;
   vdo_ctx* ctx_[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};     // front-end / camera LM / object LMs / helper thread / ORB thread
   std::unique_ptr<FramePipeline> pipe_;
-  std::vector<uint8_t> gray_;
+  std::vector<uint8_t> gray_, gray_right_;
+  std::unique_ptr<StereoMatcher> stereo_;
   bool have_frame_ = false;
   vdo_ingest* ingest_ = nullptr;       // GrabFilesRGBD: device decode of the frame's files, made on first use
   cv::Mat FinishFrame(const cv::Mat& mTcw_gt, std::chrono::steady_clock::time_point t_call);
@@ -92,6 +101,10 @@ class System {
   // transition in the same row format.  The reference writes the object motions in the BODY frame of the ground-truth object pose
   // (obj_mot_stereo_new.txt / _rf_new.txt / obj_mot_gt.txt / obj_centre.txt: ground-truth object-pose parsing, out of scope);
   // here they are written in the WORLD frame under names of their own: obj_mot_world_new.txt / obj_mot_world_rf_new.txt.
+  // A STEREO system (settings keys Stereo.MaxDisparity 128, Stereo.P1 10, Stereo.P2 120, Stereo.Paths 8, Stereo.Uniqueness 5, Stereo.LRMaxDiff 1,
+  // Stereo.SubPixel 1, all optional): Tracking::GrabImageStereo.  Exits like TrackRGBD when the sensor is not STEREO.
+  cv::Mat TrackStereo(const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat& flowmap, const cv::Mat& masksem, const cv::Mat& mTcw_gt,
+                      const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, cv::Mat& imTraj, const int& nImage);
   void SaveResults(const std::string& filename);
   Map* map();                          // brought up to date from the pipeline's GraphStore on access
   Tracking* tracker() { return mpTracker; }

@@ -12,6 +12,7 @@
 #include "ORBextractor.h"
 #include "ORBmatcher.h"
 #include "Optimizer.h"
+#include "StereoMatcher.h"
 #include "System.h"
 
 using namespace VDO_SLAM;
@@ -243,6 +244,37 @@ int host_system_frame_images(System* s, float* depth, int* mask) {
     std::memcpy(depth, T->mDepthMap.data, T->mDepthMap.step * (size_t)T->mDepthMap.rows);
     std::memcpy(mask, T->mSegMap.data, T->mSegMap.step * (size_t)T->mSegMap.rows);
   } catch (const std::exception& e) { std::fprintf(stderr, "host_system_frame_images: %s\n", e.what()); return -1; }
+  return 0;
+}
+
+// StereoMatcher::Compute on a host pair (rows left_step / right_step bytes apart).  params7: max_disparity, p1, p2, paths, uniqueness, lr_max_diff,
+// subpixel.  disparity256: [h][w].  Returns the number of valid pixels, -1 on a failure.
+int host_stereo_compute(const unsigned char* left, int left_step, const unsigned char* right, int right_step, int w, int h, const int* params7, float* disparity256) {
+  try {
+    const vdo_stereo_params p{params7[0], params7[1], params7[2], params7[3], params7[4], params7[5], params7[6]};
+    StereoMatcher m(nullptr, w, h, p);
+    cv::Mat L(h, w, cv::CV_8UC1, (void*)left), R(h, w, cv::CV_8UC1, (void*)right);
+    L.step = (size_t)left_step; R.step = (size_t)right_step;
+    int n = 0;
+    cv::Mat D = m.Compute(L, R, &n);
+    std::memcpy(disparity256, D.data, (size_t)w * h * sizeof(float));
+    return n;
+  } catch (const std::exception& e) { std::fprintf(stderr, "host_stereo_compute: %s\n", e.what()); return -1; }
+}
+
+// one TrackStereo call on host images, as host_system_track with a right image in place of the depth map
+int host_system_track_stereo(System* s, const unsigned char* left, const unsigned char* right, int channels, const float* flow, int* mask, int w, int h,
+                             const float* obj_rows, int n_rows, int row_len, int n_images, float* Tcw_out) {
+  cv::Mat L(h, w, VDO_CV_MAKETYPE(cv::CV_8U, channels), (void*)left), R(h, w, VDO_CV_MAKETYPE(cv::CV_8U, channels), (void*)right), Fl(h, w, cv::CV_32FC2, (void*)flow),
+      M(h, w, cv::CV_32SC1, mask);
+  cv::Mat gt = cv::Mat::eye(4, 4, cv::CV_32F), traj;
+  std::vector<std::vector<float> > rows(n_rows);
+  for (int i = 0; i < n_rows; ++i) rows[i].assign(obj_rows + (size_t)i * row_len, obj_rows + (size_t)(i + 1) * row_len);
+  try {
+    cv::Mat T = s->TrackStereo(L, R, Fl, M, gt, rows, 0.0, traj, n_images);
+    if (T.empty()) return -1;
+    std::memcpy(Tcw_out, T.data, 64);
+  } catch (const std::exception& e) { std::fprintf(stderr, "host_system_track_stereo: %s\n", e.what()); return -2; }
   return 0;
 }
 

@@ -51,16 +51,21 @@ def _ptr(a):
 
 
 class System:
-    def __init__(self, settings_path):
+    def __init__(self, settings_path, sensor="rgbd"):
+        """sensor: "rgbd" (System::RGBD, track_rgbd / track_files) or "stereo" (System::STEREO, track_stereo; optional Stereo.* settings keys)"""
+        if sensor not in ("rgbd", "stereo"):
+            raise ValueError(f"sensor {sensor!r}: 'rgbd' or 'stereo'")
         L = self._L = K.load_host_lib()
         L.host_system_create.restype = C.c_void_p
         L.host_system_create.argtypes = [C.c_char_p]
+        L.host_system_create_stereo.restype = C.c_void_p
+        L.host_system_create_stereo.argtypes = [C.c_char_p]
         L.host_system_destroy.argtypes = [C.c_void_p]
         L.host_system_track.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.host_system_motions.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.host_system_refined_poses.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.host_system_save.argtypes = [C.c_void_p, C.c_char_p]
-        self._h = L.host_system_create(str(settings_path).encode())
+        self._h = (L.host_system_create_stereo if sensor == "stereo" else L.host_system_create)(str(settings_path).encode())
         if not self._h:
             raise K.VdoError("System could not be created (settings file / HIP device)")
         self._T = np.zeros(16, np.float32)
@@ -74,6 +79,20 @@ class System:
         rows = None if obj_rows is None or len(obj_rows) == 0 else np.ascontiguousarray(obj_rows, np.float32)
         rc = self._L.host_system_track(self._h, _ptr(im), ch, _ptr(depth), _ptr(flow), _ptr(mask), w, h, _ptr(rows), 0 if rows is None else rows.shape[0],
                                        0 if rows is None else rows.shape[1], int(n_images), _ptr(self._T))
+        return None if rc != 0 else self._T.reshape(4, 4).copy()
+
+    def track_stereo(self, left, right, flow, mask, obj_rows=None, n_images=1 << 30):
+        """One TrackStereo call on a STEREO system: left / right [h, w] or [h, w, 3|4] uint8 (rectified), flow and mask as track_rgbd.  The
+        disparity is computed on the device and goes straight into the frame's step.  Returns Tcw 4x4 float32, or None."""
+        L = self._L
+        L.host_system_track_stereo.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        if left.shape != right.shape:
+            raise ValueError(f"left {left.shape} and right {right.shape} differ")
+        h, w = left.shape[:2]
+        ch = 1 if left.ndim == 2 else left.shape[2]
+        rows = None if obj_rows is None or len(obj_rows) == 0 else np.ascontiguousarray(obj_rows, np.float32)
+        rc = L.host_system_track_stereo(self._h, _ptr(left), _ptr(right), ch, _ptr(flow), _ptr(mask), w, h, _ptr(rows), 0 if rows is None else rows.shape[0],
+                                        0 if rows is None else rows.shape[1], int(n_images), _ptr(self._T))
         return None if rc != 0 else self._T.reshape(4, 4).copy()
 
     def track_files(self, rgb_path, depth_path, flow_path, mask_path, obj_rows=None, n_images=1 << 30):
