@@ -750,6 +750,72 @@ int vdo_stereo_device_images(vdo_stereo* h, uint8_t** left, uint8_t** right, flo
  * first call), for a caller that hands the whole frame to a device-input step (Tracking::GrabImageStereo).  Host-synchronous. */
 int vdo_stereo_stage_frame(vdo_stereo* h, const float* flow, const int32_t* mask, float** flow_dev, int32_t** mask_dev);
 
+/* ---- Dense optical-flow matcher: coarse-to-fine census search ---------------------------------------------------------------------
+ * New (the reference's TrackRGBD takes a dense flow image per frame, src/Tracking.cc:164-314 / src/Frame.cc, and leaves making it to an offline
+ * flow network): from two 8-bit grey images I0, I1 of W x H to flow[H][W][2] fp32, u then v - the .flo payload layout vdo_ingest_frame and
+ * FramePipeline::Step take.  Pixel (x, y) of I0 is seen at (x + u, y + v) in I1; the flow image handed in with frame t is the flow from frame t
+ * to frame t + 1 (the reference's Frame adds it to reach the next frame).  Integer arithmetic in every stage; no result depends on workgroup
+ * shape or order.  L = levels, r = radius, w = window; the search range per axis is r * (2^L - 1) pixels.
+ *
+ * 1. Pyramid, per image.  Level 0 is the image; level l+1 has size (ceil(W_l / 2), ceil(H_l / 2)) and
+ *    P(x, y) = (a + b + c + d + 2) >> 2 over the 2 x 2 block at (2x, 2y) of level l, the + 1 coordinates clamped to W_l - 1 / H_l - 1.
+ *    Every size >= 1 x 1 is legal at every L: a 1 x 1 level halves to 1 x 1.
+ * 2. Census, per level and image: step 1 of the stereo section above (9 x 7, 62 bits, clamped borders, the same bit order).
+ * 3. Search, from level L-1 down to 0, per pixel of the level.  Prior (u0, v0) = (0, 0) at level L-1, else 2 * F_{l+1}(x >> 1, y >> 1).
+ *    Candidates (du, dv) in [-r, r]^2, ranked k = 0, 1, .. by ascending (du^2 + dv^2, dv, du): zero displacement is k = 0.  Cost
+ *      A(k) = sum_{j=-w..w} sum_{i=-w..w} popcount(c0(cx(x+i), cy(y+j)) ^ c1(cx(x+i+u0+du), cy(y+j+v0+dv))),
+ *    cx, cy clamping into the level's image: the prior of the CENTRE pixel moves the whole block.  A <= 62 * 81.  k* = argmin of the packed
+ *    key (A << 8) | k; F_l = (u0 + du*, v0 + dv*).  If median != 0 and l >= 1, each component of F_l is then replaced by the median (the fifth of
+ *    the nine sorted values) of its clamped 3 x 3 neighbourhood before the level below reads it.  Level 0 is never filtered.
+ * 4. Sub-pixel, level 0 only, per component: for u, if subpixel != 0 and |du*| < r, with A- = A(du*-1, dv*), A+ = A(du*+1, dv*) and
+ *    den = A- + A+ - 2 A*: if den > 0, num = 128 * (A- - A+), off = sign(num) * ((2 * |num| + den) / (2 * den)) in integer division (the stereo
+ *    formula); otherwise off = 0.  v likewise with dv.  Output u = (float)(256 * u_int + off) * (1 / 256): exact in fp32.
+ * 5. Forward-backward check.  If fb_max_diff >= 0 the backward integer flow B is steps 1-3 with the images' roles swapped (the pyramids and
+ *    census images are shared); a pixel is valid iff p' = (x + u_int, y + v_int) lies in the image and
+ *    max(|u_int + B_u(p')|, |v_int + B_v(p')|) <= fb_max_diff.  With -1 nothing backward runs and every pixel is valid.  The flow is written
+ *    for EVERY pixel, valid or not (a tracker wants a guess at an occlusion); *n_valid = the number of valid pixels.
+ * A constant pair gives flow 0 everywhere (the tie rule). */
+typedef struct vdo_optflow vdo_optflow;
+typedef struct vdo_optflow_params {
+  int32_t levels;                   /* L: 1..7 pyramid levels */
+  int32_t radius;                   /* r: 1..4, search radius per level */
+  int32_t window;                   /* w: 0..4, box half-width of the block sum */
+  int32_t median;                   /* 0 / 1: 3 x 3 median between levels */
+  int32_t fb_max_diff;              /* >= -1; -1 switches the forward-backward check off */
+  int32_t subpixel;                 /* 0 / 1: sub-pixel offset */
+} vdo_optflow_params;
+/* A matcher for width x height images.  ALL device memory is taken here (per image the pyramid and its census images, per direction the integer
+ * flows of every level, one more level-1 flow image for the median, a float flow image and a validity image: about 60 bytes per pixel);
+ * vdo_optflow_compute allocates nothing.  VDO_ERR_INVALID, the message naming the argument: width or height < 1; levels outside 1..7; radius
+ * outside 1..4; window outside 0..4; median or subpixel not 0 / 1; fb_max_diff < -1; a null pointer.  VDO_ERR_UNSUPPORTED when
+ * width * height > 2^26.  VDO_ERR_OOM when the device has no room. */
+int vdo_optflow_create(vdo_ctx* ctx, int width, int height, const vdo_optflow_params* params, vdo_optflow** out);
+int vdo_optflow_destroy(vdo_optflow* h);
+/* One pair, host-synchronous, on the context's stream.  im0 / im1: rows of `width` bytes, stride* bytes apart (>= width); host pointers, or device
+ * pointers when src_is_device != 0.  flow: width x height x 2 floats, packed; valid: width x height bytes (1 = valid), packed, may be NULL; both
+ * device pointers when out_is_device != 0; n_valid: host.  VDO_ERR_INVALID, the message naming the argument, for a null image, flow or count and
+ * a stride < width - and then NOTHING is written.  No state of an earlier compute on the handle enters the result. */
+int vdo_optflow_compute(vdo_optflow* h, const uint8_t* im0, int64_t stride0, const uint8_t* im1, int64_t stride1, int src_is_device, float* flow,
+                        uint8_t* valid, int out_is_device, int32_t* n_valid);
+/* The size of pyramid level `level` (0 .. levels-1). */
+int vdo_optflow_level_size(vdo_optflow* h, int level, int* width, int* height);
+/* Inspection of the LAST compute (VDO_ERR_INVALID before the first), host outputs of the level's size: the pyramid level [H_l][W_l] and its census
+ * image of I0 (which = 0) or I1 (1); the integer flow [H_l][W_l][2] of the forward (dir = 0) or backward (1; VDO_ERR_INVALID when fb_max_diff is -1)
+ * run, as the level below reads it - after the median. */
+int vdo_optflow_get_pyramid(vdo_optflow* h, int which, int level, uint8_t* out);
+int vdo_optflow_get_census(vdo_optflow* h, int which, int level, uint64_t* out);
+int vdo_optflow_get_level_flow(vdo_optflow* h, int dir, int level, int32_t* out);
+/* The last compute: ms[0] wall time of the call, ms[1] device time from the first upload to the end of the check kernel (events). */
+int vdo_optflow_last_timing(vdo_optflow* h, double ms[2]);
+/* Device images owned by the handle, for callers without their own: the packed width x height images the pair is brought to (level 0 of the two
+ * pyramids; uploading into them and passing them as a device pair is allowed), a flow image [H][W][2] and a validity image [H][W] to pass as
+ * device outputs.  Any of the four may be NULL. */
+int vdo_optflow_device_images(vdo_optflow* h, uint8_t** im0, uint8_t** im1, float** flow, uint8_t** valid);
+/* Brings the frame's host mask (i32, width x height, packed) to a device image owned by the handle (made on the first call), for a caller that
+ * computes the flow into the handle's device flow image and hands the whole frame to a device-input step (Tracking::GrabImageStereoPair).
+ * Host-synchronous. */
+int vdo_optflow_stage_mask(vdo_optflow* h, const int32_t* mask, int32_t** mask_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,7 @@
 // of the result and the optional output scale.
 //
 //   k_stereo_census     32 x 8 pixels per workgroup from an LDS tile with a 4 / 3 pixel halo (40 x 14 bytes, borders clamped); one uint64 per pixel,
-//                       both images in one launch.
+//                       both images in one launch (the tile itself is census.hpp's, shared with optflow.hip).
 //   k_stereo_cost       one thread per pixel and 16 disparities: 16 XOR + popcounts, one 16-byte store into cost[y][x][d] (uint8, d fastest).
 //   k_stereo_aggregate  one wave per scan line, ALL directions in one launch (blockIdx.y): the disparities sit on the lanes, K = 2 (D <= 128) or 4
 //                       consecutive ones per lane; d - 1 / d + 1 come from the neighbouring lanes by shuffles, min_k L_r by a wave reduction - no LDS
@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "../../include/vdo_slam_hip.h"
+#include "census.hpp"
 #include "ctx.hpp"
 
 struct vdo_stereo {
@@ -45,39 +46,14 @@ struct vdo_stereo {
 
 namespace vdo {
 
-constexpr int kCensusTX = 32, kCensusTY = 8;            // pixels per census workgroup
 constexpr int kNoCost = 62;                             // C(x, y, d) where x - d < 0
 constexpr int kAggInf = 1 << 20;                        // "takes no part" in the recurrence: above every L_r + P2
 constexpr int64_t kStereoMaxVolume = int64_t(1) << 28;
 
 __global__ __launch_bounds__(256) void k_stereo_census(const uint8_t* __restrict__ left, int64_t left_stride, const uint8_t* __restrict__ right, int64_t right_stride,
                                                        int W, int H, int tiles_x, int tiles_per_image, uint64_t* __restrict__ out) {
-  __shared__ uint8_t tile[kCensusTY + 6][kCensusTX + 8];
   const int which = blockIdx.x / tiles_per_image, t = blockIdx.x % tiles_per_image;
-  const uint8_t* img = which ? right : left;
-  const int64_t stride = which ? right_stride : left_stride;
-  const int x0 = (t % tiles_x) * kCensusTX, y0 = (t / tiles_x) * kCensusTY;
-  for (int i = threadIdx.x; i < (kCensusTY + 6) * (kCensusTX + 8); i += 256) {
-    const int r = i / (kCensusTX + 8), c = i % (kCensusTX + 8);
-    const int gx = min(max(x0 + c - 4, 0), W - 1), gy = min(max(y0 + r - 3, 0), H - 1);
-    tile[r][c] = img[(int64_t)gy * stride + gx];
-  }
-  __syncthreads();
-  const int tx = threadIdx.x % kCensusTX, ty = threadIdx.x / kCensusTX;
-  const int x = x0 + tx, y = y0 + ty;
-  if (x >= W || y >= H) return;
-  const uint8_t centre = tile[ty + 3][tx + 4];
-  uint64_t bits = 0;
-  int k = 0;
-#pragma unroll
-  for (int dy = 0; dy < 7; ++dy)
-#pragma unroll
-    for (int dx = 0; dx < 9; ++dx) {
-      if (dy == 3 && dx == 4) continue;
-      bits |= (uint64_t)(tile[ty + dy][tx + dx] < centre) << k;
-      ++k;
-    }
-  out[(size_t)which * W * H + (size_t)y * W + x] = bits;
+  census_tile(which ? right : left, which ? right_stride : left_stride, W, H, (t % tiles_x) * kCensusTX, (t / tiles_x) * kCensusTY, out + (size_t)which * W * H);
 }
 
 __global__ __launch_bounds__(256) void k_stereo_cost(const uint64_t* __restrict__ cl, const uint64_t* __restrict__ cr, int W, int64_t n_pix, int D,

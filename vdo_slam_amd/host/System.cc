@@ -116,12 +116,17 @@ Tracking::Tracking(System*, Map* pMap, const std::string& strSettingPath, const 
     stereo_.reset(new StereoMatcher(ctx_[0], p.width, p.height, sp));
     // depth_raw = disparity x DepthMapFactor: the matcher's 1/256 px scaled by factor / 256 (one fp32 multiply in its selection kernel)
     if (vdo_stereo_set_output_scale(stereo_->handle(), mDepthMapFactor / 256.f) != VDO_OK) throw std::runtime_error(std::string("VDO_SLAM::Tracking: DepthMapFactor: ") + vdo_last_error());
+    const vdo_optflow_params fd = FlowMatcher::DefaultParams();
+    const vdo_optflow_params fp{(int)get(cfg_, "Flow.Levels", fd.levels), (int)get(cfg_, "Flow.Radius", fd.radius), (int)get(cfg_, "Flow.Window", fd.window),
+                                (int)get(cfg_, "Flow.Median", fd.median), (int)get(cfg_, "Flow.FBMaxDiff", fd.fb_max_diff), (int)get(cfg_, "Flow.SubPixel", fd.subpixel)};
+    flow_.reset(new FlowMatcher(ctx_[0], p.width, p.height, fp));
   }
 }
 
 Tracking::~Tracking() {
   pipe_.reset();
   stereo_.reset();
+  flow_.reset();
   if (ingest_) vdo_ingest_destroy(ingest_);
   for (int k = 0; k < 5; ++k) if (ctx_[k]) vdo_ctx_destroy(ctx_[k]);
 }
@@ -185,7 +190,18 @@ cv::Mat Tracking::GrabImageRGBD(const cv::Mat& imRGB, cv::Mat& imD, const cv::Ma
 
 cv::Mat Tracking::GrabImageStereo(const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat& imFlow, const cv::Mat& maskSEM, const cv::Mat& mTcw_gt,
                                   const std::vector<std::vector<float> >& vObjPose_gt, const double&, cv::Mat&, const int& nImage) {
-  if (!stereo_) { std::cerr << "VDO_SLAM::Tracking::GrabImageStereo: the sensor is not STEREO" << std::endl; return cv::Mat(); }
+  return GrabStereoFrame("GrabImageStereo", imLeft, imRight, &imFlow, nullptr, maskSEM, mTcw_gt, vObjPose_gt, nImage);
+}
+
+cv::Mat Tracking::GrabImageStereoPair(const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat& imLeftNext, const cv::Mat& maskSEM, const cv::Mat& mTcw_gt,
+                                      const std::vector<std::vector<float> >& vObjPose_gt, const double&, cv::Mat&, const int& nImage) {
+  return GrabStereoFrame("GrabImageStereoPair", imLeft, imRight, nullptr, &imLeftNext, maskSEM, mTcw_gt, vObjPose_gt, nImage);
+}
+
+// GrabImageStereo (imFlow given) and GrabImageStereoPair (imLeftNext given: the flow is computed on the device from the two left images)
+cv::Mat Tracking::GrabStereoFrame(const char* who, const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat* imFlow, const cv::Mat* imLeftNext, const cv::Mat& maskSEM,
+                                  const cv::Mat& mTcw_gt, const std::vector<std::vector<float> >& vObjPose_gt, const int& nImage) {
+  if (!stereo_) { std::cerr << "VDO_SLAM::Tracking::" << who << ": the sensor is not STEREO" << std::endl; return cv::Mat(); }
   StopFrame = nImage - 1;
   if (!have_frame_) f_id = 0;
   const auto t_call = std::chrono::steady_clock::now();
@@ -196,12 +212,13 @@ cv::Mat Tracking::GrabImageStereo(const cv::Mat& imLeft, const cv::Mat& imRight,
     auto bad = [&](const cv::Mat& m, const char* name, int depth, int ch_lo, int ch_hi) {
       const bool ok = !m.empty() && m.rows == H && m.cols == W && m.depth() == depth && m.channels() >= ch_lo && m.channels() <= ch_hi &&
                       m.step == (size_t)m.cols * m.elemSize();
-      if (!ok) std::cerr << "VDO_SLAM::Tracking::GrabImageStereo: " << name << " is " << m.cols << "x" << m.rows << " (type " << m.type() << ", step " << m.step
+      if (!ok) std::cerr << "VDO_SLAM::Tracking::" << who << ": " << name << " is " << m.cols << "x" << m.rows << " (type " << m.type() << ", step " << m.step
                          << "), expected a continuous " << W << "x" << H << " image of the settings file's Camera.width/height" << std::endl;
       return !ok;
     };
     if (bad(imLeft, "imLeft", cv::CV_8U, 1, 4) || imLeft.channels() == 2 || bad(imRight, "imRight", cv::CV_8U, 1, 4) || imRight.channels() == 2 ||
-        bad(imFlow, "imFlow", cv::CV_32F, 2, 2) || bad(maskSEM, "maskSEM", cv::CV_32S, 1, 1))
+        (imFlow && bad(*imFlow, "imFlow", cv::CV_32F, 2, 2)) || (imLeftNext && (bad(*imLeftNext, "imLeftNext", cv::CV_8U, 1, 4) || imLeftNext->channels() == 2)) ||
+        bad(maskSEM, "maskSEM", cv::CV_32S, 1, 1))
       return cv::Mat();
   }
   const int64_t n = (int64_t)W * H;
@@ -218,10 +235,19 @@ cv::Mat Tracking::GrabImageStereo(const cv::Mat& imLeft, const cv::Mat& imRight,
   vdo_stereo* sh = stereo_->handle();
   uint8_t* d_gray = nullptr; float *d_disp = nullptr, *d_flow = nullptr; int32_t* d_mask = nullptr;
   int32_t n_valid = 0;
-  if (vdo_stereo_device_images(sh, &d_gray, nullptr, &d_disp) != VDO_OK || vdo_stereo_compute(sh, gl, W, gr, W, 0, d_disp, 1, &n_valid) != VDO_OK ||
-      vdo_stereo_stage_frame(sh, (const float*)imFlow.data, (const int32_t*)maskSEM.data, &d_flow, &d_mask) != VDO_OK) {
-    std::cerr << "VDO_SLAM::Tracking::GrabImageStereo: " << vdo_last_error() << std::endl; return cv::Mat();
+  bool ok = vdo_stereo_device_images(sh, &d_gray, nullptr, &d_disp) == VDO_OK && vdo_stereo_compute(sh, gl, W, gr, W, 0, d_disp, 1, &n_valid) == VDO_OK;
+  if (ok && imFlow) ok = vdo_stereo_stage_frame(sh, (const float*)imFlow->data, (const int32_t*)maskSEM.data, &d_flow, &d_mask) == VDO_OK;
+  if (ok && imLeftNext) {
+    // the flow from this frame to the next (the convention of the flow image handed in with a frame), computed from the two grey left images into
+    // the flow matcher's device flow image: it never passes through the host.  Only the mask goes up beside it.
+    const uint8_t* gn = to_gray(*imLeftNext, gray_next_);
+    if (!gn) return cv::Mat();
+    vdo_optflow* fh = flow_->handle();
+    int32_t n_flow = 0;
+    ok = vdo_optflow_device_images(fh, nullptr, nullptr, &d_flow, nullptr) == VDO_OK && vdo_optflow_compute(fh, gl, W, gn, W, 0, d_flow, nullptr, 1, &n_flow) == VDO_OK &&
+         vdo_optflow_stage_mask(fh, (const int32_t*)maskSEM.data, &d_mask) == VDO_OK;
   }
+  if (!ok) { std::cerr << "VDO_SLAM::Tracking::" << who << ": " << vdo_last_error() << std::endl; return cv::Mat(); }
   std::vector<int> labels;
   for (const auto& row : vObjPose_gt) if (row.size() > 1) labels.push_back((int)row[1]);
   pipe_->SetObjectGate(labels.data(), (int)labels.size());
@@ -400,6 +426,12 @@ cv::Mat System::TrackStereo(const cv::Mat& imLeft, const cv::Mat& imRight, const
                             const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, cv::Mat& imTraj, const int& nImage) {
   if (mSensor != STEREO) { std::cerr << "ERROR: you called TrackStereo but input sensor was not set to STEREO." << std::endl; std::exit(-1); }
   return mpTracker->GrabImageStereo(imLeft, imRight, flowmap, masksem, mTcw_gt, vObjPose_gt, timestamp, imTraj, nImage);
+}
+
+cv::Mat System::TrackStereoPair(const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat& imLeftNext, const cv::Mat& masksem, const cv::Mat& mTcw_gt,
+                                const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, cv::Mat& imTraj, const int& nImage) {
+  if (mSensor != STEREO) { std::cerr << "ERROR: you called TrackStereoPair but input sensor was not set to STEREO." << std::endl; std::exit(-1); }
+  return mpTracker->GrabImageStereoPair(imLeft, imRight, imLeftNext, masksem, mTcw_gt, vObjPose_gt, timestamp, imTraj, nImage);
 }
 
 // The Map (reference format) is materialised from the pipeline's flat store when somebody looks at it.

@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "FlowMatcher.h"
 #include "Frame.h"
 #include "FramePipeline.h"
 #include "Map.h"
@@ -40,7 +41,13 @@ class Tracking {
   // disparity is not metric); only a power-of-two DepthMapFactor keeps that composition exact.  Inputs as GrabImageRGBD's.
   cv::Mat GrabImageStereo(const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat& imFlow, const cv::Mat& maskSEM, const cv::Mat& mTcw_gt,
                           const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, cv::Mat& imTraj, const int& nImage);
+  // As GrabImageStereo, but the flow image is made here as well: the dense flow from the grey left image to the grey NEXT left image (the flow
+  // image of frame t is the flow from t to t + 1), computed on the device (FlowMatcher, settings keys Flow.*) into the device flow image the step
+  // takes - no host round trip.  The caller is one frame ahead of the tracker: it needs image t + 1 to track frame t.
+  cv::Mat GrabImageStereoPair(const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat& imLeftNext, const cv::Mat& maskSEM, const cv::Mat& mTcw_gt,
+                              const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, cv::Mat& imTraj, const int& nImage);
   FramePipeline* pipeline() { return pipe_.get(); }
+  FlowMatcher* flow() { return flow_.get(); }            // null unless the sensor is System::STEREO
   StereoMatcher* stereo() { return stereo_.get(); }      // null unless the sensor is System::STEREO
 
   // ---- public state of the reference class (include/Tracking.h:116-198).  Scalar configuration / progress members are kept up to date by
@@ -77,8 +84,11 @@ class Tracking {
   bool mbRGB = true;
   vdo_ctx* ctx_[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};     // front-end / camera LM / object LMs / helper thread / ORB thread
   std::unique_ptr<FramePipeline> pipe_;
-  std::vector<uint8_t> gray_, gray_right_;
+  std::vector<uint8_t> gray_, gray_right_, gray_next_;
   std::unique_ptr<StereoMatcher> stereo_;
+  std::unique_ptr<FlowMatcher> flow_;
+  cv::Mat GrabStereoFrame(const char* who, const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat* imFlow, const cv::Mat* imLeftNext, const cv::Mat& maskSEM,
+                          const cv::Mat& mTcw_gt, const std::vector<std::vector<float> >& vObjPose_gt, const int& nImage);
   bool have_frame_ = false;
   vdo_ingest* ingest_ = nullptr;       // GrabFilesRGBD: device decode of the frame's files, made on first use
   cv::Mat FinishFrame(const cv::Mat& mTcw_gt, std::chrono::steady_clock::time_point t_call);
@@ -105,6 +115,10 @@ class System {
   // Stereo.SubPixel 1, all optional): Tracking::GrabImageStereo.  Exits like TrackRGBD when the sensor is not STEREO.
   cv::Mat TrackStereo(const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat& flowmap, const cv::Mat& masksem, const cv::Mat& mTcw_gt,
                       const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, cv::Mat& imTraj, const int& nImage);
+  // TrackStereo with the flow made on the device from imLeft and imLeftNext (Tracking::GrabImageStereoPair; settings keys Flow.Levels 6, Flow.Radius 2,
+  // Flow.Window 2, Flow.Median 1, Flow.FBMaxDiff 1, Flow.SubPixel 1, all optional).  Exits like TrackStereo when the sensor is not STEREO.
+  cv::Mat TrackStereoPair(const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat& imLeftNext, const cv::Mat& masksem, const cv::Mat& mTcw_gt,
+                          const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, cv::Mat& imTraj, const int& nImage);
   void SaveResults(const std::string& filename);
   Map* map();                          // brought up to date from the pipeline's GraphStore on access
   Tracking* tracker() { return mpTracker; }

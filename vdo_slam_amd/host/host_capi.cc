@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "Converter.h"
+#include "FlowMatcher.h"
 #include "Frame.h"
 #include "Map.h"
 #include "ORBextractor.h"
@@ -275,6 +276,39 @@ int host_system_track_stereo(System* s, const unsigned char* left, const unsigne
     if (T.empty()) return -1;
     std::memcpy(Tcw_out, T.data, 64);
   } catch (const std::exception& e) { std::fprintf(stderr, "host_system_track_stereo: %s\n", e.what()); return -2; }
+  return 0;
+}
+
+// FlowMatcher::Compute on a host pair (rows step0 / step1 bytes apart).  params6: levels, radius, window, median, fb_max_diff, subpixel.
+// flow: [h][w][2], valid: [h][w] (may be null).  Returns the number of valid pixels, -1 on a failure.
+int host_optflow_compute(const unsigned char* im0, int step0, const unsigned char* im1, int step1, int w, int h, const int* params6, float* flow, unsigned char* valid) {
+  try {
+    const vdo_optflow_params p{params6[0], params6[1], params6[2], params6[3], params6[4], params6[5]};
+    FlowMatcher m(nullptr, w, h, p);
+    cv::Mat A(h, w, cv::CV_8UC1, (void*)im0), B(h, w, cv::CV_8UC1, (void*)im1);
+    A.step = (size_t)step0; B.step = (size_t)step1;
+    int n = 0;
+    cv::Mat V;
+    cv::Mat F = m.Compute(A, B, valid ? &V : nullptr, &n);
+    std::memcpy(flow, F.data, (size_t)w * h * 2 * sizeof(float));
+    if (valid) std::memcpy(valid, V.data, (size_t)w * h);
+    return n;
+  } catch (const std::exception& e) { std::fprintf(stderr, "host_optflow_compute: %s\n", e.what()); return -1; }
+}
+
+// one TrackStereoPair call on host images, as host_system_track_stereo with the next left image in place of the flow image
+int host_system_track_stereo_pair(System* s, const unsigned char* left, const unsigned char* right, const unsigned char* left_next, int channels, int* mask, int w, int h,
+                                  const float* obj_rows, int n_rows, int row_len, int n_images, float* Tcw_out) {
+  const int type = VDO_CV_MAKETYPE(cv::CV_8U, channels);
+  cv::Mat L(h, w, type, (void*)left), R(h, w, type, (void*)right), N(h, w, type, (void*)left_next), M(h, w, cv::CV_32SC1, mask);
+  cv::Mat gt = cv::Mat::eye(4, 4, cv::CV_32F), traj;
+  std::vector<std::vector<float> > rows(n_rows);
+  for (int i = 0; i < n_rows; ++i) rows[i].assign(obj_rows + (size_t)i * row_len, obj_rows + (size_t)(i + 1) * row_len);
+  try {
+    cv::Mat T = s->TrackStereoPair(L, R, N, M, gt, rows, 0.0, traj, n_images);
+    if (T.empty()) return -1;
+    std::memcpy(Tcw_out, T.data, 64);
+  } catch (const std::exception& e) { std::fprintf(stderr, "host_system_track_stereo_pair: %s\n", e.what()); return -2; }
   return 0;
 }
 
