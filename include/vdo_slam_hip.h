@@ -816,6 +816,66 @@ int vdo_optflow_device_images(vdo_optflow* h, uint8_t** im0, uint8_t** im1, floa
  * Host-synchronous. */
 int vdo_optflow_stage_mask(vdo_optflow* h, const int32_t* mask, int32_t** mask_dev);
 
+/* ---- Instance labeller: connected components to the mask image ---------------------------------------------------------------------
+ * New (the reference's TrackRGBD takes an instance mask per frame - int32, 0 = background, labels below 1024 - and leaves making it to an
+ * offline instance-segmentation network): from a class image cls[H][W] (uint8, 0 = background; a semantic map without instances, or a drawn
+ * region) and optionally a disparity image to mask[H][W] int32, the layout vdo_ingest_frame and FramePipeline::Step take; and the same engine as
+ * the speckle filter a stereo matcher ends with.  Integer arithmetic in every stage; no result depends on workgroup shape or order.  Raster
+ * index i = y * W + x.  A disparity v (fp32: the disparity256 image of vdo_stereo_compute, possibly scaled) enters as d = (int32)v (truncation)
+ * when 0 <= v < 2^24, else (NaN, negative, too large) d = 0 = unknown.
+ *
+ * 1. Links.  Neighbour offsets (1,0), (0,1) at connectivity 4; also (1,1), (-1,1) at connectivity 8.
+ *    Instance mode: p and q are linked iff cls(p) == cls(q) != 0 and (max_disp_diff == -1 or d(p) == 0 or d(q) == 0 or
+ *    |d(p) - d(q)| <= max_disp_diff): an unknown disparity does not cut an object.
+ *    Speckle mode (connectivity 4): p and q are linked iff d(p) != 0, d(q) != 0 and |d(p) - d(q)| <= max_diff; pixels with d == 0 belong to
+ *    no component.
+ * 2. Components: the transitive closure of the links.  A component's root is its smallest raster index, its area its pixel count.  Pixels of
+ *    no component (background; d == 0 in speckle mode) have root -1.
+ * 3. Selection (instance mode).  Let A be the smallest value >= min_area such that at most max_labels components have area >= A (components of
+ *    equal area are kept or dropped together).  The reported threshold A* is min_area when nothing overflows (A == min_area); otherwise the area
+ *    of the smallest component of area >= A - the same components pass A and A* - or A itself when none does: areas 9, 9, 4, 4, 1 give A* = 9
+ *    with max_labels 3 and A* = 4 with max_labels 4.  The components of area >= A* are numbered 1..n_labels in
+ *    ascending order of their roots; mask(p) = the number of p's component, or 0.  The per-frame numbers carry no identity over time: the tracker
+ *    associates objects through the flow.
+ * 4. Speckle filter, in place on an fp32 disparity image: every pixel of a component with area <= max_size becomes 0.0f, every other value stays
+ *    bit for bit; *n_removed = the number of pixels zeroed. */
+typedef struct vdo_labels vdo_labels;
+typedef struct vdo_labels_params {
+  int32_t connectivity;             /* 4 or 8 */
+  int32_t max_disp_diff;            /* >= -1, in the units of the disparity image; -1 switches the disparity gate off */
+  int32_t min_area;                 /* >= 1: smaller components get no label */
+  int32_t max_labels;               /* 1..1023: labels stay below the frame step's 1024 vote bins */
+} vdo_labels_params;
+/* A labeller for width x height images.  ALL device memory is taken here (link bits, parent, area and rank per pixel, staged class, disparity and
+ * mask images: about 22 bytes per pixel); computes and filters allocate nothing.  VDO_ERR_INVALID, the message naming the argument: width or
+ * height < 1; connectivity not 4 or 8; max_disp_diff < -1; min_area < 1; max_labels outside 1..1023; a null pointer.  VDO_ERR_UNSUPPORTED when
+ * width * height > 2^26.  VDO_ERR_OOM when the device has no room. */
+int vdo_labels_create(vdo_ctx* ctx, int width, int height, const vdo_labels_params* params, vdo_labels** out);
+int vdo_labels_destroy(vdo_labels* h);
+/* One image, host-synchronous, on the context's stream.  cls: rows of `width` bytes, cls_stride bytes apart (>= width); disp: rows of `width`
+ * floats, disp_stride_floats floats apart (>= width), NULL allowed only when max_disp_diff == -1 (then it is not read); host pointers, or device
+ * pointers when src_is_device != 0 (packed device images are read where they are).  mask: width x height int32, packed, a device pointer when
+ * out_is_device != 0.  out (host): n_labels, n_components (all components, kept or not), area_threshold = A*.  VDO_ERR_INVALID, the message naming
+ * the argument, for a null cls, mask or out, a null disp with the gate on and a stride < width - and then NOTHING is written.  No state of an
+ * earlier compute or filter on the handle enters the result.  VDO_ERR_INTERNAL should a walk of the union-find pass its step bound. */
+int vdo_labels_compute(vdo_labels* h, const uint8_t* cls, int64_t cls_stride, const float* disp, int64_t disp_stride_floats, int src_is_device,
+                       int32_t* mask, int out_is_device, int32_t out[3]);
+/* Step 4 on a packed width x height fp32 image (a device pointer when is_device != 0), host-synchronous.  VDO_ERR_INVALID for max_diff < 0,
+ * max_size < 0 or a null pointer, and then nothing is written.  The handle's connectivity and selection parameters play no part. */
+int vdo_labels_filter_speckles(vdo_labels* h, float* disparity256, int is_device, int max_diff, int max_size, int32_t* n_removed);
+/* Inspection of the LAST compute or filter (VDO_ERR_INVALID before the first), host outputs [H][W]: the root of every pixel or -1; the area at
+ * each root and 0 elsewhere. */
+int vdo_labels_get_roots(vdo_labels* h, int32_t* out);
+int vdo_labels_get_areas(vdo_labels* h, int32_t* out);
+/* The last compute or filter: ms[0] wall time of the call, ms[1] device time from the first upload to the end of the last kernel (events). */
+int vdo_labels_last_timing(vdo_labels* h, double ms[2]);
+/* Device images owned by the handle, for callers without their own: a packed class image to upload into and pass as a device source, and a mask
+ * image to pass as a device output.  Either may be NULL. */
+int vdo_labels_device_images(vdo_labels* h, uint8_t** cls, int32_t** mask);
+/* Brings a host class image (rows cls_stride bytes apart) to the handle's device class image, for a caller whose disparity is already on the
+ * device (src_is_device covers both sources of a compute): Tracking::GrabImageStereoPairSemantic.  Host-synchronous. */
+int vdo_labels_stage_classes(vdo_labels* h, const uint8_t* cls, int64_t cls_stride, uint8_t** cls_dev);
+
 #ifdef __cplusplus
 }
 #endif

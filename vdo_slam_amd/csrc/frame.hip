@@ -12,30 +12,9 @@
 #include "../../include/vdo_slam_hip.h"
 #include "ctx.hpp"
 #include "frame_images.hpp"
+#include "scan.hpp"
 
 namespace vdo {
-
-__device__ __forceinline__ int wave_excl_scan(int v, int lane, int* total) {
-  int incl = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) { const int t = __shfl_up(incl, off, 64); if (lane >= off) incl += t; }
-  *total = __shfl(incl, 63, 64);
-  return incl - v;
-}
-
-// workgroup exclusive scan (<=1024 threads); returns exclusive prefix, *total = sum. lds: int[17]
-__device__ __forceinline__ int block_excl_scan(int v, int* lds, int* total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-  int wt;
-  const int ex = wave_excl_scan(v, lane, &wt);
-  __syncthreads();
-  if (lane == 0) lds[wv] = wt;
-  __syncthreads();
-  if (threadIdx.x == 0) { int a = 0; for (int q = 0; q < nw; ++q) { const int t = lds[q]; lds[q] = a; a += t; } lds[16] = a; }
-  __syncthreads();
-  *total = lds[16];
-  return ex + lds[wv];
-}
 
 // K9.  Single workgroup (n <= a few thousand keypoints), chunks of blockDim.x in input order.
 __global__ __launch_bounds__(1024) void k_static_filter(int n, const float* __restrict__ kx, const float* __restrict__ ky,

@@ -3,6 +3,7 @@
 #include <stdexcept>
 
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -120,6 +121,15 @@ Tracking::Tracking(System*, Map* pMap, const std::string& strSettingPath, const 
     const vdo_optflow_params fp{(int)get(cfg_, "Flow.Levels", fd.levels), (int)get(cfg_, "Flow.Radius", fd.radius), (int)get(cfg_, "Flow.Window", fd.window),
                                 (int)get(cfg_, "Flow.Median", fd.median), (int)get(cfg_, "Flow.FBMaxDiff", fd.fb_max_diff), (int)get(cfg_, "Flow.SubPixel", fd.subpixel)};
     flow_.reset(new FlowMatcher(ctx_[0], p.width, p.height, fp));
+    // Labels.MaxDispDiff and Stereo.SpeckleRange are given in the matcher's 1/256 px and compared in the units of the depth image it writes
+    const float unit = mDepthMapFactor / 256.f;
+    auto in_depth_units = [&](double v) { return v < 0 ? -1 : (int)std::lround(v * unit); };
+    const vdo_labels_params ld = InstanceLabeler::DefaultParams();
+    const vdo_labels_params lp{(int)get(cfg_, "Labels.Connectivity", ld.connectivity), in_depth_units(get(cfg_, "Labels.MaxDispDiff", ld.max_disp_diff)),
+                               (int)get(cfg_, "Labels.MinArea", ld.min_area), (int)get(cfg_, "Labels.MaxLabels", ld.max_labels)};
+    labels_.reset(new InstanceLabeler(ctx_[0], p.width, p.height, lp));
+    speckle_size_ = (int)get(cfg_, "Stereo.SpeckleSize", 0);
+    speckle_range_ = in_depth_units(get(cfg_, "Stereo.SpeckleRange", 256));
   }
 }
 
@@ -127,6 +137,7 @@ Tracking::~Tracking() {
   pipe_.reset();
   stereo_.reset();
   flow_.reset();
+  labels_.reset();
   if (ingest_) vdo_ingest_destroy(ingest_);
   for (int k = 0; k < 5; ++k) if (ctx_[k]) vdo_ctx_destroy(ctx_[k]);
 }
@@ -190,17 +201,23 @@ cv::Mat Tracking::GrabImageRGBD(const cv::Mat& imRGB, cv::Mat& imD, const cv::Ma
 
 cv::Mat Tracking::GrabImageStereo(const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat& imFlow, const cv::Mat& maskSEM, const cv::Mat& mTcw_gt,
                                   const std::vector<std::vector<float> >& vObjPose_gt, const double&, cv::Mat&, const int& nImage) {
-  return GrabStereoFrame("GrabImageStereo", imLeft, imRight, &imFlow, nullptr, maskSEM, mTcw_gt, vObjPose_gt, nImage);
+  return GrabStereoFrame("GrabImageStereo", imLeft, imRight, &imFlow, nullptr, &maskSEM, nullptr, mTcw_gt, vObjPose_gt, nImage);
 }
 
 cv::Mat Tracking::GrabImageStereoPair(const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat& imLeftNext, const cv::Mat& maskSEM, const cv::Mat& mTcw_gt,
                                       const std::vector<std::vector<float> >& vObjPose_gt, const double&, cv::Mat&, const int& nImage) {
-  return GrabStereoFrame("GrabImageStereoPair", imLeft, imRight, nullptr, &imLeftNext, maskSEM, mTcw_gt, vObjPose_gt, nImage);
+  return GrabStereoFrame("GrabImageStereoPair", imLeft, imRight, nullptr, &imLeftNext, &maskSEM, nullptr, mTcw_gt, vObjPose_gt, nImage);
 }
 
-// GrabImageStereo (imFlow given) and GrabImageStereoPair (imLeftNext given: the flow is computed on the device from the two left images)
-cv::Mat Tracking::GrabStereoFrame(const char* who, const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat* imFlow, const cv::Mat* imLeftNext, const cv::Mat& maskSEM,
-                                  const cv::Mat& mTcw_gt, const std::vector<std::vector<float> >& vObjPose_gt, const int& nImage) {
+cv::Mat Tracking::GrabImageStereoPairSemantic(const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat& imLeftNext, const cv::Mat& classes, const cv::Mat& mTcw_gt,
+                                              const std::vector<std::vector<float> >& vObjPose_gt, const double&, cv::Mat&, const int& nImage) {
+  return GrabStereoFrame("GrabImageStereoPairSemantic", imLeft, imRight, nullptr, &imLeftNext, nullptr, &classes, mTcw_gt, vObjPose_gt, nImage);
+}
+
+// GrabImageStereo (imFlow given), GrabImageStereoPair (imLeftNext given: the flow is computed on the device from the two left images) and
+// GrabImageStereoPairSemantic (classes given in place of maskSEM: the mask is computed on the device as well)
+cv::Mat Tracking::GrabStereoFrame(const char* who, const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat* imFlow, const cv::Mat* imLeftNext, const cv::Mat* maskSEM,
+                                  const cv::Mat* classes, const cv::Mat& mTcw_gt, const std::vector<std::vector<float> >& vObjPose_gt, const int& nImage) {
   if (!stereo_) { std::cerr << "VDO_SLAM::Tracking::" << who << ": the sensor is not STEREO" << std::endl; return cv::Mat(); }
   StopFrame = nImage - 1;
   if (!have_frame_) f_id = 0;
@@ -218,7 +235,7 @@ cv::Mat Tracking::GrabStereoFrame(const char* who, const cv::Mat& imLeft, const 
     };
     if (bad(imLeft, "imLeft", cv::CV_8U, 1, 4) || imLeft.channels() == 2 || bad(imRight, "imRight", cv::CV_8U, 1, 4) || imRight.channels() == 2 ||
         (imFlow && bad(*imFlow, "imFlow", cv::CV_32F, 2, 2)) || (imLeftNext && (bad(*imLeftNext, "imLeftNext", cv::CV_8U, 1, 4) || imLeftNext->channels() == 2)) ||
-        bad(maskSEM, "maskSEM", cv::CV_32S, 1, 1))
+        (maskSEM && bad(*maskSEM, "maskSEM", cv::CV_32S, 1, 1)) || (classes && bad(*classes, "classes", cv::CV_8U, 1, 1)))
       return cv::Mat();
   }
   const int64_t n = (int64_t)W * H;
@@ -236,7 +253,17 @@ cv::Mat Tracking::GrabStereoFrame(const char* who, const cv::Mat& imLeft, const 
   uint8_t* d_gray = nullptr; float *d_disp = nullptr, *d_flow = nullptr; int32_t* d_mask = nullptr;
   int32_t n_valid = 0;
   bool ok = vdo_stereo_device_images(sh, &d_gray, nullptr, &d_disp) == VDO_OK && vdo_stereo_compute(sh, gl, W, gr, W, 0, d_disp, 1, &n_valid) == VDO_OK;
-  if (ok && imFlow) ok = vdo_stereo_stage_frame(sh, (const float*)imFlow->data, (const int32_t*)maskSEM.data, &d_flow, &d_mask) == VDO_OK;
+  // the speckle filter (off by default), in place on the device disparity: components of at most Stereo.SpeckleSize pixels become unknown
+  if (ok && speckle_size_ > 0) { int32_t n_removed = 0; ok = vdo_labels_filter_speckles(labels_->handle(), d_disp, 1, speckle_range_, speckle_size_, &n_removed) == VDO_OK; }
+  if (ok && classes) {
+    // the instance mask from the class image and the disparity just made, into the labeller's device mask image
+    vdo_labels* lh = labels_->handle();
+    uint8_t* d_cls = nullptr;
+    int32_t counts[3];
+    ok = vdo_labels_stage_classes(lh, classes->data, W, &d_cls) == VDO_OK && vdo_labels_device_images(lh, nullptr, &d_mask) == VDO_OK &&
+         vdo_labels_compute(lh, d_cls, W, d_disp, W, 1, d_mask, 1, counts) == VDO_OK;
+  }
+  if (ok && imFlow) ok = vdo_stereo_stage_frame(sh, (const float*)imFlow->data, (const int32_t*)maskSEM->data, &d_flow, &d_mask) == VDO_OK;
   if (ok && imLeftNext) {
     // the flow from this frame to the next (the convention of the flow image handed in with a frame), computed from the two grey left images into
     // the flow matcher's device flow image: it never passes through the host.  Only the mask goes up beside it.
@@ -245,7 +272,7 @@ cv::Mat Tracking::GrabStereoFrame(const char* who, const cv::Mat& imLeft, const 
     vdo_optflow* fh = flow_->handle();
     int32_t n_flow = 0;
     ok = vdo_optflow_device_images(fh, nullptr, nullptr, &d_flow, nullptr) == VDO_OK && vdo_optflow_compute(fh, gl, W, gn, W, 0, d_flow, nullptr, 1, &n_flow) == VDO_OK &&
-         vdo_optflow_stage_mask(fh, (const int32_t*)maskSEM.data, &d_mask) == VDO_OK;
+         (!maskSEM || vdo_optflow_stage_mask(fh, (const int32_t*)maskSEM->data, &d_mask) == VDO_OK);
   }
   if (!ok) { std::cerr << "VDO_SLAM::Tracking::" << who << ": " << vdo_last_error() << std::endl; return cv::Mat(); }
   std::vector<int> labels;
@@ -253,7 +280,7 @@ cv::Mat Tracking::GrabStereoFrame(const char* who, const cv::Mat& imLeft, const 
   pipe_->SetObjectGate(labels.data(), (int)labels.size());
   FrameCounts fc{};
   if (pipe_->StepDevice(d_gray, d_disp, d_flow, d_mask, false, &fc) != 0) return cv::Mat();
-  if (fc.n_recovered_masks > 0) pipe_->DownloadMask((int32_t*)maskSEM.data);      // UpdateMask writes through the shared header, as in GrabImageRGBD
+  if (maskSEM && fc.n_recovered_masks > 0) pipe_->DownloadMask((int32_t*)maskSEM->data);      // UpdateMask writes through the shared header, as in GrabImageRGBD
   return FinishFrame(mTcw_gt, t_call);
 }
 
@@ -432,6 +459,12 @@ cv::Mat System::TrackStereoPair(const cv::Mat& imLeft, const cv::Mat& imRight, c
                                 const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, cv::Mat& imTraj, const int& nImage) {
   if (mSensor != STEREO) { std::cerr << "ERROR: you called TrackStereoPair but input sensor was not set to STEREO." << std::endl; std::exit(-1); }
   return mpTracker->GrabImageStereoPair(imLeft, imRight, imLeftNext, masksem, mTcw_gt, vObjPose_gt, timestamp, imTraj, nImage);
+}
+
+cv::Mat System::TrackStereoPairSemantic(const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat& imLeftNext, const cv::Mat& classes, const cv::Mat& mTcw_gt,
+                                        const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, cv::Mat& imTraj, const int& nImage) {
+  if (mSensor != STEREO) { std::cerr << "ERROR: you called TrackStereoPairSemantic but input sensor was not set to STEREO." << std::endl; std::exit(-1); }
+  return mpTracker->GrabImageStereoPairSemantic(imLeft, imRight, imLeftNext, classes, mTcw_gt, vObjPose_gt, timestamp, imTraj, nImage);
 }
 
 // The Map (reference format) is materialised from the pipeline's flat store when somebody looks at it.

@@ -12,6 +12,7 @@
 #include "FlowMatcher.h"
 #include "Frame.h"
 #include "FramePipeline.h"
+#include "InstanceLabeler.h"
 #include "Map.h"
 #include "StereoMatcher.h"
 #include "minicv.h"
@@ -46,7 +47,14 @@ class Tracking {
   // takes - no host round trip.  The caller is one frame ahead of the tracker: it needs image t + 1 to track frame t.
   cv::Mat GrabImageStereoPair(const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat& imLeftNext, const cv::Mat& maskSEM, const cv::Mat& mTcw_gt,
                               const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, cv::Mat& imTraj, const int& nImage);
+  // As GrabImageStereoPair, but the instance mask is made here as well, from a class image (CV_8UC1, 0 = background; a semantic map without
+  // instances): on the device, the disparity, then the speckle filter if Stereo.SpeckleSize > 0, then the connected components of the class image
+  // cut at disparity jumps (InstanceLabeler, settings keys Labels.*) written into the device mask image the step takes, then the flow.  The mask
+  // never exists on the host; its labels carry no identity from frame to frame (the tracker associates objects through the flow).
+  cv::Mat GrabImageStereoPairSemantic(const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat& imLeftNext, const cv::Mat& classes, const cv::Mat& mTcw_gt,
+                                      const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, cv::Mat& imTraj, const int& nImage);
   FramePipeline* pipeline() { return pipe_.get(); }
+  InstanceLabeler* labeler() { return labels_.get(); }   // null unless the sensor is System::STEREO
   FlowMatcher* flow() { return flow_.get(); }            // null unless the sensor is System::STEREO
   StereoMatcher* stereo() { return stereo_.get(); }      // null unless the sensor is System::STEREO
 
@@ -87,8 +95,10 @@ class Tracking {
   std::vector<uint8_t> gray_, gray_right_, gray_next_;
   std::unique_ptr<StereoMatcher> stereo_;
   std::unique_ptr<FlowMatcher> flow_;
-  cv::Mat GrabStereoFrame(const char* who, const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat* imFlow, const cv::Mat* imLeftNext, const cv::Mat& maskSEM,
-                          const cv::Mat& mTcw_gt, const std::vector<std::vector<float> >& vObjPose_gt, const int& nImage);
+  std::unique_ptr<InstanceLabeler> labels_;
+  int speckle_size_ = 0, speckle_range_ = 256;           // Stereo.SpeckleSize (0: no filter), Stereo.SpeckleRange, the latter in the depth image's units
+  cv::Mat GrabStereoFrame(const char* who, const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat* imFlow, const cv::Mat* imLeftNext, const cv::Mat* maskSEM,
+                          const cv::Mat* classes, const cv::Mat& mTcw_gt, const std::vector<std::vector<float> >& vObjPose_gt, const int& nImage);
   bool have_frame_ = false;
   vdo_ingest* ingest_ = nullptr;       // GrabFilesRGBD: device decode of the frame's files, made on first use
   cv::Mat FinishFrame(const cv::Mat& mTcw_gt, std::chrono::steady_clock::time_point t_call);
@@ -119,6 +129,12 @@ class System {
   // Flow.Window 2, Flow.Median 1, Flow.FBMaxDiff 1, Flow.SubPixel 1, all optional).  Exits like TrackStereo when the sensor is not STEREO.
   cv::Mat TrackStereoPair(const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat& imLeftNext, const cv::Mat& masksem, const cv::Mat& mTcw_gt,
                           const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, cv::Mat& imTraj, const int& nImage);
+  // TrackStereoPair with the instance mask made on the device from a class image (Tracking::GrabImageStereoPairSemantic; settings keys
+  // Labels.Connectivity 8, Labels.MaxDispDiff 512 (in 1/256 px: multiplied by DepthMapFactor / 256 into the units of the depth image),
+  // Labels.MinArea 200, Labels.MaxLabels 1023, Stereo.SpeckleSize 0 (off), Stereo.SpeckleRange 256 (as MaxDispDiff), all optional).  Exits like
+  // TrackStereo when the sensor is not STEREO.
+  cv::Mat TrackStereoPairSemantic(const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat& imLeftNext, const cv::Mat& classes, const cv::Mat& mTcw_gt,
+                                  const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, cv::Mat& imTraj, const int& nImage);
   void SaveResults(const std::string& filename);
   Map* map();                          // brought up to date from the pipeline's GraphStore on access
   Tracking* tracker() { return mpTracker; }

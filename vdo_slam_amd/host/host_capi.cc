@@ -8,6 +8,7 @@
 
 #include "Converter.h"
 #include "FlowMatcher.h"
+#include "InstanceLabeler.h"
 #include "Frame.h"
 #include "Map.h"
 #include "ORBextractor.h"
@@ -309,6 +310,40 @@ int host_system_track_stereo_pair(System* s, const unsigned char* left, const un
     if (T.empty()) return -1;
     std::memcpy(Tcw_out, T.data, 64);
   } catch (const std::exception& e) { std::fprintf(stderr, "host_system_track_stereo_pair: %s\n", e.what()); return -2; }
+  return 0;
+}
+
+// InstanceLabeler::Compute on host images (class rows cls_step bytes apart; disparity rows disp_step_floats floats apart, null allowed when
+// params4[1] is -1).  params4: connectivity, max_disp_diff, min_area, max_labels.  mask: [h][w]; counts3: n_labels, n_components, area_threshold.
+// Returns n_labels, -1 on a failure.
+int host_labels_compute(const unsigned char* cls, int cls_step, const float* disp, int disp_step_floats, int w, int h, const int* params4, int* mask, int* counts3) {
+  try {
+    const vdo_labels_params p{params4[0], params4[1], params4[2], params4[3]};
+    InstanceLabeler m(nullptr, w, h, p);
+    cv::Mat Cm(h, w, cv::CV_8UC1, (void*)cls), D;
+    Cm.step = (size_t)cls_step;
+    if (disp) { D = cv::Mat(h, w, cv::CV_32FC1, (void*)disp); D.step = (size_t)disp_step_floats * sizeof(float); }
+    int counts[3] = {0, 0, 0};
+    cv::Mat M = m.Compute(Cm, D, counts);
+    std::memcpy(mask, M.data, (size_t)w * h * sizeof(int));
+    if (counts3) std::memcpy(counts3, counts, sizeof counts);
+    return counts[0];
+  } catch (const std::exception& e) { std::fprintf(stderr, "host_labels_compute: %s\n", e.what()); return -1; }
+}
+
+// one TrackStereoPairSemantic call on host images, as host_system_track_stereo_pair with a class image (uint8, one channel) in place of the mask
+int host_system_track_stereo_pair_semantic(System* s, const unsigned char* left, const unsigned char* right, const unsigned char* left_next, int channels,
+                                           const unsigned char* classes, int w, int h, const float* obj_rows, int n_rows, int row_len, int n_images, float* Tcw_out) {
+  const int type = VDO_CV_MAKETYPE(cv::CV_8U, channels);
+  cv::Mat L(h, w, type, (void*)left), R(h, w, type, (void*)right), N(h, w, type, (void*)left_next), Cm(h, w, cv::CV_8UC1, (void*)classes);
+  cv::Mat gt = cv::Mat::eye(4, 4, cv::CV_32F), traj;
+  std::vector<std::vector<float> > rows(n_rows);
+  for (int i = 0; i < n_rows; ++i) rows[i].assign(obj_rows + (size_t)i * row_len, obj_rows + (size_t)(i + 1) * row_len);
+  try {
+    cv::Mat T = s->TrackStereoPairSemantic(L, R, N, Cm, gt, rows, 0.0, traj, n_images);
+    if (T.empty()) return -1;
+    std::memcpy(Tcw_out, T.data, 64);
+  } catch (const std::exception& e) { std::fprintf(stderr, "host_system_track_stereo_pair_semantic: %s\n", e.what()); return -2; }
   return 0;
 }
 

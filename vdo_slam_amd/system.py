@@ -109,6 +109,25 @@ class System:
                                              0 if rows is None else rows.shape[1], int(n_images), _ptr(self._T))
         return None if rc != 0 else self._T.reshape(4, 4).copy()
 
+    def track_stereo_pair_semantic(self, left, right, left_next, classes, obj_rows=None, n_images=1 << 30):
+        """One TrackStereoPairSemantic call on a STEREO system: as track_stereo_pair, with a class image (uint8 [h, w], 0 = background) in place of
+        the instance mask - the mask is made on the device from the class image and the frame's disparity (connected components; optional Labels.*
+        settings keys) and never exists on the host.  Returns Tcw 4x4 float32, or None."""
+        L = self._L
+        L.host_system_track_stereo_pair_semantic.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                             C.c_int, C.c_void_p]
+        if left.shape != right.shape or left.shape != left_next.shape:
+            raise ValueError(f"left {left.shape}, right {right.shape} and left_next {left_next.shape} differ")
+        h, w = left.shape[:2]
+        ch = 1 if left.ndim == 2 else left.shape[2]
+        classes = np.ascontiguousarray(classes)
+        if classes.dtype != np.uint8 or classes.shape != (h, w):
+            raise ValueError(f"classes: {classes.dtype} {classes.shape}, expected uint8 {(h, w)}")
+        rows = None if obj_rows is None or len(obj_rows) == 0 else np.ascontiguousarray(obj_rows, np.float32)
+        rc = L.host_system_track_stereo_pair_semantic(self._h, _ptr(left), _ptr(right), _ptr(left_next), ch, _ptr(classes), w, h, _ptr(rows), 0 if rows is None else rows.shape[0],
+                                                      0 if rows is None else rows.shape[1], int(n_images), _ptr(self._T))
+        return None if rc != 0 else self._T.reshape(4, 4).copy()
+
     def track_files(self, rgb_path, depth_path, flow_path, mask_path, obj_rows=None, n_images=1 << 30):
         """One TrackRGBDFromFiles call: the frame's colour PNG, disparity PNG, .flo and mask text decoded on the device (the reference driver's
         imread / convertTo / readOpticalFlow / LoadMask, example/vdo_slam.cc:104-131) and tracked.  Returns Tcw 4x4 float32, or None."""
