@@ -876,6 +876,101 @@ int vdo_labels_device_images(vdo_labels* h, uint8_t** cls, int32_t** mask);
  * device (src_is_device covers both sources of a compute): Tracking::GrabImageStereoPairSemantic.  Host-synchronous. */
 int vdo_labels_stage_classes(vdo_labels* h, const uint8_t* cls, int64_t cls_stride, uint8_t** cls_dev);
 
+/* ---- Stereo rectifier: lens undistortion and fixed-point remap ---------------------------------------------------------------------
+ * New (the reference's stereo example starts with cv::initUndistortRectifyMap + cv::remap; its System takes images that are already
+ * rectified): from the raw 8-bit images of one or two cameras to the rectified grey images the stereo and flow matchers take.  Two parts: a map,
+ * computed once per camera on the host, and a remap, computed per image on the device.  The weights are the project's own (5 fractional bits,
+ * not OpenCV's table): no bit equality with cv::remap is claimed.
+ *
+ * MAP, fp64, every operation rounded on its own and done in the order written (no contraction).  Raw camera K = (fx, fy, cx, cy),
+ * D = (k1, k2, p1, p2, k3), rectifying rotation R (row-major; its transpose is used, nothing is inverted), rectified camera
+ * P = (fx', fy', cx', cy'), source size Ws x Hs, destination size W x H.  For destination pixel (u, v):
+ *     x = (u - cx') / fx';  y = (v - cy') / fy'
+ *     X = (R00*x + R10*y) + R20;  Y = (R01*x + R11*y) + R21;  Wc = (R02*x + R12*y) + R22
+ *     invalid unless Wc > 0;  xn = X / Wc;  yn = Y / Wc
+ *     x2 = xn*xn; y2 = yn*yn; r2 = x2 + y2; xy2 = 2*(xn*yn)
+ *     t = r2*k3; t = k2 + t; t = r2*t; t = k1 + t; t = r2*t; kr = 1 + t
+ *     xd = (xn*kr + p1*xy2) + p2*(r2 + 2*x2)
+ *     yd = (yn*kr + p1*(r2 + 2*y2)) + p2*xy2
+ *     us = fx*xd + cx;  vs = fy*yd + cy
+ *     qx = rint(32*us), qy = rint(32*vs)        (ties to even; invalid when not finite or |.| >= 2^30)
+ *     ix = qx >> 5, ax = qx & 31, iy = qy >> 5, ay = qy & 31     (arithmetic shift)
+ *     valid iff 0 <= ix, ix + (ax > 0) <= Ws - 1, 0 <= iy, iy + (ay > 0) <= Hs - 1
+ * The stored map is int32 [H][W][2] = (qx, qy); an invalid pixel stores (INT32_MIN, INT32_MIN).  A uint8 validity image [H][W] (1 = valid) and
+ * its count go with it.
+ *
+ * REMAP, integer arithmetic only, S the source image.  For a valid pixel the taps are p00 = S(ix, iy), p01 = S(ix+1, iy), p10 = S(ix, iy+1),
+ * p11 = S(ix+1, iy+1); a tap with weight 0 is not read;
+ *     out = ((32-ax)*(32-ay)*p00 + ax*(32-ay)*p01 + (32-ax)*ay*p10 + ax*ay*p11 + 512) >> 10.
+ * An invalid pixel gets the `border` byte.  For a 3- or 4-channel source every tap is first made grey by the arithmetic of vdo_rgb2gray (K2:
+ * (r*4899 + g*9617 + b*1868 + 8192) >> 14, r = byte 0 when rgb_order != 0, else byte 2), then interpolated: vdo_rgb2gray followed by a
+ * one-channel remap.  In `nearest` mode (one channel only; for class images) out = S((qx + 16) >> 5, (qy + 16) >> 5) (the sum taken without
+ * overflow), valid iff that tap lies inside the source.
+ * NO OUT-OF-RANGE READS: the kernel re-derives validity from the stored (qx, qy) and the source size, in the remap's mode; it trusts no flag, so
+ * whatever map it is handed it cannot read outside the source image. */
+typedef struct vdo_rectify vdo_rectify;
+typedef struct vdo_rectify_camera {
+  double K[4];                      /* fx, fy, cx, cy of the raw camera; fx, fy > 0 */
+  double D[5];                      /* k1, k2, p1, p2, k3 */
+  double R[9];                      /* rectifying rotation, row-major */
+  int32_t src_width, src_height;    /* Ws x Hs, >= 1 */
+} vdo_rectify_camera;
+typedef struct vdo_rectify_params {
+  int32_t n_cams;                   /* 1 or 2 */
+  int32_t width, height;            /* W x H of every destination image, >= 1 */
+  double P[4];                      /* fx', fy', cx', cy' of the rectified camera; fx', fy' > 0 */
+  vdo_rectify_camera cam[2];
+} vdo_rectify_params;
+typedef struct vdo_rectify_job {
+  const uint8_t* src;               /* rows of Ws * channels bytes, src_stride bytes apart */
+  int64_t src_stride;
+  int32_t channels;                 /* 1, 3 or 4 */
+  int32_t rgb_order;                /* as vdo_rgb2gray; ignored with one channel */
+  int32_t cam;                      /* whose map and source size */
+  int32_t nearest;                  /* != 0: nearest mode, one channel only */
+  uint8_t* dst;                     /* rows of W bytes, dst_stride bytes apart */
+  int64_t dst_stride;
+} vdo_rectify_job;
+/* The MAP above for camera `cam` of `params`: host only, it needs no device and no context (like vdo_ba_plan_create).  map: width x height x 2
+ * int32; valid (width x height bytes) and n_valid may be NULL.  VDO_ERR_INVALID, the message naming the argument, and then nothing is written:
+ * a null params or map; n_cams outside 1..2; cam outside 0..n_cams-1; a size < 1; fx, fy, fx' or fy' not finite or <= 0; any other parameter
+ * not finite.  VDO_ERR_UNSUPPORTED when width * height or a source's width * height exceeds 2^26. */
+int vdo_rectify_plan(const vdo_rectify_params* params, int cam, int32_t* map, uint8_t* valid, int32_t* n_valid);
+/* A rectifier for params->n_cams cameras and one destination size.  ALL device memory is taken here (per camera the map, 8 bytes per destination
+ * pixel, and the validity image; staging for 4 source images of 4 channels of the largest source; 4 destination images; one float image for a
+ * host image of vdo_rectify_gate); vdo_rectify_compute and vdo_rectify_gate allocate nothing.  Refusals as vdo_rectify_plan, and a null ctx or
+ * out.  VDO_ERR_OOM when the device has no room. */
+int vdo_rectify_create(vdo_ctx* ctx, const vdo_rectify_params* params, vdo_rectify** out);
+/* The same from ready-made maps - the door for every lens model the planner leaves out (fisheye, a look-up calibration): maps[c] is
+ * width x height x 2 int32 = (qx, qy) for a source of src_width[c] x src_height[c]; any values are legal (NO OUT-OF-RANGE READS above).  The
+ * validity images are re-derived from the maps in bilinear mode. */
+int vdo_rectify_create_from_maps(vdo_ctx* ctx, int width, int height, int n_cams, const int32_t* const* maps, const int32_t* src_width,
+                                 const int32_t* src_height, vdo_rectify** out);
+int vdo_rectify_destroy(vdo_rectify* h);
+/* n_jobs = 1..4 remaps in ONE kernel launch, host-synchronous, on the context's stream.  Every src is a host pointer, or a device pointer when
+ * src_is_device != 0 (read where it lies, at its stride); every dst likewise with dst_is_device (written where it lies; any alignment).  Two
+ * jobs may share a map or a source; destinations must not overlap.  VDO_ERR_INVALID, the message naming the argument, for a null handle, jobs,
+ * src or dst; n_jobs outside 1..4; cam outside the handle's cameras; channels not 1, 3 or 4; nearest with more than one channel;
+ * src_stride < Ws * channels; dst_stride < W; border outside 0..255 - and then NOTHING is written.  No state of an earlier compute on the handle enters the result. */
+int vdo_rectify_compute(vdo_rectify* h, const vdo_rectify_job* jobs, int n_jobs, int src_is_device, int dst_is_device, int border);
+/* Writes 0.0f wherever cam's (bilinear) validity is 0 and leaves every other value bit for bit: a disparity made from border filler becomes "no
+ * depth".  image: width x height floats, rows stride_floats apart (>= width), a device pointer when is_device != 0.  *n_cleared = the number of
+ * values whose bits changed (an invalid pixel that already held +0.0f is not counted).  Host-synchronous.  VDO_ERR_INVALID for a null pointer, a
+ * cam out of range or a stride < width, and then nothing is written. */
+int vdo_rectify_gate(vdo_rectify* h, int cam, float* image, int64_t stride_floats, int is_device, int32_t* n_cleared);
+/* Host outputs: cam's map [H][W][2]; its validity image [H][W] and count (either may be NULL). */
+int vdo_rectify_get_map(vdo_rectify* h, int cam, int32_t* map);
+int vdo_rectify_get_valid(vdo_rectify* h, int cam, uint8_t* valid, int32_t* n_valid);
+/* The last compute or gate: ms[0] wall time of the call, ms[1] device time from the first upload to the end of the kernel (events). */
+int vdo_rectify_last_timing(vdo_rectify* h, double ms[2]);
+/* Device images owned by the handle, for callers without their own, k = 0..3: the staging image a host source of job k is uploaded to (room for
+ * 4 channels of the largest source; uploading into it and passing it as a device source is allowed) and a packed width x height destination
+ * image.  Either may be NULL. */
+int vdo_rectify_device_images(vdo_rectify* h, int k, uint8_t** src, uint8_t** dst);
+/* Brings a width x height destination image that lies on the device (rows stride bytes apart; e.g. the stereo matcher's left staging image a
+ * device-destination job wrote) to the host, packed: for a caller that wants to look at a rectified image.  Host-synchronous. */
+int vdo_rectify_download_image(vdo_rectify* h, const uint8_t* image_dev, int64_t stride, uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -68,6 +68,75 @@ bool read_tracking_settings(const std::string& path, TrackingSettings& t, std::m
   if (raw) *raw = c;
   return true;
 }
+// The bracketed number lists of a settings file, "key: [a, b, c]" on one line, beside the flat reader above (which skips them: strtod fails on '[').
+// A list that does not parse to its closing bracket is kept EMPTY, so that whoever asks for it sees a wrong length.  False when the file cannot be opened.
+bool read_settings_lists(const std::string& path, std::map<std::string, std::vector<double> >& out) {
+  std::ifstream f(path.c_str());
+  if (!f.is_open()) return false;
+  std::string line;
+  while (std::getline(f, line)) {
+    const size_t h = line.find('#');
+    if (h != std::string::npos) line = line.substr(0, h);
+    if (line.empty() || line[0] == '%') continue;
+    const size_t c = line.find(':');
+    if (c == std::string::npos) continue;
+    std::string key = line.substr(0, c);
+    while (!key.empty() && (key.back() == ' ' || key.back() == '\t')) key.pop_back();
+    const char* p = line.c_str() + c + 1;
+    while (*p == ' ' || *p == '\t') ++p;
+    if (*p != '[') continue;
+    ++p;
+    std::vector<double> v;
+    bool closed = false;
+    for (;;) {
+      while (*p == ' ' || *p == '\t' || *p == ',') ++p;
+      if (*p == ']') { closed = true; break; }
+      char* end = nullptr;
+      const double d = std::strtod(p, &end);
+      if (end == p) break;
+      v.push_back(d);
+      p = end;
+    }
+    if (!closed) v.clear();
+    out[key] = v;
+  }
+  return true;
+}
+// The Rectify.* keys (System.h).  present: any of them is in the file.  The returned text is empty when the keys are absent or in order; otherwise it is
+// the settings error, which ends the process in Tracking::Tracking and is a refusal in host_system_create.
+struct RectifySettings { bool present = false; vdo_rectify_params p{}; int border = 0, classes = 0; };
+std::string read_rectify_settings(const std::string& path, const TrackingSettings& t, const std::map<std::string, double>& raw, int sensor, RectifySettings& rs) {
+  std::map<std::string, std::vector<double> > lists;
+  read_settings_lists(path, lists);
+  auto is_rect = [](const std::string& k) { return k.compare(0, 8, "Rectify.") == 0; };
+  for (const auto& kv : lists) if (is_rect(kv.first)) rs.present = true;
+  for (const auto& kv : raw) if (is_rect(kv.first)) rs.present = true;
+  if (!rs.present) return "";
+  if (sensor != System::STEREO) return "settings: the Rectify.* keys need the STEREO sensor (depth, flow and mask images of the RGBD path are not remapped)";
+  rs.p.n_cams = 2;
+  rs.p.width = t.width; rs.p.height = t.height;
+  rs.p.P[0] = get(raw, "Camera.fx"); rs.p.P[1] = get(raw, "Camera.fy"); rs.p.P[2] = get(raw, "Camera.cx"); rs.p.P[3] = get(raw, "Camera.cy");
+  const int sw = (int)get(raw, "Rectify.Width", t.width), sh = (int)get(raw, "Rectify.Height", t.height);
+  static const char* const side[2] = {"Left", "Right"};
+  for (int c = 0; c < 2; ++c) {
+    vdo_rectify_camera& q = rs.p.cam[c];
+    q.src_width = sw; q.src_height = sh;
+    struct { const char* name; double* dst; size_t n_min, n_max; } want[3] = {{"K", q.K, 4, 4}, {"D", q.D, 4, 5}, {"R", q.R, 9, 9}};
+    for (const auto& w : want) {
+      const std::string key = std::string("Rectify.") + side[c] + "." + w.name;
+      const auto it = lists.find(key);
+      if (it == lists.end()) return "settings: " + key + " is missing (the Rectify.* keys come as Left and Right K, D and R)";
+      if (it->second.size() < w.n_min || it->second.size() > w.n_max)
+        return "settings: " + key + " has " + std::to_string(it->second.size()) + " values, expected " + std::to_string(w.n_max) + (w.n_min != w.n_max ? " (or 4)" : "");
+      for (size_t k = 0; k < w.n_max; ++k) w.dst[k] = k < it->second.size() ? it->second[k] : 0.0;
+    }
+  }
+  rs.border = (int)get(raw, "Rectify.Border", 0);
+  rs.classes = (int)get(raw, "Rectify.Classes", 0);
+  if (rs.border < 0 || rs.border > 255) return "settings: Rectify.Border outside 0..255";
+  if (sw < 1 || sh < 1) return "settings: Rectify.Width / Rectify.Height must be positive";
+  return "";
+}
 }  // namespace
 
 Tracking::Tracking(System*, Map* pMap, const std::string& strSettingPath, const int sensor) : mpMap(pMap) {
@@ -86,6 +155,11 @@ Tracking::Tracking(System*, Map* pMap, const std::string& strSettingPath, const 
   mDistCoef.at<float>(0, 0) = t.k1; mDistCoef.at<float>(1, 0) = t.k2; mDistCoef.at<float>(2, 0) = t.p1; mDistCoef.at<float>(3, 0) = t.p2;
   if (t.k3 != 0) mDistCoef.at<float>(4, 0) = t.k3;
   if (t.k1 != 0 || t.k2 != 0 || t.p1 != 0 || t.p2 != 0 || t.k3 != 0) { std::cerr << "settings: lens distortion (Camera.k1..k3, p1, p2) is not supported by this build" << std::endl; std::exit(-1); }
+  RectifySettings rect;
+  {
+    const std::string err = read_rectify_settings(strSettingPath, t, cfg_, sensor, rect);
+    if (!err.empty()) { std::cerr << err << std::endl; std::exit(-1); }
+  }
   PipelineParams p{};
   p.width = t.width; p.height = t.height;
   p.K4[0] = t.fx; p.K4[1] = t.fy; p.K4[2] = t.cx; p.K4[3] = t.cy;
@@ -130,11 +204,16 @@ Tracking::Tracking(System*, Map* pMap, const std::string& strSettingPath, const 
     labels_.reset(new InstanceLabeler(ctx_[0], p.width, p.height, lp));
     speckle_size_ = (int)get(cfg_, "Stereo.SpeckleSize", 0);
     speckle_range_ = in_depth_units(get(cfg_, "Stereo.SpeckleRange", 256));
+    if (rect.present) {
+      rectifier_.reset(new StereoRectifier(ctx_[0], rect.p));
+      rect_border_ = rect.border; rect_classes_ = rect.classes;
+    }
   }
 }
 
 Tracking::~Tracking() {
   pipe_.reset();
+  rectifier_.reset();
   stereo_.reset();
   flow_.reset();
   labels_.reset();
@@ -225,6 +304,7 @@ cv::Mat Tracking::GrabStereoFrame(const char* who, const cv::Mat& imLeft, const 
   mLastProcessedState = mState;
   if (mState == NO_IMAGES_YET) mState = NOT_INITIALIZED;
   const int W = pipe_->params().width, H = pipe_->params().height;
+  if (rectifier_) return GrabRawStereoFrame(who, imLeft, imRight, imFlow, imLeftNext, maskSEM, classes, mTcw_gt, vObjPose_gt, t_call);
   {
     auto bad = [&](const cv::Mat& m, const char* name, int depth, int ch_lo, int ch_hi) {
       const bool ok = !m.empty() && m.rows == H && m.cols == W && m.depth() == depth && m.channels() >= ch_lo && m.channels() <= ch_hi &&
@@ -282,6 +362,84 @@ cv::Mat Tracking::GrabStereoFrame(const char* who, const cv::Mat& imLeft, const 
   if (pipe_->StepDevice(d_gray, d_disp, d_flow, d_mask, false, &fc) != 0) return cv::Mat();
   if (maskSEM && fc.n_recovered_masks > 0) pipe_->DownloadMask((int32_t*)maskSEM->data);      // UpdateMask writes through the shared header, as in GrabImageRGBD
   return FinishFrame(mTcw_gt, t_call);
+}
+
+// GrabStereoFrame with a rectifier (Rectify.* keys): the left, right and next-left images are RAW.  One vdo_rectify_compute reads the caller's images once
+// and writes grey, rectified pixels straight into the stereo matcher's two staging images and the flow matcher's second image (and, with Rectify.Classes,
+// the class image nearest-neighbour into the labeller's): no vdo_rgb2gray round trip, no second upload.  The matchers then run on device sources.
+cv::Mat Tracking::GrabRawStereoFrame(const char* who, const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat* imFlow, const cv::Mat* imLeftNext, const cv::Mat* maskSEM,
+                                     const cv::Mat* classes, const cv::Mat& mTcw_gt, const std::vector<std::vector<float> >& vObjPose_gt,
+                                     std::chrono::steady_clock::time_point t_call) {
+  const int W = pipe_->params().width, H = pipe_->params().height, Ws = rectifier_->srcWidth(0), Hs = rectifier_->srcHeight(0);
+  {
+    auto bad = [&](const cv::Mat& m, const char* name, int depth, int ch_lo, int ch_hi, bool raw) {
+      const int w = raw ? Ws : W, h = raw ? Hs : H;
+      const bool ok = !m.empty() && m.rows == h && m.cols == w && m.depth() == depth && m.channels() >= ch_lo && m.channels() <= ch_hi &&
+                      m.step == (size_t)m.cols * m.elemSize();
+      if (!ok) std::cerr << "VDO_SLAM::Tracking::" << who << ": " << name << " is " << m.cols << "x" << m.rows << " (type " << m.type() << ", step " << m.step
+                         << "), expected a continuous " << w << "x" << h << " image of the settings file's "
+                         << (raw ? "Rectify.Width/Height (the raw size)" : "Camera.width/height (the rectified size)") << std::endl;
+      return !ok;
+    };
+    if (bad(imLeft, "imLeft", cv::CV_8U, 1, 4, true) || imLeft.channels() == 2 || bad(imRight, "imRight", cv::CV_8U, 1, 4, true) || imRight.channels() == 2 ||
+        (imFlow && bad(*imFlow, "imFlow", cv::CV_32F, 2, 2, false)) || (imLeftNext && (bad(*imLeftNext, "imLeftNext", cv::CV_8U, 1, 4, true) || imLeftNext->channels() == 2)) ||
+        (maskSEM && bad(*maskSEM, "maskSEM", cv::CV_32S, 1, 1, false)) || (classes && bad(*classes, "classes", cv::CV_8U, 1, 1, rect_classes_ != 0)))
+      return cv::Mat();
+  }
+  vdo_stereo* sh = stereo_->handle();
+  vdo_optflow* fh = flow_->handle();
+  vdo_labels* lh = labels_->handle();
+  vdo_rectify* rh = rectifier_->handle();
+  uint8_t *d_gray = nullptr, *d_right = nullptr, *d_next = nullptr, *d_cls = nullptr;
+  float *d_disp = nullptr, *d_flow = nullptr; int32_t* d_mask = nullptr;
+  bool ok = vdo_stereo_device_images(sh, &d_gray, &d_right, &d_disp) == VDO_OK;
+  const int order = mbRGB ? 1 : 0;
+  vdo_rectify_job jobs[4];
+  int n_jobs = 0;
+  jobs[n_jobs++] = vdo_rectify_job{imLeft.data, (int64_t)imLeft.step, imLeft.channels(), order, 0, 0, d_gray, W};
+  jobs[n_jobs++] = vdo_rectify_job{imRight.data, (int64_t)imRight.step, imRight.channels(), order, 1, 0, d_right, W};
+  if (ok && imLeftNext) {
+    ok = vdo_optflow_device_images(fh, nullptr, &d_next, &d_flow, nullptr) == VDO_OK;
+    jobs[n_jobs++] = vdo_rectify_job{imLeftNext->data, (int64_t)imLeftNext->step, imLeftNext->channels(), order, 0, 0, d_next, W};
+  }
+  if (ok && classes) {
+    ok = vdo_labels_device_images(lh, &d_cls, &d_mask) == VDO_OK;
+    if (rect_classes_) jobs[n_jobs++] = vdo_rectify_job{classes->data, (int64_t)classes->step, 1, 0, 0, 1, d_cls, W};
+  }
+  int32_t n_valid = 0, n_cleared = 0;
+  ok = ok && vdo_rectify_compute(rh, jobs, n_jobs, 0, 1, rect_border_) == VDO_OK && vdo_stereo_compute(sh, d_gray, W, d_right, W, 1, d_disp, 1, &n_valid) == VDO_OK &&
+       vdo_rectify_gate(rh, 0, d_disp, W, 1, &n_cleared) == VDO_OK;       // a disparity made from border filler is no depth
+  if (ok && speckle_size_ > 0) { int32_t n_removed = 0; ok = vdo_labels_filter_speckles(lh, d_disp, 1, speckle_range_, speckle_size_, &n_removed) == VDO_OK; }
+  if (ok && classes) {
+    int32_t counts[3];
+    if (!rect_classes_) ok = vdo_labels_stage_classes(lh, classes->data, W, &d_cls) == VDO_OK;
+    ok = ok && vdo_labels_compute(lh, d_cls, W, d_disp, W, 1, d_mask, 1, counts) == VDO_OK;
+  }
+  if (ok && imFlow) ok = vdo_stereo_stage_frame(sh, (const float*)imFlow->data, (const int32_t*)maskSEM->data, &d_flow, &d_mask) == VDO_OK;
+  if (ok && imLeftNext) {
+    int32_t n_flow = 0;
+    ok = vdo_optflow_compute(fh, d_gray, W, d_next, W, 1, d_flow, nullptr, 1, &n_flow) == VDO_OK &&
+         (!maskSEM || vdo_optflow_stage_mask(fh, (const int32_t*)maskSEM->data, &d_mask) == VDO_OK);
+  }
+  if (!ok) { std::cerr << "VDO_SLAM::Tracking::" << who << ": " << vdo_last_error() << std::endl; return cv::Mat(); }
+  std::vector<int> labels;
+  for (const auto& row : vObjPose_gt) if (row.size() > 1) labels.push_back((int)row[1]);
+  pipe_->SetObjectGate(labels.data(), (int)labels.size());
+  FrameCounts fc{};
+  if (pipe_->StepDevice(d_gray, d_disp, d_flow, d_mask, false, &fc) != 0) return cv::Mat();
+  if (maskSEM && fc.n_recovered_masks > 0) pipe_->DownloadMask((int32_t*)maskSEM->data);
+  return FinishFrame(mTcw_gt, t_call);
+}
+
+cv::Mat Tracking::DownloadRectifiedLeft() {
+  if (!rectifier_ || !stereo_) return cv::Mat();
+  uint8_t* d_gray = nullptr;
+  cv::Mat out(pipe_->params().height, pipe_->params().width, cv::CV_8UC1);
+  if (vdo_stereo_device_images(stereo_->handle(), &d_gray, nullptr, nullptr) != VDO_OK ||
+      vdo_rectify_download_image(rectifier_->handle(), d_gray, pipe_->params().width, out.data) != VDO_OK) {
+    std::cerr << "VDO_SLAM::Tracking::DownloadRectifiedLeft: " << vdo_last_error() << std::endl; return cv::Mat();
+  }
+  return out;
 }
 
 // What GrabImageRGBD / GrabFilesRGBD do after the frame's Step: ground-truth bookkeeping, the final batch optimisation, the returned pose
@@ -524,6 +682,9 @@ static VDO_SLAM::System* host_system_create_sensor(const char* settings, VDO_SLA
     if (raw.count("Camera.width") == 0 || raw.count("Camera.height") == 0 || raw["Camera.width"] <= 0 || raw["Camera.height"] <= 0) {
       std::fprintf(stderr, "host_system_create: Camera.width / Camera.height missing in %s\n", settings); return nullptr;
     }
+    VDO_SLAM::RectifySettings rect;
+    const std::string err = VDO_SLAM::read_rectify_settings(settings, t, raw, sensor, rect);
+    if (!err.empty()) { std::fprintf(stderr, "host_system_create: %s\n", err.c_str()); return nullptr; }
   }
   {
     const char* dev = std::getenv("VDO_DEVICE");
@@ -537,6 +698,12 @@ static VDO_SLAM::System* host_system_create_sensor(const char* settings, VDO_SLA
 VDO_SLAM::System* host_system_create(const char* settings) { return host_system_create_sensor(settings, VDO_SLAM::System::RGBD); }
 // System(settings, System::STEREO): the same checks; a Stereo.* key the matcher refuses comes back as nullptr with its message on stderr
 VDO_SLAM::System* host_system_create_stereo(const char* settings) { return host_system_create_sensor(settings, VDO_SLAM::System::STEREO); }
+// System(settings, sensor) as a C++ caller gets it, WITHOUT the checks above: a settings error ends the process with exit(-1), like the reference's
+// (tests/test_rectify_settings.py runs it in a child process)
+VDO_SLAM::System* host_system_create_unchecked(const char* settings, int stereo) {
+  try { return new VDO_SLAM::System(settings, stereo ? VDO_SLAM::System::STEREO : VDO_SLAM::System::RGBD); }
+  catch (const std::exception& e) { std::fprintf(stderr, "host_system_create_unchecked: %s\n", e.what()); return nullptr; }
+}
 void host_system_destroy(VDO_SLAM::System* s) { delete s; }
 // one TrackRGBD call on host images: im (h x w x channels u8), depth (in/out f32), flow (f32 x2), mask (in/out i32), ground-truth
 // object rows [n_rows][row_len]; Tcw_out 16 floats.  Returns 0, -1 when the tracker returned an empty pose, -2 on a GPU failure.
@@ -607,6 +774,35 @@ int host_system_frame_state(VDO_SLAM::System* s, int what, float* out, int cap) 
     }
   } catch (const std::exception& e) { std::fprintf(stderr, "host_system_frame_state: %s\n", e.what()); }
   return -1;
+}
+// The settings reader's bracketed lists alone (no GPU): the values of `key` into out (at most cap), returns their number, -1 when the key is no list
+// and -2 when the file cannot be opened.
+int host_settings_read_list(const char* path, const char* key, double* out, int cap) {
+  std::map<std::string, std::vector<double> > lists;
+  if (!VDO_SLAM::read_settings_lists(path, lists)) return -2;
+  const auto it = lists.find(key);
+  if (it == lists.end()) return -1;
+  for (int i = 0; i < (int)it->second.size() && i < cap; ++i) out[i] = it->second[i];
+  return (int)it->second.size();
+}
+// what Tracking::Tracking would exit(-1) on among the Rectify.* keys, without a GPU: 0 in order (or absent), 1 a settings error (text in msg), -2 no file
+int host_settings_check_rectify(const char* path, int stereo, char* msg, int cap) {
+  VDO_SLAM::TrackingSettings t{};
+  std::map<std::string, double> raw;
+  if (!VDO_SLAM::read_tracking_settings(path, t, &raw)) return -2;
+  VDO_SLAM::RectifySettings rect;
+  const std::string err = VDO_SLAM::read_rectify_settings(path, t, raw, stereo ? VDO_SLAM::System::STEREO : VDO_SLAM::System::RGBD, rect);
+  if (msg && cap > 0) std::snprintf(msg, (size_t)cap, "%s", err.c_str());
+  return err.empty() ? 0 : 1;
+}
+// the rectified grey left image of the last stereo call of a System with Rectify.* keys: [Camera.height][Camera.width]; 0, or -1 without a rectifier
+int host_system_rectified_left(VDO_SLAM::System* s, unsigned char* out) {
+  try {
+    cv::Mat m = s->tracker()->DownloadRectifiedLeft();
+    if (m.empty()) return -1;
+    std::memcpy(out, m.data, (size_t)m.rows * m.cols);
+    return 0;
+  } catch (const std::exception& e) { std::fprintf(stderr, "host_system_rectified_left: %s\n", e.what()); return -1; }
 }
 // throughput mode of the shell: the object stage of a frame ends inside the next TrackRGBD call (same results, the object motions of
 // frame k become visible with frame k+1; the final batch optimisation / SaveResults / map() flush it).  Off by default: the

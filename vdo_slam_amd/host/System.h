@@ -13,6 +13,7 @@
 #include "Frame.h"
 #include "FramePipeline.h"
 #include "InstanceLabeler.h"
+#include "StereoRectifier.h"
 #include "Map.h"
 #include "StereoMatcher.h"
 #include "minicv.h"
@@ -53,6 +54,13 @@ class Tracking {
   // never exists on the host; its labels carry no identity from frame to frame (the tracker associates objects through the flow).
   cv::Mat GrabImageStereoPairSemantic(const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat& imLeftNext, const cv::Mat& classes, const cv::Mat& mTcw_gt,
                                       const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, cv::Mat& imTraj, const int& nImage);
+  // Raw images (settings keys Rectify.*, STEREO only; System::TrackStereo below): with the keys present, imLeft / imRight / imLeftNext of the three
+  // entries above are the RAW images of Rectify.Width x Rectify.Height; one vdo_rectify_compute undistorts, rectifies and makes them grey straight
+  // into the matchers' device images, and the disparity is cleared wherever the left map is invalid.  rectifier() is null without the keys.
+  StereoRectifier* rectifier() { return rectifier_.get(); }
+  // The rectified grey left image of the last Grab*Stereo* call (CV_8UC1 of Camera.width x Camera.height), e.g. to run a segmentation on it; empty
+  // without a rectifier (the caller's own image is the rectified one then).
+  cv::Mat DownloadRectifiedLeft();
   FramePipeline* pipeline() { return pipe_.get(); }
   InstanceLabeler* labeler() { return labels_.get(); }   // null unless the sensor is System::STEREO
   FlowMatcher* flow() { return flow_.get(); }            // null unless the sensor is System::STEREO
@@ -96,9 +104,13 @@ class Tracking {
   std::unique_ptr<StereoMatcher> stereo_;
   std::unique_ptr<FlowMatcher> flow_;
   std::unique_ptr<InstanceLabeler> labels_;
+  std::unique_ptr<StereoRectifier> rectifier_;           // Rectify.* keys present: the stereo entries take raw images
+  int rect_border_ = 0, rect_classes_ = 0;               // Rectify.Border, Rectify.Classes
   int speckle_size_ = 0, speckle_range_ = 256;           // Stereo.SpeckleSize (0: no filter), Stereo.SpeckleRange, the latter in the depth image's units
   cv::Mat GrabStereoFrame(const char* who, const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat* imFlow, const cv::Mat* imLeftNext, const cv::Mat* maskSEM,
                           const cv::Mat* classes, const cv::Mat& mTcw_gt, const std::vector<std::vector<float> >& vObjPose_gt, const int& nImage);
+  cv::Mat GrabRawStereoFrame(const char* who, const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat* imFlow, const cv::Mat* imLeftNext, const cv::Mat* maskSEM,
+                             const cv::Mat* classes, const cv::Mat& mTcw_gt, const std::vector<std::vector<float> >& vObjPose_gt, std::chrono::steady_clock::time_point t_call);
   bool have_frame_ = false;
   vdo_ingest* ingest_ = nullptr;       // GrabFilesRGBD: device decode of the frame's files, made on first use
   cv::Mat FinishFrame(const cv::Mat& mTcw_gt, std::chrono::steady_clock::time_point t_call);
@@ -125,6 +137,11 @@ class System {
   // Stereo.SubPixel 1, all optional): Tracking::GrabImageStereo.  Exits like TrackRGBD when the sensor is not STEREO.
   cv::Mat TrackStereo(const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat& flowmap, const cv::Mat& masksem, const cv::Mat& mTcw_gt,
                       const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, cv::Mat& imTraj, const int& nImage);
+  // Raw, unrectified images (all three stereo entries): the settings keys Rectify.Left.K: [fx, fy, cx, cy], Rectify.Left.D: [k1, k2, p1, p2, k3] (4 values:
+  // k3 = 0), Rectify.Left.R: [9 values, row-major] and the same three for Rectify.Right.*, with the optional scalars Rectify.Width / Rectify.Height (the raw
+  // size; default Camera.width / Camera.height), Rectify.Border (0) and Rectify.Classes (0; 1: the class image of TrackStereoPairSemantic is raw too and
+  // is remapped nearest-neighbour through the left map).  Camera.* then describes the RECTIFIED camera, Camera.bf the rectified baseline; flow, mask and
+  // class images are taken as given in the rectified geometry.  A partial set, a wrong list length or the keys with an RGBD sensor are settings errors.
   // TrackStereo with the flow made on the device from imLeft and imLeftNext (Tracking::GrabImageStereoPair; settings keys Flow.Levels 6, Flow.Radius 2,
   // Flow.Window 2, Flow.Median 1, Flow.FBMaxDiff 1, Flow.SubPixel 1, all optional).  Exits like TrackStereo when the sensor is not STEREO.
   cv::Mat TrackStereoPair(const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat& imLeftNext, const cv::Mat& masksem, const cv::Mat& mTcw_gt,

@@ -347,4 +347,28 @@ int host_system_track_stereo_pair_semantic(System* s, const unsigned char* left,
   return 0;
 }
 
+// StereoRectifier::Rectify on n = 1..4 host images (image k: rows steps[k] bytes apart, channels[k] channels, camera cams[k], nearest[k]) in one call;
+// out[k]: [height][width] of the destination.  gate_image (may be null): a [height][width] float image gated in place through camera gate_cam after the
+// remap; its cleared count comes back in *n_cleared.  Returns 0, -1 on a failure.
+int host_rectify_compute(const vdo_rectify_params* p, int n, const unsigned char* const* src, const int* steps, const int* channels, const int* cams, const int* nearest,
+                         int rgb_order, int border, unsigned char* const* out, float* gate_image, int gate_cam, int* n_cleared) {
+  try {
+    StereoRectifier r(nullptr, *p);
+    std::vector<cv::Mat> raw(n);
+    std::vector<int> cam(cams, cams + n), nn(nearest, nearest + n);
+    for (int k = 0; k < n; ++k) {
+      raw[k] = cv::Mat(r.srcHeight(cams[k]), r.srcWidth(cams[k]), VDO_CV_MAKETYPE(cv::CV_8U, channels[k]), (void*)src[k]);
+      raw[k].step = (size_t)steps[k];
+    }
+    const std::vector<cv::Mat> res = r.Rectify(raw, cam, rgb_order != 0, nn, border);
+    for (int k = 0; k < n; ++k) std::memcpy(out[k], res[k].data, (size_t)r.width() * r.height());
+    if (gate_image) {
+      cv::Mat G(r.height(), r.width(), cv::CV_32FC1, gate_image);
+      const int c = r.Gate(G, gate_cam);
+      if (n_cleared) *n_cleared = c;
+    }
+    return 0;
+  } catch (const std::exception& e) { std::fprintf(stderr, "host_rectify_compute: %s\n", e.what()); return -1; }
+}
+
 }  // extern "C"

@@ -37,12 +37,33 @@ ORBextractor.minThFAST: 7
 """
 
 
-def write_settings(path, w, h, K4, bf, dmf, thbg, thobj, window=20, overlap=4, choose_data=2, use_sample_feature=0, sf_mg_thres=0.12, n_features=2500):
-    """A settings file in the reference's flat YAML dialect (example/kitti-0000-0013.yaml)."""
+def rectify_keys(left, right, raw_size=None, border=None, classes=None):
+    """The Rectify.* lines of a settings file.  left / right: dicts with "K" (fx, fy, cx, cy), "D" (k1, k2, p1, p2[, k3]) and "R" (9 values,
+    row-major) of the RAW cameras - Camera.* then describes the rectified one; raw_size = (width, height) of the raw images when it differs
+    from Camera.width / height; border: the byte of pixels without a source; classes = 1: the class image is raw too."""
+    out = []
+    for side, cam in (("Left", left), ("Right", right)):
+        for name in ("K", "D", "R"):
+            vals = np.asarray(cam[name], np.float64).reshape(-1)
+            out.append(f"Rectify.{side}.{name}: [" + ", ".join(repr(float(v)) for v in vals) + "]")
+    if raw_size is not None:
+        out += [f"Rectify.Width: {int(raw_size[0])}", f"Rectify.Height: {int(raw_size[1])}"]
+    if border is not None:
+        out.append(f"Rectify.Border: {int(border)}")
+    if classes is not None:
+        out.append(f"Rectify.Classes: {int(classes)}")
+    return "\n".join(out) + "\n"
+
+
+def write_settings(path, w, h, K4, bf, dmf, thbg, thobj, window=20, overlap=4, choose_data=2, use_sample_feature=0, sf_mg_thres=0.12, n_features=2500, rectify=None):
+    """A settings file in the reference's flat YAML dialect (example/kitti-0000-0013.yaml).  rectify: None, or the keyword arguments of
+    ``rectify_keys`` as a dict (STEREO systems only: the stereo entries then take raw images)."""
     fx, fy, cx, cy = K4
     with open(path, "w") as f:
         f.write(SETTINGS.format(fx=fx, fy=fy, cx=cx, cy=cy, w=w, h=h, bf=bf, dmf=dmf, thbg=thbg, thobj=thobj, window=window, overlap=overlap, choose_data=choose_data,
                                 use_sample_feature=use_sample_feature, sf_mg_thres=sf_mg_thres, n_features=n_features))
+        if rectify is not None:
+            f.write(rectify_keys(**rectify))
     return str(path)
 
 
@@ -137,6 +158,15 @@ class System:
         rc = L.host_system_track_files(self._h, str(rgb_path).encode(), str(depth_path).encode(), str(flow_path).encode(), str(mask_path).encode(), _ptr(rows),
                                        0 if rows is None else rows.shape[0], 0 if rows is None else rows.shape[1], int(n_images), _ptr(self._T))
         return None if rc != 0 else self._T.reshape(4, 4).copy()
+
+    def rectified_left(self, w, h):
+        """The rectified grey left image of the last stereo call of a System with Rectify.* keys: uint8 [h, w] (Camera.height, Camera.width)"""
+        L = self._L
+        L.host_system_rectified_left.argtypes = [C.c_void_p, C.c_void_p]
+        out = np.zeros((h, w), np.uint8)
+        if L.host_system_rectified_left(self._h, _ptr(out)) != 0:
+            raise K.VdoError("System.rectified_left: no rectifier (Rectify.* settings keys) or the download failed")
+        return out
 
     def frame_images(self, w, h):
         """Tracking::SyncFrameState()'s converted depth map (metres) and repaired mask of the last frame: (depth [h, w] f32, mask [h, w] i32)"""
