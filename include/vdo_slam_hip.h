@@ -971,6 +971,86 @@ int vdo_rectify_device_images(vdo_rectify* h, int k, uint8_t** src, uint8_t** ds
  * device-destination job wrote) to the host, packed: for a caller that wants to look at a rectified image.  Host-synchronous. */
 int vdo_rectify_download_image(vdo_rectify* h, const uint8_t* image_dev, int64_t stride, uint8_t* out);
 
+/* ---- Motion segmenter: moving pixels from disparity and flow -----------------------------------------------------------------------
+ * New (the reference takes the class of every pixel from an offline segmentation network and then tracks only what moves: bObjStat, fSFMgThres /
+ * fSFDsThres): from the disparity of frame t, the disparity of frame t + 1, the flow between them and the camera motion to the class image
+ * cls[H][W] (uint8) vdo_labels_compute takes - class_value where the pixel moves against the scene, else 0.  Three stages; stage 1 is fp32, one
+ * rounded operation per step in the order written, no contraction (/ and floorf correctly rounded); stage 2 is integer; no result depends on
+ * workgroup shape or order.  disp0, disp1: fp32 in depth-image units, disparity x disp_unit (the disparity256 image of vdo_stereo_compute with
+ * its output scale).  flow[H][W][2] from t to t + 1; flow_valid[H][W] (vdo_optflow_compute's `valid`) or NULL.  T: 4 x 4 row-major, camera
+ * t + 1 from camera t; its last row is not read.  K = (fx, fy, cx, cy).
+ *
+ * 1. Residual, per pixel (x, y), xf = (float)x, yf = (float)y, (fu, fv) = flow(y, x):
+ *      d0 = disp0(y, x) / unit;  uo = xf + fu;  vo = yf + fv;  xq = floorf(uo + 0.5f);  yq = floorf(vo + 0.5f)
+ *    The pixel is UNKNOWN (state 2, residual -1.0f) unless all of: d0 finite and d0 >= max(min_disparity, FLT_MIN); uo and vo finite;
+ *    0 <= xq <= (float)(W - 1) and 0 <= yq <= (float)(H - 1), compared as floats before any conversion to int (a NaN fails); flow_valid NULL or
+ *    non-zero at (y, x); d1 = disp1((int)yq, (int)xq) / unit finite and > 0; Z' > 0; e finite - with
+ *      Z = bf / d0;  X = ((xf - cx) * Z) / fx;  Y = ((yf - cy) * Z) / fy
+ *      X' = (T0*X + T1*Y) + (T2*Z + T3);  Y' = (T4*X + T5*Y) + (T6*Z + T7);  Z' = (T8*X + T9*Y) + (T10*Z + T11)
+ *      u' = (fx * X') / Z' + cx;  v' = (fy * Y') / Z' + cy;  d' = bf / Z'
+ *      du = uo - u';  dv = vo - v';  dd = d1 - d'
+ *      e = (du*du + dv*dv) * wf + (dd*dd) * wd,     wf = 1.0f / (sigma_flow * sigma_flow), wd = 1.0f / (sigma_disp * sigma_disp), fp32, made once
+ *    A known pixel has residual e and state 1 (moving) iff e > chi2, else state 0.
+ *    NO OUT-OF-RANGE READS: the one gathered address follows from the float compares above; no flag and no value is trusted.
+ * 2. Vote.  m(p), s(p): the numbers of state-1 and state-0 pixels in the (2r + 1)^2 window around p clipped at the image.  p is moving iff
+ *    m + s >= min_known and m * vote_den > vote_num * (m + s); cls(p) = class_value, else 0.  The pixel's own state has no special role: an
+ *    unknown hole inside an object is filled.
+ * 0. Ego-motion (vdo_motionseg_egomotion; a separate entry, so that the segmenter is a function of its inputs and T alone).  Grid positions
+ *    x = step / 2 + i * step < W, y = step / 2 + j * step < H (integer division), in raster order.  A position is kept under stage 1's tests on
+ *    d0, uo, vo, (xq, yq) and flow_valid (not on disp1).  Its sample is X3 = (X, Y, Z) of stage 1 widened to double and uv = (uo, vo) widened.
+ *    The kept samples are compacted in order on the device and downloaded once; vdo_pnp_ransac runs on them with K widened, refit = 1 (AP3P, EPnP
+ *    re-estimation) and the caller's max_iterations, threshold and confidence.  T = its result narrowed to float; with fewer than min_inliers
+ *    inliers (or no model) T is the identity and the call still answers VDO_OK. */
+typedef struct vdo_motionseg vdo_motionseg;
+typedef struct vdo_motionseg_params {
+  float K[4];                       /* fx, fy, cx, cy; fx, fy > 0 */
+  float bf;                         /* baseline x fx, > 0 */
+  float disp_unit;                  /* > 0: the disparity images hold disparity x disp_unit (DepthMapFactor) */
+  float sigma_flow, sigma_disp;     /* > 0, px */
+  float chi2;                       /* >= 0 */
+  float min_disparity;              /* >= 0, px: a source pixel below it is unknown */
+  int32_t vote_radius;              /* r: 0..7 */
+  int32_t vote_num, vote_den;       /* 0 <= vote_num < vote_den <= 65535 */
+  int32_t min_known;                /* >= 1 */
+  int32_t class_value;              /* 1..255 */
+} vdo_motionseg_params;
+/* A segmenter for width x height images.  ALL device memory is taken here (state, residual and class image; disp1 and one uint8 image for the
+ * next-right picture of a rectified frame; staging for disp0, flow and flow_valid; the sample lists at the capacity of step 1, 40 bytes per
+ * pixel, with a pinned mirror; counters: about 71 bytes per pixel); the other entries allocate nothing.  VDO_ERR_INVALID, the message naming
+ * the argument: a null pointer; width or height < 1; a parameter outside the range written beside it or not finite.  VDO_ERR_UNSUPPORTED when
+ * width * height > 2^26 or a side exceeds 2^24.  VDO_ERR_OOM when the device has no room. */
+int vdo_motionseg_create(vdo_ctx* ctx, int width, int height, const vdo_motionseg_params* params, vdo_motionseg** out);
+int vdo_motionseg_destroy(vdo_motionseg* h);
+/* Stage 0, host-synchronous, on the context's stream.  disp0: rows of `width` floats, disp0_stride_floats apart (>= width); flow: rows of
+ * 2 * width floats, flow_stride_floats apart (>= 2 * width); flow_valid: NULL or rows of `width` bytes, flow_valid_stride apart (>= width); host
+ * pointers, or device pointers when src_is_device != 0 (packed device images are read where they lie - the flow if it is 8-byte aligned -
+ * anything else goes through the handle's staging images).  T (host, 16 floats); out (host): n_samples, n_inliers, iterations_run.
+ * VDO_ERR_INVALID, the message naming the argument, and then NOTHING is written: a null handle, disp0, flow, T or out; a stride too small;
+ * step < 1; max_iterations < 0; reproj_threshold not positive and finite; confidence outside (0, 1); min_inliers < 0.  A step beyond the image
+ * leaves no samples: the identity. */
+int vdo_motionseg_egomotion(vdo_motionseg* h, const float* disp0, int64_t disp0_stride_floats, const float* flow, int64_t flow_stride_floats,
+                            const uint8_t* flow_valid, int64_t flow_valid_stride, int src_is_device, int step, int max_iterations,
+                            double reproj_threshold, double confidence, int min_inliers, float T[16], int32_t out[3]);
+/* Stages 1 and 2, host-synchronous, on the context's stream: two kernels.  Sources as above, disp1 like disp0.  T: host.  cls: width x height
+ * bytes, packed, a device pointer when out_is_device != 0.  out (host): moving pixels after the vote, state-0 pixels, state-2 pixels.
+ * VDO_ERR_INVALID, the message naming the argument, for a null handle, disp0, disp1, flow, T, cls or out and a stride too small - and then
+ * NOTHING is written.  No state of an earlier call on the handle enters the result. */
+int vdo_motionseg_compute(vdo_motionseg* h, const float* disp0, int64_t disp0_stride_floats, const float* disp1, int64_t disp1_stride_floats,
+                          const float* flow, int64_t flow_stride_floats, const uint8_t* flow_valid, int64_t flow_valid_stride, int src_is_device,
+                          const float T[16], uint8_t* cls, int out_is_device, int32_t out[3]);
+/* Inspection of the LAST compute (VDO_ERR_INVALID before the first), host outputs [H][W]: the state bytes; the residuals. */
+int vdo_motionseg_get_state(vdo_motionseg* h, uint8_t* out);
+int vdo_motionseg_get_residual(vdo_motionseg* h, float* out);
+/* The sample lists of the LAST ego-motion (VDO_ERR_INVALID before the first): *n = n_samples; X3 ([n][3]) and uv ([n][2]), host, may be NULL
+ * (a caller that sizes them asks for n first; n <= width * height always). */
+int vdo_motionseg_get_samples(vdo_motionseg* h, double* X3, double* uv, int32_t* n);
+/* The last compute or ego-motion: ms[0] wall time of the call, ms[1] device time from the first upload to the end of the last kernel (events). */
+int vdo_motionseg_last_timing(vdo_motionseg* h, double ms[2]);
+/* Device images owned by the handle, for callers without their own: a packed float image for the next pair's disparity (pass it as a matcher's
+ * device output, then as a device disp1), a packed uint8 image for the next-right picture, and a class image to pass as a device output.  Any
+ * of the three may be NULL. */
+int vdo_motionseg_device_images(vdo_motionseg* h, float** disp1, uint8_t** next_right, uint8_t** cls);
+
 #ifdef __cplusplus
 }
 #endif

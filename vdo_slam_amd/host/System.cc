@@ -137,6 +137,43 @@ std::string read_rectify_settings(const std::string& path, const TrackingSetting
   if (sw < 1 || sh < 1) return "settings: Rectify.Width / Rectify.Height must be positive";
   return "";
 }
+// The Motion.* keys (System.h), all optional.  The returned text is empty when they are in order; otherwise it is the settings error, which ends the
+// process in Tracking::Tracking and is a refusal in host_system_create.  The ranges are those of vdo_motionseg_create / vdo_motionseg_egomotion.
+struct MotionSettings { vdo_motionseg_params p{}; MotionSegmenter::EgoParams ego; };
+std::string read_motion_settings(const TrackingSettings& t, const std::map<std::string, double>& raw, MotionSettings& ms) {
+  const float K[4] = {t.fx, t.fy, t.cx, t.cy};
+  const vdo_motionseg_params d = MotionSegmenter::DefaultParams(K, t.bf, t.depth_map_factor, t.th_depth_bg > 0 ? t.bf / t.th_depth_bg : 0.f);
+  vdo_motionseg_params& p = ms.p;
+  p = d;
+  p.sigma_flow = (float)get(raw, "Motion.SigmaFlow", d.sigma_flow); p.sigma_disp = (float)get(raw, "Motion.SigmaDisp", d.sigma_disp);
+  p.chi2 = (float)get(raw, "Motion.Chi2", d.chi2); p.min_disparity = (float)get(raw, "Motion.MinDisparity", d.min_disparity);
+  const double ints[5] = {get(raw, "Motion.VoteRadius", d.vote_radius), get(raw, "Motion.VoteNum", d.vote_num), get(raw, "Motion.VoteDen", d.vote_den),
+                          get(raw, "Motion.MinKnown", d.min_known), get(raw, "Motion.Class", d.class_value)};
+  const MotionSegmenter::EgoParams e;
+  const double ego_ints[3] = {get(raw, "Motion.EgoStep", e.step), get(raw, "Motion.EgoIterations", e.iterations), get(raw, "Motion.EgoMinInliers", e.minInliers)};
+  auto whole = [](double v) { return std::isfinite(v) && std::fabs(v) <= 1e9 && v == std::floor(v); };
+  static const char* const int_keys[8] = {"VoteRadius", "VoteNum", "VoteDen", "MinKnown", "Class", "EgoStep", "EgoIterations", "EgoMinInliers"};
+  for (int k = 0; k < 8; ++k)
+    if (!whole(k < 5 ? ints[k] : ego_ints[k - 5])) return std::string("settings: Motion.") + int_keys[k] + " must be a whole number";
+  p.vote_radius = (int)ints[0]; p.vote_num = (int)ints[1]; p.vote_den = (int)ints[2]; p.min_known = (int)ints[3]; p.class_value = (int)ints[4];
+  ms.ego.step = (int)ego_ints[0]; ms.ego.iterations = (int)ego_ints[1]; ms.ego.minInliers = (int)ego_ints[2];
+  ms.ego.threshold = get(raw, "Motion.EgoThreshold", e.threshold); ms.ego.confidence = get(raw, "Motion.EgoConfidence", e.confidence);
+  if (!std::isfinite(p.sigma_flow) || !(p.sigma_flow > 0)) return "settings: Motion.SigmaFlow must be positive";
+  if (!std::isfinite(p.sigma_disp) || !(p.sigma_disp > 0)) return "settings: Motion.SigmaDisp must be positive";
+  if (!std::isfinite(p.chi2) || !(p.chi2 >= 0)) return "settings: Motion.Chi2 must not be negative";
+  if (!std::isfinite(p.min_disparity) || !(p.min_disparity >= 0)) return "settings: Motion.MinDisparity must not be negative";
+  if (p.vote_radius < 0 || p.vote_radius > 7) return "settings: Motion.VoteRadius outside 0..7";
+  if (p.vote_den < 1 || p.vote_den > 65535) return "settings: Motion.VoteDen outside 1..65535";
+  if (p.vote_num < 0 || p.vote_num >= p.vote_den) return "settings: Motion.VoteNum must be at least 0 and below Motion.VoteDen";
+  if (p.min_known < 1) return "settings: Motion.MinKnown must be at least 1";
+  if (p.class_value < 1 || p.class_value > 255) return "settings: Motion.Class outside 1..255";
+  if (ms.ego.step < 1) return "settings: Motion.EgoStep must be at least 1";
+  if (!std::isfinite(ms.ego.threshold) || !(ms.ego.threshold > 0)) return "settings: Motion.EgoThreshold must be positive";
+  if (ms.ego.iterations < 0) return "settings: Motion.EgoIterations must not be negative";
+  if (!(ms.ego.confidence > 0 && ms.ego.confidence < 1)) return "settings: Motion.EgoConfidence outside (0, 1)";
+  if (ms.ego.minInliers < 0) return "settings: Motion.EgoMinInliers must not be negative";
+  return "";
+}
 }  // namespace
 
 Tracking::Tracking(System*, Map* pMap, const std::string& strSettingPath, const int sensor) : mpMap(pMap) {
@@ -159,6 +196,12 @@ Tracking::Tracking(System*, Map* pMap, const std::string& strSettingPath, const 
   {
     const std::string err = read_rectify_settings(strSettingPath, t, cfg_, sensor, rect);
     if (!err.empty()) { std::cerr << err << std::endl; std::exit(-1); }
+  }
+  if (sensor == System::STEREO) {
+    MotionSettings ms;
+    const std::string err = read_motion_settings(t, cfg_, ms);
+    if (!err.empty()) { std::cerr << err << std::endl; std::exit(-1); }
+    motion_p_ = ms.p; ego_ = ms.ego;
   }
   PipelineParams p{};
   p.width = t.width; p.height = t.height;
@@ -214,6 +257,7 @@ Tracking::Tracking(System*, Map* pMap, const std::string& strSettingPath, const 
 Tracking::~Tracking() {
   pipe_.reset();
   rectifier_.reset();
+  motion_.reset();
   stereo_.reset();
   flow_.reset();
   labels_.reset();
@@ -431,6 +475,92 @@ cv::Mat Tracking::GrabRawStereoFrame(const char* who, const cv::Mat& imLeft, con
   return FinishFrame(mTcw_gt, t_call);
 }
 
+// Raw stereo video: both disparities, the flow, the ego-motion, the class image of the moving pixels, the instance mask and the step, all on the
+// device.  The next pair goes first: the stereo matcher's staging image must hold the CURRENT left image when the step runs.
+cv::Mat Tracking::GrabImageStereoVideo(const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat& imLeftNext, const cv::Mat& imRightNext, const cv::Mat& mTcw_gt,
+                                       const std::vector<std::vector<float> >& vObjPose_gt, const double&, cv::Mat&, const int& nImage) {
+  static const char* who = "GrabImageStereoVideo";
+  if (!stereo_) { std::cerr << "VDO_SLAM::Tracking::" << who << ": the sensor is not STEREO" << std::endl; return cv::Mat(); }
+  StopFrame = nImage - 1;
+  if (!have_frame_) f_id = 0;
+  const auto t_call = std::chrono::steady_clock::now();
+  mLastProcessedState = mState;
+  if (mState == NO_IMAGES_YET) mState = NOT_INITIALIZED;
+  const int W = pipe_->params().width, H = pipe_->params().height;
+  const bool raw = rectifier_ != nullptr;
+  {
+    const int w = raw ? rectifier_->srcWidth(0) : W, h = raw ? rectifier_->srcHeight(0) : H;
+    auto bad = [&](const cv::Mat& m, const char* name) {
+      const bool ok = !m.empty() && m.rows == h && m.cols == w && m.depth() == cv::CV_8U && m.channels() >= 1 && m.channels() <= 4 && m.channels() != 2 &&
+                      m.step == (size_t)m.cols * m.elemSize();
+      if (!ok) std::cerr << "VDO_SLAM::Tracking::" << who << ": " << name << " is " << m.cols << "x" << m.rows << " (type " << m.type() << ", step " << m.step
+                         << "), expected a continuous " << w << "x" << h << " image of the settings file's "
+                         << (raw ? "Rectify.Width/Height (the raw size)" : "Camera.width/height") << std::endl;
+      return !ok;
+    };
+    if (bad(imLeft, "imLeft") || bad(imRight, "imRight") || bad(imLeftNext, "imLeftNext") || bad(imRightNext, "imRightNext")) return cv::Mat();
+  }
+  if (!motion_) motion_.reset(new MotionSegmenter(ctx_[0], W, H, motion_p_));
+  vdo_stereo* sh = stereo_->handle();
+  vdo_optflow* fh = flow_->handle();
+  vdo_labels* lh = labels_->handle();
+  vdo_motionseg* mh = motion_->handle();
+  uint8_t *d_gray = nullptr, *d_right = nullptr, *d_next = nullptr, *d_next_right = nullptr, *d_cls = nullptr, *d_valid = nullptr;
+  float *d_disp = nullptr, *d_disp1 = nullptr, *d_flow = nullptr; int32_t* d_mask = nullptr;
+  int32_t n_valid = 0, n_flow = 0;
+  bool ok = vdo_stereo_device_images(sh, &d_gray, &d_right, &d_disp) == VDO_OK && vdo_optflow_device_images(fh, nullptr, &d_next, &d_flow, &d_valid) == VDO_OK &&
+            vdo_labels_device_images(lh, &d_cls, &d_mask) == VDO_OK && vdo_motionseg_device_images(mh, &d_disp1, &d_next_right, nullptr) == VDO_OK;
+  if (ok && raw) {
+    // the four pictures are the four jobs of one remap; the matchers then read device sources where they lie
+    vdo_rectify* rh = rectifier_->handle();
+    const int order = mbRGB ? 1 : 0;
+    const vdo_rectify_job jobs[4] = {{imLeft.data, (int64_t)imLeft.step, imLeft.channels(), order, 0, 0, d_gray, W},
+                                     {imRight.data, (int64_t)imRight.step, imRight.channels(), order, 1, 0, d_right, W},
+                                     {imLeftNext.data, (int64_t)imLeftNext.step, imLeftNext.channels(), order, 0, 0, d_next, W},
+                                     {imRightNext.data, (int64_t)imRightNext.step, imRightNext.channels(), order, 1, 0, d_next_right, W}};
+    int32_t n_cleared = 0;
+    ok = vdo_rectify_compute(rh, jobs, 4, 0, 1, rect_border_) == VDO_OK && vdo_stereo_compute(sh, d_next, W, d_next_right, W, 1, d_disp1, 1, &n_valid) == VDO_OK &&
+         vdo_rectify_gate(rh, 0, d_disp1, W, 1, &n_cleared) == VDO_OK && vdo_stereo_compute(sh, d_gray, W, d_right, W, 1, d_disp, 1, &n_valid) == VDO_OK &&
+         vdo_rectify_gate(rh, 0, d_disp, W, 1, &n_cleared) == VDO_OK;       // a disparity made from border filler is no depth
+    if (ok && speckle_size_ > 0) { int32_t n_removed = 0; ok = vdo_labels_filter_speckles(lh, d_disp, 1, speckle_range_, speckle_size_, &n_removed) == VDO_OK; }
+    ok = ok && vdo_optflow_compute(fh, d_gray, W, d_next, W, 1, d_flow, d_valid, 1, &n_flow) == VDO_OK;
+  } else if (ok) {
+    const int64_t n = (int64_t)W * H;
+    auto to_gray = [&](const cv::Mat& im, std::vector<uint8_t>& buf) -> const uint8_t* {      // (cvtColor as in GrabImageRGBD; the caller's image is not touched)
+      if (im.channels() < 3) return im.data;
+      buf.resize((size_t)n);
+      if (vdo_rgb2gray(ctx_[0], im.data, n, im.channels(), mbRGB ? 1 : 0, buf.data()) != VDO_OK) { std::cerr << vdo_last_error() << std::endl; return nullptr; }
+      return buf.data();
+    };
+    const uint8_t *gl = to_gray(imLeft, gray_), *gr = to_gray(imRight, gray_right_), *gn = to_gray(imLeftNext, gray_next_), *gnr = to_gray(imRightNext, gray_next_right_);
+    if (!gl || !gr || !gn || !gnr) return cv::Mat();
+    ok = vdo_stereo_compute(sh, gn, W, gnr, W, 0, d_disp1, 1, &n_valid) == VDO_OK && vdo_stereo_compute(sh, gl, W, gr, W, 0, d_disp, 1, &n_valid) == VDO_OK;
+    if (ok && speckle_size_ > 0) { int32_t n_removed = 0; ok = vdo_labels_filter_speckles(lh, d_disp, 1, speckle_range_, speckle_size_, &n_removed) == VDO_OK; }
+    ok = ok && vdo_optflow_compute(fh, gl, W, gn, W, 0, d_flow, d_valid, 1, &n_flow) == VDO_OK;
+  }
+  float T[16];
+  int32_t ego[3] = {0, 0, 0}, moved[3] = {0, 0, 0}, counts[3] = {0, 0, 0};
+  ok = ok && vdo_motionseg_egomotion(mh, d_disp, W, d_flow, 2 * (int64_t)W, d_valid, W, 1, ego_.step, ego_.iterations, ego_.threshold, ego_.confidence, ego_.minInliers, T, ego) == VDO_OK;
+  if (ok && ego[1] < ego_.minInliers) {
+    // no camera motion, no statement about what moves against it: an empty class image, the frame is tracked as static-only
+    std::cerr << "VDO_SLAM::Tracking::" << who << ": frame " << f_id << ": the ego-motion has " << ego[1] << " inliers of " << ego[0] << " samples (Motion.EgoMinInliers "
+              << ego_.minInliers << "): no object is tracked in this frame" << std::endl;
+    zero_classes_.assign((size_t)W * H, 0);
+    ok = vdo_labels_stage_classes(lh, zero_classes_.data(), W, &d_cls) == VDO_OK;
+  } else if (ok) {
+    ok = vdo_motionseg_compute(mh, d_disp, W, d_disp1, W, d_flow, 2 * (int64_t)W, d_valid, W, 1, T, d_cls, 1, moved) == VDO_OK;
+  }
+  ok = ok && vdo_labels_compute(lh, d_cls, W, d_disp, W, 1, d_mask, 1, counts) == VDO_OK;
+  if (!ok) { std::cerr << "VDO_SLAM::Tracking::" << who << ": " << vdo_last_error() << std::endl; return cv::Mat(); }
+  video_counts_[0] = ego[1]; video_counts_[1] = moved[0]; video_counts_[2] = counts[0];
+  std::vector<int> labels;
+  for (const auto& row : vObjPose_gt) if (row.size() > 1) labels.push_back((int)row[1]);
+  pipe_->SetObjectGate(labels.data(), (int)labels.size());
+  FrameCounts fc{};
+  if (pipe_->StepDevice(d_gray, d_disp, d_flow, d_mask, false, &fc) != 0) return cv::Mat();
+  return FinishFrame(mTcw_gt, t_call);
+}
+
 cv::Mat Tracking::DownloadRectifiedLeft() {
   if (!rectifier_ || !stereo_) return cv::Mat();
   uint8_t* d_gray = nullptr;
@@ -625,6 +755,12 @@ cv::Mat System::TrackStereoPairSemantic(const cv::Mat& imLeft, const cv::Mat& im
   return mpTracker->GrabImageStereoPairSemantic(imLeft, imRight, imLeftNext, classes, mTcw_gt, vObjPose_gt, timestamp, imTraj, nImage);
 }
 
+cv::Mat System::TrackStereoVideo(const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat& imLeftNext, const cv::Mat& imRightNext, const cv::Mat& mTcw_gt,
+                                 const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, cv::Mat& imTraj, const int& nImage) {
+  if (mSensor != STEREO) { std::cerr << "ERROR: you called TrackStereoVideo but input sensor was not set to STEREO." << std::endl; std::exit(-1); }
+  return mpTracker->GrabImageStereoVideo(imLeft, imRight, imLeftNext, imRightNext, mTcw_gt, vObjPose_gt, timestamp, imTraj, nImage);
+}
+
 // The Map (reference format) is materialised from the pipeline's flat store when somebody looks at it.
 Map* System::map() { mpTracker->pipeline()->SyncMap(); return mpMap; }
 
@@ -685,6 +821,11 @@ static VDO_SLAM::System* host_system_create_sensor(const char* settings, VDO_SLA
     VDO_SLAM::RectifySettings rect;
     const std::string err = VDO_SLAM::read_rectify_settings(settings, t, raw, sensor, rect);
     if (!err.empty()) { std::fprintf(stderr, "host_system_create: %s\n", err.c_str()); return nullptr; }
+    if (sensor == VDO_SLAM::System::STEREO) {
+      VDO_SLAM::MotionSettings ms;
+      const std::string merr = VDO_SLAM::read_motion_settings(t, raw, ms);
+      if (!merr.empty()) { std::fprintf(stderr, "host_system_create: %s\n", merr.c_str()); return nullptr; }
+    }
   }
   {
     const char* dev = std::getenv("VDO_DEVICE");
@@ -795,6 +936,26 @@ int host_settings_check_rectify(const char* path, int stereo, char* msg, int cap
   if (msg && cap > 0) std::snprintf(msg, (size_t)cap, "%s", err.c_str());
   return err.empty() ? 0 : 1;
 }
+// the Motion.* keys as a STEREO Tracking::Tracking reads them, without a GPU: 0 in order, 1 a settings error (text in msg), -2 no file.  out14 (may be
+// null): SigmaFlow, SigmaDisp, Chi2, VoteRadius, VoteNum, VoteDen, MinKnown, MinDisparity, Class, EgoStep, EgoThreshold, EgoIterations, EgoConfidence,
+// EgoMinInliers
+int host_settings_check_motion(const char* path, char* msg, int cap, double* out14) {
+  VDO_SLAM::TrackingSettings t{};
+  std::map<std::string, double> raw;
+  if (!VDO_SLAM::read_tracking_settings(path, t, &raw)) return -2;
+  VDO_SLAM::MotionSettings ms;
+  const std::string err = VDO_SLAM::read_motion_settings(t, raw, ms);
+  if (msg && cap > 0) std::snprintf(msg, (size_t)cap, "%s", err.c_str());
+  if (out14 && err.empty()) {
+    const vdo_motionseg_params& p = ms.p;
+    const double v[14] = {p.sigma_flow, p.sigma_disp, p.chi2, (double)p.vote_radius, (double)p.vote_num, (double)p.vote_den, (double)p.min_known, p.min_disparity,
+                          (double)p.class_value, (double)ms.ego.step, ms.ego.threshold, (double)ms.ego.iterations, ms.ego.confidence, (double)ms.ego.minInliers};
+    for (int i = 0; i < 14; ++i) out14[i] = v[i];
+  }
+  return err.empty() ? 0 : 1;
+}
+// what the last TrackStereoVideo call found: ego-motion inliers, moving pixels after the vote, labels
+void host_system_video_counts(VDO_SLAM::System* s, int* out3) { for (int k = 0; k < 3; ++k) out3[k] = s->tracker()->video_counts()[k]; }
 // the rectified grey left image of the last stereo call of a System with Rectify.* keys: [Camera.height][Camera.width]; 0, or -1 without a rectifier
 int host_system_rectified_left(VDO_SLAM::System* s, unsigned char* out) {
   try {

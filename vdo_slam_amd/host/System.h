@@ -15,6 +15,7 @@
 #include "InstanceLabeler.h"
 #include "StereoRectifier.h"
 #include "Map.h"
+#include "MotionSegmenter.h"
 #include "StereoMatcher.h"
 #include "minicv.h"
 
@@ -54,6 +55,18 @@ class Tracking {
   // never exists on the host; its labels carry no identity from frame to frame (the tracker associates objects through the flow).
   cv::Mat GrabImageStereoPairSemantic(const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat& imLeftNext, const cv::Mat& classes, const cv::Mat& mTcw_gt,
                                       const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, cv::Mat& imTraj, const int& nImage);
+  // As GrabImageStereoPairSemantic, but the class image is made here as well: "which pixels move against the scene", from the next stereo pair.  On
+  // the device, in this order: the disparity of the next pair (into the segmenter's own image), the disparity of the current pair (gate and
+  // speckle filter as above; the matcher's staging image then holds the current left image for the step), the flow with its validity image, the
+  // camera motion from grid samples (vdo_motionseg_egomotion, settings keys Motion.Ego*), the class image (MotionSegmenter, settings keys Motion.*)
+  // straight into the labeller's device class image, the instance mask, the step.  With too few ego-motion inliers the class image is all zero
+  // for that frame - it is tracked as static-only - and a line goes to stderr.  With Rectify.* keys the four pictures are the four jobs of one
+  // vdo_rectify_compute.  The segmenter is made on the first call.
+  cv::Mat GrabImageStereoVideo(const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat& imLeftNext, const cv::Mat& imRightNext, const cv::Mat& mTcw_gt,
+                               const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, cv::Mat& imTraj, const int& nImage);
+  MotionSegmenter* motion() { return motion_.get(); }    // null before the first GrabImageStereoVideo
+  // What the last GrabImageStereoVideo found: ego-motion inliers, moving pixels after the vote (0 when the ego-motion failed), labels
+  const int* video_counts() const { return video_counts_; }
   // Raw images (settings keys Rectify.*, STEREO only; System::TrackStereo below): with the keys present, imLeft / imRight / imLeftNext of the three
   // entries above are the RAW images of Rectify.Width x Rectify.Height; one vdo_rectify_compute undistorts, rectifies and makes them grey straight
   // into the matchers' device images, and the disparity is cleared wherever the left map is invalid.  rectifier() is null without the keys.
@@ -106,6 +119,11 @@ class Tracking {
   std::unique_ptr<InstanceLabeler> labels_;
   std::unique_ptr<StereoRectifier> rectifier_;           // Rectify.* keys present: the stereo entries take raw images
   int rect_border_ = 0, rect_classes_ = 0;               // Rectify.Border, Rectify.Classes
+  std::unique_ptr<MotionSegmenter> motion_;              // made by the first GrabImageStereoVideo from motion_p_
+  vdo_motionseg_params motion_p_{};                      // Motion.* keys (read and checked with the STEREO sensor only)
+  MotionSegmenter::EgoParams ego_;                       // Motion.Ego* keys
+  std::vector<uint8_t> gray_next_right_, zero_classes_;
+  int video_counts_[3] = {0, 0, 0};
   int speckle_size_ = 0, speckle_range_ = 256;           // Stereo.SpeckleSize (0: no filter), Stereo.SpeckleRange, the latter in the depth image's units
   cv::Mat GrabStereoFrame(const char* who, const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat* imFlow, const cv::Mat* imLeftNext, const cv::Mat* maskSEM,
                           const cv::Mat* classes, const cv::Mat& mTcw_gt, const std::vector<std::vector<float> >& vObjPose_gt, const int& nImage);
@@ -152,6 +170,14 @@ class System {
   // TrackStereo when the sensor is not STEREO.
   cv::Mat TrackStereoPairSemantic(const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat& imLeftNext, const cv::Mat& classes, const cv::Mat& mTcw_gt,
                                   const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, cv::Mat& imTraj, const int& nImage);
+  // Raw stereo video in, trajectories out: TrackStereoPairSemantic with the class image made on the device from the next pair - the pixels that move
+  // against the scene (Tracking::GrabImageStereoVideo).  Settings keys, all optional: Motion.SigmaFlow 0.5, Motion.SigmaDisp 0.5 (px), Motion.Chi2 9,
+  // Motion.VoteRadius 2, Motion.VoteNum 1, Motion.VoteDen 2, Motion.MinKnown 6, Motion.MinDisparity Camera.bf / ThDepthBG (px), Motion.Class 1,
+  // Motion.EgoStep 16, Motion.EgoThreshold 1.0, Motion.EgoIterations 500, Motion.EgoConfidence 0.98, Motion.EgoMinInliers 50.  A value outside its
+  // range is a settings error with the STEREO sensor.  The caller is one frame ahead of the tracker, as with TrackStereoPair.  Exits like TrackStereo when
+  // the sensor is not STEREO.
+  cv::Mat TrackStereoVideo(const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat& imLeftNext, const cv::Mat& imRightNext, const cv::Mat& mTcw_gt,
+                           const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, cv::Mat& imTraj, const int& nImage);
   void SaveResults(const std::string& filename);
   Map* map();                          // brought up to date from the pipeline's GraphStore on access
   Tracking* tracker() { return mpTracker; }

@@ -11,6 +11,7 @@
 #include "InstanceLabeler.h"
 #include "Frame.h"
 #include "Map.h"
+#include "MotionSegmenter.h"
 #include "ORBextractor.h"
 #include "ORBmatcher.h"
 #include "Optimizer.h"
@@ -344,6 +345,53 @@ int host_system_track_stereo_pair_semantic(System* s, const unsigned char* left,
     if (T.empty()) return -1;
     std::memcpy(Tcw_out, T.data, 64);
   } catch (const std::exception& e) { std::fprintf(stderr, "host_system_track_stereo_pair_semantic: %s\n", e.what()); return -2; }
+  return 0;
+}
+
+// MotionSegmenter on host images (rows *_step_floats floats / valid_step bytes apart; valid may be null).  params: the library's struct.  ego3 (may be
+// null): step, max_iterations, min_inliers, with threshold and confidence as doubles in ego2 - with them the camera motion comes from
+// MotionSegmenter::EgoMotion (T16 is written, ego_counts3 filled); without them T16 is read.  cls: [h][w]; counts3: moving, static, unknown.
+// Returns the moving pixel count, -1 on a failure.
+int host_motionseg_compute(const float* disp0, int disp0_step_floats, const float* disp1, int disp1_step_floats, const float* flow, int flow_step_floats,
+                           const unsigned char* valid, int valid_step, int w, int h, const vdo_motionseg_params* params, const int* ego3, const double* ego2, float* T16,
+                           unsigned char* cls, int* counts3, int* ego_counts3) {
+  try {
+    MotionSegmenter m(nullptr, w, h, *params);
+    cv::Mat D0(h, w, cv::CV_32FC1, (void*)disp0), D1(h, w, cv::CV_32FC1, (void*)disp1), F(h, w, cv::CV_32FC2, (void*)flow), V;
+    D0.step = (size_t)disp0_step_floats * sizeof(float); D1.step = (size_t)disp1_step_floats * sizeof(float); F.step = (size_t)flow_step_floats * sizeof(float);
+    if (valid) { V = cv::Mat(h, w, cv::CV_8UC1, (void*)valid); V.step = (size_t)valid_step; }
+    cv::Mat T(4, 4, cv::CV_32F);
+    if (ego3) {
+      MotionSegmenter::EgoParams e;
+      e.step = ego3[0]; e.iterations = ego3[1]; e.minInliers = ego3[2]; e.threshold = ego2[0]; e.confidence = ego2[1];
+      int ec[3] = {0, 0, 0};
+      T = m.EgoMotion(D0, F, V, e, ec);
+      std::memcpy(T16, T.data, 64);
+      if (ego_counts3) std::memcpy(ego_counts3, ec, sizeof ec);
+    } else {
+      std::memcpy(T.data, T16, 64);
+    }
+    int counts[3] = {0, 0, 0};
+    cv::Mat Cm = m.Compute(D0, D1, F, V, T, counts);
+    std::memcpy(cls, Cm.data, (size_t)w * h);
+    if (counts3) std::memcpy(counts3, counts, sizeof counts);
+    return counts[0];
+  } catch (const std::exception& e) { std::fprintf(stderr, "host_motionseg_compute: %s\n", e.what()); return -1; }
+}
+
+// one TrackStereoVideo call on host images: the current and the next pair (all four of `channels` channels), nothing else
+int host_system_track_stereo_video(System* s, const unsigned char* left, const unsigned char* right, const unsigned char* left_next, const unsigned char* right_next, int channels,
+                                   int w, int h, const float* obj_rows, int n_rows, int row_len, int n_images, float* Tcw_out) {
+  const int type = VDO_CV_MAKETYPE(cv::CV_8U, channels);
+  cv::Mat L(h, w, type, (void*)left), R(h, w, type, (void*)right), N(h, w, type, (void*)left_next), NR(h, w, type, (void*)right_next);
+  cv::Mat gt = cv::Mat::eye(4, 4, cv::CV_32F), traj;
+  std::vector<std::vector<float> > rows(n_rows);
+  for (int i = 0; i < n_rows; ++i) rows[i].assign(obj_rows + (size_t)i * row_len, obj_rows + (size_t)(i + 1) * row_len);
+  try {
+    cv::Mat T = s->TrackStereoVideo(L, R, N, NR, gt, rows, 0.0, traj, n_images);
+    if (T.empty()) return -1;
+    std::memcpy(Tcw_out, T.data, 64);
+  } catch (const std::exception& e) { std::fprintf(stderr, "host_system_track_stereo_video: %s\n", e.what()); return -2; }
   return 0;
 }
 

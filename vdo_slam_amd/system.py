@@ -149,6 +149,30 @@ class System:
                                                       0 if rows is None else rows.shape[1], int(n_images), _ptr(self._T))
         return None if rc != 0 else self._T.reshape(4, 4).copy()
 
+    def track_stereo_video(self, left, right, left_next, right_next, obj_rows=None, n_images=1 << 30):
+        """One TrackStereoVideo call on a STEREO system: the current and the NEXT stereo pair, nothing else.  Both disparities, the flow, the camera
+        motion, the class image of the pixels that move against the scene (optional Motion.* settings keys) and the instance mask are made on the
+        device.  Returns Tcw 4x4 float32, or None."""
+        L = self._L
+        L.host_system_track_stereo_video.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                     C.c_void_p]
+        if not (left.shape == right.shape == left_next.shape == right_next.shape):
+            raise ValueError(f"left {left.shape}, right {right.shape}, left_next {left_next.shape} and right_next {right_next.shape} differ")
+        h, w = left.shape[:2]
+        ch = 1 if left.ndim == 2 else left.shape[2]
+        rows = None if obj_rows is None or len(obj_rows) == 0 else np.ascontiguousarray(obj_rows, np.float32)
+        rc = L.host_system_track_stereo_video(self._h, _ptr(left), _ptr(right), _ptr(left_next), _ptr(right_next), ch, w, h, _ptr(rows), 0 if rows is None else rows.shape[0],
+                                              0 if rows is None else rows.shape[1], int(n_images), _ptr(self._T))
+        return None if rc != 0 else self._T.reshape(4, 4).copy()
+
+    def video_counts(self):
+        """What the last track_stereo_video found: (ego-motion inliers, moving pixels after the vote, labels)"""
+        L = self._L
+        L.host_system_video_counts.argtypes = [C.c_void_p, C.c_void_p]
+        out = np.zeros(3, np.int32)
+        L.host_system_video_counts(self._h, _ptr(out))
+        return tuple(int(v) for v in out)
+
     def track_files(self, rgb_path, depth_path, flow_path, mask_path, obj_rows=None, n_images=1 << 30):
         """One TrackRGBDFromFiles call: the frame's colour PNG, disparity PNG, .flo and mask text decoded on the device (the reference driver's
         imread / convertTo / readOpticalFlow / LoadMask, example/vdo_slam.cc:104-131) and tracked.  Returns Tcw 4x4 float32, or None."""
