@@ -1051,6 +1051,84 @@ int vdo_motionseg_last_timing(vdo_motionseg* h, double ms[2]);
  * of the three may be NULL. */
 int vdo_motionseg_device_images(vdo_motionseg* h, float** disp1, uint8_t** next_right, uint8_t** cls);
 
+/* ---- Dense mapper: TSDF fusion of the static scene ---------------------------------------------------------------------------------
+ * New (the reference keeps no dense map): a truncated-signed-distance voxel volume on the device, world-aligned, cyclically addressed, following
+ * the camera; every frame's metric depth is fused into it projectively with the frame's pose, pixels with a non-zero instance mask left out;
+ * surface points are extracted in a fixed order.  The geometry is fp32, one rounded operation per step in the order written, no contraction
+ * (/ and floorf correctly rounded); the fusion and everything after it is integer; no result depends on workgroup shape, on the voxels a thread
+ * takes or on the schedule.
+ *
+ * Volume.  n = (nx, ny, nz) voxels of edge `voxel`; the integer origin o, in global voxel units: the volume stands for the global voxels
+ *   o_a <= g_a < o_a + n_a, every |g| in use below 2^22 (so (float)g + 0.5f is exact).  Voxel g lives at slot (g_a mod n_a) per axis (the
+ *   mathematical, non-negative mod), slots laid out x fastest, then y, then z.  One 32-bit word per voxel: the low 16 bits the TSDF t as int16,
+ *   -32767..32767, the high 16 bits the weight w; w = 0 is "never seen" and the whole word is then 0.  The centre of g: p_a = ((float)g_a + 0.5f) * voxel.
+ * Integrate.  depth[H][W] fp32 metres; mask[H][W] int32 or NULL; T 4 x 4 row-major, world -> camera (mTcw), last row not read; K = (fx, fy, cx, cy).
+ *   Every voxel of the volume, from its own integer index:
+ *      Xc = (T0*px + T1*py) + (T2*pz + T3);  Yc = (T4*px + T5*py) + (T6*pz + T7);  Zc = (T8*px + T9*py) + (T10*pz + T11)
+ *      skip unless Zc finite and Zc > max(min_depth, FLT_MIN)
+ *      u = (fx*Xc)/Zc + cx;  v = (fy*Yc)/Zc + cy;  xq = floorf(u + 0.5f);  yq = floorf(v + 0.5f)
+ *      skip unless u, v finite and 0 <= xq <= (float)(W-1) and 0 <= yq <= (float)(H-1), compared as floats before any conversion to int (a NaN fails)
+ *      d = depth((int)yq, (int)xq);  skip unless d finite, d > min_depth, d <= max_depth
+ *      skip (counted as masked) if mask != NULL and mask((int)yq, (int)xq) != 0
+ *      s = d - Zc;  skip (counted as occluded) if s < -trunc;  s = fminf(s, trunc)
+ *      q = (int)floorf((s / trunc) * 32767.0f + 0.5f)
+ *      t' = floor_div(2*(t*w + q) + (w+1), 2*(w+1))  (floor towards -inf; below 2^25 in magnitude);   w' = min(w+1, max_weight)
+ *   A skipped voxel keeps its word bit for bit.  NO OUT-OF-RANGE READS: the one gathered address follows from the float compares alone.
+ * Recenter.  The slots whose global voxel changes are set to 0, every other word is untouched; a shift of >= n_a on any axis clears everything, a
+ *   shift of 0 nothing; only the leaving slabs are written.
+ * Extract.  A box [lo, hi) in global voxels, clipped to the volume; min_weight >= 1.  The voxels a of the box in the order z, y, x (x fastest),
+ *   axes 0, 1, 2 within a voxel: the neighbour b = a + e_axis must be inside the VOLUME (not the box), both weights >= min_weight; a crossing iff
+ *   (ta < 0) != (tb < 0); frac = (float)ta / (float)(ta - tb); the coordinate on the axis (((float)g_a + 0.5f) + frac) * voxel, the other two the
+ *   centre's.  Per point: xyz float[3]; grad int32[3] = t(a+e_k) - t(a), k = 0..2, if all three neighbours are inside the volume with
+ *   w >= min_weight, else (0, 0, 0) - unnormalised, so that no sqrt enters the parity; weight int32, the smaller of the two weights.  The points are
+ *   compacted in the visiting order; the call returns the total count and writes exactly the first min(capacity, count) points. */
+typedef struct vdo_dense vdo_dense;
+typedef struct vdo_dense_params {
+  int32_t n[3];                     /* 1..4096 each, nx * ny * nz <= 2^31 */
+  float voxel;                      /* > 0, metres */
+  int32_t origin[3];                /* global voxels; -2^22 < origin_a and origin_a + n_a <= 2^22 */
+  float K[4];                       /* fx, fy, cx, cy; fx, fy > 0 */
+  float trunc;                      /* > 0, metres */
+  float min_depth, max_depth;       /* 0 <= min_depth < max_depth, metres */
+  int32_t max_weight;               /* 1..255 */
+  int32_t stage_points;             /* >= 1: the points one window of a host-output extraction holds on the device (28 bytes each) */
+} vdo_dense_params;
+/* A mapper for width x height depth and mask images.  ALL device memory is taken here (the volume, 4 bytes per voxel, cleared; the compaction
+ * offsets, 8 bytes per 256 voxels; the counters; staging for a host or strided depth and mask, 8 bytes per pixel; the point staging); the other
+ * entries allocate nothing.  VDO_ERR_INVALID, the message naming the argument: a null pointer; a size < 1; a parameter outside the range written
+ * beside it or not finite; an origin out of range.  VDO_ERR_UNSUPPORTED when nx * ny * nz > 2^31 or a side exceeds 2^12 (or the image exceeds
+ * 2^26 pixels or 2^24 on a side).  VDO_ERR_OOM when the device has no room. */
+int vdo_dense_create(vdo_ctx* ctx, int width, int height, const vdo_dense_params* params, vdo_dense** out);
+int vdo_dense_destroy(vdo_dense* h);
+/* One frame, host-synchronous, on the context's stream: one kernel.  depth: rows of `width` floats, depth_stride_floats apart (>= width); mask:
+ * NULL or rows of `width` int32, mask_stride_ints apart (>= width); host pointers, or device pointers when src_is_device != 0 (packed device images
+ * are read where they lie, anything else goes through the handle's staging images).  T: host.  out (host): updated voxels, voxels skipped by the
+ * mask, voxels skipped as occluded.  VDO_ERR_INVALID, the message naming the argument, and then NOTHING is written: a null handle, depth, T or
+ * out; a stride too small. */
+int vdo_dense_integrate(vdo_dense* h, const float* depth, int64_t depth_stride_floats, const int32_t* mask, int64_t mask_stride_ints, int src_is_device,
+                        const float T[16], int64_t out[3]);
+/* The same from the resident depth (after K1: metres) and mask of a vdo_frame_images of the mapper's size, read where they lie and not written. */
+int vdo_dense_integrate_frame(vdo_dense* h, const vdo_frame_images* frame, const float T[16], int64_t out[3]);
+/* Moves the volume to new_origin (host, global voxels).  VDO_ERR_INVALID for a null pointer or an origin out of range, and then nothing changes. */
+int vdo_dense_recenter(vdo_dense* h, const int32_t new_origin[3]);
+/* Surface points of the box [lo, hi) (host, global voxels; an empty or outside box has no points).  xyz [capacity][3], grad [capacity][3],
+ * weight [capacity]: host pointers, or device pointers when out_is_device != 0; all three may be NULL when capacity is 0.  *count (host): the
+ * total, whatever the capacity.  VDO_ERR_INVALID, the message naming the argument, and then NOTHING is written: a null handle, lo, hi or count;
+ * min_weight < 1; capacity < 0; a null output with capacity > 0. */
+int vdo_dense_extract(vdo_dense* h, const int32_t lo[3], const int32_t hi[3], int min_weight, int64_t capacity, float* xyz, int32_t* grad, int32_t* weight,
+                      int out_is_device, int64_t* count);
+/* Inspection: the words in slot order (host, nx * ny * nz; may be NULL) and the origin (host; may be NULL; not both). */
+int vdo_dense_get_volume(vdo_dense* h, uint32_t* words, int32_t origin[3]);
+/* The reverse: nx * ny * nz host words in slot order replace the volume (a saved volume; the origin is not changed).  The caller keeps the
+ * format: w = 0 only with the whole word 0, w <= 255, t not -32768. */
+int vdo_dense_set_volume(vdo_dense* h, const uint32_t* words);
+/* The last integrate, recenter or extract: ms[0] wall time of the call, ms[1] device time from the first upload to the end of the last kernel. */
+int vdo_dense_last_timing(vdo_dense* h, double ms[2]);
+/* The volume where it lives (a device pointer owned by the handle). */
+int vdo_dense_device_volume(vdo_dense* h, uint32_t** words);
+/* The voxels along y one thread of the integrate kernel takes: 1, 2, 4 (the default) or 8.  No result depends on it. */
+int vdo_dense_set_voxels_per_thread(vdo_dense* h, int voxels);
+
 #ifdef __cplusplus
 }
 #endif

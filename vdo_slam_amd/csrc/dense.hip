@@ -1,0 +1,537 @@
+// Dense mapper: a truncated-signed-distance (TSDF) voxel volume of the static scene on the device - world-aligned, cyclically addressed, following the
+// camera - fused projectively from a frame's metric depth, its instance mask (non-zero pixels are left out) and its camera pose; surface points are
+// extracted from it in a fixed order.  The reference keeps no dense map; the semantics are this library's own, stated in include/vdo_slam_hip.h
+// (vdo_dense_integrate) and restated in NumPy by tests/dense_ref.py.  The geometry is fp32 with one rounded operation per step (the library is built
+// with -ffp-contract=off; / and floorf are correctly rounded), the fusion and everything after it is integer: no result depends on workgroup shape,
+// on the voxels a thread takes or on the schedule.
+//
+//   k_dn_integrate<VPT>  x on the lanes (one wave = 64 consecutive slots of a row: the 4-byte words are read and written coalesced), 4 z per workgroup,
+//                        VPT consecutive y per thread: T0 * px, T2 * pz + T3, K and the thresholds stay in registers, the VPT words are loaded before
+//                        the first is used.  Every voxel is computed from its own integer index.  A word is written only when it changed.  The three
+//                        counts by wave ballot, summed over the workgroup in LDS, one 64-bit integer atomic per workgroup and counter on one of
+//                        1024 copies of the counters, which the host adds up.
+//   k_dn_clear           recenter: the slots of ONE leaving slab (a cyclic range on one axis, everything on the other two) are set to 0.
+//   k_dn_extract<FILL>   one thread per voxel of the box (x fastest), up to three points each: count per workgroup, k_dn_scan (one workgroup, 64-bit
+//                        carry), then the same kernel writes the points of a window [base, base + cap) of the visiting order.
+//
+// NO OUT-OF-RANGE ACCESS: the one gathered address comes from float compares against 0 and W - 1 / H - 1 made before any conversion to int (a NaN
+// fails them); every volume index is built from slot coordinates tested against n; an extracted point is written only inside its window.
+#include <hip/hip_runtime.h>
+
+#include <cfloat>
+#include <chrono>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+
+#include "../../include/vdo_slam_hip.h"
+#include "ctx.hpp"
+#include "frame_images.hpp"
+#include "scan.hpp"
+
+namespace vdo {
+
+constexpr int kDnMaxSide = 1 << 12;
+constexpr int64_t kDnMaxVoxels = int64_t(1) << 31;
+constexpr int kDnMaxOrigin = 1 << 22;                                      // every |g| in use stays below it: (float)g + 0.5f is exact
+constexpr int64_t kDnMaxPixels = int64_t(1) << 26;
+constexpr int kDnMaxImageSide = 1 << 24;                                   // (float)(W - 1) is exact
+constexpr int kDnZ = 4;                                                    // z slots per workgroup of k_dn_integrate
+enum { kDnUpdated = 0, kDnMasked, kDnOccluded, kDnCounters = 4 };
+constexpr int kDnSlots = 1024;                                             // the counters of k_dn_integrate are kept kDnSlots times, 32 bytes apart; the host adds them up
+constexpr int kDnTotal = kDnSlots * kDnCounters;                           // then the point count of k_dn_scan
+
+// what the kernels take by value
+struct DnArgs {
+  float fx, fy, cx, cy, trunc, min_z, min_d, max_d, voxel;
+  int max_w;
+  float T[12];
+  int n[3], o[3], om[3];                                                   // size, origin, origin mod size (non-negative)
+};
+
+}  // namespace vdo
+
+struct vdo_dense {
+  vdo_ctx* ctx = nullptr;
+  int W = 0, H = 0;
+  vdo_dense_params p{};
+  vdo::DnArgs a{};
+  int vpt = 4;
+  int64_t nvox = 0, stage_points = 0;
+  uint32_t* d_vol = nullptr;                              // [nz][ny][nx] words in slot order
+  float* d_depth = nullptr;                               // [H][W] staging
+  int32_t* d_mask = nullptr;                              // [H][W] staging
+  long long* d_blk = nullptr;                             // per 256 voxels of a box: its points, then their exclusive scan
+  unsigned long long* d_cnt = nullptr;                    // [kDnSlots][kDnCounters], then the point count of the last extraction
+  unsigned long long* h_cnt = nullptr;                    // pinned
+  float* d_xyz = nullptr; int32_t* d_grad = nullptr; int32_t* d_wgt = nullptr;      // [stage_points] staging of host outputs
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  double ms[2] = {0, 0};
+};
+
+namespace vdo {
+
+__device__ __forceinline__ bool dn_finite(float v) { return fabsf(v) <= FLT_MAX; }       // false for NaN and the infinities
+
+__device__ __forceinline__ int dn_floor_div(int a, int d) { return a >= 0 ? a / d : -((-a + d - 1) / d); }      // d > 0
+
+// slot -> global voxel on one axis: the one g in [o, o + n) with g mod n == s
+__device__ __forceinline__ int dn_global(int s, int o, int om, int n) { return o + (s - om) + (s < om ? n : 0); }
+
+template <int VPT>
+__global__ __launch_bounds__(256) void k_dn_integrate(DnArgs a, const float* __restrict__ depth, const int32_t* __restrict__ mask, int W, int H, uint32_t* __restrict__ vol,
+                                                      unsigned long long* __restrict__ cnt) {
+  const int nx = a.n[0], ny = a.n[1], nz = a.n[2];
+  const int sx = blockIdx.x * 64 + threadIdx.x, sz = blockIdx.z * kDnZ + threadIdx.z, sy0 = blockIdx.y * VPT;
+  const bool in_xz = sx < nx && sz < nz;
+  float ax = 0.f, ay = 0.f, az = 0.f, bx = 0.f, by = 0.f, bz = 0.f;
+  if (in_xz) {
+    const float px = ((float)dn_global(sx, a.o[0], a.om[0], nx) + 0.5f) * a.voxel, pz = ((float)dn_global(sz, a.o[2], a.om[2], nz) + 0.5f) * a.voxel;
+    ax = a.T[0] * px; ay = a.T[4] * px; az = a.T[8] * px;
+    bx = a.T[2] * pz + a.T[3]; by = a.T[6] * pz + a.T[7]; bz = a.T[10] * pz + a.T[11];
+  }
+  const size_t row0 = ((size_t)(in_xz ? sz : 0) * ny) * nx + (in_xz ? sx : 0);
+  uint32_t word[VPT];
+#pragma unroll
+  for (int k = 0; k < VPT; ++k) word[k] = (in_xz && sy0 + k < ny) ? vol[row0 + (size_t)(sy0 + k) * nx] : 0u;
+  int n_upd = 0, n_msk = 0, n_occ = 0;
+#pragma unroll
+  for (int k = 0; k < VPT; ++k) {
+    const int sy = sy0 + k;
+    bool upd = false, msk = false, occ = false;
+    if (in_xz && sy < ny) {
+      const float py = ((float)dn_global(sy, a.o[1], a.om[1], ny) + 0.5f) * a.voxel;
+      const float Xc = (ax + a.T[1] * py) + bx, Yc = (ay + a.T[5] * py) + by, Zc = (az + a.T[9] * py) + bz;
+      if (dn_finite(Zc) && Zc > a.min_z) {
+        const float u = (a.fx * Xc) / Zc + a.cx, v = (a.fy * Yc) / Zc + a.cy;
+        const float xq = floorf(u + 0.5f), yq = floorf(v + 0.5f);
+        if (dn_finite(u) && dn_finite(v) && xq >= 0.f && xq <= (float)(W - 1) && yq >= 0.f && yq <= (float)(H - 1)) {
+          const int j = (int)yq * W + (int)xq;
+          const float d = depth[j];
+          if (dn_finite(d) && d > a.min_d && d <= a.max_d) {
+            if (mask && mask[j] != 0) {
+              msk = true;
+            } else {
+              float s = d - Zc;
+              if (s < -a.trunc) {
+                occ = true;
+              } else {
+                s = fminf(s, a.trunc);
+                const int q = (int)floorf((s / a.trunc) * 32767.0f + 0.5f);
+                const int t = (int)(int16_t)(word[k] & 0xffffu), w = (int)(word[k] >> 16);
+                const int t1 = dn_floor_div(2 * (t * w + q) + (w + 1), 2 * (w + 1));      // |t|, |q| <= 32767, w <= 255: below 2^25
+                const int w1 = w + 1 < a.max_w ? w + 1 : a.max_w;
+                const uint32_t nw = ((uint32_t)w1 << 16) | ((uint32_t)t1 & 0xffffu);
+                if (nw != word[k]) vol[row0 + (size_t)sy * nx] = nw;
+                upd = true;
+              }
+            }
+          }
+        }
+      }
+    }
+    n_upd += (int)__popcll(__ballot(upd)); n_msk += (int)__popcll(__ballot(msk)); n_occ += (int)__popcll(__ballot(occ));
+  }
+  // the four waves' counts through LDS (blockDim.x == 64: one wave per threadIdx.z), then at most three atomics per workgroup, on one of kDnSlots
+  // copies of the counters: with one copy and one atomic per wave the kernel took the time of its atomics, not of its voxels
+  __shared__ int red[kDnZ][3];
+  if (threadIdx.x == 0) { red[threadIdx.z][0] = n_upd; red[threadIdx.z][1] = n_msk; red[threadIdx.z][2] = n_occ; }
+  __syncthreads();
+  if (threadIdx.x < 3 && threadIdx.z == 0) {
+    int sum = 0;
+    for (int z = 0; z < kDnZ; ++z) sum += red[z][threadIdx.x];
+    const unsigned slot = (blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)) & (unsigned)(kDnSlots - 1);
+    if (sum) atomicAdd(cnt + slot * kDnCounters + threadIdx.x, (unsigned long long)sum);
+  }
+}
+
+// the slab of `len` slots from slot s0 on (cyclic) on `axis`, whole on the other two axes
+__global__ __launch_bounds__(256) void k_dn_clear(uint32_t* __restrict__ vol, int nx, int ny, int nz, int axis, int s0, int len) {
+  const int lx = axis == 0 ? len : nx, ly = axis == 1 ? len : ny, lz = axis == 2 ? len : nz;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long long)lx * ly * lz) return;
+  int x = (int)(i % lx), y = (int)((i / lx) % ly), z = (int)(i / ((long long)lx * ly));
+  if (axis == 0) { x += s0; if (x >= nx) x -= nx; }
+  if (axis == 1) { y += s0; if (y >= ny) y -= ny; }
+  if (axis == 2) { z += s0; if (z >= nz) z -= nz; }
+  vol[((size_t)z * ny + y) * nx + x] = 0u;
+}
+
+struct DnBox { int lo[3], b[3]; };                                           // the clipped box: its first global voxel and its size (all > 0)
+
+// Voxel i of the box in the visiting order (x fastest): its points on axes 0, 1, 2.  !FILL: the workgroup's number of points.  FILL: the points
+// whose place in the visiting order lies in [base, base + cap) are written at place - base.
+template <bool FILL>
+__global__ __launch_bounds__(256) void k_dn_extract(DnArgs a, DnBox bx, long long nbox, int min_w, const uint32_t* __restrict__ vol, long long* __restrict__ blk, long long base,
+                                                    long long cap, float* __restrict__ xyz, int32_t* __restrict__ grad, int32_t* __restrict__ wgt) {
+  __shared__ int lds[17];
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  int cross = 0, g[3] = {0, 0, 0}, ta = 0, wa = 0, tb[3] = {0, 0, 0}, wb[3] = {0, 0, 0};
+  bool all_in = false;
+  if (i < nbox) {
+    g[0] = bx.lo[0] + (int)(i % bx.b[0]); g[1] = bx.lo[1] + (int)((i / bx.b[0]) % bx.b[1]); g[2] = bx.lo[2] + (int)(i / ((long long)bx.b[0] * bx.b[1]));
+    int s[3];
+    for (int k = 0; k < 3; ++k) { s[k] = g[k] % a.n[k]; if (s[k] < 0) s[k] += a.n[k]; }
+    const uint32_t w0 = vol[((size_t)s[2] * a.n[1] + s[1]) * a.n[0] + s[0]];
+    ta = (int)(int16_t)(w0 & 0xffffu); wa = (int)(w0 >> 16);
+    all_in = true;
+    for (int k = 0; k < 3; ++k) {
+      const bool inside = g[k] + 1 < a.o[k] + a.n[k];
+      if (inside) {
+        int t[3] = {s[0], s[1], s[2]};
+        t[k] = s[k] + 1 == a.n[k] ? 0 : s[k] + 1;
+        const uint32_t w1 = vol[((size_t)t[2] * a.n[1] + t[1]) * a.n[0] + t[0]];
+        tb[k] = (int)(int16_t)(w1 & 0xffffu); wb[k] = (int)(w1 >> 16);
+      }
+      const bool usable = inside && wb[k] >= min_w;
+      all_in = all_in && usable;
+      if (usable && wa >= min_w && ((ta < 0) != (tb[k] < 0))) cross |= 1 << k;
+    }
+  }
+  int total;
+  const int ex = block_excl_scan(__popc(cross), lds, &total);
+  if (!FILL) {
+    if (threadIdx.x == 0) blk[blockIdx.x] = total;
+    return;
+  }
+  long long pos = blk[blockIdx.x] + ex;
+  for (int k = 0; k < 3; ++k) {
+    if (!(cross >> k & 1)) continue;
+    if (pos >= base && pos < base + cap) {
+      const long long r = pos - base;
+      const float frac = (float)ta / (float)(ta - tb[k]);
+      for (int c = 0; c < 3; ++c) {
+        const float centre = (float)g[c] + 0.5f;
+        xyz[3 * r + c] = (c == k ? centre + frac : centre) * a.voxel;
+        grad[3 * r + c] = all_in ? tb[c] - ta : 0;
+      }
+      wgt[r] = wa < wb[k] ? wa : wb[k];
+    }
+    ++pos;
+  }
+}
+
+// exclusive scan of the workgroup counts (single workgroup) with a 64-bit carry; the total goes to total[0]
+__global__ __launch_bounds__(1024) void k_dn_scan(long long* __restrict__ blk, long long nblk, unsigned long long* __restrict__ total_out) {
+  __shared__ int lds[17];
+  long long carry = 0;
+  for (long long b0 = 0; b0 < nblk; b0 += 1024) {
+    const long long i = b0 + threadIdx.x;
+    const int v = i < nblk ? (int)blk[i] : 0;                                // <= 768 each, <= 786432 per round
+    int total;
+    const int ex = block_excl_scan(v, lds, &total);
+    if (i < nblk) blk[i] = carry + ex;
+    carry += total;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) total_out[0] = (unsigned long long)carry;
+}
+
+static int dn_check_hip(const char* who, hipError_t e) { return e == hipSuccess ? VDO_OK : set_error(VDO_ERR_NO_DEVICE, "%s: %s", who, hipGetErrorString(e)); }
+
+static void dn_free(vdo_dense* h) {
+  hipFree(h->d_vol); hipFree(h->d_depth); hipFree(h->d_mask); hipFree(h->d_blk); hipFree(h->d_cnt); hipFree(h->d_xyz); hipFree(h->d_grad); hipFree(h->d_wgt);
+  if (h->h_cnt) hipHostFree(h->h_cnt);
+  if (h->ev0) hipEventDestroy(h->ev0);
+  if (h->ev1) hipEventDestroy(h->ev1);
+  delete h;
+}
+
+static bool dn_good(float v) { return std::fabs(v) <= FLT_MAX; }
+
+static int dn_mod(int g, int n) { const int m = g % n; return m < 0 ? m + n : m; }
+
+// an origin whose volume stays inside (-2^22, 2^22) on every axis; 0 when it does
+static int dn_check_origin(const char* who, const char* name, const int32_t o[3], const int32_t n[3]) {
+  for (int k = 0; k < 3; ++k)
+    if (o[k] <= -kDnMaxOrigin || (int64_t)o[k] + n[k] > kDnMaxOrigin)
+      return set_error(VDO_ERR_INVALID, "%s: %s[%d] = %d: the volume must stay inside (-2^22, 2^22) voxels", who, name, k, o[k]);
+  return VDO_OK;
+}
+
+static void dn_set_origin(vdo_dense* h, const int32_t o[3]) {
+  for (int k = 0; k < 3; ++k) { h->p.origin[k] = o[k]; h->a.o[k] = o[k]; h->a.om[k] = dn_mod(o[k], h->a.n[k]); }
+}
+
+template <int VPT>
+static void dn_launch_integrate(vdo_dense* h, hipStream_t s, const DnArgs& a, const float* depth, const int32_t* mask) {
+  const dim3 grid((a.n[0] + 63) / 64, (a.n[1] + VPT - 1) / VPT, (a.n[2] + kDnZ - 1) / kDnZ);
+  hipLaunchKernelGGL(k_dn_integrate<VPT>, grid, dim3(64, 1, kDnZ), 0, s, a, depth, mask, h->W, h->H, h->d_vol, h->d_cnt);
+}
+
+// the launch, the download of the counts and the timing the two integrate entries share; depth and mask are packed device images
+static int dn_integrate(const char* who, vdo_dense* h, const float* d_depth, const int32_t* d_mask, const float T[16], int64_t out[3], std::chrono::steady_clock::time_point t0) {
+  hipStream_t s = h->ctx->stream;
+  DnArgs a = h->a;
+  for (int k = 0; k < 12; ++k) a.T[k] = T[k];
+  hipMemsetAsync(h->d_cnt, 0, kDnTotal * sizeof(unsigned long long), s);
+  switch (h->vpt) {
+    case 1: dn_launch_integrate<1>(h, s, a, d_depth, d_mask); break;
+    case 2: dn_launch_integrate<2>(h, s, a, d_depth, d_mask); break;
+    case 8: dn_launch_integrate<8>(h, s, a, d_depth, d_mask); break;
+    default: dn_launch_integrate<4>(h, s, a, d_depth, d_mask); break;
+  }
+  hipEventRecord(h->ev1, s);
+  hipMemcpyAsync(h->h_cnt, h->d_cnt, kDnTotal * sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
+  hipError_t e = hipStreamSynchronize(s);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e != hipSuccess) return dn_check_hip(who, e);
+  for (int k = 0; k < 3; ++k) {
+    unsigned long long sum = 0;
+    for (int slot = 0; slot < kDnSlots; ++slot) sum += h->h_cnt[slot * kDnCounters + k];
+    out[k] = (int64_t)sum;
+  }
+  float dev_ms = 0.f;
+  hipEventElapsedTime(&dev_ms, h->ev0, h->ev1);
+  h->ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  h->ms[1] = dev_ms;
+  return VDO_OK;
+}
+
+}  // namespace vdo
+
+using namespace vdo;
+
+extern "C" int vdo_dense_create(vdo_ctx* ctx, int width, int height, const vdo_dense_params* p, vdo_dense** out) {
+  static const char* who = "vdo_dense_create";
+  if (!ctx) return set_error(VDO_ERR_INVALID, "%s: ctx is null", who);
+  if (!out) return set_error(VDO_ERR_INVALID, "%s: out is null", who);
+  if (!p) return set_error(VDO_ERR_INVALID, "%s: params is null", who);
+  if (width < 1) return set_error(VDO_ERR_INVALID, "%s: width %d < 1", who, width);
+  if (height < 1) return set_error(VDO_ERR_INVALID, "%s: height %d < 1", who, height);
+  for (int k = 0; k < 3; ++k) if (p->n[k] < 1) return set_error(VDO_ERR_INVALID, "%s: n[%d] = %d < 1", who, k, p->n[k]);
+  if (!dn_good(p->voxel) || !(p->voxel > 0.f)) return set_error(VDO_ERR_INVALID, "%s: voxel %g must be positive and finite", who, (double)p->voxel);
+  for (int k = 0; k < 4; ++k) if (!dn_good(p->K[k])) return set_error(VDO_ERR_INVALID, "%s: K[%d] is not finite", who, k);
+  if (!(p->K[0] > 0.f) || !(p->K[1] > 0.f)) return set_error(VDO_ERR_INVALID, "%s: K: fx %g, fy %g must be positive", who, (double)p->K[0], (double)p->K[1]);
+  if (!dn_good(p->trunc) || !(p->trunc > 0.f)) return set_error(VDO_ERR_INVALID, "%s: trunc %g must be positive and finite", who, (double)p->trunc);
+  if (!dn_good(p->min_depth) || !(p->min_depth >= 0.f)) return set_error(VDO_ERR_INVALID, "%s: min_depth %g must be finite and >= 0", who, (double)p->min_depth);
+  if (!dn_good(p->max_depth) || !(p->max_depth > p->min_depth)) return set_error(VDO_ERR_INVALID, "%s: max_depth %g must be finite and above min_depth %g", who, (double)p->max_depth, (double)p->min_depth);
+  if (p->max_weight < 1 || p->max_weight > 255) return set_error(VDO_ERR_INVALID, "%s: max_weight %d outside 1..255", who, p->max_weight);
+  if (p->stage_points < 1) return set_error(VDO_ERR_INVALID, "%s: stage_points %d < 1", who, p->stage_points);
+  for (int k = 0; k < 3; ++k) if (p->n[k] > kDnMaxSide) return set_error(VDO_ERR_UNSUPPORTED, "%s: n[%d] = %d exceeds 2^12", who, k, p->n[k]);
+  const int64_t nvox = (int64_t)p->n[0] * p->n[1] * p->n[2];
+  if (nvox > kDnMaxVoxels) return set_error(VDO_ERR_UNSUPPORTED, "%s: %d x %d x %d voxels exceed 2^31", who, p->n[0], p->n[1], p->n[2]);
+  if ((int64_t)width * height > kDnMaxPixels || width > kDnMaxImageSide || height > kDnMaxImageSide)
+    return set_error(VDO_ERR_UNSUPPORTED, "%s: width x height = %d x %d exceeds 2^26 pixels or 2^24 on a side", who, width, height);
+  int rc = dn_check_origin(who, "origin", p->origin, p->n);
+  if (rc != VDO_OK) return rc;
+  rc = ctx_bind(ctx);
+  if (rc != VDO_OK) return rc;
+  vdo_dense* h = new vdo_dense;
+  h->ctx = ctx; h->W = width; h->H = height; h->p = *p; h->nvox = nvox; h->stage_points = p->stage_points;
+  DnArgs& a = h->a;
+  a.fx = p->K[0]; a.fy = p->K[1]; a.cx = p->K[2]; a.cy = p->K[3]; a.trunc = p->trunc; a.min_d = p->min_depth; a.max_d = p->max_depth; a.voxel = p->voxel;
+  a.min_z = p->min_depth > FLT_MIN ? p->min_depth : FLT_MIN;
+  a.max_w = p->max_weight;
+  for (int k = 0; k < 3; ++k) a.n[k] = p->n[k];
+  dn_set_origin(h, p->origin);
+  const size_t npix = (size_t)width * height, nblk = (size_t)((nvox + 255) / 256), sp = (size_t)p->stage_points;
+  const bool ok = hipMalloc((void**)&h->d_vol, (size_t)nvox * sizeof(uint32_t)) == hipSuccess && hipMalloc((void**)&h->d_depth, npix * sizeof(float)) == hipSuccess &&
+                  hipMalloc((void**)&h->d_mask, npix * sizeof(int32_t)) == hipSuccess && hipMalloc((void**)&h->d_blk, nblk * sizeof(long long)) == hipSuccess &&
+                  hipMalloc((void**)&h->d_cnt, (kDnTotal + 1) * sizeof(unsigned long long)) == hipSuccess && hipMalloc((void**)&h->d_xyz, sp * 3 * sizeof(float)) == hipSuccess &&
+                  hipMalloc((void**)&h->d_grad, sp * 3 * sizeof(int32_t)) == hipSuccess && hipMalloc((void**)&h->d_wgt, sp * sizeof(int32_t)) == hipSuccess &&
+                  hipHostMalloc((void**)&h->h_cnt, (kDnTotal + 1) * sizeof(unsigned long long), hipHostMallocDefault) == hipSuccess && hipEventCreate(&h->ev0) == hipSuccess &&
+                  hipEventCreate(&h->ev1) == hipSuccess && hipMemsetAsync(h->d_vol, 0, (size_t)nvox * sizeof(uint32_t), ctx->stream) == hipSuccess &&
+                  hipStreamSynchronize(ctx->stream) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    dn_free(h);
+    return set_error(VDO_ERR_OOM, "%s: device allocation failed for %d x %d x %d voxels and %d x %d images", who, p->n[0], p->n[1], p->n[2], width, height);
+  }
+  *out = h;
+  return VDO_OK;
+}
+
+extern "C" int vdo_dense_destroy(vdo_dense* h) {
+  if (!h) return VDO_OK;
+  if (ctx_bind(h->ctx) == VDO_OK) hipStreamSynchronize(h->ctx->stream);
+  dn_free(h);
+  return VDO_OK;
+}
+
+extern "C" int vdo_dense_set_voxels_per_thread(vdo_dense* h, int voxels) {
+  if (!h) return set_error(VDO_ERR_INVALID, "vdo_dense_set_voxels_per_thread: handle is null");
+  if (voxels != 1 && voxels != 2 && voxels != 4 && voxels != 8) return set_error(VDO_ERR_INVALID, "vdo_dense_set_voxels_per_thread: voxels %d not 1, 2, 4 or 8", voxels);
+  h->vpt = voxels;
+  return VDO_OK;
+}
+
+extern "C" int vdo_dense_integrate(vdo_dense* h, const float* depth, int64_t depth_stride_floats, const int32_t* mask, int64_t mask_stride_ints, int src_is_device, const float T[16],
+                                   int64_t out[3]) {
+  static const char* who = "vdo_dense_integrate";
+  if (!h) return set_error(VDO_ERR_INVALID, "%s: handle is null", who);
+  if (!depth) return set_error(VDO_ERR_INVALID, "%s: depth is null", who);
+  if (depth_stride_floats < h->W) return set_error(VDO_ERR_INVALID, "%s: depth_stride_floats %lld smaller than the width %d", who, (long long)depth_stride_floats, h->W);
+  if (mask && mask_stride_ints < h->W) return set_error(VDO_ERR_INVALID, "%s: mask_stride_ints %lld smaller than the width %d", who, (long long)mask_stride_ints, h->W);
+  if (!T) return set_error(VDO_ERR_INVALID, "%s: T is null", who);
+  if (!out) return set_error(VDO_ERR_INVALID, "%s: out is null", who);
+  const int rc = ctx_bind(h->ctx);
+  if (rc != VDO_OK) return rc;
+  const auto t0 = std::chrono::steady_clock::now();
+  hipStream_t s = h->ctx->stream;
+  const int W = h->W, H = h->H;
+  const hipMemcpyKind kind = src_is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  hipEventRecord(h->ev0, s);
+  const float* d_depth = depth;
+  const int32_t* d_mask = mask;
+  if (!(src_is_device && depth_stride_floats == W)) {
+    hipMemcpy2DAsync(h->d_depth, W * sizeof(float), depth, (size_t)depth_stride_floats * sizeof(float), W * sizeof(float), H, kind, s);
+    d_depth = h->d_depth;
+  }
+  if (mask && !(src_is_device && mask_stride_ints == W)) {
+    hipMemcpy2DAsync(h->d_mask, W * sizeof(int32_t), mask, (size_t)mask_stride_ints * sizeof(int32_t), W * sizeof(int32_t), H, kind, s);
+    d_mask = h->d_mask;
+  }
+  return dn_integrate(who, h, d_depth, d_mask, T, out, t0);
+}
+
+extern "C" int vdo_dense_integrate_frame(vdo_dense* h, const vdo_frame_images* f, const float T[16], int64_t out[3]) {
+  static const char* who = "vdo_dense_integrate_frame";
+  if (!h) return set_error(VDO_ERR_INVALID, "%s: handle is null", who);
+  if (!f) return set_error(VDO_ERR_INVALID, "%s: frame is null", who);
+  if (f->w != h->W || f->h != h->H) return set_error(VDO_ERR_INVALID, "%s: frame is %d x %d, the mapper's images are %d x %d", who, f->w, f->h, h->W, h->H);
+  if (!T) return set_error(VDO_ERR_INVALID, "%s: T is null", who);
+  if (!out) return set_error(VDO_ERR_INVALID, "%s: out is null", who);
+  const int rc = ctx_bind(h->ctx);
+  if (rc != VDO_OK) return rc;
+  const auto t0 = std::chrono::steady_clock::now();
+  hipEventRecord(h->ev0, h->ctx->stream);
+  return dn_integrate(who, h, f->d_depth, f->d_mask, T, out, t0);
+}
+
+extern "C" int vdo_dense_recenter(vdo_dense* h, const int32_t new_origin[3]) {
+  static const char* who = "vdo_dense_recenter";
+  if (!h) return set_error(VDO_ERR_INVALID, "%s: handle is null", who);
+  if (!new_origin) return set_error(VDO_ERR_INVALID, "%s: new_origin is null", who);
+  int rc = dn_check_origin(who, "new_origin", new_origin, h->p.n);
+  if (rc != VDO_OK) return rc;
+  rc = ctx_bind(h->ctx);
+  if (rc != VDO_OK) return rc;
+  const auto t0 = std::chrono::steady_clock::now();
+  hipStream_t s = h->ctx->stream;
+  const int* n = h->a.n;
+  int64_t d[3];
+  bool all = false;
+  for (int k = 0; k < 3; ++k) { d[k] = (int64_t)new_origin[k] - h->a.o[k]; all = all || d[k] >= n[k] || -d[k] >= n[k]; }
+  hipEventRecord(h->ev0, s);
+  if (all) {
+    hipMemsetAsync(h->d_vol, 0, (size_t)h->nvox * sizeof(uint32_t), s);
+  } else {
+    for (int k = 0; k < 3; ++k) {
+      if (d[k] == 0) continue;
+      // leaving: the first d voxels of the axis when the volume moves up, the last -d when it moves down
+      const int len = (int)(d[k] > 0 ? d[k] : -d[k]), g0 = d[k] > 0 ? h->a.o[k] : h->a.o[k] + n[k] - len;
+      const long long cells = (long long)len * (h->nvox / n[k]);
+      hipLaunchKernelGGL(k_dn_clear, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, h->d_vol, n[0], n[1], n[2], k, dn_mod(g0, n[k]), len);
+    }
+  }
+  hipEventRecord(h->ev1, s);
+  hipError_t e = hipStreamSynchronize(s);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e != hipSuccess) return dn_check_hip(who, e);
+  dn_set_origin(h, new_origin);
+  float dev_ms = 0.f;
+  hipEventElapsedTime(&dev_ms, h->ev0, h->ev1);
+  h->ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  h->ms[1] = dev_ms;
+  return VDO_OK;
+}
+
+extern "C" int vdo_dense_extract(vdo_dense* h, const int32_t lo[3], const int32_t hi[3], int min_weight, int64_t capacity, float* xyz, int32_t* grad, int32_t* weight, int out_is_device,
+                                 int64_t* count) {
+  static const char* who = "vdo_dense_extract";
+  if (!h) return set_error(VDO_ERR_INVALID, "%s: handle is null", who);
+  if (!lo) return set_error(VDO_ERR_INVALID, "%s: lo is null", who);
+  if (!hi) return set_error(VDO_ERR_INVALID, "%s: hi is null", who);
+  if (min_weight < 1) return set_error(VDO_ERR_INVALID, "%s: min_weight %d < 1", who, min_weight);
+  if (capacity < 0) return set_error(VDO_ERR_INVALID, "%s: capacity %lld < 0", who, (long long)capacity);
+  if (capacity > 0 && !xyz) return set_error(VDO_ERR_INVALID, "%s: xyz is null", who);
+  if (capacity > 0 && !grad) return set_error(VDO_ERR_INVALID, "%s: grad is null", who);
+  if (capacity > 0 && !weight) return set_error(VDO_ERR_INVALID, "%s: weight is null", who);
+  if (!count) return set_error(VDO_ERR_INVALID, "%s: count is null", who);
+  const int rc = ctx_bind(h->ctx);
+  if (rc != VDO_OK) return rc;
+  const auto t0 = std::chrono::steady_clock::now();
+  hipStream_t s = h->ctx->stream;
+  DnBox bx;
+  long long nbox = 1;
+  for (int k = 0; k < 3; ++k) {
+    const int64_t a0 = lo[k] > h->a.o[k] ? lo[k] : h->a.o[k], a1 = hi[k] < (int64_t)h->a.o[k] + h->a.n[k] ? hi[k] : (int64_t)h->a.o[k] + h->a.n[k];
+    bx.lo[k] = (int)a0; bx.b[k] = a1 > a0 ? (int)(a1 - a0) : 0;
+    nbox *= bx.b[k];
+  }
+  hipEventRecord(h->ev0, s);
+  long long total = 0;
+  if (nbox > 0) {
+    const long long nblk = (nbox + 255) / 256;
+    hipLaunchKernelGGL(k_dn_extract<false>, dim3((unsigned)nblk), dim3(256), 0, s, h->a, bx, nbox, min_weight, (const uint32_t*)h->d_vol, h->d_blk, 0LL, 0LL, (float*)nullptr,
+                       (int32_t*)nullptr, (int32_t*)nullptr);
+    hipLaunchKernelGGL(k_dn_scan, dim3(1), dim3(1024), 0, s, h->d_blk, nblk, h->d_cnt + kDnTotal);
+    hipMemcpyAsync(h->h_cnt + kDnTotal, h->d_cnt + kDnTotal, sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
+    hipError_t e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) return dn_check_hip(who, e);
+    total = (long long)h->h_cnt[kDnTotal];
+    const long long want = total < capacity ? total : capacity;
+    // a device output is one window; a host output goes through the staging lists, stage_points at a time
+    for (long long base = 0; base < want; base += out_is_device ? want : h->stage_points) {
+      const long long cap = out_is_device ? want : (want - base < h->stage_points ? want - base : h->stage_points);
+      float* o_xyz = out_is_device ? xyz : h->d_xyz; int32_t* o_grad = out_is_device ? grad : h->d_grad; int32_t* o_wgt = out_is_device ? weight : h->d_wgt;
+      hipLaunchKernelGGL(k_dn_extract<true>, dim3((unsigned)nblk), dim3(256), 0, s, h->a, bx, nbox, min_weight, (const uint32_t*)h->d_vol, h->d_blk, base, cap, o_xyz, o_grad, o_wgt);
+      if (!out_is_device) {
+        hipMemcpyAsync(xyz + 3 * base, h->d_xyz, (size_t)cap * 3 * sizeof(float), hipMemcpyDeviceToHost, s);
+        hipMemcpyAsync(grad + 3 * base, h->d_grad, (size_t)cap * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+        hipMemcpyAsync(weight + base, h->d_wgt, (size_t)cap * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+        e = hipStreamSynchronize(s);                                         // the staging lists are free for the next window
+        if (e != hipSuccess) return dn_check_hip(who, e);
+      }
+    }
+  }
+  hipEventRecord(h->ev1, s);
+  hipError_t e = hipStreamSynchronize(s);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e != hipSuccess) return dn_check_hip(who, e);
+  *count = total;
+  float dev_ms = 0.f;
+  hipEventElapsedTime(&dev_ms, h->ev0, h->ev1);
+  h->ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  h->ms[1] = dev_ms;
+  return VDO_OK;
+}
+
+extern "C" int vdo_dense_get_volume(vdo_dense* h, uint32_t* words, int32_t origin[3]) {
+  static const char* who = "vdo_dense_get_volume";
+  if (!h) return set_error(VDO_ERR_INVALID, "%s: handle is null", who);
+  if (!words && !origin) return set_error(VDO_ERR_INVALID, "%s: words and origin are both null", who);
+  if (words) {
+    const int rc = ctx_bind(h->ctx);
+    if (rc != VDO_OK) return rc;
+    hipMemcpyAsync(words, h->d_vol, (size_t)h->nvox * sizeof(uint32_t), hipMemcpyDeviceToHost, h->ctx->stream);
+    const int rs = dn_check_hip(who, hipStreamSynchronize(h->ctx->stream));
+    if (rs != VDO_OK) return rs;
+  }
+  if (origin) for (int k = 0; k < 3; ++k) origin[k] = h->a.o[k];
+  return VDO_OK;
+}
+
+extern "C" int vdo_dense_set_volume(vdo_dense* h, const uint32_t* words) {
+  static const char* who = "vdo_dense_set_volume";
+  if (!h) return set_error(VDO_ERR_INVALID, "%s: handle is null", who);
+  if (!words) return set_error(VDO_ERR_INVALID, "%s: words is null", who);
+  const int rc = ctx_bind(h->ctx);
+  if (rc != VDO_OK) return rc;
+  hipMemcpyAsync(h->d_vol, words, (size_t)h->nvox * sizeof(uint32_t), hipMemcpyHostToDevice, h->ctx->stream);
+  return dn_check_hip(who, hipStreamSynchronize(h->ctx->stream));
+}
+
+extern "C" int vdo_dense_last_timing(vdo_dense* h, double ms[2]) {
+  if (!h || !ms) return set_error(VDO_ERR_INVALID, "vdo_dense_last_timing: %s is null", !h ? "handle" : "ms");
+  ms[0] = h->ms[0]; ms[1] = h->ms[1];
+  return VDO_OK;
+}
+
+extern "C" int vdo_dense_device_volume(vdo_dense* h, uint32_t** words) {
+  if (!h || !words) return set_error(VDO_ERR_INVALID, "vdo_dense_device_volume: %s is null", !h ? "handle" : "words");
+  *words = h->d_vol;
+  return VDO_OK;
+}

@@ -1,0 +1,62 @@
+// DenseMapper - the dense map of the static scene: a TSDF voxel volume on the device (vdo_dense_* of libvdo_hip) that follows the camera, and the
+// surface points of what has left it, on the host.  The reference keeps no dense map; the semantics of the volume are stated in
+// include/vdo_slam_hip.h, the per-frame flow below is restated by vdo_slam_amd/dense.py (FollowingMap).
+#pragma once
+#include <string>
+#include <vector>
+
+#include "host_context.h"
+#include "minicv.h"
+
+namespace VDO_SLAM {
+
+class DenseMapper {
+ public:
+  // The settings file's Dense.* keys (System.h): the volume and the fusion (params.origin is where the volume waits for the first frame), the camera
+  // centre's target place in the volume as fractions of its size, the distance in voxels from that place at which the volume moves, and the smallest
+  // weight of an extracted voxel
+  struct Settings { vdo_dense_params params{}; double anchor[3] = {0.5, 0.5, 0.25}; int margin = 0; int minWeight = 2; };
+  static Settings DefaultSettings(const float K[4], float voxel, float maxDepth) {
+    Settings s;
+    s.params = vdo_dense_params{{256, 128, 256}, voxel, {0, 0, 0}, {K[0], K[1], K[2], K[3]}, 4.f * voxel, 0.f, maxDepth, 64, 1 << 20};
+    s.margin = 128 / 8;
+    return s;
+  }
+  // The surface points kept on the host: xyz [n][3], the unnormalised integer gradient [n][3], the weight [n]
+  struct Points { std::vector<float> xyz; std::vector<int32_t> grad, weight; size_t size() const { return weight.size(); } };
+
+  // A mapper for width x height depth and mask images on `ctx` (HostContext() when null).  Throws std::runtime_error when the library refuses.
+  DenseMapper(vdo_ctx* ctx, int width, int height, const Settings& settings);
+  ~DenseMapper();
+  DenseMapper(const DenseMapper&) = delete;
+  DenseMapper& operator=(const DenseMapper&) = delete;
+  // One frame.  Before it is fused the camera centre's voxel c = floor(-R^T t / voxel) is computed in double; if the volume has not started, or c is
+  // further than `margin` voxels from origin + floor(anchor * n) on any axis, what leaves the volume is extracted (the x slab, then the y slab of what
+  // stays on x, then the z slab of what stays on x and y; the whole volume for a move of n or more) and appended to kept(), and the volume moves so
+  // that c sits at its target place.  Then the frame's resident depth and mask (or the cv::Mats: CV_32FC1 metres, CV_32SC1 or empty) are fused with
+  // Tcw (16 floats, world -> camera).  counts (optional): updated, masked and occluded voxels.
+  void FuseFrame(const vdo_frame_images* frame, const float Tcw[16], int64_t counts[3] = nullptr);
+  void Fuse(const cv::Mat& depth, const cv::Mat& mask, const float Tcw[16], int64_t counts[3] = nullptr);
+  // kept() followed by what is in the volume now (neither is changed)
+  Points AllPoints();
+  // AllPoints() as a binary little-endian PLY: x, y, z, nx, ny, nz (float; the gradient normalised in double and narrowed, or 0) and weight (int).
+  // False when the file cannot be written.
+  bool SavePLY(const std::string& path);
+  const Points& kept() const { return kept_; }
+  int recenters() const { return recenters_; }
+  void origin(int32_t out[3]) const;
+  vdo_dense* handle() { return h_; }
+  const Settings& settings() const { return s_; }
+
+ private:
+  void Follow(const float Tcw[16]);
+  void Append(const int32_t lo[3], const int32_t hi[3], Points& to);
+  vdo_dense* h_ = nullptr;
+  Settings s_;
+  int w_, h_px_;
+  bool started_ = false;
+  int recenters_ = 0;
+  Points kept_;
+};
+
+}  // namespace VDO_SLAM

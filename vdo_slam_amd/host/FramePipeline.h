@@ -86,6 +86,8 @@ class FramePipeline {
   int DownloadMask(int32_t* mask_out);
   // the depth map of the last frame given to Step after K1 (metres): what GrabImageRGBD leaves in the caller's imD
   int DownloadDepth(float* depth_out);
+  // the resident images of the last frame given to Step (depth after K1, the mask as the step left it): for a reader that does not write them
+  vdo_frame_images* LastImages() { return img_[cur_ ^ 1]; }
   // "Save Graph Structure" of Track() (src/Tracking.cc:1031-1159, Initialization :1238-1246): once KeepGraph() / AttachMap()
   // was called every frame appends its static / dynamic features, depths, 3-D points, camera pose and rigid motions (+ labels)
   // to a flat GraphStore (plain array appends: a few microseconds per frame) - what Optimizer::Full/PartialBatchOptimization

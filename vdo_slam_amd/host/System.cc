@@ -174,6 +174,55 @@ std::string read_motion_settings(const TrackingSettings& t, const std::map<std::
   if (ms.ego.minInliers < 0) return "settings: Motion.EgoMinInliers must not be negative";
   return "";
 }
+// The Dense.* keys (System.h), all optional.  present: Dense.VoxelSize is in the file - without it the other keys are not read and no mapper is made.
+// The returned text is empty when the keys are absent or in order; otherwise it is the settings error, which ends the process in Tracking::Tracking
+// and is a refusal in host_system_create.  The ranges are those of vdo_dense_create.
+struct DenseSettings { bool present = false; DenseMapper::Settings s; };
+std::string read_dense_settings(const std::string& path, const TrackingSettings& t, const std::map<std::string, double>& raw, DenseSettings& ds) {
+  std::map<std::string, std::vector<double> > lists;
+  read_settings_lists(path, lists);
+  ds.present = raw.count("Dense.VoxelSize") != 0 || lists.count("Dense.VoxelSize") != 0;
+  if (!ds.present) return "";
+  const double voxel = get(raw, "Dense.VoxelSize", 0);
+  if (!std::isfinite(voxel) || !(voxel > 0) || !((float)voxel > 0) || !std::isfinite((float)voxel)) return "settings: Dense.VoxelSize must be positive";
+  const float K[4] = {t.fx, t.fy, t.cx, t.cy};
+  DenseMapper::Settings& s = ds.s;
+  s = DenseMapper::DefaultSettings(K, (float)voxel, t.th_depth_bg);
+  vdo_dense_params& p = s.params;
+  auto whole = [](double v) { return std::isfinite(v) && std::fabs(v) <= 1e9 && v == std::floor(v); };
+  if (raw.count("Dense.Size")) return "settings: Dense.Size must be a list [nx, ny, nz]";
+  const auto size = lists.find("Dense.Size");
+  if (size != lists.end()) {
+    if (size->second.size() != 3) return "settings: Dense.Size has " + std::to_string(size->second.size()) + " values, expected [nx, ny, nz]";
+    for (int a = 0; a < 3; ++a) {
+      if (!whole(size->second[a]) || size->second[a] < 1 || size->second[a] > 4096) return "settings: Dense.Size: every side must be a whole number in 1..4096";
+      p.n[a] = (int32_t)size->second[a];
+    }
+  }
+  if ((int64_t)p.n[0] * p.n[1] * p.n[2] > (int64_t(1) << 31)) return "settings: Dense.Size: more than 2^31 voxels";
+  p.trunc = (float)get(raw, "Dense.Truncation", p.trunc); p.min_depth = (float)get(raw, "Dense.MinDepth", p.min_depth); p.max_depth = (float)get(raw, "Dense.MaxDepth", p.max_depth);
+  const int min_n = std::min(p.n[0], std::min(p.n[1], p.n[2]));
+  const double ints[3] = {get(raw, "Dense.MaxWeight", p.max_weight), get(raw, "Dense.MinWeight", s.minWeight), get(raw, "Dense.RecenterMargin", min_n / 8)};
+  static const char* const int_keys[3] = {"MaxWeight", "MinWeight", "RecenterMargin"};
+  for (int k = 0; k < 3; ++k) if (!whole(ints[k])) return std::string("settings: Dense.") + int_keys[k] + " must be a whole number";
+  p.max_weight = (int32_t)ints[0]; s.minWeight = (int)ints[1]; s.margin = (int)ints[2];
+  if (raw.count("Dense.Anchor")) return "settings: Dense.Anchor must be a list [ax, ay, az]";
+  const auto anchor = lists.find("Dense.Anchor");
+  if (anchor != lists.end()) {
+    if (anchor->second.size() != 3) return "settings: Dense.Anchor has " + std::to_string(anchor->second.size()) + " values, expected [ax, ay, az]";
+    for (int a = 0; a < 3; ++a) {
+      if (!(anchor->second[a] > 0 && anchor->second[a] < 1)) return "settings: Dense.Anchor: every value must lie in (0, 1)";
+      s.anchor[a] = anchor->second[a];
+    }
+  }
+  if (!std::isfinite(p.trunc) || !(p.trunc > 0)) return "settings: Dense.Truncation must be positive";
+  if (!std::isfinite(p.min_depth) || !(p.min_depth >= 0)) return "settings: Dense.MinDepth must not be negative";
+  if (!std::isfinite(p.max_depth) || !(p.max_depth > p.min_depth)) return "settings: Dense.MaxDepth must be above Dense.MinDepth";
+  if (p.max_weight < 1 || p.max_weight > 255) return "settings: Dense.MaxWeight outside 1..255";
+  if (s.minWeight < 1 || s.minWeight > 255) return "settings: Dense.MinWeight outside 1..255";
+  if (s.margin < 0) return "settings: Dense.RecenterMargin must not be negative";
+  return "";
+}
 }  // namespace
 
 Tracking::Tracking(System*, Map* pMap, const std::string& strSettingPath, const int sensor) : mpMap(pMap) {
@@ -203,6 +252,11 @@ Tracking::Tracking(System*, Map* pMap, const std::string& strSettingPath, const 
     if (!err.empty()) { std::cerr << err << std::endl; std::exit(-1); }
     motion_p_ = ms.p; ego_ = ms.ego;
   }
+  DenseSettings dense;
+  {
+    const std::string err = read_dense_settings(strSettingPath, t, cfg_, dense);
+    if (!err.empty()) { std::cerr << err << std::endl; std::exit(-1); }
+  }
   PipelineParams p{};
   p.width = t.width; p.height = t.height;
   p.K4[0] = t.fx; p.K4[1] = t.fy; p.K4[2] = t.cx; p.K4[3] = t.cy;
@@ -226,6 +280,11 @@ Tracking::Tracking(System*, Map* pMap, const std::string& strSettingPath, const 
   pipe_.reset(new FramePipeline(ctx_[0], ctx_[1], p, ctx_[2], ctx_[3], ctx_[4]));
   if (!pipe_->ok()) throw std::runtime_error(std::string("VDO_SLAM::Tracking: FramePipeline: ") + vdo_last_error());
   pipe_->AttachMap(mpMap);
+  if (dense.present) {
+    // a context of its own: the fusion waits for nothing the frame step has queued, and nothing of the frame step waits for it
+    if (vdo_ctx_create(dev ? std::atoi(dev) : 0, nullptr, &ctx_dense_) != VDO_OK) throw std::runtime_error(std::string("VDO_SLAM::Tracking: no HIP device: ") + vdo_last_error());
+    dense_.reset(new DenseMapper(ctx_dense_, p.width, p.height, dense.s));
+  }
   if (mSensor == System::STEREO) {
     const vdo_stereo_params d = StereoMatcher::DefaultParams();
     const vdo_stereo_params sp{(int)get(cfg_, "Stereo.MaxDisparity", d.max_disparity), (int)get(cfg_, "Stereo.P1", d.p1), (int)get(cfg_, "Stereo.P2", d.p2),
@@ -255,6 +314,8 @@ Tracking::Tracking(System*, Map* pMap, const std::string& strSettingPath, const 
 }
 
 Tracking::~Tracking() {
+  dense_.reset();
+  if (ctx_dense_) vdo_ctx_destroy(ctx_dense_);
   pipe_.reset();
   rectifier_.reset();
   motion_.reset();
@@ -583,6 +644,8 @@ cv::Mat Tracking::FinishFrame(const cv::Mat& mTcw_gt, std::chrono::steady_clock:
     mpMap->vmCameraPose_GT.push_back(Converter::toInvMatrix(Tgt));
   }
   have_frame_ = true;
+  // the dense map: the frame's resident depth (metres) and mask, as the step left them, fused with the pose the tracker has just found
+  if (dense_) dense_->FuseFrame(pipe_->LastImages(), pipe_->Tcw_out_, dense_counts_);
   // full batch optimisation after the last frame, KITTI only (Tracking.cc:1189-1210: `bGlobalBatch && mTestData==KITTI`)
   if (f_id == StopFrame && f_id > 1 && bGlobalBatch && mTestData == KITTI) {
     if (pipe_->FullBatchOptimization() != 0) return cv::Mat();     // graph built straight from the pipeline's GraphStore
@@ -761,6 +824,13 @@ cv::Mat System::TrackStereoVideo(const cv::Mat& imLeft, const cv::Mat& imRight, 
   return mpTracker->GrabImageStereoVideo(imLeft, imRight, imLeftNext, imRightNext, mTcw_gt, vObjPose_gt, timestamp, imTraj, nImage);
 }
 
+bool System::SaveDenseMap(const std::string& path) {
+  DenseMapper* d = mpTracker->dense();
+  if (!d) { std::cerr << "VDO_SLAM::System::SaveDenseMap: no dense map (the settings file has no Dense.VoxelSize)" << std::endl; return false; }
+  if (!d->SavePLY(path)) { std::cerr << "VDO_SLAM::System::SaveDenseMap: cannot write " << path << std::endl; return false; }
+  return true;
+}
+
 // The Map (reference format) is materialised from the pipeline's flat store when somebody looks at it.
 Map* System::map() { mpTracker->pipeline()->SyncMap(); return mpMap; }
 
@@ -826,6 +896,9 @@ static VDO_SLAM::System* host_system_create_sensor(const char* settings, VDO_SLA
       const std::string merr = VDO_SLAM::read_motion_settings(t, raw, ms);
       if (!merr.empty()) { std::fprintf(stderr, "host_system_create: %s\n", merr.c_str()); return nullptr; }
     }
+    VDO_SLAM::DenseSettings dense;
+    const std::string derr = VDO_SLAM::read_dense_settings(settings, t, raw, dense);
+    if (!derr.empty()) { std::fprintf(stderr, "host_system_create: %s\n", derr.c_str()); return nullptr; }
   }
   {
     const char* dev = std::getenv("VDO_DEVICE");
@@ -953,6 +1026,50 @@ int host_settings_check_motion(const char* path, char* msg, int cap, double* out
     for (int i = 0; i < 14; ++i) out14[i] = v[i];
   }
   return err.empty() ? 0 : 1;
+}
+// the Dense.* keys as Tracking::Tracking reads them, without a GPU: 0 in order, 1 a settings error (text in msg), -2 no file.  out14 (may be null):
+// present (0 / 1: Dense.VoxelSize is in the file; the rest only then), VoxelSize, nx, ny, nz, Truncation, MinDepth, MaxDepth, MaxWeight, MinWeight,
+// the three Anchor values, RecenterMargin
+int host_settings_check_dense(const char* path, char* msg, int cap, double* out14) {
+  VDO_SLAM::TrackingSettings t{};
+  std::map<std::string, double> raw;
+  if (!VDO_SLAM::read_tracking_settings(path, t, &raw)) return -2;
+  VDO_SLAM::DenseSettings ds;
+  const std::string err = VDO_SLAM::read_dense_settings(path, t, raw, ds);
+  if (msg && cap > 0) std::snprintf(msg, (size_t)cap, "%s", err.c_str());
+  if (out14 && err.empty()) {
+    out14[0] = ds.present ? 1 : 0;
+    if (ds.present) {
+      const vdo_dense_params& p = ds.s.params;
+      const double v[13] = {p.voxel, (double)p.n[0], (double)p.n[1], (double)p.n[2], p.trunc, p.min_depth, p.max_depth, (double)p.max_weight, (double)ds.s.minWeight,
+                            ds.s.anchor[0], ds.s.anchor[1], ds.s.anchor[2], (double)ds.s.margin};
+      for (int i = 0; i < 13; ++i) out14[1 + i] = v[i];
+    }
+  }
+  return err.empty() ? 0 : 1;
+}
+// the dense map of a System with Dense.* keys.  info8: the origin (3), the recentrings so far, the points kept on the host, and the updated, masked
+// and occluded voxels of the last frame.  0, or -1 without a mapper.
+int host_system_dense_info(VDO_SLAM::System* s, long long* info8) {
+  try {
+    VDO_SLAM::DenseMapper* d = s->tracker()->dense();
+    if (!d) return -1;
+    int32_t o[3];
+    d->origin(o);
+    info8[0] = o[0]; info8[1] = o[1]; info8[2] = o[2]; info8[3] = d->recenters(); info8[4] = (long long)d->kept().size();
+    for (int k = 0; k < 3; ++k) info8[5 + k] = s->tracker()->dense_counts()[k];
+  } catch (const std::exception& e) { std::fprintf(stderr, "host_system_dense_info: %s\n", e.what()); return -1; }
+  return 0;
+}
+// System::SaveDenseMap: 0, -1 without a mapper or when the file cannot be written
+int host_system_save_dense_map(VDO_SLAM::System* s, const char* path) {
+  try { return s->SaveDenseMap(path) ? 0 : -1; }
+  catch (const std::exception& e) { std::fprintf(stderr, "host_system_save_dense_map: %s\n", e.what()); return -1; }
+}
+// what the dense mapper fused last: the resident depth (metres) and mask of the last frame, [Camera.height][Camera.width] each.  0, or -1
+int host_system_last_depth_mask(VDO_SLAM::System* s, float* depth, int* mask) {
+  VDO_SLAM::FramePipeline* fp = s->tracker()->pipeline();
+  return fp->DownloadDepth(depth) == 0 && fp->DownloadMask(mask) == 0 ? 0 : -1;
 }
 // what the last TrackStereoVideo call found: ego-motion inliers, moving pixels after the vote, labels
 void host_system_video_counts(VDO_SLAM::System* s, int* out3) { for (int k = 0; k < 3; ++k) out3[k] = s->tracker()->video_counts()[k]; }

@@ -12,6 +12,7 @@
 #include "FlowMatcher.h"
 #include "Frame.h"
 #include "FramePipeline.h"
+#include "DenseMapper.h"
 #include "InstanceLabeler.h"
 #include "StereoRectifier.h"
 #include "Map.h"
@@ -64,6 +65,10 @@ class Tracking {
   // vdo_rectify_compute.  The segmenter is made on the first call.
   cv::Mat GrabImageStereoVideo(const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat& imLeftNext, const cv::Mat& imRightNext, const cv::Mat& mTcw_gt,
                                const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, cv::Mat& imTraj, const int& nImage);
+  // The dense map (settings keys Dense.*, System::SaveDenseMap below): null without Dense.VoxelSize.  Every Grab* entry fuses its frame in FinishFrame,
+  // after the pose is known: the frame's resident depth and mask with that pose, on a context of its own.
+  DenseMapper* dense() { return dense_.get(); }
+  const int64_t* dense_counts() const { return dense_counts_; }      // updated, masked and occluded voxels of the last frame
   MotionSegmenter* motion() { return motion_.get(); }    // null before the first GrabImageStereoVideo
   // What the last GrabImageStereoVideo found: ego-motion inliers, moving pixels after the vote (0 when the ego-motion failed), labels
   const int* video_counts() const { return video_counts_; }
@@ -119,6 +124,9 @@ class Tracking {
   std::unique_ptr<InstanceLabeler> labels_;
   std::unique_ptr<StereoRectifier> rectifier_;           // Rectify.* keys present: the stereo entries take raw images
   int rect_border_ = 0, rect_classes_ = 0;               // Rectify.Border, Rectify.Classes
+  std::unique_ptr<DenseMapper> dense_;                   // Dense.VoxelSize present: the dense map of the static scene
+  vdo_ctx* ctx_dense_ = nullptr;                         // its context (made only with the mapper)
+  int64_t dense_counts_[3] = {0, 0, 0};
   std::unique_ptr<MotionSegmenter> motion_;              // made by the first GrabImageStereoVideo from motion_p_
   vdo_motionseg_params motion_p_{};                      // Motion.* keys (read and checked with the STEREO sensor only)
   MotionSegmenter::EgoParams ego_;                       // Motion.Ego* keys
@@ -178,6 +186,16 @@ class System {
   // the sensor is not STEREO.
   cv::Mat TrackStereoVideo(const cv::Mat& imLeft, const cv::Mat& imRight, const cv::Mat& imLeftNext, const cv::Mat& imRightNext, const cv::Mat& mTcw_gt,
                            const std::vector<std::vector<float> >& vObjPose_gt, const double& timestamp, cv::Mat& imTraj, const int& nImage);
+  // The dense map of the static scene.  Settings keys, all optional; the mapper exists only if Dense.VoxelSize (the voxel edge in metres) is present,
+  // and without it nothing changes: Dense.Size [nx, ny, nz] ([256, 128, 256]), Dense.Truncation (4 x voxel), Dense.MinDepth (0), Dense.MaxDepth
+  // (ThDepthBG), Dense.MaxWeight (64), Dense.MinWeight (2: the smallest weight of an extracted voxel), Dense.Anchor [ax, ay, az] in (0, 1), the camera
+  // centre's target place in the volume ([0.5, 0.5, 0.25]), Dense.RecenterMargin in voxels (min(n) / 8).  A value outside its range is a settings error
+  // with every sensor.  Every Track* entry fuses its frame once the pose is known (DenseMapper::FuseFrame): the volume follows the camera, and what
+  // leaves it is kept as points on the host.  SaveDenseMap writes those points and the surface in the volume as a binary little-endian PLY (x, y, z,
+  // nx, ny, nz, weight); false without a mapper or when the file cannot be written.  Limits: the map is fused with the tracker's per-frame poses and is
+  // not re-fused after a bundle adjustment; an edge between a leaving and a staying voxel can be lost when the volume moves towards a negative axis;
+  // objects are not reconstructed; with semantic masks on the RGBD path parked instances are left out too.
+  bool SaveDenseMap(const std::string& path);
   void SaveResults(const std::string& filename);
   Map* map();                          // brought up to date from the pipeline's GraphStore on access
   Tracking* tracker() { return mpTracker; }

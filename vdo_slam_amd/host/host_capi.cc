@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "Converter.h"
+#include "DenseMapper.h"
 #include "FlowMatcher.h"
 #include "InstanceLabeler.h"
 #include "Frame.h"
@@ -377,6 +378,27 @@ int host_motionseg_compute(const float* disp0, int disp0_step_floats, const floa
     if (counts3) std::memcpy(counts3, counts, sizeof counts);
     return counts[0];
   } catch (const std::exception& e) { std::fprintf(stderr, "host_motionseg_compute: %s\n", e.what()); return -1; }
+}
+
+// DenseMapper::Fuse on k host frames (depth [k][h][w] metres, mask [k][h][w] or null, Tcw [k][16] world -> camera).  params: the library's struct;
+// anchor3, margin, min_weight: DenseMapper::Settings.  ply_path (may be null): DenseMapper::SavePLY after the last frame.  info2 (may be null):
+// recentrings, points kept on the host.  Returns the number of points of AllPoints(), -1 on a failure.
+long long host_dense_fuse(const float* depth, const int* mask, const float* Tcw, int k, int w, int h, const vdo_dense_params* params, const double* anchor3, int margin,
+                          int min_weight, const char* ply_path, long long* info2) {
+  try {
+    DenseMapper::Settings s;
+    s.params = *params; s.margin = margin; s.minWeight = min_weight;
+    for (int a = 0; a < 3; ++a) s.anchor[a] = anchor3[a];
+    DenseMapper m(nullptr, w, h, s);
+    for (int i = 0; i < k; ++i) {
+      cv::Mat D(h, w, cv::CV_32FC1, (void*)(depth + (size_t)i * w * h)), M;
+      if (mask) M = cv::Mat(h, w, cv::CV_32SC1, (void*)(mask + (size_t)i * w * h));
+      m.Fuse(D, M, Tcw + 16 * (size_t)i);
+    }
+    if (ply_path && !m.SavePLY(ply_path)) return -1;
+    if (info2) { info2[0] = m.recenters(); info2[1] = (long long)m.kept().size(); }
+    return (long long)m.AllPoints().size();
+  } catch (const std::exception& e) { std::fprintf(stderr, "host_dense_fuse: %s\n", e.what()); return -1; }
 }
 
 // one TrackStereoVideo call on host images: the current and the next pair (all four of `channels` channels), nothing else

@@ -265,6 +265,32 @@ class System:
     def save(self, path):
         self._L.host_system_save(self._h, str(path).encode())
 
+    def dense_info(self):
+        """The dense map of a system whose settings carry Dense.VoxelSize: dict(origin, recenters, kept_points, counts = (updated, masked, occluded)
+        voxels of the last frame), or None when the system has no mapper (Tracking::dense() is null)."""
+        L = self._L
+        L.host_system_dense_info.argtypes = [C.c_void_p, C.c_void_p]
+        out = np.zeros(8, np.int64)
+        if L.host_system_dense_info(self._h, _ptr(out)) != 0:
+            return None
+        return dict(origin=tuple(int(v) for v in out[:3]), recenters=int(out[3]), kept_points=int(out[4]), counts=tuple(int(v) for v in out[5:8]))
+
+    def save_dense_map(self, path):
+        """System::SaveDenseMap: the points kept so far and the surface in the volume as a binary little-endian PLY (``dense.read_ply`` reads it).
+        False without a mapper or when the file cannot be written."""
+        L = self._L
+        L.host_system_save_dense_map.argtypes = [C.c_void_p, C.c_char_p]
+        return L.host_system_save_dense_map(self._h, str(path).encode()) == 0
+
+    def last_depth_mask(self, w, h):
+        """The resident depth (metres) and mask of the last frame as the step left them - what the dense mapper fused: (depth [h, w] f32, mask [h, w] i32)"""
+        L = self._L
+        L.host_system_last_depth_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        d = np.zeros((h, w), np.float32); m = np.zeros((h, w), np.int32)
+        if L.host_system_last_depth_mask(self._h, _ptr(d), _ptr(m)) != 0:
+            raise K.VdoError("System.last_depth_mask failed")
+        return d, m
+
     def close(self):
         if self._h:
             self._L.host_system_destroy(self._h); self._h = None
