@@ -1129,6 +1129,64 @@ int vdo_dense_device_volume(vdo_dense* h, uint32_t** words);
 /* The voxels along y one thread of the integrate kernel takes: 1, 2, 4 (the default) or 8.  No result depends on it. */
 int vdo_dense_set_voxels_per_thread(vdo_dense* h, int voxels);
 
+/* ---- Raycaster: depth and normal views of the TSDF volume ---------------------------------------------------------------------------
+ * New (the reference keeps no dense map): what the dense mapper's volume predicts a camera at pose T would see - per pixel a depth, an
+ * unnormalised surface gradient and a weight, from a march along the pixel's ray through the cyclic volume with trilinear sampling.  A raycaster
+ * is a VIEW onto one vdo_dense with an image size and intrinsics of its own (a viewer window need not have the frame's size).  It BORROWS the map:
+ * the caller destroys every view before the map.  All arithmetic is fp32, one rounded operation per step in the order written, no contraction
+ * (/ and floorf correctly rounded); every sample is computed from its integer k; no result depends on workgroup shape, on the schedule or on the
+ * empty-space skipping.
+ *
+ * T is what vdo_dense_integrate takes: 4 x 4 row-major, world -> camera, last row not read; Tij below is row i, column j.
+ * Camera centre, once per call, a = 0..2:   c_a = -((T0a*T03 + T1a*T13) + T2a*T23)
+ * Ray of pixel (x, y):   dx = ((float)x - cx) / fx;  dy = ((float)y - cy) / fy;  r_a = (T0a*dx + T1a*dy) + T2a.  Its camera-z component is 1, so
+ *   the parameter lambda is z-depth, comparable with a depth image.
+ * Sample k = 0 .. n_steps-1 at lambda_k = near + (float)k * step (from the integer k, never accumulated).  Per axis:
+ *      p_a = c_a + lambda_k * r_a;   g_a = p_a / voxel - 0.5f;   b_a = floorf(g_a);   f_a = g_a - b_a
+ *   VALID iff (1) every g_a is finite and (float)o_a <= b_a && b_a <= (float)(o_a + n_a - 2), compared as floats before any conversion to int
+ *   (a NaN fails), and (2) all eight corner words - the global voxels b + {0,1}^3, each at slot (g mod n) per axis - have weight >= min_weight.
+ *   Value: with t the corners' int16 as float and lerp(u, v, f) = u + f*(v - u) (three operations): four lerps along x with f_0 (the pairs at
+ *   (y, z) = (0,0), (1,0), (0,1), (1,1)), two along y with f_1, one along z with f_2 -> F_k, in TSDF units.
+ * Hit: the first k >= 1 with samples k-1 and k both valid, F_{k-1} > 0 and F_k <= 0:
+ *      depth = lambda_{k-1} + step * (F_{k-1} / (F_{k-1} - F_k)),   lambda_{k-1} from the integer k-1.
+ *   Nothing else ends a ray: an invalid sample breaks the pair, a crossing from negative to positive is not a hit.
+ * Outputs.  depth[H][W]: the hit depth, 0.0f without a hit.  weight[H][W] (int32): the smallest of the eight corner weights of sample k, 0 without
+ *   a hit.  grad[H][W][3]: the hit point is sampled again (p_a = c_a + depth * r_a, then g, b, f as above); grad_a = S(b + e_a) - S(b - e_a), where
+ *   S(b') is the same trilinear form at the base cell b' with the SAME fractions f ((float)b_a +- 1 is exact; a base cell is compared as floats
+ *   against the same bounds).  If any of the six evaluations is invalid, or the hit point's own cell is, all three components are 0.0f.  The
+ *   gradient is in the world frame, unnormalised (no sqrt enters the parity), and points into free space.
+ * Counts.  out[0] rays that hit, out[1] rays with at least one valid sample and no hit, out[2] rays with no valid sample; they sum to W*H.
+ * NO OUT-OF-RANGE READS: every gathered address follows from the float compares alone; a skipped or invalid sample reads nothing, or reads only
+ *   inside the volume.
+ * Empty-space skipping (on by default): every render first builds an occupancy grid over bricks of 8 x 8 x 8 SLOTS - a brick's flag is set iff
+ *   any word of the brick, dilated by one slot towards +x, +y, +z cyclically, is non-zero: exactly the slots a sample with its base cell in the
+ *   brick can touch - and a sample whose base brick is clear is invalid without touching the volume (all eight weights are 0 < min_weight).  The
+ *   grid is rebuilt per call, since the volume is also writable through vdo_dense_device_volume.  NO result depends on it. */
+typedef struct vdo_raycast vdo_raycast;
+typedef struct vdo_raycast_params {
+  float K[4];                       /* fx, fy, cx, cy; fx, fy > 0, all finite */
+  float near;                       /* >= 0, finite: the z-depth of sample 0, metres */
+  float step;                       /* > 0, finite: z-depth between samples, metres */
+  int32_t n_steps;                  /* 1..65536 samples per ray ((float)k exact) */
+  int32_t min_weight;               /* 1..255 */
+} vdo_raycast_params;
+/* A width x height view of `map`.  ALL the view's device memory is taken here (staging for host outputs, 20 bytes per pixel; the counters; the
+ * occupancy grid, one byte per brick); the other entries allocate nothing.  VDO_ERR_INVALID, the message naming the argument: a null map, params
+ * or out; a size < 1; a parameter outside the range written beside it or not finite.  VDO_ERR_UNSUPPORTED for an image over 2^26 pixels or 2^24
+ * on a side.  VDO_ERR_OOM when the device has no room. */
+int vdo_raycast_create(vdo_dense* map, int width, int height, const vdo_raycast_params* params, vdo_raycast** out);
+int vdo_raycast_destroy(vdo_raycast* h);
+/* One view, host-synchronous, on the map's context stream.  T: host.  depth [H][W], grad [H][W][3], weight [H][W]: host pointers, or device
+ * pointers when out_is_device != 0; each may be NULL (it is then not produced).  out (host): the three counts.  VDO_ERR_INVALID, the message
+ * naming the argument, and then NOTHING is written: a null handle, T or out.  A non-finite T is not refused: its rays have no valid sample. */
+int vdo_raycast_render(vdo_raycast* h, const float T[16], float* depth, float* grad, int32_t* weight, int out_is_device, int64_t out[3]);
+/* Empty-space skipping on (the default) or off.  NO result depends on it. */
+int vdo_raycast_set_skip(vdo_raycast* h, int on);
+/* The last render: ms[0] wall time of the call, ms[1] device time from the first command to the end of the last kernel (events). */
+int vdo_raycast_last_timing(vdo_raycast* h, double ms[2]);
+/* The part of ms[1] the last render spent building the occupancy grid (0 with skipping off). */
+int vdo_raycast_grid_timing(vdo_raycast* h, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

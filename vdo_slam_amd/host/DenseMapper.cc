@@ -18,7 +18,52 @@ DenseMapper::DenseMapper(vdo_ctx* ctx, int width, int height, const Settings& se
   if (vdo_dense_create(ctx ? ctx : HostContext(), width, height, &s_.params, &h_) != VDO_OK) die("vdo_dense_create");
 }
 
-DenseMapper::~DenseMapper() { vdo_dense_destroy(h_); }
+DenseMapper::~DenseMapper() {
+  vdo_raycast_destroy(view_);                             // the view borrows the map
+  vdo_dense_destroy(h_);
+}
+
+void DenseMapper::ViewDefaults(Settings& s) {
+  const vdo_dense_params& p = s.params;
+  s.viewNear = p.min_depth > p.voxel ? p.min_depth : p.voxel;
+  s.viewStep = p.trunc / 2.f;
+  s.viewMinWeight = s.minWeight;
+}
+
+std::string DenseMapper::CheckView(Settings& s) {
+  const vdo_dense_params& p = s.params;
+  if (!std::isfinite(s.viewNear) || !(s.viewNear >= 0.f)) return "settings: Dense.View.Near must not be negative";
+  if (!(s.viewNear < p.max_depth)) return "settings: Dense.View.Near must be below Dense.MaxDepth";
+  if (!std::isfinite(s.viewStep) || !(s.viewStep > 0.f)) return "settings: Dense.View.Step must be positive";
+  if (s.viewMinWeight < 1 || s.viewMinWeight > 255) return "settings: Dense.View.MinWeight outside 1..255";
+  const double steps = std::ceil(((double)p.max_depth - (double)s.viewNear) / (double)s.viewStep) + 1.0;
+  if (!(steps <= 65536.0)) return "settings: Dense.View.Step: more than 65536 samples per ray between Dense.View.Near and Dense.MaxDepth";
+  s.viewSteps = (int)steps;
+  return "";
+}
+
+void DenseMapper::Render(const float Tcw[16], cv::Mat& depth, cv::Mat& normals, cv::Mat* weight, int64_t counts[3]) {
+  if (!view_) {
+    if (s_.viewSteps == 0) ViewDefaults(s_);
+    const std::string err = CheckView(s_);
+    if (!err.empty()) throw std::runtime_error("VDO_SLAM::DenseMapper: " + err);
+    const vdo_raycast_params rp{{s_.params.K[0], s_.params.K[1], s_.params.K[2], s_.params.K[3]}, s_.viewNear, s_.viewStep, s_.viewSteps, s_.viewMinWeight};
+    if (vdo_raycast_create(h_, w_, h_px_, &rp, &view_) != VDO_OK) die("vdo_raycast_create");
+    grad_.resize((size_t)w_ * h_px_ * 3);
+  }
+  depth.create(h_px_, w_, cv::CV_32FC1);
+  normals.create(h_px_, w_, cv::CV_32FC3);
+  if (weight) weight->create(h_px_, w_, cv::CV_32SC1);
+  int64_t out[3] = {0, 0, 0};
+  if (vdo_raycast_render(view_, Tcw, (float*)depth.data, grad_.data(), weight ? (int32_t*)weight->data : nullptr, 0, out) != VDO_OK) die("vdo_raycast_render");
+  float* nrm = (float*)normals.data;
+  for (size_t i = 0; i < (size_t)w_ * h_px_; ++i) {
+    const double g[3] = {(double)grad_[3 * i], (double)grad_[3 * i + 1], (double)grad_[3 * i + 2]};
+    const double len = std::sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
+    for (int k = 0; k < 3; ++k) nrm[3 * i + k] = len > 0 ? (float)(g[k] / len) : 0.f;
+  }
+  if (counts) for (int k = 0; k < 3; ++k) counts[k] = out[k];
+}
 
 void DenseMapper::origin(int32_t out[3]) const {
   if (vdo_dense_get_volume(h_, nullptr, out) != VDO_OK) die("vdo_dense_get_volume");

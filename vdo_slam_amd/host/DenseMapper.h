@@ -15,7 +15,18 @@ class DenseMapper {
   // The settings file's Dense.* keys (System.h): the volume and the fusion (params.origin is where the volume waits for the first frame), the camera
   // centre's target place in the volume as fractions of its size, the distance in voxels from that place at which the volume moves, and the smallest
   // weight of an extracted voxel
-  struct Settings { vdo_dense_params params{}; double anchor[3] = {0.5, 0.5, 0.25}; int margin = 0; int minWeight = 2; };
+  struct Settings {
+    vdo_dense_params params{}; double anchor[3] = {0.5, 0.5, 0.25}; int margin = 0; int minWeight = 2;
+    // The view Render makes (settings keys Dense.View.*): the z-depth of a ray's first sample and between samples (metres), the samples per ray and the
+    // smallest weight of a sampled voxel.  viewSteps == 0: not set yet - Render then takes ViewDefaults.
+    float viewNear = 0.f, viewStep = 0.f; int viewSteps = 0, viewMinWeight = 0;
+  };
+  // The defaults of the view from the fields above: Near max(min_depth, voxel); Step trunc / 2 - half the thickness of the valid negative band behind a
+  // surface, so that a pair of samples cannot step over that band from the fusing direction; MinWeight minWeight.
+  static void ViewDefaults(Settings& s);
+  // viewSteps = ceil((max_depth - Near) / Step) + 1 in double.  Returns the settings error ("" when in order): a non-finite value, Step <= 0, Near < 0,
+  // Near >= max_depth, MinWeight outside 1..255, more than 65536 samples.
+  static std::string CheckView(Settings& s);
   static Settings DefaultSettings(const float K[4], float voxel, float maxDepth) {
     Settings s;
     s.params = vdo_dense_params{{256, 128, 256}, voxel, {0, 0, 0}, {K[0], K[1], K[2], K[3]}, 4.f * voxel, 0.f, maxDepth, 64, 1 << 20};
@@ -42,16 +53,25 @@ class DenseMapper {
   // AllPoints() as a binary little-endian PLY: x, y, z, nx, ny, nz (float; the gradient normalised in double and narrowed, or 0) and weight (int).
   // False when the file cannot be written.
   bool SavePLY(const std::string& path);
+  // What the map predicts a camera at Tcw (16 floats, world -> camera) would see (vdo_raycast_render): depth CV_32FC1 (metres, 0 without a surface),
+  // normals CV_32FC3 (world frame, towards free space: the gradient normalised in double and narrowed, or 0, as SavePLY writes them) and, optionally,
+  // weight CV_32SC1.  The view is made on first use at the mapper's image size and K with the settings' view fields; nothing of the map changes.
+  // counts (optional): rays that hit, rays that missed, rays with no valid sample.
+  void Render(const float Tcw[16], cv::Mat& depth, cv::Mat& normals, cv::Mat* weight = nullptr, int64_t counts[3] = nullptr);
   const Points& kept() const { return kept_; }
   int recenters() const { return recenters_; }
   void origin(int32_t out[3]) const;
   vdo_dense* handle() { return h_; }
+  int width() const { return w_; }
+  int height() const { return h_px_; }
   const Settings& settings() const { return s_; }
 
  private:
   void Follow(const float Tcw[16]);
   void Append(const int32_t lo[3], const int32_t hi[3], Points& to);
   vdo_dense* h_ = nullptr;
+  vdo_raycast* view_ = nullptr;                          // made by the first Render; destroyed before the map
+  std::vector<float> grad_;                              // [h][w][3]: the gradient image of the last Render
   Settings s_;
   int w_, h_px_;
   bool started_ = false;

@@ -221,7 +221,13 @@ std::string read_dense_settings(const std::string& path, const TrackingSettings&
   if (p.max_weight < 1 || p.max_weight > 255) return "settings: Dense.MaxWeight outside 1..255";
   if (s.minWeight < 1 || s.minWeight > 255) return "settings: Dense.MinWeight outside 1..255";
   if (s.margin < 0) return "settings: Dense.RecenterMargin must not be negative";
-  return "";
+  // the view System::RenderDenseView makes: Dense.View.Near, Dense.View.Step, Dense.View.MinWeight over the defaults of DenseMapper::ViewDefaults
+  DenseMapper::ViewDefaults(s);
+  s.viewNear = (float)get(raw, "Dense.View.Near", s.viewNear); s.viewStep = (float)get(raw, "Dense.View.Step", s.viewStep);
+  const double view_w = get(raw, "Dense.View.MinWeight", s.viewMinWeight);
+  if (!whole(view_w)) return "settings: Dense.View.MinWeight must be a whole number";
+  s.viewMinWeight = (int)view_w;
+  return DenseMapper::CheckView(s);
 }
 }  // namespace
 
@@ -831,6 +837,16 @@ bool System::SaveDenseMap(const std::string& path) {
   return true;
 }
 
+bool System::RenderDenseView(const cv::Mat& Tcw, cv::Mat& depth, cv::Mat& normals) {
+  DenseMapper* d = mpTracker->dense();
+  if (!d) return false;
+  if (Tcw.rows != 4 || Tcw.cols != 4 || Tcw.type() != cv::CV_32FC1) throw std::runtime_error("VDO_SLAM::System::RenderDenseView: Tcw must be a 4 x 4 CV_32F matrix");
+  float T[16];
+  for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) T[4 * r + c] = Tcw.at<float>(r, c);
+  d->Render(T, depth, normals);
+  return true;
+}
+
 // The Map (reference format) is materialised from the pipeline's flat store when somebody looks at it.
 Map* System::map() { mpTracker->pipeline()->SyncMap(); return mpMap; }
 
@@ -1047,6 +1063,36 @@ int host_settings_check_dense(const char* path, char* msg, int cap, double* out1
     }
   }
   return err.empty() ? 0 : 1;
+}
+// the Dense.View.* keys as Tracking::Tracking reads them, without a GPU: 0 in order, 1 a settings error (text in msg), -2 no file.  out5 (may be null):
+// present (0 / 1: Dense.VoxelSize is in the file; the rest only then), Near, Step, MinWeight, the samples per ray
+int host_settings_check_dense_view(const char* path, char* msg, int cap, double* out5) {
+  VDO_SLAM::TrackingSettings t{};
+  std::map<std::string, double> raw;
+  if (!VDO_SLAM::read_tracking_settings(path, t, &raw)) return -2;
+  VDO_SLAM::DenseSettings ds;
+  const std::string err = VDO_SLAM::read_dense_settings(path, t, raw, ds);
+  if (msg && cap > 0) std::snprintf(msg, (size_t)cap, "%s", err.c_str());
+  if (out5 && err.empty()) {
+    out5[0] = ds.present ? 1 : 0;
+    if (ds.present) { out5[1] = ds.s.viewNear; out5[2] = ds.s.viewStep; out5[3] = ds.s.viewMinWeight; out5[4] = ds.s.viewSteps; }
+  }
+  return err.empty() ? 0 : 1;
+}
+// System::RenderDenseView: Tcw [16] world -> camera; depth [Camera.height][Camera.width], normals [Camera.height][Camera.width][3]; wh2 (may be null)
+// receives Camera.width and Camera.height, and with depth null nothing else happens.  0, 1 without a mapper (nothing is written), -1 on a failure
+int host_system_render_dense_view(VDO_SLAM::System* s, const float* Tcw, int* wh2, float* depth, float* normals) {
+  try {
+    VDO_SLAM::DenseMapper* d = s->tracker()->dense();
+    if (!d) return 1;
+    if (wh2) { wh2[0] = d->width(); wh2[1] = d->height(); }
+    if (!depth) return 0;
+    cv::Mat T(4, 4, cv::CV_32FC1, (void*)Tcw), D, N;
+    if (!s->RenderDenseView(T, D, N)) return 1;
+    std::memcpy(depth, D.data, D.total() * sizeof(float));
+    std::memcpy(normals, N.data, N.total() * 3 * sizeof(float));
+  } catch (const std::exception& e) { std::fprintf(stderr, "host_system_render_dense_view: %s\n", e.what()); return -1; }
+  return 0;
 }
 // the dense map of a System with Dense.* keys.  info8: the origin (3), the recentrings so far, the points kept on the host, and the updated, masked
 // and occluded voxels of the last frame.  0, or -1 without a mapper.

@@ -196,6 +196,13 @@ class System {
   // not re-fused after a bundle adjustment; an edge between a leaving and a staying voxel can be lost when the volume moves towards a negative axis;
   // objects are not reconstructed; with semantic masks on the RGBD path parked instances are left out too.
   bool SaveDenseMap(const std::string& path);
+  // What the dense map predicts a camera at Tcw (4 x 4 CV_32F, world -> camera) would see (DenseMapper::Render, vdo_raycast_render): depth CV_32FC1 in
+  // metres, 0 where no surface is met, and normals CV_32FC3 in the world frame, towards free space, 0 where the surface has an unseen neighbour - at the
+  // camera's image size and K.  Settings keys, all optional and read only with Dense.VoxelSize: Dense.View.Near (max(Dense.MinDepth, Dense.VoxelSize)),
+  // the z-depth of a ray's first sample; Dense.View.Step (Dense.Truncation / 2), the z-depth between samples; Dense.View.MinWeight (Dense.MinWeight);
+  // a ray has ceil((Dense.MaxDepth - Near) / Step) + 1 samples, at most 65536.  A non-finite value, Step <= 0, Near < 0, Near >= Dense.MaxDepth or too
+  // many samples is a settings error.  False without a mapper; nothing of the map or of the tracker changes.
+  bool RenderDenseView(const cv::Mat& Tcw, cv::Mat& depth, cv::Mat& normals);
   void SaveResults(const std::string& filename);
   Map* map();                          // brought up to date from the pipeline's GraphStore on access
   Tracking* tracker() { return mpTracker; }

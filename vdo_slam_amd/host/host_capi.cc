@@ -401,6 +401,35 @@ long long host_dense_fuse(const float* depth, const int* mask, const float* Tcw,
   } catch (const std::exception& e) { std::fprintf(stderr, "host_dense_fuse: %s\n", e.what()); return -1; }
 }
 
+// host_dense_fuse's frames, then DenseMapper::Render at T_view (16 floats, world -> camera): depth [h][w], normals [h][w][3], weight [h][w] (may be
+// null), counts3 (may be null).  view3 (may be null: DenseMapper::ViewDefaults): Near, Step, MinWeight.  0, -1 on a failure.
+int host_dense_render(const float* depth, const int* mask, const float* Tcw, int k, int w, int h, const vdo_dense_params* params, const double* anchor3, int margin, int min_weight,
+                      const double* view3, const float* T_view, float* out_depth, float* out_normals, int* out_weight, long long* counts3) {
+  try {
+    DenseMapper::Settings s;
+    s.params = *params; s.margin = margin; s.minWeight = min_weight;
+    for (int a = 0; a < 3; ++a) s.anchor[a] = anchor3[a];
+    DenseMapper::ViewDefaults(s);
+    if (view3) { s.viewNear = (float)view3[0]; s.viewStep = (float)view3[1]; s.viewMinWeight = (int)view3[2]; }
+    const std::string err = DenseMapper::CheckView(s);
+    if (!err.empty()) { std::fprintf(stderr, "host_dense_render: %s\n", err.c_str()); return -1; }
+    DenseMapper m(nullptr, w, h, s);
+    for (int i = 0; i < k; ++i) {
+      cv::Mat D(h, w, cv::CV_32FC1, (void*)(depth + (size_t)i * w * h)), M;
+      if (mask) M = cv::Mat(h, w, cv::CV_32SC1, (void*)(mask + (size_t)i * w * h));
+      m.Fuse(D, M, Tcw + 16 * (size_t)i);
+    }
+    cv::Mat rd, rn, rw;
+    int64_t counts[3];
+    m.Render(T_view, rd, rn, out_weight ? &rw : nullptr, counts);
+    std::memcpy(out_depth, rd.data, (size_t)w * h * sizeof(float));
+    std::memcpy(out_normals, rn.data, (size_t)w * h * 3 * sizeof(float));
+    if (out_weight) std::memcpy(out_weight, rw.data, (size_t)w * h * sizeof(int));
+    if (counts3) for (int a = 0; a < 3; ++a) counts3[a] = counts[a];
+    return 0;
+  } catch (const std::exception& e) { std::fprintf(stderr, "host_dense_render: %s\n", e.what()); return -1; }
+}
+
 // one TrackStereoVideo call on host images: the current and the next pair (all four of `channels` channels), nothing else
 int host_system_track_stereo_video(System* s, const unsigned char* left, const unsigned char* right, const unsigned char* left_next, const unsigned char* right_next, int channels,
                                    int w, int h, const float* obj_rows, int n_rows, int row_len, int n_images, float* Tcw_out) {

@@ -16,7 +16,8 @@ enum { CV_8U = 0, CV_32S = 4, CV_32F = 5 };
 #define VDO_CV_MAKETYPE(depth, cn) ((depth) + (((cn) - 1) << 3))
 enum {
   CV_8UC1 = VDO_CV_MAKETYPE(CV_8U, 1), CV_8UC3 = VDO_CV_MAKETYPE(CV_8U, 3), CV_8UC4 = VDO_CV_MAKETYPE(CV_8U, 4),
-  CV_32SC1 = VDO_CV_MAKETYPE(CV_32S, 1), CV_32FC1 = VDO_CV_MAKETYPE(CV_32F, 1), CV_32FC2 = VDO_CV_MAKETYPE(CV_32F, 2)
+  CV_32SC1 = VDO_CV_MAKETYPE(CV_32S, 1), CV_32FC1 = VDO_CV_MAKETYPE(CV_32F, 1), CV_32FC2 = VDO_CV_MAKETYPE(CV_32F, 2),
+  CV_32FC3 = VDO_CV_MAKETYPE(CV_32F, 3)
 };
 
 struct Point2f { float x = 0, y = 0; Point2f() {} Point2f(float x_, float y_) : x(x_), y(y_) {} };

@@ -282,6 +282,21 @@ class System:
         L.host_system_save_dense_map.argtypes = [C.c_void_p, C.c_char_p]
         return L.host_system_save_dense_map(self._h, str(path).encode()) == 0
 
+    def render_dense_view(self, T):
+        """System::RenderDenseView: what the dense map predicts a camera at T (4 x 4, world -> camera) would see, at the camera's image size:
+        (depth [h, w] f32 in metres, normals [h, w, 3] f32), or None when the system has no mapper."""
+        L = self._L
+        L.host_system_render_dense_view.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        Tc = np.ascontiguousarray(np.asarray(T, np.float32).reshape(16))
+        wh = np.zeros(2, np.int32)
+        if L.host_system_render_dense_view(self._h, _ptr(Tc), _ptr(wh), None, None) == 1:
+            return None
+        d = np.zeros((int(wh[1]), int(wh[0])), np.float32); n = np.zeros((int(wh[1]), int(wh[0]), 3), np.float32)
+        rc = L.host_system_render_dense_view(self._h, _ptr(Tc), _ptr(wh), _ptr(d), _ptr(n))
+        if rc != 0:
+            raise K.VdoError("System.render_dense_view failed")
+        return d, n
+
     def last_depth_mask(self, w, h):
         """The resident depth (metres) and mask of the last frame as the step left them - what the dense mapper fused: (depth [h, w] f32, mask [h, w] i32)"""
         L = self._L
