@@ -1187,6 +1187,109 @@ int vdo_raycast_last_timing(vdo_raycast* h, double ms[2]);
 /* The part of ms[1] the last render spent building the occupancy grid (0 with skipping off). */
 int vdo_raycast_grid_timing(vdo_raycast* h, double* ms);
 
+/* ---- Aligner: point-to-plane ICP of a depth frame against a view of the map ---------------------------------------------------------
+ * New (the reference has no dense pose estimator): projective data association of a measured depth frame against a MODEL - a depth and a gradient
+ * image exactly as vdo_raycast_render writes them, with the pose Tm and the intrinsics Km they were rendered at -, point-to-plane residuals, their
+ * normal equations summed over the image, and a Gauss-Newton refinement of the frame's pose.  All per-sample arithmetic is fp32, one rounded
+ * operation per step in the order written, no contraction (/ and floorf correctly rounded); every gathered address is bounded by float compares
+ * made before any conversion to int (a NaN fails them); the sums are in double in ONE fixed tree.  No result depends on workgroup shape, on the
+ * launch shape or on the schedule; two runs give the same bits.
+ *
+ * Inputs.  depth D[H][W] fp32 metres; mask[H][W] int32 or NULL (a non-zero value skips the pixel, as the mapper does); K = (fx, fy, cx, cy);
+ *   T, the current estimate: 4 x 4 row-major, world -> camera, last row not read, Tab below is row a, column b.  The model: Dm[Hm][Wm],
+ *   Gm[Hm][Wm][3], Tm (as T), Km = (fxm, fym, cxm, cym); its size and intrinsics may differ from the frame's.
+ * Samples.  subsample s (1..8): Ws = ceil(W/s), Hs = ceil(H/s); sample (i, j) is pixel (x, y) = (i*s, j*s).
+ * Per sample:
+ *      d = D(y,x);                 skip[no depth] unless d finite, d > max(min_depth, 0) and d <= max_depth
+ *                                  skip[masked] if mask != NULL and mask(y,x) != 0
+ *      dx = ((float)x - cx)/fx;  dy = ((float)y - cy)/fy;  Pc = (dx*d, dy*d, d)
+ *      q_a = Pc_a - Ta3;           Pw_a = (T0a*q0 + T1a*q1) + T2a*q2                                      (a = 0..2)
+ *      Xm = (Tm00*Pw0 + Tm01*Pw1) + (Tm02*Pw2 + Tm03);  Ym, Zm likewise with rows 1, 2 (the association of vdo_dense_integrate)
+ *                                  skip[no model] unless Zm finite and Zm > FLT_MIN
+ *      u = (fxm*Xm)/Zm + cxm;  v = (fym*Ym)/Zm + cym;  xq = floorf(u + 0.5f);  yq = floorf(v + 0.5f)
+ *                                  skip[no model] unless u, v finite, 0 <= xq <= (float)(Wm-1), 0 <= yq <= (float)(Hm-1)
+ *      dm = Dm(yq,xq);  g = Gm(yq,xq);  gg = (g0*g0 + g1*g1) + g2*g2
+ *                                  skip[no model] unless dm finite and dm > 0, and gg finite and gg > 0
+ *      the model point by the raycaster's own formulas: the camera centre c of Tm (once per call), the ray r of pixel (xq, yq) with Km,
+ *      Vm_a = c_a + dm*r_a;        del_a = Pw_a - Vm_a;  dist2 = (del0*del0 + del1*del1) + del2*del2
+ *                                  skip[far] unless dist2 <= max_dist*max_dist   (the product once, in fp32)
+ *      e = (g0*del0 + g1*del1) + g2*del2;   w = 1.0f / gg          (no sqrt: w*e*e = (g.del)^2 / (g.g) is the squared point-to-plane distance)
+ *      gc_a = (Ta0*g0 + Ta1*g1) + Ta2*g2                           (the gradient in the camera frame)
+ *      J = (gc0, gc1, gc2,  Pc1*gc2 - Pc2*gc1,  Pc2*gc0 - Pc0*gc2,  Pc0*gc1 - Pc1*gc0);   h_i = w*J_i;   we = w*e
+ *   The twist is taken about the camera, not the world origin: the system stays well conditioned hundreds of metres into a sequence.
+ * Terms, in double and exact (each is a product of two floats), 28 per sample: the 21 upper-triangle A_ij = (double)h_i * (double)J_j, i <= j,
+ *   row-major (A00 A01 .. A05 A11 .. A55); the 6 b_i = (double)h_i * (double)e; chi2 = (double)we * (double)e.  A skipped sample contributes +0.0.
+ * The sum.  The sample grid is cut into 8 x 8 tiles, tiles_x = ceil(Ws/8), tiles_y = ceil(Hs/8); sample (i, j) has slot
+ *   ((j/8)*tiles_x + i/8)*64 + (j%8)*8 + (i%8); slots with no sample hold +0.0; the slot vector is padded with +0.0 to the next power of two.
+ *   Each of the 28 sums is the adjacent-pair tree over that vector in double, v[k] = v[2k] + v[2k+1], level by level, down to one value.  (On the
+ *   device a wave's xor-butterfly over its tile is the first six levels, a tree over the tile partials the rest.)  No float atomics.
+ * Counts, int64: used, no depth, masked, no model, far; they add up to Ws*Hs.
+ * Step (vdo_align_step, pure host code, no device or context).  The symmetric A is rebuilt from the 21 sums and A xi = -b is solved by a Cholesky
+ *   factorisation in double (lower, column by column, pivot p_j = A_jj - sum_k L_jk^2; no threshold: a rank-deficient system whose rounding leaves a
+ *   tiny positive pivot is stepped, and its step is as large as that pivot is small - min_pixels, max_dist and the caller's own look at xi and the rms
+ *   are the guards).  T' = Exp(-xi) * T in double,
+ *   xi = (v, omega), Exp the SE(3) exponential: theta = |omega|, R = I + A[w]x + B[w]x^2, t = (I + B[w]x + C[w]x^2) v with A = sin(theta)/theta,
+ *   B = (1 - cos(theta))/theta^2, C = (theta - sin(theta))/theta^3, and below theta = 1e-4 the series A = 1 - theta^2/6, B = 1/2 - theta^2/24,
+ *   C = 1/6 - theta^2/120; T' is rounded to float, its last row (0, 0, 0, 1).  Status 0: stepped.  1: used < min_pixels.  2: a pivot was not
+ *   positive, or a sum, xi or T' was not finite.  On 1 and 2 T' = T bit for bit and xi = 0.  rms = sqrt(chi2 / used), 0 when used is 0. */
+typedef struct vdo_align vdo_align;
+typedef struct vdo_align_params {
+  float K[4];                       /* fx, fy, cx, cy of the frame; fx, fy > 0, all finite */
+  float min_depth, max_depth;       /* 0 <= min_depth < max_depth, finite, metres */
+  float max_dist;                   /* > 0, finite, metres: the gate on the distance between a point and its model point */
+  int32_t subsample;                /* 1..8 */
+  int32_t min_pixels;               /* >= 6 */
+  int32_t max_iterations;           /* 1..64 */
+  float eps;                        /* >= 0, finite: a solve stops when every component of xi is at most eps in magnitude */
+  int32_t keep_rows;                /* 0 / 1: keep the row image of the last linearisation (vdo_align_get_rows) */
+} vdo_align_params;
+typedef struct vdo_align_report {
+  int32_t iterations;               /* linearisations done */
+  int32_t status;                   /* of the last step: 0, 1, 2 */
+  int64_t used;                     /* samples used at the last linearisation */
+  double rms_first, rms_last;       /* the RMS point-to-plane distance before the first step and at the last linearisation, metres */
+  double xi[6];                     /* of the last step (0 unless its status is 0) */
+} vdo_align_report;
+/* An aligner for width x height depth and mask images.  ALL device memory is taken here (staging for a host or strided depth and mask, 8 bytes per
+ * pixel; the tile partials, 256 bytes per 8 x 8 sample tile, and the levels above them; the model images the handle owns, 16 bytes per pixel of
+ * the FRAME's size - a host model or a view with more pixels than the frame is refused, a borrowed device model may have any size; with keep_rows
+ * the row image, 32 bytes per sample); the other entries allocate nothing.  VDO_ERR_INVALID, the message naming the argument: a null ctx, params
+ * or out; a size < 1; a parameter outside the range written beside it or not finite.  VDO_ERR_UNSUPPORTED for an image over 2^26 pixels or 2^24
+ * on a side.  VDO_ERR_OOM when the device has no room. */
+int vdo_align_create(vdo_ctx* ctx, int width, int height, const vdo_align_params* params, vdo_align** out);
+int vdo_align_destroy(vdo_align* h);
+/* The model.  depth [Hm][Wm], grad [Hm][Wm][3] (packed), Km and Tm host.  is_device == 0: host images, copied into the handle's model images
+ * (VDO_ERR_UNSUPPORTED when Wm * Hm exceeds width * height).  is_device != 0: packed device images, BORROWED - the caller keeps them alive and
+ * unchanged until the next set_model.  VDO_ERR_INVALID, the message naming the argument, and then nothing changes: a null pointer, a size < 1,
+ * a Km that is not finite or has fxm, fym <= 0.  A non-finite Tm is not refused: every sample is then skipped. */
+int vdo_align_set_model(vdo_align* h, const float* depth, const float* grad, int model_width, int model_height, const float Km[4], const float Tm[16], int is_device);
+/* Renders `view` at Tm (vdo_raycast_render) straight into the handle's device model images, no host round trip, and takes the view's size and K as
+ * the model's.  counts (host, may be NULL): the render's three counts.  The render is host-synchronous on the view's own context, which may differ from
+ * the aligner's on the same device.  VDO_ERR_INVALID for a view on another device, VDO_ERR_UNSUPPORTED when the view has more pixels than the frame. */
+int vdo_align_set_model_from_view(vdo_align* h, vdo_raycast* view, const float Tm[16], int64_t counts[3]);
+/* One linearisation at T, host-synchronous on the context's stream.  depth, mask, strides and src_is_device as vdo_dense_integrate takes them.
+ * sums (host): the 28 sums in the order of the contract.  counts (host): used, no depth, masked, no model, far.  VDO_ERR_INVALID, the message
+ * naming the argument, and then NOTHING is written: a null handle, depth, T, sums or counts; a stride too small; no model set.  A non-finite T is
+ * not refused: every sample is then skipped. */
+int vdo_align_linearise(vdo_align* h, const float* depth, int64_t depth_stride_floats, const int32_t* mask, int64_t mask_stride_ints, int src_is_device, const float T[16],
+                        double sums[28], int64_t counts[5]);
+/* The same from the resident depth (after K1: metres) and mask of a vdo_frame_images of the aligner's size, read where they lie and not written. */
+int vdo_align_linearise_frame(vdo_align* h, const vdo_frame_images* frame, const float T[16], double sums[28], int64_t counts[5]);
+/* The host step of the contract.  Returns the status 0, 1 or 2, or VDO_ERR_INVALID for a null sums, T or T_out.  xi (6) and rms may be NULL. */
+int vdo_align_step(const double sums[28], int64_t used, int64_t min_pixels, const float T[16], float T_out[16], double xi[6], double* rms);
+/* Up to max_iterations rounds of linearise + step from T_init; the model stays fixed.  It stops after a step whose status is not 0 (T_out is then
+ * the T of that linearisation) or whose xi is at most eps in every component.  report (host, may be NULL).  trace (host, may be NULL):
+ * [max_iterations][16 + 28 + 5] doubles, per linearisation done the T it used, its sums and its counts; later rows are not written.  Refusals as
+ * vdo_align_linearise, and a null T_init or T_out. */
+int vdo_align_solve(vdo_align* h, const float* depth, int64_t depth_stride_floats, const int32_t* mask, int64_t mask_stride_ints, int src_is_device, const float T_init[16],
+                    float T_out[16], vdo_align_report* report, double* trace);
+int vdo_align_solve_frame(vdo_align* h, const vdo_frame_images* frame, const float T_init[16], float T_out[16], vdo_align_report* report, double* trace);
+/* With keep_rows: rows (host) [Hs][Ws][8] floats of the last linearisation - J (6), e, w, all 0 where the sample was skipped.  Storing them changes
+ * no sum.  VDO_ERR_INVALID without keep_rows, before the first linearisation, or for a null pointer. */
+int vdo_align_get_rows(vdo_align* h, float* rows);
+/* The last linearise or solve: ms[0] wall time of the call, ms[1] device time of its linearisations, first command to last kernel (events). */
+int vdo_align_last_timing(vdo_align* h, double ms[2]);
+
 #ifdef __cplusplus
 }
 #endif

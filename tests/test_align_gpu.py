@@ -1,0 +1,471 @@
+"""GPU: the device aligner (vdo_align_*, csrc/align.hip) against the NumPy restatement of its contract (tests/align_ref.py).  Sums are compared as
+uint64 views, counts with array_equal, rows as uint32 views; a solve is walked through its trace."""
+import ctypes as C
+import gc
+
+import numpy as np
+import pytest
+
+from tests import align_ref as A
+from tests.test_align_ref import _ulps, check_corner
+
+pytestmark = pytest.mark.gpu
+
+F = np.float32
+VOXEL = 0.1
+PRM = dict(min_depth=0.3, max_depth=7.0, max_dist=0.35)
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    from vdo_slam_amd.ba import Context
+    c = Context(0)
+    yield c
+    gc.collect()                                        # whatever a raised error's traceback kept alive is destroyed while its context exists
+    c.close()
+
+
+def _dense_words(n, seed, p_light=0.05):
+    """Random well-formed words: crossings everywhere, weights 1 (a few) .. 5 straddling min_weight 2"""
+    rng = np.random.default_rng(seed)
+    shape = tuple(n)[::-1]
+    t = rng.integers(-32767, 32768, shape)
+    w = np.where(rng.random(shape) < p_light, 1, rng.integers(2, 6, shape))
+    return ((w << 16) | (t & 0xFFFF)).astype(np.uint32)
+
+
+class Model:
+    """A mapper, a view of it and the view's render at Tm on the host: the model of both sides"""
+
+    def __init__(self, ctx, n, o, Wm, Hm, Km, Tm, near, step, n_steps, words=None, fuse=None):
+        from vdo_slam_amd.dense import DenseMapper
+        from vdo_slam_amd.raycast import Raycaster
+        self.m = DenseMapper(ctx, Wm, Hm, n, VOXEL, Km, origin=o, stage_points=4096, trunc=0.4, max_depth=10.0)
+        if words is not None:
+            self.m.set_volume(words)
+        for depth, T in fuse or []:
+            self.m.integrate(depth, None, T)
+        self.view = Raycaster(self.m, Wm, Hm, Km, near, step, n_steps, 2)
+        self.Wm, self.Hm, self.Km, self.Tm = Wm, Hm, Km, np.asarray(Tm, F)
+        self.Dm, self.Gm, _, self.counts = self.view.render(self.Tm)
+
+    def close(self):
+        self.view.close(); self.m.close()
+
+
+@pytest.fixture(scope="module")
+def random_model(ctx):
+    """A view of a random volume: hits, holes and misses, a gradient of every direction and length"""
+    n, o = (24, 16, 20), (-12, -8, 4)
+    Km = (44.0, 40.0, 19.7, 12.1)
+    Tm = A.perturbed(np.eye(4), (0.02, -0.01, 0.8), (1.0, -2.0, 0.5))
+    M = Model(ctx, n, o, 40, 24, Km, Tm, 0.5, 0.07, 60, words=_dense_words(n, 17))
+    assert M.counts[0] > 300 and M.counts[0] < 40 * 24 and (np.abs(M.Gm).sum(-1) > 0).sum() > 200
+    yield M
+    M.close()
+
+
+@pytest.fixture(scope="module")
+def plane_model(ctx):
+    """Two fused planes that meet in the view"""
+    Wm, Hm, Km = 48, 32, (40.0, 40.0, 23.5, 15.5)
+    planes = [((0.0, 0.0, 1.0), 5.0), ((0.6, 0.0, 0.8), 4.6)]
+    I4 = np.eye(4, dtype=F)
+    fuse = [(A.plane_depth(planes, I4, Wm, Hm, Km), I4)] * 3
+    M = Model(ctx, (64, 48, 40), (-32, -24, 30), Wm, Hm, Km, A.perturbed(I4, (0.1, 0.0, 0.0), (0.0, 3.0, 0.0)), 3.0, 0.2, 25, fuse=fuse)
+    M.planes = planes
+    assert M.counts[0] > 1000
+    yield M
+    M.close()
+
+
+def _frame_for(M, W, H, seed, noise=0.02):
+    """A W x H frame looking where the model looks: K scaled from Km, depth the model's at the matching pixel plus noise, a pose near Tm"""
+    rng = np.random.default_rng(seed)
+    sx, sy = W / M.Wm, H / M.Hm
+    K4 = (M.Km[0] * sx, M.Km[1] * sy, (M.Km[2] + 0.5) * sx - 0.5, (M.Km[3] + 0.5) * sy - 0.5)
+    ys = np.minimum((np.arange(H) + 0.5) / sy, M.Hm - 1).astype(int); xs = np.minimum((np.arange(W) + 0.5) / sx, M.Wm - 1).astype(int)
+    D = (M.Dm[ys][:, xs] * (1.0 + rng.normal(0, noise, (H, W)))).astype(F)
+    mask = (rng.random((H, W)) < 0.08).astype(np.int32) * 5
+    T = A.perturbed(M.Tm, (0.01, -0.005, 0.008), (0.2, -0.3, 0.1))
+    return D, mask, K4, T
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint64 if a.dtype == np.float64 else np.uint32)
+
+
+def _same(got, want, what):
+    assert np.array_equal(got[1], want[1]), f"{what}: counts {got[1].tolist()} against {want[1].tolist()}"
+    assert np.array_equal(_bits(got[0]), _bits(want[0])), f"{what}: sums differ at {np.nonzero(_bits(got[0]) != _bits(want[0]))[0].tolist()}: {got[0]} against {want[0]}"
+
+
+class FrameImages:
+    """The resident images of a frame (vdo_frame_images_*), called with typed pointers and no argtypes of its own, so that this module declares nothing
+    another test's calls into the library could trip over"""
+
+    def __init__(self, ctx, width, height):
+        from vdo_slam_amd import align as AL
+        self._L, self.w, self.h = AL._lib(), width, height
+        self._h = C.c_void_p()
+        assert self._L.vdo_frame_images_create(ctx._h, C.c_int(width), C.c_int(height), C.byref(self._h)) == 0
+
+    def upload(self, depth, flow, mask):
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        d = np.ascontiguousarray(depth, F); f = np.ascontiguousarray(flow, F); m = np.ascontiguousarray(mask, np.int32)
+        assert self._L.vdo_frame_images_upload(self._h, d.ctypes.data_as(fp), f.ctypes.data_as(fp), m.ctypes.data_as(ip)) == 0
+
+    def download_depth(self):
+        out = np.zeros((self.h, self.w), F)
+        assert self._L.vdo_frame_images_download_depth(self._h, out.ctypes.data_as(C.POINTER(C.c_float))) == 0
+        return out
+
+    def close(self):
+        if self._h:
+            self._L.vdo_frame_images_destroy(self._h); self._h = C.c_void_p()
+
+    def __del__(self):
+        self.close()
+
+
+def _aligner(ctx, W, H, K4, **kw):
+    from vdo_slam_amd.align import Aligner
+    prm = dict(PRM); prm.update(kw)
+    return Aligner(ctx, W, H, K4, **prm)
+
+
+# ---- shapes --------------------------------------------------------------------------------------------------------------------------------------
+# frames at the tile edges; tiles = ceil(Ws/8) * ceil(Hs/8): 1, 2, 4 (powers of two) and 3, 5, 21 (not), one level of the tree kernel and two (375 tiles)
+SHAPES = [(1, 1, 1), (7, 9, 1), (8, 8, 1), (9, 8, 1), (16, 16, 1), (40, 8, 1), (56, 24, 1), (200, 120, 1)] + [(w, h, s) for w, h in ((17, 65), (96, 48)) for s in (1, 2, 3)] + \
+         [(9, 8, 2), (8, 8, 3), (24, 8, 1)]
+
+
+def test_the_shapes_cover_the_tile_counts():
+    tiles = {(-(-(-(-w // s)) // 8)) * (-(-(-(-h // s)) // 8)) for w, h, s in SHAPES}
+    assert {1, 2, 4, 3, 5, 21, 375} <= tiles, tiles
+
+
+@pytest.mark.parametrize("W,H,s", SHAPES, ids=lambda v: str(v))
+def test_shapes_against_a_model_of_another_size(ctx, random_model, W, H, s):
+    M = random_model
+    D, mask, K4, T = _frame_for(M, W, H, 100 * W + H + s)
+    want = A.linearise(D, mask, K4, T, M.Dm, M.Gm, M.Km, M.Tm, subsample=s, **PRM)
+    al = _aligner(ctx, W, H, K4, subsample=s, keep_rows=True)
+    _set_any(al, M)
+    got = al.linearise(D, mask, T)
+    _same(got, want, f"{W}x{H} / {s}")
+    assert np.array_equal(_bits(al.rows()), _bits(want[2])), "rows"
+    if W * H >= 96 * 48:
+        assert want[1][0] > 50 and (want[1][1:] > 0).all(), want[1]              # every class occurs (96 x 48 / 3 has 512 samples)
+    _same(al.linearise(D, mask, T), want, "again")                              # two runs, the same bits
+    al.close()
+
+
+def test_more_than_65536_tiles_take_a_third_tree_launch(ctx):
+    """A frame of ONE row, 524 289 pixels wide: 65 537 tiles of at most eight samples each, the fewest samples that pad to 2^17 nodes - 512 workgroups
+    of the tree kernel, then 2, then 1: the only size at which the third launch and its buffer turn can go wrong.  The restatement is taken for three
+    of the 28 sums (the first, one in the middle, the last: the tree kernel treats the 32 values alike, a value is a thread coordinate; all 28 over 2^23
+    slots would take 2 GiB) and for the counts.  The model is a host image without holes, so that every part of the row has used samples."""
+    from types import SimpleNamespace
+    rng = np.random.default_rng(23)
+    M = SimpleNamespace(Wm=40, Hm=24, Km=(44.0, 40.0, 19.7, 12.1), Tm=A.perturbed(np.eye(4), (0.02, -0.01, 0.8), (1.0, -2.0, 0.5)),
+                        Dm=rng.uniform(1.0, 3.0, (24, 40)).astype(F), Gm=rng.normal(0, 1000, (24, 40, 3)).astype(F))
+    W, H = 8 * 65536 + 1, 1
+    D, _, K4, T = _frame_for(M, W, H, 7)
+    rw, cls = A.rows(D, None, K4, T, M.Dm, M.Gm, M.Km, M.Tm, **PRM)
+    used = cls[0] == A.USED
+    assert used[:W // 4].any() and used[W // 4:W // 2].any() and used[W // 2:3 * W // 4].any() and used[3 * W // 4:].any()      # both workgroups of the second launch carry sums
+    al = _aligner(ctx, W, H, K4)
+    al.set_model(M.Dm, M.Gm, M.Km, M.Tm)
+    sums, counts = al.linearise(D, None, T)
+    al.close()
+    assert counts.tolist() == [int((cls == k).sum()) for k in range(5)]
+    for k in (0, 13, 27):
+        want = A.pair_tree(A.slot_vector(A.term(rw, k)[..., None]))[0]
+        assert sums[k].view(np.uint64) == want.view(np.uint64), (k, sums[k], want)
+
+
+def _set_any(al, M):
+    """A host model where the handle's own images can hold it, else borrowed device images"""
+    import torch
+    if al.width * al.height >= M.Wm * M.Hm:
+        al.set_model(M.Dm, M.Gm, M.Km, M.Tm)
+    else:
+        d = torch.from_numpy(M.Dm.copy()).cuda(); g = torch.from_numpy(M.Gm.copy()).cuda()
+        torch.cuda.synchronize()
+        al.set_model_device(d.data_ptr(), g.data_ptr(), M.Wm, M.Hm, M.Km, M.Tm, keep=(d, g))
+
+
+# ---- inputs and models -----------------------------------------------------------------------------------------------------------------------------
+def test_host_strided_device_and_frame_inputs_borrowed_copied_and_rendered_models(ctx, plane_model):
+    import torch
+    M = plane_model
+    W, H = 61, 37
+    D, mask, K4, T = _frame_for(M, W, H, 3, noise=0.004)
+    want = A.linearise(D, mask, K4, T, M.Dm, M.Gm, M.Km, M.Tm, **PRM)
+    want_nomask = A.linearise(D, None, K4, T, M.Dm, M.Gm, M.Km, M.Tm, **PRM)
+    assert want[1][0] > 500 and want[1][2] > 50
+    al = _aligner(ctx, W, H, K4)
+    al.set_model(M.Dm, M.Gm, M.Km, M.Tm)
+    _same(al.linearise(D, mask, T), want, "host")
+    _same(al.linearise(D, None, T), want_nomask, "host, no mask")
+    wide_d = np.full((H, W + 5), np.nan, F); wide_d[:, :W] = D
+    wide_m = np.full((H, W + 3), 9, np.int32); wide_m[:, :W] = mask
+    _same(al.linearise(wide_d[:, :W], wide_m[:, :W], T), want, "strided host")
+    dd = torch.from_numpy(D.copy()).cuda(); dm = torch.from_numpy(mask.copy()).cuda()
+    dwide = torch.from_numpy(wide_d.copy()).cuda()
+    torch.cuda.synchronize()
+    _same(al.linearise_raw(dd.data_ptr(), W, dm.data_ptr(), W, True, T), want, "packed device")
+    _same(al.linearise_raw(dwide.data_ptr(), W + 5, dm.data_ptr(), W, True, T), want, "strided device")
+    fi = FrameImages(ctx, W, H)
+    fi.upload(D, np.zeros((H, W, 2), F), mask)
+    _same(al.linearise_frame(fi._h, T), want, "frame images")
+    assert np.array_equal(_bits(fi.download_depth()), _bits(D))                 # read-only on them
+    # the model borrowed on the device, and rendered by the view straight into the handle
+    gd = torch.from_numpy(M.Dm.copy()).cuda(); gg = torch.from_numpy(M.Gm.copy()).cuda()
+    torch.cuda.synchronize()
+    al.set_model_device(gd.data_ptr(), gg.data_ptr(), M.Wm, M.Hm, M.Km, M.Tm, keep=(gd, gg))
+    _same(al.linearise(D, mask, T), want, "borrowed model")
+    assert tuple(al.set_model_from_view(M.view, M.Tm)) == tuple(M.counts)
+    _same(al.linearise(D, mask, T), want, "model from the view")
+    # another pose of the view: against a render followed by set_model
+    Tm2 = A.perturbed(M.Tm, (-0.05, 0.02, 0.0), (0.0, -1.0, 0.4))
+    Dm2, Gm2, _, c2 = M.view.render(Tm2)
+    assert tuple(al.set_model_from_view(M.view, Tm2)) == tuple(c2)
+    via_view = al.linearise(D, mask, T)
+    al.set_model(Dm2, Gm2, M.Km, Tm2)
+    _same(via_view, al.linearise(D, mask, T), "from the view against render + set_model")
+    _same(via_view, A.linearise(D, mask, K4, T, Dm2, Gm2, M.Km, Tm2, **PRM), "from the view against the restatement")
+    wall, dev = al.timing()
+    assert wall > 0 and dev >= 0
+    al.close()
+
+
+# ---- skips, each through its count -----------------------------------------------------------------------------------------------------------------------
+def test_skips(ctx, plane_model):
+    M = plane_model
+    W, H = M.Wm, M.Hm
+    I4 = np.eye(4, dtype=F)
+    D = A.plane_depth(M.planes, M.Tm, W, H, M.Km)
+    al = _aligner(ctx, W, H, M.Km, keep_rows=True)
+    off = _aligner(ctx, W, H, M.Km, keep_rows=False)
+    for a in (al, off):
+        a.set_model(M.Dm, M.Gm, M.Km, M.Tm)
+
+    def both(D, mask, T, Dm=None, Gm=None, Tm=None, what=""):
+        if Dm is not None:
+            for a in (al, off):
+                a.set_model(Dm, Gm, M.Km, M.Tm if Tm is None else Tm)
+        want = A.linearise(D, mask, M.Km, T, M.Dm if Dm is None else Dm, M.Gm if Gm is None else Gm, M.Km, M.Tm if Tm is None else Tm, **PRM)
+        got = al.linearise(D, mask, T)
+        _same(got, want, what)
+        _same(off.linearise(D, mask, T), want, what + ", keep_rows off")       # the stored image changes no sum
+        assert np.array_equal(_bits(al.rows()), _bits(want[2])), what + ": rows"
+        if Dm is not None:
+            for a in (al, off):
+                a.set_model(M.Dm, M.Gm, M.Km, M.Tm)
+        return want[1]
+
+    base = both(D, None, M.Tm, what="clean")
+    assert base[A.USED] > 1000 and base[A.NO_DEPTH] == 0 and base[A.MASKED] == 0 and base[A.FAR] == 0
+    bad = D.copy(); bad[3, 4] = np.nan; bad[6, 6] = np.inf; bad[7, 8] = -np.inf; bad[9, 10] = 0.0; bad[11, 12] = 7.5; bad[13, 14] = 0.3; bad[15, 16] = -2.0
+    c = both(bad, None, M.Tm, what="NaN, Inf, zero, too far, at min_depth, negative")
+    assert c[A.NO_DEPTH] == 7 and c[A.USED] + c[A.NO_MODEL] == base[A.USED] + base[A.NO_MODEL] - 7
+    mask = np.zeros((H, W), np.int32); mask[2:6, 3:9] = -1; mask[20, 20] = 1 << 30
+    c = both(bad, mask, M.Tm, what="a mask")
+    assert c[A.NO_DEPTH] == 7 and c[A.MASKED] == 25 - 1                  # the NaN at (3, 4) lies under the mask: no depth comes first
+    side = A.perturbed(M.Tm, (0.0, 0.0, 0.0), (0.0, 35.0, 0.0))
+    c = both(D, None, side, what="a projection outside the model")
+    assert c[A.NO_MODEL] > base[A.NO_MODEL] + 200
+    back = A.perturbed(M.Tm, (0.0, 0.0, 0.0), (0.0, 180.0, 0.0))
+    c = both(D, None, back, what="behind the model's camera")
+    assert c[A.NO_MODEL] == W * H
+    hole = M.Dm.copy(); hole[10:14, 10:20] = 0.0; flat = M.Gm.copy(); flat[20:23, 5:9] = 0.0; flat[25, 12] = np.nan; hole[26, 13] = np.inf
+    c = both(D, None, M.Tm, Dm=hole, Gm=flat, what="model holes, zero and NaN gradients")
+    assert base[A.NO_MODEL] + 40 <= c[A.NO_MODEL] <= base[A.NO_MODEL] + 40 + 12 + 2
+    shifted = A.perturbed(M.Tm, (0.0, 0.0, 0.5), (0.0, 0.0, 0.0))
+    c = both(D, None, shifted, what="too far from the model")
+    assert c[A.FAR] > 500
+    # nothing used: all sums +0.0, and a solve stops with status 1 at T_init
+    none = both(np.zeros((H, W), F), None, M.Tm, what="no depth anywhere")
+    assert none.tolist() == [0, W * H, 0, 0, 0]
+    sums, _ = al.linearise(np.zeros((H, W), F), None, M.Tm)
+    assert not sums.any() and not np.signbit(sums).any()
+    T, rep, trace = al.solve(np.zeros((H, W), F), None, M.Tm)
+    assert rep["status"] == 1 and rep["iterations"] == 1 and rep["used"] == 0 and np.array_equal(_bits(T), _bits(M.Tm)) and not trace[0, 16:44].any()
+    # a non-finite T: every sample skipped, no fault
+    for bad_v in (np.nan, np.inf, -np.inf):
+        for at in (0, 3, 5, 6, 10, 11):
+            Tb = M.Tm.copy(); Tb.reshape(16)[at] = bad_v
+            c = both(D, None, Tb, what=f"T[{at}] = {bad_v}")
+            assert c[A.USED] == 0
+    for at in (2, 7, 9):
+        Tb = M.Tm.copy(); Tb.reshape(16)[at] = np.nan
+        c = both(D, None, M.Tm, Dm=M.Dm, Gm=M.Gm, Tm=Tb, what=f"Tm[{at}] = NaN")
+        assert c[A.USED] == 0
+    al.close(); off.close()
+
+
+def test_the_far_gate_exactly_at_max_dist(ctx):
+    """The two pixels worked by hand in test_align_ref.py: pixel 0 lies 0.5 from its model point"""
+    K1 = (1.0, 1.0, 0.0, 0.0)
+    I4 = np.eye(4, dtype=F)
+    D = np.array([[2.0, 2.0]], F); Dm = np.array([[1.5, 1.0]], F); Gm = np.array([[[0.0, 0.0, -2.0], [-1.0, 0.0, -1.0]]], F)
+    for max_dist, counts in ((2.0, [2, 0, 0, 0, 0]), (0.5, [1, 0, 0, 0, 1]), (float(np.nextafter(F(0.5), F(0))), [0, 0, 0, 0, 2])):
+        al = _aligner(ctx, 2, 1, K1, min_depth=0.0, max_depth=10.0, max_dist=max_dist)
+        al.set_model(Dm, Gm, K1, I4)
+        got = al.linearise(D, None, I4)
+        _same(got, A.linearise(D, None, K1, I4, Dm, Gm, K1, I4, 0.0, 10.0, max_dist), f"max_dist {max_dist}")
+        assert got[1].tolist() == counts
+        al.close()
+
+
+# ---- refusals ----------------------------------------------------------------------------------------------------------------------------------------
+def test_refusals_write_nothing(ctx, plane_model):
+    from vdo_slam_amd import align as AL
+    L = AL._lib()
+    L.vdo_last_error.restype = C.c_char_p
+    h = C.c_void_p()
+    K4 = (4.0, 4.0, 4.0, 4.0)
+
+    def create(W=8, H=8, c=ctx._h, **kw):
+        prm = dict(K4=K4); prm.update(kw)
+        pc = AL.params(**prm)
+        return L.vdo_align_create(c, W, H, C.byref(pc), C.byref(h)), L.vdo_last_error().decode()
+
+    nan, inf = float("nan"), float("inf")
+    for kw, word in [(dict(W=0), "width"), (dict(H=0), "height"), (dict(K4=(0.0, 4.0, 4.0, 4.0)), "fx"), (dict(K4=(4.0, -1.0, 4.0, 4.0)), "fy"), (dict(K4=(4.0, 4.0, nan, 4.0)), "K[2]"),
+                     (dict(K4=(inf, 4.0, 4.0, 4.0)), "K[0]"), (dict(min_depth=-0.1), "min_depth"), (dict(min_depth=nan), "min_depth"), (dict(max_depth=0.0), "max_depth"),
+                     (dict(max_depth=inf), "max_depth"), (dict(max_dist=0.0), "max_dist"), (dict(max_dist=nan), "max_dist"), (dict(max_dist=inf), "max_dist"), (dict(subsample=0), "subsample"),
+                     (dict(subsample=9), "subsample"), (dict(min_pixels=5), "min_pixels"), (dict(max_iterations=0), "max_iterations"), (dict(max_iterations=65), "max_iterations"),
+                     (dict(eps=-1e-9), "eps"), (dict(eps=nan), "eps"), (dict(keep_rows=2), "keep_rows"), (dict(c=None), "ctx is null")]:
+        rc, msg = create(**kw)
+        assert rc == -1 and word in msg and not h.value, (kw, rc, msg)
+    for W, H in (((1 << 24) + 1, 1), (1 << 14, 1 << 13)):
+        rc, msg = create(W=W, H=H)
+        assert rc == -4 and not h.value, (W, H, rc, msg)
+    pc = AL.params(K4)
+    assert L.vdo_align_create(ctx._h, 8, 8, None, C.byref(h)) == -1 and "params is null" in L.vdo_last_error().decode()
+    assert L.vdo_align_create(ctx._h, 8, 8, C.byref(pc), None) == -1 and "out is null" in L.vdo_last_error().decode()
+    for edge in (dict(subsample=8, min_pixels=6, max_iterations=64, eps=0.0, min_depth=0.0, keep_rows=1), dict(subsample=1, max_iterations=1)):      # the range edges are taken
+        rc, msg = create(**edge)
+        assert rc == 0 and h.value, (edge, msg)
+        assert L.vdo_align_destroy(h) == 0
+        h = C.c_void_p()
+    assert L.vdo_align_create(ctx._h, 8, 8, C.byref(pc), C.byref(h)) == 0 and h.value
+    W = H = 8
+    D = np.ones((H, W), F); mask = np.zeros((H, W), np.int32)
+    T = np.ascontiguousarray(np.eye(4, dtype=F).reshape(16)); Km = np.array(K4, F)
+    sums = np.full(28, -7.0); counts = np.full(5, -5, np.int64); out = np.full(16, -7.0, F); rep = AL.AlignReportC(); rep.iterations = -3; trace = np.full(10 * 49, -7.0)
+    p = lambda a: a.ctypes.data
+    lin = lambda *a: L.vdo_align_linearise(*a)
+    assert lin(h, p(D), W, p(mask), W, 0, p(T), p(sums), p(counts)) == -1 and "no model" in L.vdo_last_error().decode()
+    assert L.vdo_align_solve(h, p(D), W, None, 0, 0, p(T), p(out), C.addressof(rep), p(trace)) == -1 and "no model" in L.vdo_last_error().decode()
+    Dm = np.ones((H, W), F); Gm = np.ones((H, W, 3), F); K_fx = np.array([0, 4, 4, 4], F); K_nan = np.array([4, 4, nan, 4], F); big_g = np.ones((H + 1, W, 3), F)
+    for args, word in [((None, p(Dm), p(Gm), W, H, p(Km), p(T), 0), "handle is null"), ((h, None, p(Gm), W, H, p(Km), p(T), 0), "depth is null"), ((h, p(Dm), None, W, H, p(Km), p(T), 0), "grad is null"),
+                       ((h, p(Dm), p(Gm), 0, H, p(Km), p(T), 0), "model_width"), ((h, p(Dm), p(Gm), W, -1, p(Km), p(T), 0), "model_height"), ((h, p(Dm), p(Gm), W, H, None, p(T), 0), "Km is null"),
+                       ((h, p(Dm), p(Gm), W, H, p(Km), None, 0), "Tm is null"), ((h, p(Dm), p(Gm), W, H, p(K_fx), p(T), 0), "fx"),
+                       ((h, p(Dm), p(Gm), W, H, p(K_nan), p(T), 0), "Km[2]")]:
+        assert L.vdo_align_set_model(*args) == -1 and word in L.vdo_last_error().decode(), word
+    big = np.ones((H + 1, W), F)
+    assert L.vdo_align_set_model(h, p(big), p(big_g), W, H + 1, p(Km), p(T), 0) == -4                  # more pixels than the handle's model images
+    assert L.vdo_align_set_model_from_view(h, plane_model.view._h, p(T), None) == -4
+    assert L.vdo_align_set_model_from_view(h, None, p(T), None) == -1 and L.vdo_align_set_model_from_view(None, plane_model.view._h, p(T), None) == -1
+    assert lin(h, p(D), W, p(mask), W, 0, p(T), p(sums), p(counts)) == -1                                                    # still no model
+    assert L.vdo_align_set_model(h, p(Dm), p(Gm), W, H, p(Km), p(T), 0) == 0
+    for args, word in [((None, p(D), W, p(mask), W, 0, p(T), p(sums), p(counts)), "handle is null"), ((h, None, W, p(mask), W, 0, p(T), p(sums), p(counts)), "depth is null"),
+                       ((h, p(D), W - 1, p(mask), W, 0, p(T), p(sums), p(counts)), "depth_stride"), ((h, p(D), W, p(mask), W - 1, 0, p(T), p(sums), p(counts)), "mask_stride"),
+                       ((h, p(D), W, p(mask), W, 0, None, p(sums), p(counts)), "T is null"), ((h, p(D), W, p(mask), W, 0, p(T), None, p(counts)), "sums is null"),
+                       ((h, p(D), W, p(mask), W, 0, p(T), p(sums), None), "counts is null")]:
+        assert lin(*args) == -1 and word in L.vdo_last_error().decode(), word
+    for args, word in [((None, p(D), W, None, 0, 0, p(T), p(out), C.addressof(rep), p(trace)), "handle is null"), ((h, None, W, None, 0, 0, p(T), p(out), C.addressof(rep), p(trace)), "depth is null"),
+                       ((h, p(D), W - 1, None, 0, 0, p(T), p(out), C.addressof(rep), p(trace)), "depth_stride"), ((h, p(D), W, None, 0, 0, None, p(out), C.addressof(rep), p(trace)), "T_init is null"),
+                       ((h, p(D), W, None, 0, 0, p(T), None, C.addressof(rep), p(trace)), "T_out is null")]:
+        assert L.vdo_align_solve(*args) == -1 and word in L.vdo_last_error().decode(), word
+    small = FrameImages(ctx, W - 1, H)
+    assert L.vdo_align_linearise_frame(h, small._h, p(T), p(sums), p(counts)) == -1 and "frame is" in L.vdo_last_error().decode()
+    assert L.vdo_align_linearise_frame(h, None, p(T), p(sums), p(counts)) == -1 and L.vdo_align_linearise_frame(None, small._h, p(T), p(sums), p(counts)) == -1
+    assert L.vdo_align_solve_frame(h, small._h, p(T), p(out), None, None) == -1 and L.vdo_align_solve_frame(h, None, p(T), p(out), None, None) == -1
+    small.close()
+    rows = np.full((H, W, 8), -7.0, F)
+    assert L.vdo_align_get_rows(h, p(rows)) == -1 and "keep_rows" in L.vdo_last_error().decode() and L.vdo_align_get_rows(None, p(rows)) == -1
+    assert (sums == -7).all() and (counts == -5).all() and (out == -7).all() and rep.iterations == -3 and (trace == -7).all() and (rows == -7).all()
+    ms = (C.c_double * 2)()
+    assert L.vdo_align_last_timing(h, None) == -1 and L.vdo_align_last_timing(None, ms) == -1 and L.vdo_align_destroy(None) == 0
+    assert lin(h, p(D), W, p(mask), W, 0, p(T), p(sums), p(counts)) == 0 and counts.sum() == W * H
+    assert L.vdo_align_solve(h, p(D), W, None, 0, 0, p(T), p(out), None, None) == 0                                          # report and trace are optional
+    assert L.vdo_align_destroy(h) == 0
+    kr = _aligner(ctx, W, H, K4, keep_rows=True)
+    with pytest.raises(Exception, match="no linearisation"):
+        kr.rows()
+    kr.close()
+
+
+# ---- the solve, walked through its trace ------------------------------------------------------------------------------------------------------------------
+def _walk(trace, rep, T_out, D, mask, K4, Dm, Gm, Km, Tm, prm, subsample, min_pixels, max_iterations, eps, what, equilibrated=False):
+    """Every iteration's sums and counts against the restatement's linearise AT THE DEVICE'S T; every next T against the restatement's step from those
+    sums within one float ulp (both sides work in double on a system with cond(A) < 1e6: they differ only where a rounding to float sits on an edge).
+    equilibrated: for a scene whose depths reach tens of metres, where the rotation columns of J are that much larger than the translation columns and
+    cond(A) measures the units, not the geometry.  The error of a Cholesky solve is bounded through the condition of the matrix scaled to a unit
+    diagonal, H = D^-1 A D^-1 with D = sqrt(diag A) (van der Sluis; Higham, Accuracy and Stability of Numerical Algorithms, theorem 10.6), so the same
+    1e6 is then asserted of cond(H)."""
+    assert len(trace) == rep["iterations"] >= 1
+    for it, row in enumerate(trace):
+        T = row[:16].astype(F).reshape(4, 4)
+        assert np.array_equal(T.astype(np.float64).ravel(), row[:16])
+        sums, counts, _ = A.linearise(D, mask, K4, T, Dm, Gm, Km, Tm, subsample=subsample, **prm)
+        _same((row[16:44], row[44:49].astype(np.int64)), (sums, counts), f"{what}, iteration {it}")
+        status, Tn, xi, rms = A.step(sums, int(counts[0]), min_pixels, T)
+        last = it == len(trace) - 1
+        if status == 0:
+            Am = np.zeros((6, 6))
+            for t, (r, c) in enumerate(A.UPPER):
+                Am[r, c] = Am[c, r] = sums[t]
+            if equilibrated:
+                d = np.sqrt(np.diag(Am))
+                print(f"{what}, iteration {it}: cond(A) {np.linalg.cond(Am):.3g}, equilibrated {np.linalg.cond(Am / np.outer(d, d)):.3g}, max |xi| {np.abs(xi).max():.3g}")
+                Am = Am / np.outer(d, d)
+            assert np.linalg.cond(Am) < 1e6, np.linalg.cond(Am)
+        nxt = T_out if last else trace[it + 1][:16].astype(F).reshape(4, 4)
+        assert _ulps(nxt, Tn) <= 1, f"{what}, iteration {it}: the step"
+        if last:
+            assert rep["status"] == status and rep["used"] == counts[0] and rep["rms_last"] == pytest.approx(rms, rel=1e-12)
+            assert np.allclose(rep["xi"], xi, rtol=1e-9, atol=1e-15)
+            assert status != 0 or (np.abs(xi) <= F(eps)).all() or it + 1 == max_iterations      # why it stopped
+        else:
+            assert status == 0 and not (np.abs(xi) <= F(eps)).all()
+        if it == 0:
+            assert rep["rms_first"] == pytest.approx(rms, rel=1e-12)
+
+
+@pytest.mark.parametrize("k", range(len(A.PERTURBATIONS)))
+def test_a_solve_in_the_room_corner_on_the_device(ctx, k):
+    """The CPU test's scene, model and bound (tests/test_align_ref.py: the restatement's measured errors times 1.5), the solve on the device"""
+    c = A.CORNER
+    D, T_true, T_init, Dm, Gm = A.corner_case(k)
+    min_pixels = c["W"] * c["H"] // 16
+    prm = dict(min_depth=0.0, max_depth=c["max_depth"], max_dist=c["max_dist"])
+    al = _aligner(ctx, c["W"], c["H"], c["K4"], subsample=1, min_pixels=min_pixels, max_iterations=c["max_iterations"], eps=c["eps"], **prm)
+    al.set_model(Dm, Gm, c["K4"], T_init)
+    T, rep, trace = al.solve(D, None, T_init)
+    _walk(trace, rep, T, D, None, c["K4"], Dm, Gm, c["K4"], T_init, prm, 1, min_pixels, c["max_iterations"], c["eps"], f"corner {k}")
+    check_corner(k, T, rep, [(r[:16], r[16:44], r[44:49]) for r in trace], T_true, T_init)
+    al.close()
+
+
+def test_a_solve_from_a_frame_with_subsampling_and_the_iteration_cap(ctx):
+    c = A.CORNER
+    D, T_true, T_init, Dm, Gm = A.corner_case(4)
+    mask = np.zeros(D.shape, np.int32); mask[:, :6] = 2
+    prm = dict(min_depth=0.0, max_depth=c["max_depth"], max_dist=c["max_dist"])
+    fi = FrameImages(ctx, c["W"], c["H"])
+    fi.upload(D, np.zeros(D.shape + (2,), F), mask)
+    for s, iters, eps in ((2, 2, 0.0), (3, 12, 1e-4)):
+        al = _aligner(ctx, c["W"], c["H"], c["K4"], subsample=s, min_pixels=40, max_iterations=iters, eps=eps, **prm)
+        al.set_model(Dm, Gm, c["K4"], T_init)
+        T, rep, trace = al.solve_frame(fi._h, T_init)
+        _walk(trace, rep, T, D, mask, c["K4"], Dm, Gm, c["K4"], T_init, prm, s, 40, iters, eps, f"subsample {s}")
+        assert rep["status"] == 0 and (rep["iterations"] == 2 if iters == 2 else rep["iterations"] < 12)
+        T2, rep2, trace2 = al.solve(D, mask, T_init)
+        assert np.array_equal(_bits(T), _bits(T2)) and np.array_equal(_bits(trace), _bits(trace2)) and rep2["iterations"] == rep["iterations"]      # two runs, two sources: the same bits
+        al.close()

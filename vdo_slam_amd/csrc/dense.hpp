@@ -57,4 +57,20 @@ __device__ __forceinline__ int dn_floor_div(int a, int d) { return a >= 0 ? a / 
 // slot -> global voxel on one axis: the one g in [o, o + n) with g mod n == s
 __device__ __forceinline__ int dn_global(int s, int o, int om, int n) { return o + (s - om) + (s < om ? n : 0); }
 
+// The camera centre of T (4 x 4 row-major, world -> camera) as the raycaster states it: c_a = -((T0a*T03 + T1a*T13) + T2a*T23).  Host, once per call.
+inline void dn_centre(const float T[16], float c[3]) {
+  for (int a = 0; a < 3; ++a) c[a] = -((T[a] * T[3] + T[4 + a] * T[7]) + T[8 + a] * T[11]);
+}
+
+// The world-frame ray of pixel (x, y), camera-z component 1: r_a = (T0a*dx + T1a*dy) + T2a with R[3 * i + a] = T(i, a).  A view's kernel and the
+// aligner's model point (c_a + depth * r_a) share it, so that both name the same point bit for bit.
+__device__ __forceinline__ void dn_ray(float x, float y, float fx, float fy, float cx, float cy, const float R[9], float r[3]) {
+  const float dx = (x - cx) / fx, dy = (y - cy) / fy;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) r[a] = (R[a] * dx + R[3 + a] * dy) + R[6 + a];
+}
+
+// What another handle needs of a view (raycast.hip): its image size, its intrinsics (fx, fy, cx, cy) and the context of its map
+void rc_view_info(const vdo_raycast* view, int* W, int* H, float K[4], vdo_ctx** ctx);
+
 }  // namespace vdo

@@ -190,10 +190,8 @@ __global__ __launch_bounds__(256) void k_rc_march(RcArgs a, const uint32_t* __re
   const bool in = x < a.W && y < a.H;
   bool hit = false, any = false;
   if (in) {
-    const float dx = ((float)x - a.cx) / a.fx, dy = ((float)y - a.cy) / a.fy;
     float r[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) r[k] = (a.R[k] * dx + a.R[3 + k] * dy) + a.R[6 + k];
+    dn_ray((float)x, (float)y, a.fx, a.fy, a.cx, a.cy, a.R, r);
     float d_out = 0.f, pF = 0.f;
     int w_out = 0;
     bool pv = false;
@@ -251,6 +249,11 @@ struct vdo_raycast {
 };
 
 using namespace vdo;
+
+void vdo::rc_view_info(const vdo_raycast* view, int* W, int* H, float K[4], vdo_ctx** ctx) {
+  *W = view->a.W; *H = view->a.H; *ctx = view->map->ctx;
+  K[0] = view->a.fx; K[1] = view->a.fy; K[2] = view->a.cx; K[3] = view->a.cy;
+}
 
 static void rc_free(vdo_raycast* h) {
   hipFree(h->d_stage); hipFree(h->d_grid); hipFree(h->d_cnt);
@@ -322,8 +325,8 @@ extern "C" int vdo_raycast_render(vdo_raycast* h, const float T[16], float* dept
   const auto t0 = std::chrono::steady_clock::now();
   hipStream_t s = h->map->ctx->stream;
   RcArgs a = h->a;
+  dn_centre(T, a.c);
   for (int k = 0; k < 3; ++k) {
-    a.c[k] = -((T[k] * T[3] + T[4 + k] * T[7]) + T[8 + k] * T[11]);
     a.R[k] = T[k]; a.R[3 + k] = T[4 + k]; a.R[6 + k] = T[8 + k];
     a.o[k] = h->map->a.o[k]; a.om[k] = h->map->a.om[k];
     a.lo[k] = (float)a.o[k]; a.hi[k] = (float)(a.o[k] + a.n[k] - 2);

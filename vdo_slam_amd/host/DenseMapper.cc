@@ -14,11 +14,12 @@ static void die(const char* what) {   // (as MotionSegmenter.cc: a failure surfa
   throw std::runtime_error(std::string("VDO_SLAM::DenseMapper: ") + what + ": " + vdo_last_error());
 }
 
-DenseMapper::DenseMapper(vdo_ctx* ctx, int width, int height, const Settings& settings) : s_(settings), w_(width), h_px_(height) {
-  if (vdo_dense_create(ctx ? ctx : HostContext(), width, height, &s_.params, &h_) != VDO_OK) die("vdo_dense_create");
+DenseMapper::DenseMapper(vdo_ctx* ctx, int width, int height, const Settings& settings) : ctx_(ctx ? ctx : HostContext()), s_(settings), w_(width), h_px_(height) {
+  if (vdo_dense_create(ctx_, width, height, &s_.params, &h_) != VDO_OK) die("vdo_dense_create");
 }
 
 DenseMapper::~DenseMapper() {
+  vdo_align_destroy(align_);
   vdo_raycast_destroy(view_);                             // the view borrows the map
   vdo_dense_destroy(h_);
 }
@@ -42,15 +43,61 @@ std::string DenseMapper::CheckView(Settings& s) {
   return "";
 }
 
-void DenseMapper::Render(const float Tcw[16], cv::Mat& depth, cv::Mat& normals, cv::Mat* weight, int64_t counts[3]) {
-  if (!view_) {
-    if (s_.viewSteps == 0) ViewDefaults(s_);
-    const std::string err = CheckView(s_);
+std::string DenseMapper::CheckAlign(const Settings& s) {
+  if (s.alignIterations < 0 || s.alignIterations > 64) return "settings: Dense.Align.Iterations outside 0..64";
+  if (!std::isfinite(s.alignMaxDist) || !(s.alignMaxDist >= 0.f)) return "settings: Dense.Align.MaxDist must be finite and not negative (0 stands for Dense.Truncation)";
+  if (s.alignSubsample < 1 || s.alignSubsample > 8) return "settings: Dense.Align.Subsample outside 1..8";
+  if (s.alignMinPixels != 0 && s.alignMinPixels < 6) return "settings: Dense.Align.MinPixels must be at least 6";
+  return "";
+}
+
+int DenseMapper::AlignMinPixels(const Settings& s, int width, int height) {
+  if (s.alignMinPixels > 0) return s.alignMinPixels;
+  const int64_t ws = (width + s.alignSubsample - 1) / s.alignSubsample, hs = (height + s.alignSubsample - 1) / s.alignSubsample;
+  const int64_t n = ws * hs / 16;
+  return n < 6 ? 6 : (int)n;
+}
+
+void DenseMapper::EnsureView() {
+  if (view_) return;
+  if (s_.viewSteps == 0) ViewDefaults(s_);
+  const std::string err = CheckView(s_);
+  if (!err.empty()) throw std::runtime_error("VDO_SLAM::DenseMapper: " + err);
+  const vdo_raycast_params rp{{s_.params.K[0], s_.params.K[1], s_.params.K[2], s_.params.K[3]}, s_.viewNear, s_.viewStep, s_.viewSteps, s_.viewMinWeight};
+  if (vdo_raycast_create(h_, w_, h_px_, &rp, &view_) != VDO_OK) die("vdo_raycast_create");
+  grad_.resize((size_t)w_ * h_px_ * 3);
+}
+
+void DenseMapper::EnsureAligner(const float Tcw_init[16]) {
+  EnsureView();
+  if (!align_) {
+    const std::string err = CheckAlign(s_);
     if (!err.empty()) throw std::runtime_error("VDO_SLAM::DenseMapper: " + err);
-    const vdo_raycast_params rp{{s_.params.K[0], s_.params.K[1], s_.params.K[2], s_.params.K[3]}, s_.viewNear, s_.viewStep, s_.viewSteps, s_.viewMinWeight};
-    if (vdo_raycast_create(h_, w_, h_px_, &rp, &view_) != VDO_OK) die("vdo_raycast_create");
-    grad_.resize((size_t)w_ * h_px_ * 3);
+    const vdo_dense_params& p = s_.params;
+    const vdo_align_params ap{{p.K[0], p.K[1], p.K[2], p.K[3]}, p.min_depth, p.max_depth, s_.alignMaxDist > 0.f ? s_.alignMaxDist : p.trunc, s_.alignSubsample,
+                              AlignMinPixels(s_, w_, h_px_), s_.alignIterations > 0 ? s_.alignIterations : 10, 1e-5f, 0};
+    if (vdo_align_create(ctx_, w_, h_px_, &ap, &align_) != VDO_OK) die("vdo_align_create");
   }
+  if (vdo_align_set_model_from_view(align_, view_, Tcw_init, nullptr) != VDO_OK) die("vdo_align_set_model_from_view");
+}
+
+void DenseMapper::Align(const cv::Mat& depth, const cv::Mat& mask, const float Tcw_init[16], float Tcw_out[16], vdo_align_report* report) {
+  auto image = [&](const cv::Mat& m, int type) { return !m.empty() && m.rows == h_px_ && m.cols == w_ && m.depth() == type && m.channels() == 1 && m.step % 4 == 0; };
+  if (!image(depth, cv::CV_32F)) throw std::runtime_error("VDO_SLAM::DenseMapper: depth must be CV_32FC1 of the mapper's size");
+  if (!mask.empty() && !image(mask, cv::CV_32S)) throw std::runtime_error("VDO_SLAM::DenseMapper: mask must be empty or CV_32SC1 of the mapper's size");
+  EnsureAligner(Tcw_init);
+  if (vdo_align_solve(align_, (const float*)depth.data, (int64_t)(depth.step / 4), mask.empty() ? nullptr : (const int32_t*)mask.data, mask.empty() ? 0 : (int64_t)(mask.step / 4), 0,
+                      Tcw_init, Tcw_out, report, nullptr) != VDO_OK)
+    die("vdo_align_solve");
+}
+
+void DenseMapper::AlignFrame(const vdo_frame_images* frame, const float Tcw_init[16], float Tcw_out[16], vdo_align_report* report) {
+  EnsureAligner(Tcw_init);
+  if (vdo_align_solve_frame(align_, frame, Tcw_init, Tcw_out, report, nullptr) != VDO_OK) die("vdo_align_solve_frame");
+}
+
+void DenseMapper::Render(const float Tcw[16], cv::Mat& depth, cv::Mat& normals, cv::Mat* weight, int64_t counts[3]) {
+  EnsureView();
   depth.create(h_px_, w_, cv::CV_32FC1);
   normals.create(h_px_, w_, cv::CV_32FC3);
   if (weight) weight->create(h_px_, w_, cv::CV_32SC1);

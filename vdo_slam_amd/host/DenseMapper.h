@@ -20,7 +20,16 @@ class DenseMapper {
     // The view Render makes (settings keys Dense.View.*): the z-depth of a ray's first sample and between samples (metres), the samples per ray and the
     // smallest weight of a sampled voxel.  viewSteps == 0: not set yet - Render then takes ViewDefaults.
     float viewNear = 0.f, viewStep = 0.f; int viewSteps = 0, viewMinWeight = 0;
+    // The alignment Align makes (settings keys Dense.Align.*): the Gauss-Newton rounds (0: System aligns no frame; Align itself then takes 10), the
+    // gate on the distance between a point and its model point in metres (0: params.trunc), the sample stride, the smallest number of used samples
+    // (0: a sixteenth of the sample grid, at least 6), and whether System fuses with the aligned pose.
+    int alignIterations = 0; float alignMaxDist = 0.f; int alignSubsample = 1, alignMinPixels = 0; bool alignApply = false;
   };
+  // The settings error of the alignment fields ("" when in order): Iterations outside 0..64, MaxDist negative or not finite (0 stands for the default; the settings reader itself refuses a zero key), Subsample
+  // outside 1..8, MinPixels below 6 (0 stands for the default).
+  static std::string CheckAlign(const Settings& s);
+  // The smallest number of used samples Align asks for on width x height images
+  static int AlignMinPixels(const Settings& s, int width, int height);
   // The defaults of the view from the fields above: Near max(min_depth, voxel); Step trunc / 2 - half the thickness of the valid negative band behind a
   // surface, so that a pair of samples cannot step over that band from the fusing direction; MinWeight minWeight.
   static void ViewDefaults(Settings& s);
@@ -58,6 +67,13 @@ class DenseMapper {
   // weight CV_32SC1.  The view is made on first use at the mapper's image size and K with the settings' view fields; nothing of the map changes.
   // counts (optional): rays that hit, rays that missed, rays with no valid sample.
   void Render(const float Tcw[16], cv::Mat& depth, cv::Mat& normals, cv::Mat* weight = nullptr, int64_t counts[3] = nullptr);
+  // How far a pose is from the geometry in the map: the view is rendered at Tcw_init straight into the aligner's model (vdo_align_set_model_from_view)
+  // and the frame - the cv::Mats as Fuse takes them, or a frame's resident depth and mask - is aligned against it (vdo_align_solve: point-to-plane
+  // ICP, the model fixed, eps 1e-5).  Tcw_out: the refined pose, Tcw_init bit for bit unless report->status is 0 (1: too few samples met the map -
+  // an empty map, for instance; 2: the geometry does not constrain all six motions).  The view and the aligner are made on first use; nothing of
+  // the map changes.
+  void Align(const cv::Mat& depth, const cv::Mat& mask, const float Tcw_init[16], float Tcw_out[16], vdo_align_report* report = nullptr);
+  void AlignFrame(const vdo_frame_images* frame, const float Tcw_init[16], float Tcw_out[16], vdo_align_report* report = nullptr);
   const Points& kept() const { return kept_; }
   int recenters() const { return recenters_; }
   void origin(int32_t out[3]) const;
@@ -69,8 +85,12 @@ class DenseMapper {
  private:
   void Follow(const float Tcw[16]);
   void Append(const int32_t lo[3], const int32_t hi[3], Points& to);
+  void EnsureView();
+  void EnsureAligner(const float Tcw_init[16]);          // and renders the view at Tcw_init into its model
+  vdo_ctx* ctx_ = nullptr;
   vdo_dense* h_ = nullptr;
-  vdo_raycast* view_ = nullptr;                          // made by the first Render; destroyed before the map
+  vdo_raycast* view_ = nullptr;                          // made by the first Render or Align; destroyed before the map
+  vdo_align* align_ = nullptr;                           // made by the first Align; destroyed before the view
   std::vector<float> grad_;                              // [h][w][3]: the gradient image of the last Render
   Settings s_;
   int w_, h_px_;

@@ -227,7 +227,18 @@ std::string read_dense_settings(const std::string& path, const TrackingSettings&
   const double view_w = get(raw, "Dense.View.MinWeight", s.viewMinWeight);
   if (!whole(view_w)) return "settings: Dense.View.MinWeight must be a whole number";
   s.viewMinWeight = (int)view_w;
-  return DenseMapper::CheckView(s);
+  const std::string view_err = DenseMapper::CheckView(s);
+  if (!view_err.empty()) return view_err;
+  // the alignment of every frame against the map: Dense.Align.Iterations (absent or 0: off), MaxDist, Subsample, MinPixels, Apply
+  const double al[4] = {get(raw, "Dense.Align.Iterations", 0), get(raw, "Dense.Align.Subsample", 1), get(raw, "Dense.Align.MinPixels", 0), get(raw, "Dense.Align.Apply", 0)};
+  static const char* const al_keys[4] = {"Iterations", "Subsample", "MinPixels", "Apply"};
+  for (int k = 0; k < 4; ++k) if (!whole(al[k])) return std::string("settings: Dense.Align.") + al_keys[k] + " must be a whole number";
+  if (al[3] != 0 && al[3] != 1) return "settings: Dense.Align.Apply must be 0 or 1";
+  if (raw.count("Dense.Align.MinPixels") && al[2] < 6) return "settings: Dense.Align.MinPixels must be at least 6";
+  const double max_dist = get(raw, "Dense.Align.MaxDist", p.trunc);
+  if (!std::isfinite(max_dist) || !(max_dist > 0) || !((float)max_dist > 0) || !std::isfinite((float)max_dist)) return "settings: Dense.Align.MaxDist must be positive";
+  s.alignIterations = (int)al[0]; s.alignSubsample = (int)al[1]; s.alignMinPixels = (int)al[2]; s.alignApply = al[3] == 1; s.alignMaxDist = (float)max_dist;
+  return DenseMapper::CheckAlign(s);
 }
 }  // namespace
 
@@ -651,7 +662,19 @@ cv::Mat Tracking::FinishFrame(const cv::Mat& mTcw_gt, std::chrono::steady_clock:
   }
   have_frame_ = true;
   // the dense map: the frame's resident depth (metres) and mask, as the step left them, fused with the pose the tracker has just found
-  if (dense_) dense_->FuseFrame(pipe_->LastImages(), pipe_->Tcw_out_, dense_counts_);
+  // With Dense.Align.Iterations the frame is first aligned against the map at that pose; only with Dense.Align.Apply, and only when the alignment
+  // stepped (status 0), is the aligned pose the one the frame is fused with.  The tracker's pose is not touched.
+  if (dense_) {
+    std::memcpy(dense_fused_, pipe_->Tcw_out_, sizeof dense_fused_);
+    if (dense_->settings().alignIterations > 0) {
+      float aligned[16];
+      dense_->AlignFrame(pipe_->LastImages(), pipe_->Tcw_out_, aligned, &dense_align_);
+      dense_align_valid_ = true;
+      ++dense_align_count_;
+      if (dense_->settings().alignApply && dense_align_.status == 0) std::memcpy(dense_fused_, aligned, sizeof dense_fused_);
+    }
+    dense_->FuseFrame(pipe_->LastImages(), dense_fused_, dense_counts_);
+  }
   // full batch optimisation after the last frame, KITTI only (Tracking.cc:1189-1210: `bGlobalBatch && mTestData==KITTI`)
   if (f_id == StopFrame && f_id > 1 && bGlobalBatch && mTestData == KITTI) {
     if (pipe_->FullBatchOptimization() != 0) return cv::Mat();     // graph built straight from the pipeline's GraphStore
@@ -844,6 +867,28 @@ bool System::RenderDenseView(const cv::Mat& Tcw, cv::Mat& depth, cv::Mat& normal
   float T[16];
   for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) T[4 * r + c] = Tcw.at<float>(r, c);
   d->Render(T, depth, normals);
+  return true;
+}
+
+bool System::AlignDenseView(const cv::Mat& Tcw, const cv::Mat& imD, const cv::Mat& mask, cv::Mat& Tcw_out) {
+  DenseMapper* d = mpTracker->dense();
+  if (!d) return false;
+  if (Tcw.rows != 4 || Tcw.cols != 4 || Tcw.type() != cv::CV_32FC1) throw std::runtime_error("VDO_SLAM::System::AlignDenseView: Tcw must be a 4 x 4 CV_32F matrix");
+  float T[16], Tn[16];
+  for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) T[4 * r + c] = Tcw.at<float>(r, c);
+  d->Align(imD, mask, T, Tn, &view_align_);
+  view_align_valid_ = true;
+  view_align_at_ = mpTracker->dense_alignments();
+  Tcw_out.create(4, 4, cv::CV_32FC1);
+  std::memcpy(Tcw_out.data, Tn, sizeof Tn);
+  return true;
+}
+
+bool System::LastDenseAlignment(vdo_align_report& report) const {
+  if (view_align_valid_ && view_align_at_ == mpTracker->dense_alignments()) { report = view_align_; return true; }      // no frame has been aligned since
+  const vdo_align_report* r = mpTracker->dense_alignment();
+  if (!r) return false;
+  report = *r;
   return true;
 }
 
@@ -1078,6 +1123,67 @@ int host_settings_check_dense_view(const char* path, char* msg, int cap, double*
     if (ds.present) { out5[1] = ds.s.viewNear; out5[2] = ds.s.viewStep; out5[3] = ds.s.viewMinWeight; out5[4] = ds.s.viewSteps; }
   }
   return err.empty() ? 0 : 1;
+}
+// the Dense.Align.* keys as Tracking::Tracking reads them, without a GPU: 0 in order, 1 a settings error (text in msg), -2 no file.  out6 (may be null):
+// present (0 / 1: Dense.VoxelSize is in the file; the rest only then), Iterations, MaxDist, Subsample, MinPixels as DenseMapper::Align will use it, Apply
+int host_settings_check_dense_align(const char* path, char* msg, int cap, double* out6) {
+  VDO_SLAM::TrackingSettings t{};
+  std::map<std::string, double> raw;
+  if (!VDO_SLAM::read_tracking_settings(path, t, &raw)) return -2;
+  VDO_SLAM::DenseSettings ds;
+  const std::string err = VDO_SLAM::read_dense_settings(path, t, raw, ds);
+  if (msg && cap > 0) std::snprintf(msg, (size_t)cap, "%s", err.c_str());
+  if (out6 && err.empty()) {
+    out6[0] = ds.present ? 1 : 0;
+    if (ds.present) {
+      out6[1] = ds.s.alignIterations; out6[2] = ds.s.alignMaxDist; out6[3] = ds.s.alignSubsample;
+      out6[4] = VDO_SLAM::DenseMapper::AlignMinPixels(ds.s, t.width, t.height); out6[5] = ds.s.alignApply ? 1 : 0;
+    }
+  }
+  return err.empty() ? 0 : 1;
+}
+// The alignment of the last frame of a System with Dense.Align.Iterations > 0 (Tracking::dense_alignment): report11 = iterations, status, used,
+// rms_first, rms_last, xi (6); fused16 (may be null): the pose the frame was fused with.  0, 1 when there is none (nothing is written), -1 on a failure.
+int host_system_dense_alignment(VDO_SLAM::System* s, double* report11, float* fused16) {
+  try {
+    const vdo_align_report* r = s->tracker()->dense_alignment();
+    if (!r) return 1;
+    report11[0] = r->iterations; report11[1] = r->status; report11[2] = (double)r->used; report11[3] = r->rms_first; report11[4] = r->rms_last;
+    for (int k = 0; k < 6; ++k) report11[5 + k] = r->xi[k];
+    if (fused16) std::memcpy(fused16, s->tracker()->dense_fused_pose(), 16 * sizeof(float));
+  } catch (const std::exception& e) { std::fprintf(stderr, "host_system_dense_alignment: %s\n", e.what()); return -1; }
+  return 0;
+}
+// System::LastDenseAlignment alone: report11 as above.  0, 1 when there has been no alignment (nothing is written), -1 on a failure.
+int host_system_last_dense_alignment(VDO_SLAM::System* s, double* report11) {
+  try {
+    vdo_align_report r{};
+    if (!s->LastDenseAlignment(r)) return 1;
+    report11[0] = r.iterations; report11[1] = r.status; report11[2] = (double)r.used; report11[3] = r.rms_first; report11[4] = r.rms_last;
+    for (int k = 0; k < 6; ++k) report11[5 + k] = r.xi[k];
+  } catch (const std::exception& e) { std::fprintf(stderr, "host_system_last_dense_alignment: %s\n", e.what()); return -1; }
+  return 0;
+}
+// System::AlignDenseView + System::LastDenseAlignment: Tcw [16], depth [Camera.height][Camera.width] metres, mask the same or null; Tcw_out [16],
+// report11 as above.  0, 1 without a mapper (nothing is written), -1 on a failure.
+int host_system_align_dense_view(VDO_SLAM::System* s, const float* Tcw, const float* depth, const int* mask, float* Tcw_out, double* report11) {
+  try {
+    VDO_SLAM::DenseMapper* d = s->tracker()->dense();
+    if (!d) {
+      cv::Mat T(4, 4, cv::CV_32FC1, (void*)Tcw), D, M, To;
+      return s->AlignDenseView(T, D, M, To) ? -1 : 1;
+    }
+    const int w = d->width(), h = d->height();
+    cv::Mat T(4, 4, cv::CV_32FC1, (void*)Tcw), D(h, w, cv::CV_32FC1, (void*)depth), M, To;
+    if (mask) M = cv::Mat(h, w, cv::CV_32SC1, (void*)mask);
+    if (!s->AlignDenseView(T, D, M, To)) return 1;
+    std::memcpy(Tcw_out, To.data, 16 * sizeof(float));
+    vdo_align_report r{};
+    if (!s->LastDenseAlignment(r)) return -1;
+    report11[0] = r.iterations; report11[1] = r.status; report11[2] = (double)r.used; report11[3] = r.rms_first; report11[4] = r.rms_last;
+    for (int k = 0; k < 6; ++k) report11[5 + k] = r.xi[k];
+  } catch (const std::exception& e) { std::fprintf(stderr, "host_system_align_dense_view: %s\n", e.what()); return -1; }
+  return 0;
 }
 // System::RenderDenseView: Tcw [16] world -> camera; depth [Camera.height][Camera.width], normals [Camera.height][Camera.width][3]; wh2 (may be null)
 // receives Camera.width and Camera.height, and with depth null nothing else happens.  0, 1 without a mapper (nothing is written), -1 on a failure

@@ -69,6 +69,11 @@ class Tracking {
   // after the pose is known: the frame's resident depth and mask with that pose, on a context of its own.
   DenseMapper* dense() { return dense_.get(); }
   const int64_t* dense_counts() const { return dense_counts_; }      // updated, masked and occluded voxels of the last frame
+  // With Dense.Align.Iterations > 0: the alignment of the last frame against the map, made at the tracker's pose before the frame was fused
+  // (null otherwise, and before the first frame), and the pose the frame was fused with
+  const vdo_align_report* dense_alignment() const { return dense_align_valid_ ? &dense_align_ : nullptr; }
+  long long dense_alignments() const { return dense_align_count_; }      // frames aligned so far
+  const float* dense_fused_pose() const { return dense_fused_; }
   MotionSegmenter* motion() { return motion_.get(); }    // null before the first GrabImageStereoVideo
   // What the last GrabImageStereoVideo found: ego-motion inliers, moving pixels after the vote (0 when the ego-motion failed), labels
   const int* video_counts() const { return video_counts_; }
@@ -127,6 +132,10 @@ class Tracking {
   std::unique_ptr<DenseMapper> dense_;                   // Dense.VoxelSize present: the dense map of the static scene
   vdo_ctx* ctx_dense_ = nullptr;                         // its context (made only with the mapper)
   int64_t dense_counts_[3] = {0, 0, 0};
+  vdo_align_report dense_align_{};                       // Dense.Align.Iterations > 0: the last frame against the map
+  bool dense_align_valid_ = false;
+  long long dense_align_count_ = 0;
+  float dense_fused_[16] = {0};                          // the pose the last frame was fused with
   std::unique_ptr<MotionSegmenter> motion_;              // made by the first GrabImageStereoVideo from motion_p_
   vdo_motionseg_params motion_p_{};                      // Motion.* keys (read and checked with the STEREO sensor only)
   MotionSegmenter::EgoParams ego_;                       // Motion.Ego* keys
@@ -192,8 +201,8 @@ class System {
   // centre's target place in the volume ([0.5, 0.5, 0.25]), Dense.RecenterMargin in voxels (min(n) / 8).  A value outside its range is a settings error
   // with every sensor.  Every Track* entry fuses its frame once the pose is known (DenseMapper::FuseFrame): the volume follows the camera, and what
   // leaves it is kept as points on the host.  SaveDenseMap writes those points and the surface in the volume as a binary little-endian PLY (x, y, z,
-  // nx, ny, nz, weight); false without a mapper or when the file cannot be written.  Limits: the map is fused with the tracker's per-frame poses and is
-  // not re-fused after a bundle adjustment; an edge between a leaving and a staying voxel can be lost when the volume moves towards a negative axis;
+  // nx, ny, nz, weight); false without a mapper or when the file cannot be written.  Limits: the map is fused with the tracker's per-frame poses - or,
+  // with Dense.Align.Apply, with those poses refined against the map itself, which the tracker never sees - and is not re-fused after a bundle adjustment; an edge between a leaving and a staying voxel can be lost when the volume moves towards a negative axis;
   // objects are not reconstructed; with semantic masks on the RGBD path parked instances are left out too.
   bool SaveDenseMap(const std::string& path);
   // What the dense map predicts a camera at Tcw (4 x 4 CV_32F, world -> camera) would see (DenseMapper::Render, vdo_raycast_render): depth CV_32FC1 in
@@ -203,6 +212,18 @@ class System {
   // a ray has ceil((Dense.MaxDepth - Near) / Step) + 1 samples, at most 65536.  A non-finite value, Step <= 0, Near < 0, Near >= Dense.MaxDepth or too
   // many samples is a settings error.  False without a mapper; nothing of the map or of the tracker changes.
   bool RenderDenseView(const cv::Mat& Tcw, cv::Mat& depth, cv::Mat& normals);
+  // How far a pose is from the geometry in the map (DenseMapper::Align, vdo_align_solve): imD (CV_32FC1 metres) and mask (CV_32SC1 or empty) of the
+  // camera's image size are aligned by point-to-plane ICP against the map's view at Tcw (4 x 4 CV_32F, world -> camera); Tcw_out receives the refined
+  // pose (Tcw itself unless LastDenseAlignment's status is 0).  False without a mapper; nothing of the map or of the tracker changes.  Settings keys,
+  // all optional and read only with Dense.VoxelSize: Dense.Align.Iterations (0: off; 1..64: every Track* entry aligns its frame against the map at the
+  // tracker's pose before it fuses, and keeps the report), Dense.Align.MaxDist (Dense.Truncation), Dense.Align.Subsample (1; 1..8),
+  // Dense.Align.MinPixels (a sixteenth of the sample grid; at least 6), Dense.Align.Apply (0; 1: the frame is fused with the aligned pose when the
+  // alignment's status is 0, with the tracker's pose otherwise - on the first frame, for instance, when the map is empty).  The TRACKER's trajectory
+  // is the same bytes in every case.  A value outside its range is a settings error.
+  bool AlignDenseView(const cv::Mat& Tcw, const cv::Mat& imD, const cv::Mat& mask, cv::Mat& Tcw_out);
+  // The report of the last alignment - of AlignDenseView, or of the last frame with Dense.Align.Iterations > 0, whichever came later.  False when
+  // there has been none.
+  bool LastDenseAlignment(vdo_align_report& report) const;
   void SaveResults(const std::string& filename);
   Map* map();                          // brought up to date from the pipeline's GraphStore on access
   Tracking* tracker() { return mpTracker; }
@@ -211,6 +232,9 @@ class System {
   eSensor mSensor;
   Map* mpMap;
   Tracking* mpTracker;
+  vdo_align_report view_align_{};      // of the last AlignDenseView
+  bool view_align_valid_ = false;
+  long long view_align_at_ = 0;        // the frames the tracker had aligned when AlignDenseView ran: a later frame's report is the newer one
 };
 
 }  // namespace VDO_SLAM

@@ -430,6 +430,36 @@ int host_dense_render(const float* depth, const int* mask, const float* Tcw, int
   } catch (const std::exception& e) { std::fprintf(stderr, "host_dense_render: %s\n", e.what()); return -1; }
 }
 
+// host_dense_fuse's frames, then DenseMapper::Align of one more frame (a_depth [h][w], a_mask [h][w] or null) at T_init (16 floats, world -> camera).
+// align5: Iterations (0: the class default), MaxDist (0: trunc), Subsample, MinPixels (0: the default), unused.  T_out [16]; report11: iterations,
+// status, used, rms_first, rms_last, xi (6).  words (may be null): the volume afterwards, nx * ny * nz in slot order - Align changes nothing of it.
+// 0, -1 on a failure.
+int host_dense_align(const float* depth, const int* mask, const float* Tcw, int k, int w, int h, const vdo_dense_params* params, const double* anchor3, int margin, int min_weight,
+                     const double* align5, const float* a_depth, const int* a_mask, const float* T_init, float* T_out, double* report11, unsigned int* words) {
+  try {
+    DenseMapper::Settings s;
+    s.params = *params; s.margin = margin; s.minWeight = min_weight;
+    for (int a = 0; a < 3; ++a) s.anchor[a] = anchor3[a];
+    s.alignIterations = (int)align5[0]; s.alignMaxDist = (float)align5[1]; s.alignSubsample = (int)align5[2]; s.alignMinPixels = (int)align5[3];
+    const std::string err = DenseMapper::CheckAlign(s);
+    if (!err.empty()) { std::fprintf(stderr, "host_dense_align: %s\n", err.c_str()); return -1; }
+    DenseMapper m(nullptr, w, h, s);
+    for (int i = 0; i < k; ++i) {
+      cv::Mat D(h, w, cv::CV_32FC1, (void*)(depth + (size_t)i * w * h)), M;
+      if (mask) M = cv::Mat(h, w, cv::CV_32SC1, (void*)(mask + (size_t)i * w * h));
+      m.Fuse(D, M, Tcw + 16 * (size_t)i);
+    }
+    cv::Mat D(h, w, cv::CV_32FC1, (void*)a_depth), M;
+    if (a_mask) M = cv::Mat(h, w, cv::CV_32SC1, (void*)a_mask);
+    vdo_align_report r{};
+    m.Align(D, M, T_init, T_out, &r);
+    report11[0] = r.iterations; report11[1] = r.status; report11[2] = (double)r.used; report11[3] = r.rms_first; report11[4] = r.rms_last;
+    for (int a = 0; a < 6; ++a) report11[5 + a] = r.xi[a];
+    if (words && vdo_dense_get_volume(m.handle(), words, nullptr) != VDO_OK) return -1;
+    return 0;
+  } catch (const std::exception& e) { std::fprintf(stderr, "host_dense_align: %s\n", e.what()); return -1; }
+}
+
 // one TrackStereoVideo call on host images: the current and the next pair (all four of `channels` channels), nothing else
 int host_system_track_stereo_video(System* s, const unsigned char* left, const unsigned char* right, const unsigned char* left_next, const unsigned char* right_next, int channels,
                                    int w, int h, const float* obj_rows, int n_rows, int row_len, int n_images, float* Tcw_out) {

@@ -297,6 +297,50 @@ class System:
             raise K.VdoError("System.render_dense_view failed")
         return d, n
 
+    @staticmethod
+    def _align_report(r):
+        return dict(iterations=int(r[0]), status=int(r[1]), used=int(r[2]), rms_first=float(r[3]), rms_last=float(r[4]), xi=r[5:11].copy())
+
+    def dense_alignment(self):
+        """With Dense.Align.Iterations > 0: (report dict of the last frame's alignment against the map - iterations, status, used, rms_first, rms_last,
+        xi -, the pose [4, 4] f32 the frame was fused with), or None when there has been none."""
+        L = self._L
+        L.host_system_dense_alignment.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        r = np.zeros(11, np.float64); fused = np.zeros(16, np.float32)
+        rc = L.host_system_dense_alignment(self._h, _ptr(r), _ptr(fused))
+        if rc == 1:
+            return None
+        if rc != 0:
+            raise K.VdoError("System.dense_alignment failed")
+        return self._align_report(r), fused.reshape(4, 4)
+
+    def last_dense_alignment(self):
+        """System::LastDenseAlignment: the report dict of AlignDenseView or of the last aligned frame, whichever came later; None when there has been none."""
+        L = self._L
+        L.host_system_last_dense_alignment.argtypes = [C.c_void_p, C.c_void_p]
+        r = np.zeros(11, np.float64)
+        rc = L.host_system_last_dense_alignment(self._h, _ptr(r))
+        if rc == 1:
+            return None
+        if rc != 0:
+            raise K.VdoError("System.last_dense_alignment failed")
+        return self._align_report(r)
+
+    def align_dense_view(self, T, depth, mask=None):
+        """System::AlignDenseView + LastDenseAlignment: depth [h, w] f32 metres and mask [h, w] i32 (or None) at the camera's image size aligned against
+        the map's view at T (4 x 4, world -> camera): (refined T [4, 4] f32, report dict), or None when the system has no mapper."""
+        L = self._L
+        L.host_system_align_dense_view.argtypes = [C.c_void_p] * 6
+        Tc = np.ascontiguousarray(np.asarray(T, np.float32).reshape(16))
+        d = np.ascontiguousarray(depth, np.float32); m = np.ascontiguousarray(mask, np.int32) if mask is not None else None
+        out = np.zeros(16, np.float32); r = np.zeros(11, np.float64)
+        rc = L.host_system_align_dense_view(self._h, _ptr(Tc), _ptr(d), _ptr(m) if m is not None else None, _ptr(out), _ptr(r))
+        if rc == 1:
+            return None
+        if rc != 0:
+            raise K.VdoError("System.align_dense_view failed")
+        return out.reshape(4, 4), self._align_report(r)
+
     def last_depth_mask(self, w, h):
         """The resident depth (metres) and mask of the last frame as the step left them - what the dense mapper fused: (depth [h, w] f32, mask [h, w] i32)"""
         L = self._L
