@@ -1128,6 +1128,72 @@ int vdo_dense_last_timing(vdo_dense* h, double ms[2]);
 int vdo_dense_device_volume(vdo_dense* h, uint32_t** words);
 /* The voxels along y one thread of the integrate kernel takes: 1, 2, 4 (the default) or 8.  No result depends on it. */
 int vdo_dense_set_voxels_per_thread(vdo_dense* h, int voxels);
+/* Sets every word of the volume to 0 on the context's stream (host-synchronous) and leaves the origin alone: a retired handle is reused. */
+int vdo_dense_clear(vdo_dense* h);
+
+/* ---- Object mapper: label statistics and a batched, label-selecting TSDF fusion -----------------------------------------------------------
+ * New: the per-frame device stage of a volume per tracked object.  An object's volume is a plain vdo_dense in a frame of the object's own
+ * (vdo_dense_extract, vdo_raycast_* and vdo_align_* work on it unchanged with T = Tcw * Two); a vdo_objects handle owns the label table, the
+ * counters, the batch table and the image staging, and NO volume.  fp32 with one rounded operation per step in the order written, no contraction;
+ * everything accumulated is an integer, so no result depends on workgroup shape, on the schedule or on the culling.
+ *
+ * Stats.  depth[H][W] fp32 metres, mask[H][W] int32 (required), K = (fx, fy, cx, cy).  A pixel (x, y) COUNTS when its depth d is finite with
+ *   min_depth < d <= max_depth and its mask value l lies in 1..max_labels.  Row l of the table, int64[8]:
+ *      [0] the number of counting pixels;  [1..4] their inclusive box x0, y0, x1, y1;  [5..7] the sums over them of
+ *      qx = (int64) floorf(((((float)x - cx) * d) / fx) * 1024.f + 0.5f)
+ *      qy = (int64) floorf(((((float)y - cy) * d) / fy) * 1024.f + 0.5f)
+ *      qz = (int64) floorf(d * 1024.f + 0.5f)                                   (the back-projected point in 2^-10 m)
+ *   A label without a counting pixel: (0, width, height, -1, -1, 0, 0, 0).  Row 0: [0] the pixels of usable depth whose label is non-zero and
+ *   outside 1..max_labels (negative labels among them), the rest as for an empty label.  The table has max_labels + 1 rows.
+ *   Accumulation: 64-bit integer atomics on global memory (add, min, max), after the lanes of a wave that carry the same label were combined in
+ *   registers - any order gives the same table.
+ *   BOUND.  With m = max(width + |cx|, height + |cy|) and term = max(m / min(fx, fy), 1) * max_depth * 1024 + 1, no |q| exceeds term (to rounding),
+ *   and vdo_objects_create refuses parameters with width * height * term > 2^62: no sum leaves int64, no q the range of the conversion.
+ * Integrate.  n objects: maps[i] (a vdo_dense of the same context and image size whose depth range lies inside the stage's), labels[i] in
+ *   1..max_labels, T[i] 4 x 4 row-major, object frame -> camera (Tcw * Two), last row not read.  One call = the stats pass on its images, then ONE
+ *   fusion launch over all n volumes: a device table holds per object the map's own kernel arguments (size, origin, voxel, K, truncation, depth
+ *   range, weight cap), its volume, its label and the label's pixel box; the object index rides on the grid's x, the grid is sized for the largest
+ *   volume, threads outside an object's own volume do nothing.  Per voxel everything is vdo_dense_integrate's (the same device functions), with
+ *   one difference: after `d usable`, the voxel is left alone unless mask((int)yq, (int)xq) == labels[i].  The volume and the first two counts
+ *   equal vdo_dense_integrate on the map with the mask image (mask != labels[i]).
+ *   out[i] = updated voxels, occluded voxels, row labels[i] [0] of the stats.
+ * Culling (vdo_objects_set_cull; off by default - profiles/objects_timing.txt: it did not pay at 8 objects of 96 x 64 x 96): an object whose label counts 0 pixels gets no workgroup; a voxel whose (xq, yq) lies outside
+ *   the label's box is dropped before any image read.  Every pixel with mask == label and a depth the map accepts is inside that box (the map's
+ *   depth range lies inside the stage's), so NO volume word and NO count depends on the switch.
+ * NO OUT-OF-RANGE ACCESS: the gathered address follows from float compares against 0 and W - 1 / H - 1 made before any conversion to int; every
+ *   volume index is built from slot coordinates tested against the object's own n; a stats row is addressed by a label tested against
+ *   1..max_labels. */
+typedef struct vdo_objects vdo_objects;
+typedef struct vdo_objects_params {
+  float K[4];                       /* fx, fy, cx, cy; fx, fy > 0 */
+  float min_depth, max_depth;       /* 0 <= min_depth < max_depth, metres */
+  int32_t max_labels;               /* 1..1023 */
+  int32_t max_batch;                /* 1..64 objects per integrate call */
+} vdo_objects_params;
+/* ALL device memory is taken here.  VDO_ERR_INVALID, the message naming the argument: a null pointer, a size < 1, a parameter outside its range
+ * or not finite.  VDO_ERR_UNSUPPORTED: the BOUND above, or an image beyond 2^26 pixels or 2^24 on a side. */
+int vdo_objects_create(vdo_ctx* ctx, int width, int height, const vdo_objects_params* params, vdo_objects** out);
+int vdo_objects_destroy(vdo_objects* h);
+/* The stats of one frame, host-synchronous.  Images, strides and src_is_device as vdo_dense_integrate takes them, the mask required.
+ * stats (host, [(max_labels + 1)][8]) may be NULL (read it later with vdo_objects_last_stats).  VDO_ERR_INVALID and nothing written: a null
+ * handle, depth or mask; a stride too small. */
+int vdo_objects_stats(vdo_objects* h, const float* depth, int64_t depth_stride_floats, const int32_t* mask, int64_t mask_stride_ints, int src_is_device,
+                      int64_t* stats);
+int vdo_objects_stats_frame(vdo_objects* h, const vdo_frame_images* frame, int64_t* stats);
+/* Stats, then the batched fusion, host-synchronous.  maps, labels, T ([n][16]) and out ([n][3]) are host arrays; n == 0 refreshes the stats only
+ * (the arrays may then be NULL).  VDO_ERR_INVALID, the message naming the argument, and then NO volume and no stats change: n < 0 or n > max_batch;
+ * a null array or a null maps[i]; the same map twice; a map of another context, another image size or a depth range outside the stage's;
+ * labels[i] < 1 or > max_labels; a null depth or mask; a stride too small. */
+int vdo_objects_integrate(vdo_objects* h, const float* depth, int64_t depth_stride_floats, const int32_t* mask, int64_t mask_stride_ints, int src_is_device,
+                          int n, vdo_dense* const* maps, const int32_t* labels, const float* T, int64_t* out);
+int vdo_objects_integrate_frame(vdo_objects* h, const vdo_frame_images* frame, int n, vdo_dense* const* maps, const int32_t* labels, const float* T,
+                                int64_t* out);
+/* The A/B switch of the culling (default 0).  No result depends on it. */
+int vdo_objects_set_cull(vdo_objects* h, int on);
+/* The table of the last stats or integrate call (host, [(max_labels + 1)][8]); VDO_ERR_INVALID before the first. */
+int vdo_objects_last_stats(vdo_objects* h, int64_t* stats);
+/* The last stats or integrate call: ms[0] wall time of the call, ms[1] device time from the first upload to the end of the last kernel. */
+int vdo_objects_last_timing(vdo_objects* h, double ms[2]);
 
 /* ---- Raycaster: depth and normal views of the TSDF volume ---------------------------------------------------------------------------
  * New (the reference keeps no dense map): what the dense mapper's volume predicts a camera at pose T would see - per pixel a depth, an

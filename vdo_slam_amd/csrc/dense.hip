@@ -56,30 +56,19 @@ __global__ __launch_bounds__(256) void k_dn_integrate(DnArgs a, const float* __r
     if (in_xz && sy < ny) {
       const float py = ((float)dn_global(sy, a.o[1], a.om[1], ny) + 0.5f) * a.voxel;
       const float Xc = (ax + a.T[1] * py) + bx, Yc = (ay + a.T[5] * py) + by, Zc = (az + a.T[9] * py) + bz;
-      if (dn_finite(Zc) && Zc > a.min_z) {
-        const float u = (a.fx * Xc) / Zc + a.cx, v = (a.fy * Yc) / Zc + a.cy;
-        const float xq = floorf(u + 0.5f), yq = floorf(v + 0.5f);
-        if (dn_finite(u) && dn_finite(v) && xq >= 0.f && xq <= (float)(W - 1) && yq >= 0.f && yq <= (float)(H - 1)) {
-          const int j = (int)yq * W + (int)xq;
-          const float d = depth[j];
-          if (dn_finite(d) && d > a.min_d && d <= a.max_d) {
-            if (mask && mask[j] != 0) {
-              msk = true;
-            } else {
-              float s = d - Zc;
-              if (s < -a.trunc) {
-                occ = true;
-              } else {
-                s = fminf(s, a.trunc);
-                const int q = (int)floorf((s / a.trunc) * 32767.0f + 0.5f);
-                const int t = (int)(int16_t)(word[k] & 0xffffu), w = (int)(word[k] >> 16);
-                const int t1 = dn_floor_div(2 * (t * w + q) + (w + 1), 2 * (w + 1));      // |t|, |q| <= 32767, w <= 255: below 2^25
-                const int w1 = w + 1 < a.max_w ? w + 1 : a.max_w;
-                const uint32_t nw = ((uint32_t)w1 << 16) | ((uint32_t)t1 & 0xffffu);
-                if (nw != word[k]) vol[row0 + (size_t)sy * nx] = nw;
-                upd = true;
-              }
-            }
+      float xq, yq;
+      if (dn_pixel(a, Xc, Yc, Zc, W, H, &xq, &yq)) {
+        const int j = (int)yq * W + (int)xq;
+        const float d = depth[j];
+        if (dn_depth_ok(a, d)) {
+          uint32_t nw;
+          if (mask && mask[j] != 0) {
+            msk = true;
+          } else if (!dn_fuse(a, d, Zc, word[k], &nw)) {
+            occ = true;
+          } else {
+            if (nw != word[k]) vol[row0 + (size_t)sy * nx] = nw;
+            upd = true;
           }
         }
       }
@@ -475,6 +464,15 @@ extern "C" int vdo_dense_set_volume(vdo_dense* h, const uint32_t* words) {
   const int rc = ctx_bind(h->ctx);
   if (rc != VDO_OK) return rc;
   hipMemcpyAsync(h->d_vol, words, (size_t)h->nvox * sizeof(uint32_t), hipMemcpyHostToDevice, h->ctx->stream);
+  return dn_check_hip(who, hipStreamSynchronize(h->ctx->stream));
+}
+
+extern "C" int vdo_dense_clear(vdo_dense* h) {
+  static const char* who = "vdo_dense_clear";
+  if (!h) return set_error(VDO_ERR_INVALID, "%s: handle is null", who);
+  const int rc = ctx_bind(h->ctx);
+  if (rc != VDO_OK) return rc;
+  hipMemsetAsync(h->d_vol, 0, (size_t)h->nvox * sizeof(uint32_t), h->ctx->stream);
   return dn_check_hip(who, hipStreamSynchronize(h->ctx->stream));
 }
 

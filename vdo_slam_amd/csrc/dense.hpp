@@ -57,6 +57,31 @@ __device__ __forceinline__ int dn_floor_div(int a, int d) { return a >= 0 ? a / 
 // slot -> global voxel on one axis: the one g in [o, o + n) with g mod n == s
 __device__ __forceinline__ int dn_global(int s, int o, int om, int n) { return o + (s - om) + (s < om ? n : 0); }
 
+// The per-voxel arithmetic of the fusion, shared by k_dn_integrate (dense.hip) and k_ob_integrate (objects.hip) so that both produce the same bits.
+// The pixel a camera-frame point falls on, as floats (exact integers); false unless Zc is finite and above min_z, u and v are finite and the rounded
+// pixel lies in the image - compared as floats, so (int)xq, (int)yq are safe after a true.
+__device__ __forceinline__ bool dn_pixel(const DnArgs& a, float Xc, float Yc, float Zc, int W, int H, float* xq, float* yq) {
+  if (!(dn_finite(Zc) && Zc > a.min_z)) return false;
+  const float u = (a.fx * Xc) / Zc + a.cx, v = (a.fy * Yc) / Zc + a.cy;
+  *xq = floorf(u + 0.5f); *yq = floorf(v + 0.5f);
+  return dn_finite(u) && dn_finite(v) && *xq >= 0.f && *xq <= (float)(W - 1) && *yq >= 0.f && *yq <= (float)(H - 1);
+}
+
+__device__ __forceinline__ bool dn_depth_ok(const DnArgs& a, float d) { return dn_finite(d) && d > a.min_d && d <= a.max_d; }
+
+// One usable depth d seen from a voxel at camera depth Zc: false when the voxel is occluded (s < -trunc), else *nw is the word after the running mean.
+__device__ __forceinline__ bool dn_fuse(const DnArgs& a, float d, float Zc, uint32_t word, uint32_t* nw) {
+  float s = d - Zc;
+  if (s < -a.trunc) return false;
+  s = fminf(s, a.trunc);
+  const int q = (int)floorf((s / a.trunc) * 32767.0f + 0.5f);
+  const int t = (int)(int16_t)(word & 0xffffu), w = (int)(word >> 16);
+  const int t1 = dn_floor_div(2 * (t * w + q) + (w + 1), 2 * (w + 1));      // |t|, |q| <= 32767, w <= 255: below 2^25
+  const int w1 = w + 1 < a.max_w ? w + 1 : a.max_w;
+  *nw = ((uint32_t)w1 << 16) | ((uint32_t)t1 & 0xffffu);
+  return true;
+}
+
 // The camera centre of T (4 x 4 row-major, world -> camera) as the raycaster states it: c_a = -((T0a*T03 + T1a*T13) + T2a*T23).  Host, once per call.
 inline void dn_centre(const float T[16], float c[3]) {
   for (int a = 0; a < 3; ++a) c[a] = -((T[a] * T[3] + T[4 + a] * T[7]) + T[8 + a] * T[11]);

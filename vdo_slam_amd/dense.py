@@ -35,7 +35,8 @@ def _lib():
         L.vdo_dense_last_timing.argtypes = [vp, K.c_double_p]
         L.vdo_dense_device_volume.argtypes = [vp, C.POINTER(vp)]
         L.vdo_dense_set_voxels_per_thread.argtypes = [vp, C.c_int]
-        for f in ("create", "destroy", "integrate", "integrate_frame", "recenter", "extract", "get_volume", "set_volume", "last_timing", "device_volume", "set_voxels_per_thread"):
+        L.vdo_dense_clear.argtypes = [vp]
+        for f in ("create", "destroy", "integrate", "integrate_frame", "recenter", "extract", "get_volume", "set_volume", "last_timing", "device_volume", "set_voxels_per_thread", "clear"):
             getattr(L, "vdo_dense_" + f).restype = C.c_int
         _declared = True
     return L
@@ -129,6 +130,10 @@ class DenseMapper:
         if w.shape != self.n[::-1]:
             raise ValueError(f"words: {w.shape}, expected {self.n[::-1]}")
         K.check(self._L.vdo_dense_set_volume(self._h, w.ctypes.data))
+
+    def clear(self):
+        """Every word 0, the origin kept: a retired volume is reused"""
+        K.check(self._L.vdo_dense_clear(self._h))
 
     def origin(self):
         o = (C.c_int32 * 3)()

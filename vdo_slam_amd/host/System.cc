@@ -177,7 +177,38 @@ std::string read_motion_settings(const TrackingSettings& t, const std::map<std::
 // The Dense.* keys (System.h), all optional.  present: Dense.VoxelSize is in the file - without it the other keys are not read and no mapper is made.
 // The returned text is empty when the keys are absent or in order; otherwise it is the settings error, which ends the process in Tracking::Tracking
 // and is a refusal in host_system_create.  The ranges are those of vdo_dense_create.
-struct DenseSettings { bool present = false; DenseMapper::Settings s; };
+struct DenseSettings { bool present = false; DenseMapper::Settings s; bool objects = false; ObjectMapper::Settings os; };
+// The Dense.Objects.* keys (System.h), read only with Dense.VoxelSize; objects: Dense.Objects.VoxelSize is in the file - without it no object mapper is made.
+std::string read_dense_objects_settings(const TrackingSettings& t, const std::map<std::string, double>& raw, const std::map<std::string, std::vector<double> >& lists, DenseSettings& ds) {
+  ds.objects = raw.count("Dense.Objects.VoxelSize") != 0 || lists.count("Dense.Objects.VoxelSize") != 0;
+  if (!ds.objects) return "";
+  const double voxel = get(raw, "Dense.Objects.VoxelSize", 0);
+  if (!std::isfinite(voxel) || !(voxel > 0) || !((float)voxel > 0) || !std::isfinite((float)voxel)) return "settings: Dense.Objects.VoxelSize must be positive";
+  ObjectMapper::Settings& o = ds.os;
+  const vdo_dense_params& d = ds.s.params;
+  o.params = vdo_dense_params{{96, 64, 96}, (float)voxel, {0, 0, 0}, {d.K[0], d.K[1], d.K[2], d.K[3]}, 4.f * (float)voxel, d.min_depth, t.th_depth_obj, d.max_weight, 1 << 16};
+  vdo_dense_params& p = o.params;
+  auto whole = [](double v) { return std::isfinite(v) && std::fabs(v) <= 1e9 && v == std::floor(v); };
+  if (raw.count("Dense.Objects.Size")) return "settings: Dense.Objects.Size must be a list [nx, ny, nz]";
+  const auto size = lists.find("Dense.Objects.Size");
+  if (size != lists.end()) {
+    if (size->second.size() != 3) return "settings: Dense.Objects.Size has " + std::to_string(size->second.size()) + " values, expected [nx, ny, nz]";
+    for (int a = 0; a < 3; ++a) {
+      if (!whole(size->second[a]) || size->second[a] < 1 || size->second[a] > 4096) return "settings: Dense.Objects.Size: every side must be a whole number in 1..4096";
+      p.n[a] = (int32_t)size->second[a];
+    }
+  }
+  if ((int64_t)p.n[0] * p.n[1] * p.n[2] > (int64_t(1) << 31)) return "settings: Dense.Objects.Size: more than 2^31 voxels";
+  p.trunc = (float)get(raw, "Dense.Objects.Truncation", p.trunc); p.max_depth = (float)get(raw, "Dense.Objects.MaxDepth", p.max_depth);
+  const double ints[4] = {get(raw, "Dense.Objects.MaxObjects", o.maxObjects), get(raw, "Dense.Objects.MinPixels", o.minPixels), get(raw, "Dense.Objects.MinFrames", o.minFrames),
+                          get(raw, "Dense.Objects.MinWeight", ds.s.minWeight)};
+  static const char* const int_keys[4] = {"MaxObjects", "MinPixels", "MinFrames", "MinWeight"};
+  for (int k = 0; k < 4; ++k) if (!whole(ints[k])) return std::string("settings: Dense.Objects.") + int_keys[k] + " must be a whole number";
+  o.maxObjects = (int)ints[0]; o.minPixels = (int)ints[1]; o.minFrames = (int)ints[2]; o.minWeight = (int)ints[3];
+  if (!std::isfinite(p.trunc) || !(p.trunc > 0)) return "settings: Dense.Objects.Truncation must be positive";
+  if (!std::isfinite(p.max_depth) || !(p.max_depth > p.min_depth)) return "settings: Dense.Objects.MaxDepth must be above Dense.MinDepth";
+  return ObjectMapper::Check(o);
+}
 std::string read_dense_settings(const std::string& path, const TrackingSettings& t, const std::map<std::string, double>& raw, DenseSettings& ds) {
   std::map<std::string, std::vector<double> > lists;
   read_settings_lists(path, lists);
@@ -238,7 +269,9 @@ std::string read_dense_settings(const std::string& path, const TrackingSettings&
   const double max_dist = get(raw, "Dense.Align.MaxDist", p.trunc);
   if (!std::isfinite(max_dist) || !(max_dist > 0) || !((float)max_dist > 0) || !std::isfinite((float)max_dist)) return "settings: Dense.Align.MaxDist must be positive";
   s.alignIterations = (int)al[0]; s.alignSubsample = (int)al[1]; s.alignMinPixels = (int)al[2]; s.alignApply = al[3] == 1; s.alignMaxDist = (float)max_dist;
-  return DenseMapper::CheckAlign(s);
+  const std::string align_err = DenseMapper::CheckAlign(s);
+  if (!align_err.empty()) return align_err;
+  return read_dense_objects_settings(t, raw, lists, ds);
 }
 }  // namespace
 
@@ -301,6 +334,7 @@ Tracking::Tracking(System*, Map* pMap, const std::string& strSettingPath, const 
     // a context of its own: the fusion waits for nothing the frame step has queued, and nothing of the frame step waits for it
     if (vdo_ctx_create(dev ? std::atoi(dev) : 0, nullptr, &ctx_dense_) != VDO_OK) throw std::runtime_error(std::string("VDO_SLAM::Tracking: no HIP device: ") + vdo_last_error());
     dense_.reset(new DenseMapper(ctx_dense_, p.width, p.height, dense.s));
+    if (dense.objects) objects_.reset(new ObjectMapper(ctx_dense_, p.width, p.height, dense.os));
   }
   if (mSensor == System::STEREO) {
     const vdo_stereo_params d = StereoMatcher::DefaultParams();
@@ -331,6 +365,7 @@ Tracking::Tracking(System*, Map* pMap, const std::string& strSettingPath, const 
 }
 
 Tracking::~Tracking() {
+  objects_.reset();
   dense_.reset();
   if (ctx_dense_) vdo_ctx_destroy(ctx_dense_);
   pipe_.reset();
@@ -674,6 +709,16 @@ cv::Mat Tracking::FinishFrame(const cv::Mat& mTcw_gt, std::chrono::steady_clock:
       if (dense_->settings().alignApply && dense_align_.status == 0) std::memcpy(dense_fused_, aligned, sizeof dense_fused_);
     }
     dense_->FuseFrame(pipe_->LastImages(), dense_fused_, dense_counts_);
+    // the object models: the same images and pose, and the motions of the step that made them (FramePipeline::FinishObjects: mod_label, the label in
+    // the repaired mask, the world-frame motion from the last frame).  With deferred objects the motions at hand are the last frame's: nothing is fused.
+    if (objects_ && !pipe_->params().defer_objects) {
+      std::vector<ObjectMapper::Motion> motions(pipe_->motions_.size());
+      for (size_t a = 0; a < motions.size(); ++a) {
+        motions[a].mod_label = pipe_->motions_[a].mod_label; motions[a].sem_label = pipe_->motions_[a].sem_label;
+        for (int i = 0; i < 16; ++i) motions[a].H[i] = (double)pipe_->motions_[a].H[i];
+      }
+      objects_->FuseFrame(f_id, pipe_->LastImages(), dense_fused_, motions);
+    }
   }
   // full batch optimisation after the last frame, KITTI only (Tracking.cc:1189-1210: `bGlobalBatch && mTestData==KITTI`)
   if (f_id == StopFrame && f_id > 1 && bGlobalBatch && mTestData == KITTI) {
@@ -858,6 +903,31 @@ bool System::SaveDenseMap(const std::string& path) {
   if (!d) { std::cerr << "VDO_SLAM::System::SaveDenseMap: no dense map (the settings file has no Dense.VoxelSize)" << std::endl; return false; }
   if (!d->SavePLY(path)) { std::cerr << "VDO_SLAM::System::SaveDenseMap: cannot write " << path << std::endl; return false; }
   return true;
+}
+
+bool System::SaveObjectMaps(const std::string& prefix) {
+  ObjectMapper* o = mpTracker->objects();
+  if (!o) { std::cerr << "VDO_SLAM::System::SaveObjectMaps: no object mapper (the settings file has no Dense.Objects.VoxelSize)" << std::endl; return false; }
+  if (!o->SaveModels(prefix)) { std::cerr << "VDO_SLAM::System::SaveObjectMaps: cannot write " << prefix << "_*" << std::endl; return false; }
+  return true;
+}
+
+bool System::RenderObjectView(int mod_label, const cv::Mat& Tcw, cv::Mat& depth, cv::Mat& normals) {
+  ObjectMapper* o = mpTracker->objects();
+  if (!o) return false;
+  if (Tcw.rows != 4 || Tcw.cols != 4 || Tcw.type() != cv::CV_32FC1) throw std::runtime_error("VDO_SLAM::System::RenderObjectView: Tcw must be a 4 x 4 CV_32F matrix");
+  float T[16];
+  for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) T[4 * r + c] = Tcw.at<float>(r, c);
+  return o->Render(mod_label, T, depth, normals);
+}
+
+int System::ObjectModelInfo(std::vector<std::array<long long, 4> >& rows, long long counts2[2]) {
+  ObjectMapper* o = mpTracker->objects();
+  rows.clear();
+  if (!o) return -1;
+  for (const ObjectMapper::Model& m : o->Models()) rows.push_back({(long long)m.mod_label, m.live ? 1LL : 0LL, (long long)m.frames, (long long)m.points.size()});
+  if (counts2) { counts2[0] = o->dropped(); counts2[1] = o->skipped(); }
+  return (int)rows.size();
 }
 
 bool System::RenderDenseView(const cv::Mat& Tcw, cv::Mat& depth, cv::Mat& normals) {
@@ -1141,6 +1211,61 @@ int host_settings_check_dense_align(const char* path, char* msg, int cap, double
     }
   }
   return err.empty() ? 0 : 1;
+}
+// the Dense.Objects.* keys as Tracking::Tracking reads them, without a GPU: 0 in order, 1 a settings error (text in msg), -2 no file.  out13 (may be null):
+// present (0 / 1: Dense.VoxelSize AND Dense.Objects.VoxelSize are in the file; the rest only then), VoxelSize, nx, ny, nz, Truncation, MinDepth, MaxDepth,
+// MaxWeight, MaxObjects, MinPixels, MinFrames, MinWeight
+int host_settings_check_dense_objects(const char* path, char* msg, int cap, double* out13) {
+  VDO_SLAM::TrackingSettings t{};
+  std::map<std::string, double> raw;
+  if (!VDO_SLAM::read_tracking_settings(path, t, &raw)) return -2;
+  VDO_SLAM::DenseSettings ds;
+  const std::string err = VDO_SLAM::read_dense_settings(path, t, raw, ds);
+  if (msg && cap > 0) std::snprintf(msg, (size_t)cap, "%s", err.c_str());
+  if (out13 && err.empty()) {
+    out13[0] = ds.present && ds.objects ? 1 : 0;
+    if (ds.present && ds.objects) {
+      const vdo_dense_params& p = ds.os.params;
+      const double v[12] = {p.voxel, (double)p.n[0], (double)p.n[1], (double)p.n[2], p.trunc, p.min_depth, p.max_depth, (double)p.max_weight, (double)ds.os.maxObjects,
+                            (double)ds.os.minPixels, (double)ds.os.minFrames, (double)ds.os.minWeight};
+      for (int i = 0; i < 12; ++i) out13[1 + i] = v[i];
+    }
+  }
+  return err.empty() ? 0 : 1;
+}
+// The motions of the last frame as the object mapper takes them (FramePipeline::motions_): mod_label, sem_label, n_inliers [cap] and H [cap][16];
+// returns their number (the first min(cap, n) are written).  host_system_motions above stays as it is.
+int host_system_object_motions(VDO_SLAM::System* s, int cap, int* mod_label, int* sem_label, int* n_inliers, float* H16) {
+  const auto& m = s->tracker()->pipeline()->motions_;
+  const int n = std::min(cap, (int)m.size());
+  for (int a = 0; a < n; ++a) { mod_label[a] = m[a].mod_label; sem_label[a] = m[a].sem_label; n_inliers[a] = m[a].n_inliers; std::memcpy(H16 + 16 * a, m[a].H, 64); }
+  return (int)m.size();
+}
+// System::ObjectModelInfo: rows [cap][4] = mod_label, live, frames fused, points (finished models first); counts2 (may be null): dropped, skipped.
+// Returns the number of models (the first min(cap, n) rows are written), -1 without an object mapper, -2 on a failure.
+int host_system_object_info(VDO_SLAM::System* s, int cap, long long* rows, long long* counts2) {
+  try {
+    std::vector<std::array<long long, 4> > r;
+    const int n = s->ObjectModelInfo(r, counts2);
+    for (int i = 0; i < n && i < cap; ++i) std::memcpy(rows + 4 * (size_t)i, r[i].data(), 4 * sizeof(long long));
+    return n;
+  } catch (const std::exception& e) { std::fprintf(stderr, "host_system_object_info: %s\n", e.what()); return -2; }
+}
+// System::SaveObjectMaps: 0, -1 without an object mapper or when a file cannot be written
+int host_system_save_object_maps(VDO_SLAM::System* s, const char* prefix) {
+  try { return s->SaveObjectMaps(prefix) ? 0 : -1; }
+  catch (const std::exception& e) { std::fprintf(stderr, "host_system_save_object_maps: %s\n", e.what()); return -1; }
+}
+// System::RenderObjectView: Tcw [16] world -> camera; depth [Camera.height][Camera.width], normals [Camera.height][Camera.width][3].  0, 1 without an
+// object mapper or a live model of that id (nothing is written), -1 on a failure
+int host_system_render_object_view(VDO_SLAM::System* s, int mod_label, const float* Tcw, float* depth, float* normals) {
+  try {
+    cv::Mat T(4, 4, cv::CV_32FC1, (void*)Tcw), D, N;
+    if (!s->RenderObjectView(mod_label, T, D, N)) return 1;
+    std::memcpy(depth, D.data, D.total() * sizeof(float));
+    std::memcpy(normals, N.data, N.total() * 3 * sizeof(float));
+  } catch (const std::exception& e) { std::fprintf(stderr, "host_system_render_object_view: %s\n", e.what()); return -1; }
+  return 0;
 }
 // The alignment of the last frame of a System with Dense.Align.Iterations > 0 (Tracking::dense_alignment): report11 = iterations, status, used,
 // rms_first, rms_last, xi (6); fused16 (may be null): the pose the frame was fused with.  0, 1 when there is none (nothing is written), -1 on a failure.

@@ -3,6 +3,7 @@
 // gate of the object tracker, Map bookkeeping, the batch optimisations and SaveResults' five text files (src/System.cc:75-100).  Visualisation (imTraj)
 // and metric printing are out of scope; the hot path is entirely behind FramePipeline.
 #pragma once
+#include <array>
 #include <chrono>
 #include <map>
 #include <memory>
@@ -13,6 +14,7 @@
 #include "Frame.h"
 #include "FramePipeline.h"
 #include "DenseMapper.h"
+#include "ObjectMapper.h"
 #include "InstanceLabeler.h"
 #include "StereoRectifier.h"
 #include "Map.h"
@@ -74,6 +76,9 @@ class Tracking {
   const vdo_align_report* dense_alignment() const { return dense_align_valid_ ? &dense_align_ : nullptr; }
   long long dense_alignments() const { return dense_align_count_; }      // frames aligned so far
   const float* dense_fused_pose() const { return dense_fused_; }
+  // The object mapper (settings keys Dense.Objects.*, System::SaveObjectMaps below): null without Dense.VoxelSize and Dense.Objects.VoxelSize.
+  // FinishFrame runs its frame right after the static map's, on the same context, with the pose that map was fused with and the step's motions.
+  ObjectMapper* objects() { return objects_.get(); }
   MotionSegmenter* motion() { return motion_.get(); }    // null before the first GrabImageStereoVideo
   // What the last GrabImageStereoVideo found: ego-motion inliers, moving pixels after the vote (0 when the ego-motion failed), labels
   const int* video_counts() const { return video_counts_; }
@@ -131,6 +136,7 @@ class Tracking {
   int rect_border_ = 0, rect_classes_ = 0;               // Rectify.Border, Rectify.Classes
   std::unique_ptr<DenseMapper> dense_;                   // Dense.VoxelSize present: the dense map of the static scene
   vdo_ctx* ctx_dense_ = nullptr;                         // its context (made only with the mapper)
+  std::unique_ptr<ObjectMapper> objects_;                // Dense.Objects.VoxelSize present as well: a volume per tracked object, on ctx_dense_
   int64_t dense_counts_[3] = {0, 0, 0};
   vdo_align_report dense_align_{};                       // Dense.Align.Iterations > 0: the last frame against the map
   bool dense_align_valid_ = false;
@@ -203,7 +209,7 @@ class System {
   // leaves it is kept as points on the host.  SaveDenseMap writes those points and the surface in the volume as a binary little-endian PLY (x, y, z,
   // nx, ny, nz, weight); false without a mapper or when the file cannot be written.  Limits: the map is fused with the tracker's per-frame poses - or,
   // with Dense.Align.Apply, with those poses refined against the map itself, which the tracker never sees - and is not re-fused after a bundle adjustment; an edge between a leaving and a staying voxel can be lost when the volume moves towards a negative axis;
-  // objects are not reconstructed; with semantic masks on the RGBD path parked instances are left out too.
+  // objects are left out of this map (their own models: SaveObjectMaps below); with semantic masks on the RGBD path parked instances are left out too.
   bool SaveDenseMap(const std::string& path);
   // What the dense map predicts a camera at Tcw (4 x 4 CV_32F, world -> camera) would see (DenseMapper::Render, vdo_raycast_render): depth CV_32FC1 in
   // metres, 0 where no surface is met, and normals CV_32FC3 in the world frame, towards free space, 0 where the surface has an unseen neighbour - at the
@@ -224,6 +230,25 @@ class System {
   // The report of the last alignment - of AlignDenseView, or of the last frame with Dense.Align.Iterations > 0, whichever came later.  False when
   // there has been none.
   bool LastDenseAlignment(vdo_align_report& report) const;
+  // A dense model per tracked object (ObjectMapper).  Settings keys, read only with Dense.VoxelSize; the object mapper exists only if
+  // Dense.Objects.VoxelSize (the voxel edge in metres) is present as well, and without it nothing changes: Dense.Objects.Size [nx, ny, nz] ([96, 64, 96]),
+  // Dense.Objects.Truncation (4 x voxel), Dense.Objects.MaxDepth (ThDepthOBJ; above Dense.MinDepth, which is the objects' too), Dense.Objects.MaxObjects
+  // (16; 1..64 live models), Dense.Objects.MinPixels (200: the pixels a label needs to start a model or to be fused), Dense.Objects.MinFrames (3: a
+  // retired model fused in fewer frames is dropped), Dense.Objects.MinWeight (Dense.MinWeight); the weight cap is Dense.MaxWeight.  A value outside its
+  // range is a settings error.  Every Track* entry runs the object stage right after the static map's frame, with the pose that map was fused with
+  // and the step's object motions (mod_label: the tracking id; sem_label: the label the object's pixels carry in the frame's repaired mask; H: the
+  // world-frame motion from the last frame).  Limits: a model is fused with the tracker's per-frame motions and not re-fused after a bundle
+  // adjustment; free space is not carved from other labels' pixels; an object that comes back under a new tracking id starts a new model; in the
+  // shell's throughput mode (the object stage of a frame ends inside the next call) the motions at hand are the last frame's, and the object stage is skipped.
+  // SaveObjectMaps: <prefix>_<mod_label>.ply per finished and live model in the OBJECT frame and <prefix>_poses.txt (frame, mod_label, the 16
+  // entries of Two); false without an object mapper or when a file cannot be written.
+  bool SaveObjectMaps(const std::string& prefix);
+  // What the model of the live object mod_label predicts a camera at Tcw (4 x 4 CV_32F, world -> camera) would see: depth CV_32FC1, normals CV_32FC3 in
+  // the object frame.  False without an object mapper or a live model of that id.
+  bool RenderObjectView(int mod_label, const cv::Mat& Tcw, cv::Mat& depth, cv::Mat& normals);
+  // The finished models, then the live ones: per model mod_label, live (0 / 1), frames fused, points.  Returns their number, -1 without an object
+  // mapper; counts2 (may be null): objects dropped (MinFrames) and skipped (MaxObjects, MinPixels) so far.
+  int ObjectModelInfo(std::vector<std::array<long long, 4> >& rows, long long counts2[2] = nullptr);
   void SaveResults(const std::string& filename);
   Map* map();                          // brought up to date from the pipeline's GraphStore on access
   Tracking* tracker() { return mpTracker; }

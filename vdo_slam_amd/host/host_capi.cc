@@ -13,6 +13,7 @@
 #include "Frame.h"
 #include "Map.h"
 #include "MotionSegmenter.h"
+#include "ObjectMapper.h"
 #include "ORBextractor.h"
 #include "ORBmatcher.h"
 #include "Optimizer.h"
@@ -399,6 +400,36 @@ long long host_dense_fuse(const float* depth, const int* mask, const float* Tcw,
     if (info2) { info2[0] = m.recenters(); info2[1] = (long long)m.kept().size(); }
     return (long long)m.AllPoints().size();
   } catch (const std::exception& e) { std::fprintf(stderr, "host_dense_fuse: %s\n", e.what()); return -1; }
+}
+
+// ObjectMapper::Fuse on k host frames (depth [k][h][w] metres, mask [k][h][w], Tcw [k][16] world -> camera).  Frame i has n_mot[i] motions, one after
+// the other in mod_label / sem_label / H ([16] each, float).  params: every object's volume (the origin is not read); life5: MaxObjects, MinPixels,
+// MinFrames, MinWeight, MaxLabels.  prefix (may be null): ObjectMapper::SaveModels after the last frame.  rows [cap][4] (may be null): mod_label, live,
+// frames fused, points of every model after the last frame; counts2 (may be null): dropped, skipped.  Returns the number of models, -1 on a failure.
+int host_objects_fuse(const float* depth, const int* mask, const float* Tcw, int k, int w, int h, const vdo_dense_params* params, const int* life5, const int* n_mot,
+                      const int* mod_label, const int* sem_label, const float* H, const char* prefix, int cap, long long* rows, long long* counts2) {
+  try {
+    ObjectMapper::Settings s;
+    s.params = *params; s.maxObjects = life5[0]; s.minPixels = life5[1]; s.minFrames = life5[2]; s.minWeight = life5[3]; s.maxLabels = life5[4];
+    ObjectMapper m(nullptr, w, h, s);
+    size_t at = 0;
+    for (int i = 0; i < k; ++i) {
+      cv::Mat D(h, w, cv::CV_32FC1, (void*)(depth + (size_t)i * w * h)), M(h, w, cv::CV_32SC1, (void*)(mask + (size_t)i * w * h));
+      std::vector<ObjectMapper::Motion> motions((size_t)n_mot[i]);
+      for (int a = 0; a < n_mot[i]; ++a, ++at) {
+        motions[a].mod_label = mod_label[at]; motions[a].sem_label = sem_label[at];
+        for (int q = 0; q < 16; ++q) motions[a].H[q] = (double)H[16 * at + q];
+      }
+      m.Fuse(i, D, M, Tcw + 16 * (size_t)i, motions);
+    }
+    if (prefix && !m.SaveModels(prefix)) return -1;
+    const std::vector<ObjectMapper::Model> all = m.Models();
+    for (size_t i = 0; rows && i < all.size() && (int)i < cap; ++i) {
+      rows[4 * i] = all[i].mod_label; rows[4 * i + 1] = all[i].live ? 1 : 0; rows[4 * i + 2] = all[i].frames; rows[4 * i + 3] = (long long)all[i].points.size();
+    }
+    if (counts2) { counts2[0] = m.dropped(); counts2[1] = m.skipped(); }
+    return (int)all.size();
+  } catch (const std::exception& e) { std::fprintf(stderr, "host_objects_fuse: %s\n", e.what()); return -1; }
 }
 
 // host_dense_fuse's frames, then DenseMapper::Render at T_view (16 floats, world -> camera): depth [h][w], normals [h][w][3], weight [h][w] (may be

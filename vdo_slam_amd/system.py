@@ -341,6 +341,50 @@ class System:
             raise K.VdoError("System.align_dense_view failed")
         return out.reshape(4, 4), self._align_report(r)
 
+    def object_motions(self, cap=64):
+        """The motions of the last frame as the object mapper takes them (host_system_object_motions): [(mod_label, sem_label, n_inliers, H [4, 4] f32)]
+        in the tracker's order - mod_label the tracking id, sem_label the label the object's pixels carry in the frame's mask, H the world-frame motion
+        from the last frame to this one."""
+        L = self._L
+        L.host_system_object_motions.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        mod = np.zeros(cap, np.int32); sem = np.zeros(cap, np.int32); inl = np.zeros(cap, np.int32); H = np.zeros((cap, 4, 4), np.float32)
+        n = min(cap, L.host_system_object_motions(self._h, cap, _ptr(mod), _ptr(sem), _ptr(inl), _ptr(H)))
+        return [(int(mod[a]), int(sem[a]), int(inl[a]), H[a].copy()) for a in range(n)]
+
+    def object_info(self, cap=256):
+        """System::ObjectModelInfo: dict(models = [(mod_label, live, frames fused, points)] - finished first, then live -, dropped, skipped), or None
+        when the system has no object mapper (no Dense.Objects.VoxelSize)."""
+        L = self._L
+        L.host_system_object_info.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        rows = np.zeros((cap, 4), np.int64); counts = np.zeros(2, np.int64)
+        n = L.host_system_object_info(self._h, cap, _ptr(rows), _ptr(counts))
+        if n == -1:
+            return None
+        if n < 0:
+            raise K.VdoError("System.object_info failed")
+        return dict(models=[(int(r[0]), bool(r[1]), int(r[2]), int(r[3])) for r in rows[:min(n, cap)]], dropped=int(counts[0]), skipped=int(counts[1]))
+
+    def save_object_maps(self, prefix):
+        """System::SaveObjectMaps: <prefix>_<mod_label>.ply per model in the object frame and <prefix>_poses.txt.  False without an object mapper or
+        when a file cannot be written."""
+        L = self._L
+        L.host_system_save_object_maps.argtypes = [C.c_void_p, C.c_char_p]
+        return L.host_system_save_object_maps(self._h, str(prefix).encode()) == 0
+
+    def render_object_view(self, mod_label, T, w, h):
+        """System::RenderObjectView: what the model of the live object mod_label predicts a camera at T (4 x 4, world -> camera) would see, at the
+        camera's image size (w, h): (depth [h, w] f32, normals [h, w, 3] f32 in the object frame), or None without an object mapper or such a model."""
+        L = self._L
+        L.host_system_render_object_view.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        Tc = np.ascontiguousarray(np.asarray(T, np.float32).reshape(16))
+        d = np.zeros((h, w), np.float32); n = np.zeros((h, w, 3), np.float32)
+        rc = L.host_system_render_object_view(self._h, int(mod_label), _ptr(Tc), _ptr(d), _ptr(n))
+        if rc == 1:
+            return None
+        if rc != 0:
+            raise K.VdoError("System.render_object_view failed")
+        return d, n
+
     def last_depth_mask(self, w, h):
         """The resident depth (metres) and mask of the last frame as the step left them - what the dense mapper fused: (depth [h, w] f32, mask [h, w] i32)"""
         L = self._L
