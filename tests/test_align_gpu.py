@@ -241,6 +241,33 @@ def test_host_strided_device_and_frame_inputs_borrowed_copied_and_rendered_model
     al.close()
 
 
+def test_solve_and_linearise_of_strided_host_and_device_sources(ctx, plane_model):
+    """Both entries that take images bring them to the device the same way: host rows with a stride, device rows with a stride (depth AND mask) and
+    packed device images (read where they lie) give the sums, the counts and the solve of the packed host call, bit for bit"""
+    import torch
+    M = plane_model
+    W, H = 13, 7
+    D, mask, K4, T = _frame_for(M, W, H, 5, noise=0.004)
+    mask[3, 4] = 5
+    al = _aligner(ctx, W, H, K4, max_iterations=3)
+    _set_any(al, M)
+    want = al.linearise(D, mask, T)
+    want_T, want_rep, want_trace = al.solve(D, mask, T)
+    assert want[1][0] > 0 and want[1].sum() == W * H and want_rep["iterations"] >= 1
+    wide_d = np.full((H, 16), np.nan, F); wide_d[:, :W] = D
+    wide_m = np.full((H, 16), 9, np.int32); wide_m[:, :W] = mask
+    td, tm, twd, twm = (torch.from_numpy(a.copy()).cuda() for a in (D, mask, wide_d, wide_m))
+    torch.cuda.synchronize()
+    forms = [("strided host", lambda f, g: f(wide_d[:, :W], wide_m[:, :W], T)), ("strided device", lambda f, g: g(twd.data_ptr(), 16, twm.data_ptr(), 16, True, T)),
+             ("packed device", lambda f, g: g(td.data_ptr(), W, tm.data_ptr(), W, True, T))]
+    for what, call in forms:
+        _same(call(al.linearise, al.linearise_raw), want, what)
+        got_T, rep, trace = call(al.solve, al.solve_raw)
+        assert np.array_equal(_bits(got_T), _bits(want_T)) and np.array_equal(_bits(trace), _bits(want_trace)), what
+        assert rep["iterations"] == want_rep["iterations"] and rep["status"] == want_rep["status"] and rep["used"] == want_rep["used"], what
+    al.close()
+
+
 # ---- skips, each through its count -----------------------------------------------------------------------------------------------------------------------
 def test_skips(ctx, plane_model):
     M = plane_model

@@ -312,6 +312,33 @@ def test_padded_strides_and_memory_spaces(ctx):
     m.close()
 
 
+def test_egomotion_of_strided_host_and_device_sources(ctx):
+    """vdo_motionseg_egomotion brings its images to the device as vdo_motionseg_compute does: host rows with a stride, device rows with a stride and
+    packed device images (read where they lie) give the sample lists, the pose and the counts of the packed host call, bit for bit"""
+    import torch
+    W, H = 13, 7
+    d0, _, flow = _noise(H, W, 51)
+    valid = (np.random.default_rng(4).random((H, W)) < 0.8).astype(np.uint8)
+    kw = dict(step=1, max_iterations=20, threshold=1.0, confidence=0.98, min_inliers=5)
+    m = _segmenter(ctx, H, W)
+    want = m.egomotion(d0, flow, valid, **kw)
+    want_X, want_uv = m.samples()
+    assert want[1][0] > 0 and len(want_X) == want[1][0]
+    p0 =np.full((H, 16), 7, F); p0[:, :W] = d0
+    pf = np.full((H, 16, 2), 7, F); pf[:, :W] = flow
+    pv = np.full((H, 16), 7, np.uint8); pv[:, :W] = valid
+    t0, tf, tv, tp0, tpf, tpv = (torch.from_numpy(a).cuda() for a in (d0, flow, valid, p0, pf, pv))
+    torch.cuda.synchronize()
+    assert tf.data_ptr() % 8 == 0
+    for what, call in [("strided host", lambda: m.egomotion(p0[:, :W], pf[:, :W], pv[:, :W], **kw)),
+                       ("strided device", lambda: m.egomotion_raw(tp0.data_ptr(), 16, tpf.data_ptr(), 32, tpv.data_ptr(), 16, True, **kw)),
+                       ("packed device", lambda: m.egomotion_raw(t0.data_ptr(), W, tf.data_ptr(), 2 * W, tv.data_ptr(), W, True, **kw))]:
+        T, out = call()
+        X, uv = m.samples()
+        assert np.array_equal(X, want_X) and np.array_equal(uv, want_uv) and out == want[1] and np.array_equal(T, want[0]), what
+    m.close()
+
+
 def test_the_handles_own_device_images_and_no_shared_state(ctx):
     import torch
     W, H = 70, 18

@@ -177,6 +177,40 @@ def test_a_mixed_batch_against_the_restatement_and_the_dense_mapper(ctx, cull):
     st.close()
 
 
+def test_integrate_of_strided_host_and_device_sources(ctx):
+    """vdo_objects_integrate brings its images to the device as vdo_objects_stats does: host rows with a stride, device rows with a stride and packed
+    device images (read where they lie) give the words and the counts of the packed host call, bit for bit"""
+    import torch
+    from vdo_slam_amd.dense import DenseMapper
+    w, h, k4, n = 13, 7, (10.0, 9.0, 6.2, 3.1), (6, 5, 4)
+    rng = np.random.default_rng(3)
+    depth = rng.uniform(0.8, 1.2, (h, w)).astype(F); depth[2, 6] = np.nan
+    mask = np.repeat((np.arange(w) // 4).astype(np.int32)[None, :], h, 0)    # stripes of the labels 0 .. 3; the volumes see the columns 3 .. 9
+    wide_d = np.full((h, 16), 1.0, F); wide_d[:, :w] = depth
+    wide_m = np.full((h, 16), 1, np.int32); wide_m[:, :w] = mask
+    T = np.stack([np.eye(4, dtype=F)] * 2)
+    st = _stage(ctx, w, h, k4, max_labels=4, max_batch=2, **PRM)
+
+    def run(call):
+        maps = [DenseMapper(ctx, w, h, n, 0.1, k4, origin=(-3, -2, 8), min_depth=0.0, max_depth=10.0, stage_points=64) for _ in range(2)]
+        out = call(maps)
+        words = [m.volume()[0] for m in maps]
+        for m in maps:
+            m.close()
+        return out, words
+
+    want_out, want_words = run(lambda maps: st.integrate(depth, mask, maps, [1, 2], T))
+    assert (want_out[:, 0] > 0).all() and all(wd.any() for wd in want_words)
+    td, tm, twd, twm = (torch.from_numpy(a).cuda() for a in (depth, mask, wide_d, wide_m))
+    torch.cuda.synchronize()
+    for what, call in [("strided host", lambda maps: st.integrate(wide_d[:, :w], wide_m[:, :w], maps, [1, 2], T)),
+                       ("strided device", lambda maps: st.integrate_raw(twd.data_ptr(), 16, twm.data_ptr(), 16, True, maps, [1, 2], T)),
+                       ("packed device", lambda maps: st.integrate_raw(td.data_ptr(), w, tm.data_ptr(), w, True, maps, [1, 2], T))]:
+        out, words = run(call)
+        assert np.array_equal(out, want_out) and all(np.array_equal(a, b) for a, b in zip(words, want_words)), what
+    st.close()
+
+
 @pytest.mark.parametrize("cull", [1, 0])
 def test_a_batch_of_max_batch(ctx, cull):
     depth, mask = _images(7, n_labels=5)

@@ -215,6 +215,58 @@ def _declare(L):
         getattr(L, f).restype = C.c_int
 
 
+_declared = set()
+
+
+def declare(L, prefix, argtypes):
+    """Once per prefix: the ``argtypes`` of ``L.<prefix><name>`` for every name of the dict, with ``restype = c_int``; returns L."""
+    if prefix not in _declared:
+        for name, args in argtypes.items():
+            fn = getattr(L, prefix + name)
+            fn.argtypes = args; fn.restype = C.c_int
+        _declared.add(prefix)
+    return L
+
+
+def rows(a, name, dtype, shape, unit=None):
+    """A host image whose rows the C entry can read at their own stride: (array kept alive, address, stride in units of ``unit`` bytes - an element's
+    when None).  Everything within a row must be packed; a trailing channel axis belongs to the row."""
+    a = np.asarray(a)
+    if a.dtype != dtype or a.shape != shape:
+        raise ValueError(f"{name}: {a.dtype} {a.shape}, expected {np.dtype(dtype).name} {shape}")
+    unit = unit or a.itemsize
+    packed = a.strides[1:] == np.empty(shape, dtype).strides[1:]
+    if not packed or a.strides[0] < a.shape[1] * a.strides[1] or a.strides[0] % unit:
+        a = np.ascontiguousarray(a)
+    return a, a.ctypes.data, a.strides[0] // unit
+
+
+class StageHandle:
+    """What the handle classes of the image stages share: the library, the handle, ``timing()``, ``close()`` and ``__del__``.  ``_prefix`` names the
+    stage's entries: ``<prefix>destroy`` and ``<prefix>last_timing``."""
+    _prefix = None
+    _L = None
+    _h = None
+
+    def __init__(self, L):
+        self._L = L
+        self._h = C.c_void_p()
+
+    def timing(self):
+        """(wall ms of the call, device ms by events) of the last timed call"""
+        ms = (C.c_double * 2)()
+        check(getattr(self._L, self._prefix + "last_timing")(self._h, ms))
+        return ms[0], ms[1]
+
+    def close(self):
+        if self._h:
+            getattr(self._L, self._prefix + "destroy")(self._h); self._h = C.c_void_p()
+
+    def __del__(self):
+        try: self.close()
+        except Exception: pass
+
+
 class VdoError(RuntimeError):
     code = None        # the library's return code (VDO_ERR_* of include/vdo_slam_hip.h)
 

@@ -7,7 +7,6 @@ import ctypes as C
 import numpy as np
 
 from . import _capi as K
-from . import dense as _dense
 from . import raycast as _raycast
 
 
@@ -21,29 +20,21 @@ class AlignReportC(C.Structure):
 
 
 TRACE_ROW = 16 + 28 + 5
-_declared = False
-
-
 def _lib():
-    global _declared
-    L = _raycast._lib()
-    if not _declared:
-        vp, i64 = C.c_void_p, C.c_int64
-        L.vdo_align_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(AlignParamsC), C.POINTER(vp)]
-        L.vdo_align_destroy.argtypes = [vp]
-        L.vdo_align_set_model.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int]
-        L.vdo_align_set_model_from_view.argtypes = [vp, vp, vp, vp]
-        L.vdo_align_linearise.argtypes = [vp, vp, i64, vp, i64, C.c_int, vp, vp, vp]
-        L.vdo_align_linearise_frame.argtypes = [vp, vp, vp, vp, vp]
-        L.vdo_align_step.argtypes = [vp, i64, i64, vp, vp, vp, vp]
-        L.vdo_align_solve.argtypes = [vp, vp, i64, vp, i64, C.c_int, vp, vp, vp, vp]
-        L.vdo_align_solve_frame.argtypes = [vp, vp, vp, vp, vp, vp]
-        L.vdo_align_get_rows.argtypes = [vp, vp]
-        L.vdo_align_last_timing.argtypes = [vp, K.c_double_p]
-        for f in ("create", "destroy", "set_model", "set_model_from_view", "linearise", "linearise_frame", "step", "solve", "solve_frame", "get_rows", "last_timing"):
-            getattr(L, "vdo_align_" + f).restype = C.c_int
-        _declared = True
-    return L
+    vp, i64 = C.c_void_p, C.c_int64
+    return K.declare(_raycast._lib(), "vdo_align_", {
+        "create": [vp, C.c_int, C.c_int, C.POINTER(AlignParamsC), C.POINTER(vp)],
+        "destroy": [vp],
+        "set_model": [vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int],
+        "set_model_from_view": [vp, vp, vp, vp],
+        "linearise": [vp, vp, i64, vp, i64, C.c_int, vp, vp, vp],
+        "linearise_frame": [vp, vp, vp, vp, vp],
+        "step": [vp, i64, i64, vp, vp, vp, vp],
+        "solve": [vp, vp, i64, vp, i64, C.c_int, vp, vp, vp, vp],
+        "solve_frame": [vp, vp, vp, vp, vp, vp],
+        "get_rows": [vp, vp],
+        "last_timing": [vp, K.c_double_p],
+    })
 
 
 def params(K4, min_depth=0.0, max_depth=40.0, max_dist=0.4, subsample=1, min_pixels=6, max_iterations=10, eps=1e-5, keep_rows=False) -> AlignParamsC:
@@ -70,12 +61,12 @@ def _report(r):
     return dict(iterations=r.iterations, status=r.status, used=r.used, rms_first=r.rms_first, rms_last=r.rms_last, xi=np.array(list(r.xi), np.float64))
 
 
-class Aligner:
+class Aligner(K.StageHandle):
     """``vdo_align`` handle for width x height frames with intrinsics K4 = (fx, fy, cx, cy).  Every device buffer is allocated here."""
+    _prefix = "vdo_align_"
 
     def __init__(self, ctx, width, height, K4, **prm):
-        self._L = _lib()
-        self._h = C.c_void_p()
+        super().__init__(_lib())
         self._ctx = ctx
         self._model = None                                      # what a borrowed or rendered model needs kept alive
         self.width, self.height = int(width), int(height)
@@ -115,8 +106,8 @@ class Aligner:
 
     def linearise(self, depth, mask, T):
         """Host images (row strides are honoured); -> (sums, counts: used, no depth, masked, no model, far)"""
-        d, pd, sd = _dense._rows(depth, "depth", np.float32, (self.height, self.width))
-        m, pm, sm = _dense._rows(mask, "mask", np.int32, (self.height, self.width)) if mask is not None else (None, None, 0)
+        d, pd, sd = K.rows(depth, "depth", np.float32, (self.height, self.width))
+        m, pm, sm = K.rows(mask, "mask", np.int32, (self.height, self.width)) if mask is not None else (None, None, 0)
         return self.linearise_raw(pd, sd, pm, sm, False, T)
 
     def linearise_frame(self, frame_handle, T):
@@ -136,8 +127,8 @@ class Aligner:
         return out.reshape(4, 4), _report(rep), trace[:rep.iterations]
 
     def solve(self, depth, mask, T_init):
-        d, pd, sd = _dense._rows(depth, "depth", np.float32, (self.height, self.width))
-        m, pm, sm = _dense._rows(mask, "mask", np.int32, (self.height, self.width)) if mask is not None else (None, None, 0)
+        d, pd, sd = K.rows(depth, "depth", np.float32, (self.height, self.width))
+        m, pm, sm = K.rows(mask, "mask", np.int32, (self.height, self.width)) if mask is not None else (None, None, 0)
         return self.solve_raw(pd, sd, pm, sm, False, T_init)
 
     def solve_frame(self, frame_handle, T_init):
@@ -152,16 +143,6 @@ class Aligner:
         K.check(self._L.vdo_align_get_rows(self._h, r.ctypes.data))
         return r
 
-    def timing(self):
-        ms = (C.c_double * 2)()
-        K.check(self._L.vdo_align_last_timing(self._h, ms))
-        return ms[0], ms[1]
-
     def close(self):
-        if self._h:
-            self._L.vdo_align_destroy(self._h); self._h = C.c_void_p()
+        super().close()
         self._model = None
-
-    def __del__(self):
-        try: self.close()
-        except Exception: pass

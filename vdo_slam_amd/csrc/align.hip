@@ -20,7 +20,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
-#include <chrono>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -28,6 +27,7 @@
 #include "../../include/vdo_slam_hip.h"
 #include "ctx.hpp"
 #include "frame_images.hpp"
+#include "stage.hpp"
 #include "dense.hpp"
 
 namespace vdo {
@@ -174,10 +174,6 @@ __global__ __launch_bounds__(256) void k_al_tree(const double* __restrict__ in, 
   out[(size_t)blockIdx.x * kAlVals + term] = r[0];
 }
 
-static int al_check_hip(const char* who, hipError_t e) { return e == hipSuccess ? VDO_OK : set_error(VDO_ERR_NO_DEVICE, "%s: %s", who, hipGetErrorString(e)); }
-
-static bool al_good(float v) { return std::fabs(v) <= FLT_MAX; }
-
 static int al_pow2(int n) { int p = 1; while (p < n) p <<= 1; return p; }
 
 }  // namespace vdo
@@ -198,8 +194,7 @@ struct vdo_align {
   double* d_part[2] = {nullptr, nullptr};                 // [tiles][32] the tile partials; [max(P / 256, 1)][32] the level above; then in turns
   float* d_rows = nullptr;                                // [Hs][Ws][8] with keep_rows
   double* h_sums = nullptr;                               // pinned, [32]
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  double ms[2] = {0, 0};
+  vdo::StageTimer tm;
 };
 
 using namespace vdo;
@@ -207,8 +202,7 @@ using namespace vdo;
 static void al_free(vdo_align* h) {
   hipFree(h->d_depth); hipFree(h->d_mask); hipFree(h->d_mdepth); hipFree(h->d_mgrad); hipFree(h->d_part[0]); hipFree(h->d_part[1]); hipFree(h->d_rows);
   if (h->h_sums) hipHostFree(h->h_sums);
-  if (h->ev0) hipEventDestroy(h->ev0);
-  if (h->ev1) hipEventDestroy(h->ev1);
+  h->tm.destroy();
   delete h;
 }
 
@@ -219,19 +213,17 @@ extern "C" int vdo_align_create(vdo_ctx* ctx, int width, int height, const vdo_a
   if (!p) return set_error(VDO_ERR_INVALID, "%s: params is null", who);
   if (width < 1) return set_error(VDO_ERR_INVALID, "%s: width %d < 1", who, width);
   if (height < 1) return set_error(VDO_ERR_INVALID, "%s: height %d < 1", who, height);
-  for (int k = 0; k < 4; ++k) if (!al_good(p->K[k])) return set_error(VDO_ERR_INVALID, "%s: K[%d] is not finite", who, k);
-  if (!(p->K[0] > 0.f) || !(p->K[1] > 0.f)) return set_error(VDO_ERR_INVALID, "%s: K: fx %g, fy %g must be positive", who, (double)p->K[0], (double)p->K[1]);
-  if (!al_good(p->min_depth) || !(p->min_depth >= 0.f)) return set_error(VDO_ERR_INVALID, "%s: min_depth %g must be finite and >= 0", who, (double)p->min_depth);
-  if (!al_good(p->max_depth) || !(p->max_depth > p->min_depth)) return set_error(VDO_ERR_INVALID, "%s: max_depth %g must be finite and above min_depth %g", who, (double)p->max_depth, (double)p->min_depth);
-  if (!al_good(p->max_dist) || !(p->max_dist > 0.f)) return set_error(VDO_ERR_INVALID, "%s: max_dist %g must be positive and finite", who, (double)p->max_dist);
+  int rc = check_intrinsics(who, "K", p->K);
+  if (rc == VDO_OK) rc = check_depth_range(who, p->min_depth, p->max_depth);
+  if (rc != VDO_OK) return rc;
+  if (!is_finite(p->max_dist) || !(p->max_dist > 0.f)) return set_error(VDO_ERR_INVALID, "%s: max_dist %g must be positive and finite", who, (double)p->max_dist);
   if (p->subsample < 1 || p->subsample > 8) return set_error(VDO_ERR_INVALID, "%s: subsample %d outside 1..8", who, p->subsample);
   if (p->min_pixels < 6) return set_error(VDO_ERR_INVALID, "%s: min_pixels %d < 6", who, p->min_pixels);
   if (p->max_iterations < 1 || p->max_iterations > 64) return set_error(VDO_ERR_INVALID, "%s: max_iterations %d outside 1..64", who, p->max_iterations);
-  if (!al_good(p->eps) || !(p->eps >= 0.f)) return set_error(VDO_ERR_INVALID, "%s: eps %g must be finite and >= 0", who, (double)p->eps);
+  if (!is_finite(p->eps) || !(p->eps >= 0.f)) return set_error(VDO_ERR_INVALID, "%s: eps %g must be finite and >= 0", who, (double)p->eps);
   if (p->keep_rows != 0 && p->keep_rows != 1) return set_error(VDO_ERR_INVALID, "%s: keep_rows %d not 0 or 1", who, p->keep_rows);
-  if ((int64_t)width * height > kDnMaxPixels || width > kDnMaxImageSide || height > kDnMaxImageSide)
-    return set_error(VDO_ERR_UNSUPPORTED, "%s: width x height = %d x %d exceeds 2^26 pixels or 2^24 on a side", who, width, height);
-  const int rc = ctx_bind(ctx);
+  rc = check_image_size(who, "width x height =", width, height);
+  if (rc == VDO_OK) rc = ctx_bind(ctx);
   if (rc != VDO_OK) return rc;
   vdo_align* h = new vdo_align;
   h->ctx = ctx; h->W = width; h->H = height; h->p = *p;
@@ -246,8 +238,7 @@ extern "C" int vdo_align_create(vdo_ctx* ctx, int width, int height, const vdo_a
   bool ok = hipMalloc((void**)&h->d_depth, h->npix * sizeof(float)) == hipSuccess && hipMalloc((void**)&h->d_mask, h->npix * sizeof(int32_t)) == hipSuccess &&
             hipMalloc((void**)&h->d_mdepth, h->npix * sizeof(float)) == hipSuccess && hipMalloc((void**)&h->d_mgrad, h->npix * 3 * sizeof(float)) == hipSuccess &&
             hipMalloc((void**)&h->d_part[0], (size_t)a.tiles * kAlVals * sizeof(double)) == hipSuccess && hipMalloc((void**)&h->d_part[1], n1 * kAlVals * sizeof(double)) == hipSuccess &&
-            hipHostMalloc((void**)&h->h_sums, kAlVals * sizeof(double), hipHostMallocDefault) == hipSuccess && hipEventCreate(&h->ev0) == hipSuccess &&
-            hipEventCreate(&h->ev1) == hipSuccess;
+            hipHostMalloc((void**)&h->h_sums, kAlVals * sizeof(double), hipHostMallocDefault) == hipSuccess && h->tm.create();
   if (ok && p->keep_rows) ok = hipMalloc((void**)&h->d_rows, (size_t)h->Ws * h->Hs * 8 * sizeof(float)) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
@@ -284,21 +275,19 @@ extern "C" int vdo_align_set_model(vdo_align* h, const float* depth, const float
   if (!Tm) return set_error(VDO_ERR_INVALID, "%s: Tm is null", who);
   if (Wm < 1) return set_error(VDO_ERR_INVALID, "%s: model_width %d < 1", who, Wm);
   if (Hm < 1) return set_error(VDO_ERR_INVALID, "%s: model_height %d < 1", who, Hm);
-  for (int k = 0; k < 4; ++k) if (!al_good(Km[k])) return set_error(VDO_ERR_INVALID, "%s: Km[%d] is not finite", who, k);
-  if (!(Km[0] > 0.f) || !(Km[1] > 0.f)) return set_error(VDO_ERR_INVALID, "%s: Km: fx %g, fy %g must be positive", who, (double)Km[0], (double)Km[1]);
-  if ((int64_t)Wm * Hm > kDnMaxPixels || Wm > kDnMaxImageSide || Hm > kDnMaxImageSide)
-    return set_error(VDO_ERR_UNSUPPORTED, "%s: the model of %d x %d exceeds 2^26 pixels or 2^24 on a side", who, Wm, Hm);
+  int rc = check_intrinsics(who, "Km", Km);
+  if (rc == VDO_OK) rc = check_image_size(who, "the model of", Wm, Hm);
+  if (rc != VDO_OK) return rc;
   if (!is_device) {
     const size_t nm = (size_t)Wm * Hm;
     if (nm > h->npix) return set_error(VDO_ERR_UNSUPPORTED, "%s: a host model of %d x %d has more pixels than the %d x %d frame the handle's model images were sized for", who, Wm, Hm, h->W, h->H);
-    const int rc = ctx_bind(h->ctx);
+    rc = ctx_bind(h->ctx);
     if (rc != VDO_OK) return rc;
     hipStream_t s = h->ctx->stream;
     hipMemcpyAsync(h->d_mdepth, depth, nm * sizeof(float), hipMemcpyHostToDevice, s);
     hipMemcpyAsync(h->d_mgrad, grad, nm * 3 * sizeof(float), hipMemcpyHostToDevice, s);
-    hipError_t e = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) { h->has_model = false; return al_check_hip(who, e); }
+    rc = sync_check(who, s);
+    if (rc != VDO_OK) { h->has_model = false; return rc; }
     depth = h->d_mdepth; grad = h->d_mgrad;
   }
   al_take_model(h, depth, grad, Wm, Hm, Km, Tm);
@@ -331,18 +320,7 @@ struct AlSrc { const float* depth; const int32_t* mask; };
 
 static AlSrc al_stage(vdo_align* h, const float* depth, int64_t dstride, const int32_t* mask, int64_t mstride, int src_is_device) {
   hipStream_t s = h->ctx->stream;
-  const int W = h->W, H = h->H;
-  const hipMemcpyKind kind = src_is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  AlSrc src{depth, mask};
-  if (!(src_is_device && dstride == W)) {
-    hipMemcpy2DAsync(h->d_depth, W * sizeof(float), depth, (size_t)dstride * sizeof(float), W * sizeof(float), H, kind, s);
-    src.depth = h->d_depth;
-  }
-  if (mask && !(src_is_device && mstride == W)) {
-    hipMemcpy2DAsync(h->d_mask, W * sizeof(int32_t), mask, (size_t)mstride * sizeof(int32_t), W * sizeof(int32_t), H, kind, s);
-    src.mask = h->d_mask;
-  }
-  return src;
+  return AlSrc{stage_rows(s, h->d_depth, depth, dstride, h->W, h->H, src_is_device), mask ? stage_rows(s, h->d_mask, mask, mstride, h->W, h->H, src_is_device) : nullptr};
 }
 
 // one linearisation of packed device images at T: the launches, the download of the 32 values; *dev_ms the device time from ev0 (recorded by the caller)
@@ -360,34 +338,26 @@ static int al_linearise(const char* who, vdo_align* h, AlSrc src, const float T[
     n = P = blocks;
     from ^= 1;
   } while (P > 1);
-  hipEventRecord(h->ev1, s);
+  h->tm.mark_end(s);
   hipMemcpyAsync(h->h_sums, h->d_part[from], kAlVals * sizeof(double), hipMemcpyDeviceToHost, s);
-  hipError_t e = hipStreamSynchronize(s);
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e != hipSuccess) return al_check_hip(who, e);
+  const int rc = sync_check(who, s);
+  if (rc != VDO_OK) return rc;
   h->has_rows = h->d_rows != nullptr;
   for (int k = 0; k < kAlTerms; ++k) sums[k] = h->h_sums[k];
   counts[kAlUsed] = (int64_t)h->h_sums[28]; counts[kAlMasked] = (int64_t)h->h_sums[29]; counts[kAlNoModel] = (int64_t)h->h_sums[30]; counts[kAlFar] = (int64_t)h->h_sums[31];
   counts[kAlNoDepth] = (int64_t)h->Ws * h->Hs - counts[kAlUsed] - counts[kAlMasked] - counts[kAlNoModel] - counts[kAlFar];
-  float ms = 0.f;
-  hipEventElapsedTime(&ms, h->ev0, h->ev1);
-  *dev_ms = ms;
+  *dev_ms = elapsed_ms(h->tm.ev0, h->tm.ev1);
   return VDO_OK;
 }
 
 static int al_check_images(const char* who, vdo_align* h, const float* depth, int64_t dstride, const int32_t* mask, int64_t mstride) {
   if (!h) return set_error(VDO_ERR_INVALID, "%s: handle is null", who);
-  if (!depth) return set_error(VDO_ERR_INVALID, "%s: depth is null", who);
-  if (dstride < h->W) return set_error(VDO_ERR_INVALID, "%s: depth_stride_floats %lld smaller than the width %d", who, (long long)dstride, h->W);
-  if (mask && mstride < h->W) return set_error(VDO_ERR_INVALID, "%s: mask_stride_ints %lld smaller than the width %d", who, (long long)mstride, h->W);
-  return VDO_OK;
+  return check_depth_mask(who, h->W, depth, dstride, mask, mstride, false);
 }
 
 static int al_check_frame(const char* who, vdo_align* h, const vdo_frame_images* f) {
   if (!h) return set_error(VDO_ERR_INVALID, "%s: handle is null", who);
-  if (!f) return set_error(VDO_ERR_INVALID, "%s: frame is null", who);
-  if (f->w != h->W || f->h != h->H) return set_error(VDO_ERR_INVALID, "%s: frame is %d x %d, the aligner's images are %d x %d", who, f->w, f->h, h->W, h->H);
-  return VDO_OK;
+  return check_frame(who, f, h->W, h->H, "the aligner's");
 }
 
 // the two linearise entries after their own checks; staged: the images go through al_stage
@@ -399,16 +369,14 @@ static int al_linearise_entry(const char* who, vdo_align* h, bool staged, const 
   if (!h->has_model) return set_error(VDO_ERR_INVALID, "%s: no model is set", who);
   const int rc = ctx_bind(h->ctx);
   if (rc != VDO_OK) return rc;
-  const auto t0 = std::chrono::steady_clock::now();
-  hipEventRecord(h->ev0, h->ctx->stream);
+  const auto t0 = h->tm.begin(h->ctx->stream);
   const AlSrc src = staged ? al_stage(h, depth, dstride, mask, mstride, src_is_device) : AlSrc{depth, mask};
   double s28[28], dev_ms = 0;
   int64_t c5[5];
   const int rl = al_linearise(who, h, src, T, s28, c5, &dev_ms);
   if (rl != VDO_OK) return rl;
   std::memcpy(sums, s28, sizeof s28); std::memcpy(counts, c5, sizeof c5);
-  h->ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  h->ms[1] = dev_ms;
+  h->tm.finish(t0, dev_ms);
   return VDO_OK;
 }
 
@@ -420,8 +388,7 @@ static int al_solve_entry(const char* who, vdo_align* h, bool staged, const floa
   if (!h->has_model) return set_error(VDO_ERR_INVALID, "%s: no model is set", who);
   const int rc = ctx_bind(h->ctx);
   if (rc != VDO_OK) return rc;
-  const auto t0 = std::chrono::steady_clock::now();
-  hipEventRecord(h->ev0, h->ctx->stream);
+  const auto t0 = h->tm.begin(h->ctx->stream);
   const AlSrc src = staged ? al_stage(h, depth, dstride, mask, mstride, src_is_device) : AlSrc{depth, mask};
   float T[16], Tn[16];
   std::memcpy(T, T_init, sizeof T);
@@ -430,7 +397,7 @@ static int al_solve_entry(const char* who, vdo_align* h, bool staged, const floa
   for (int it = 0; it < h->p.max_iterations; ++it) {
     double sums[28], dev_ms = 0, rms = 0;
     int64_t counts[5];
-    if (it > 0) hipEventRecord(h->ev0, h->ctx->stream);
+    if (it > 0) hipEventRecord(h->tm.ev0, h->ctx->stream);
     const int rl = al_linearise(who, h, src, T, sums, counts, &dev_ms);
     if (rl != VDO_OK) return rl;
     dev_total += dev_ms;
@@ -451,8 +418,7 @@ static int al_solve_entry(const char* who, vdo_align* h, bool staged, const floa
   }
   std::memcpy(T_out, T, sizeof T);
   if (report) *report = rep;
-  h->ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  h->ms[1] = dev_total;
+  h->tm.finish(t0, dev_total);
   return VDO_OK;
 }
 
@@ -568,11 +534,9 @@ extern "C" int vdo_align_get_rows(vdo_align* h, float* rows) {
   const int rc = ctx_bind(h->ctx);
   if (rc != VDO_OK) return rc;
   hipMemcpyAsync(rows, h->d_rows, (size_t)h->Ws * h->Hs * 8 * sizeof(float), hipMemcpyDeviceToHost, h->ctx->stream);
-  return al_check_hip(who, hipStreamSynchronize(h->ctx->stream));
+  return check_hip(who, hipStreamSynchronize(h->ctx->stream));
 }
 
 extern "C" int vdo_align_last_timing(vdo_align* h, double ms[2]) {
-  if (!h || !ms) return set_error(VDO_ERR_INVALID, "vdo_align_last_timing: %s is null", !h ? "handle" : "ms");
-  ms[0] = h->ms[0]; ms[1] = h->ms[1];
-  return VDO_OK;
+  return last_timing("vdo_align_last_timing", h ? &h->tm : nullptr, ms);
 }

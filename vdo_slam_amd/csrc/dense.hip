@@ -19,14 +19,13 @@
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
-#include <chrono>
-#include <cmath>
 #include <cstdint>
 #include <cstring>
 
 #include "../../include/vdo_slam_hip.h"
 #include "ctx.hpp"
 #include "frame_images.hpp"
+#include "stage.hpp"
 #include "dense.hpp"
 #include "scan.hpp"
 
@@ -170,17 +169,12 @@ __global__ __launch_bounds__(1024) void k_dn_scan(long long* __restrict__ blk, l
   if (threadIdx.x == 0) total_out[0] = (unsigned long long)carry;
 }
 
-static int dn_check_hip(const char* who, hipError_t e) { return e == hipSuccess ? VDO_OK : set_error(VDO_ERR_NO_DEVICE, "%s: %s", who, hipGetErrorString(e)); }
-
 static void dn_free(vdo_dense* h) {
   hipFree(h->d_vol); hipFree(h->d_depth); hipFree(h->d_mask); hipFree(h->d_blk); hipFree(h->d_cnt); hipFree(h->d_xyz); hipFree(h->d_grad); hipFree(h->d_wgt);
   if (h->h_cnt) hipHostFree(h->h_cnt);
-  if (h->ev0) hipEventDestroy(h->ev0);
-  if (h->ev1) hipEventDestroy(h->ev1);
+  h->tm.destroy();
   delete h;
 }
-
-static bool dn_good(float v) { return std::fabs(v) <= FLT_MAX; }
 
 static int dn_mod(int g, int n) { const int m = g % n; return m < 0 ? m + n : m; }
 
@@ -203,7 +197,7 @@ static void dn_launch_integrate(vdo_dense* h, hipStream_t s, const DnArgs& a, co
 }
 
 // the launch, the download of the counts and the timing the two integrate entries share; depth and mask are packed device images
-static int dn_integrate(const char* who, vdo_dense* h, const float* d_depth, const int32_t* d_mask, const float T[16], int64_t out[3], std::chrono::steady_clock::time_point t0) {
+static int dn_integrate(const char* who, vdo_dense* h, const float* d_depth, const int32_t* d_mask, const float T[16], int64_t out[3], StageClock::time_point t0) {
   hipStream_t s = h->ctx->stream;
   DnArgs a = h->a;
   for (int k = 0; k < 12; ++k) a.T[k] = T[k];
@@ -214,20 +208,16 @@ static int dn_integrate(const char* who, vdo_dense* h, const float* d_depth, con
     case 8: dn_launch_integrate<8>(h, s, a, d_depth, d_mask); break;
     default: dn_launch_integrate<4>(h, s, a, d_depth, d_mask); break;
   }
-  hipEventRecord(h->ev1, s);
+  h->tm.mark_end(s);
   hipMemcpyAsync(h->h_cnt, h->d_cnt, kDnTotal * sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
-  hipError_t e = hipStreamSynchronize(s);
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e != hipSuccess) return dn_check_hip(who, e);
+  const int rc = sync_check(who, s);
+  if (rc != VDO_OK) return rc;
   for (int k = 0; k < 3; ++k) {
     unsigned long long sum = 0;
     for (int slot = 0; slot < kDnSlots; ++slot) sum += h->h_cnt[slot * kDnCounters + k];
     out[k] = (int64_t)sum;
   }
-  float dev_ms = 0.f;
-  hipEventElapsedTime(&dev_ms, h->ev0, h->ev1);
-  h->ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  h->ms[1] = dev_ms;
+  h->tm.finish(t0);
   return VDO_OK;
 }
 
@@ -243,20 +233,20 @@ extern "C" int vdo_dense_create(vdo_ctx* ctx, int width, int height, const vdo_d
   if (width < 1) return set_error(VDO_ERR_INVALID, "%s: width %d < 1", who, width);
   if (height < 1) return set_error(VDO_ERR_INVALID, "%s: height %d < 1", who, height);
   for (int k = 0; k < 3; ++k) if (p->n[k] < 1) return set_error(VDO_ERR_INVALID, "%s: n[%d] = %d < 1", who, k, p->n[k]);
-  if (!dn_good(p->voxel) || !(p->voxel > 0.f)) return set_error(VDO_ERR_INVALID, "%s: voxel %g must be positive and finite", who, (double)p->voxel);
-  for (int k = 0; k < 4; ++k) if (!dn_good(p->K[k])) return set_error(VDO_ERR_INVALID, "%s: K[%d] is not finite", who, k);
-  if (!(p->K[0] > 0.f) || !(p->K[1] > 0.f)) return set_error(VDO_ERR_INVALID, "%s: K: fx %g, fy %g must be positive", who, (double)p->K[0], (double)p->K[1]);
-  if (!dn_good(p->trunc) || !(p->trunc > 0.f)) return set_error(VDO_ERR_INVALID, "%s: trunc %g must be positive and finite", who, (double)p->trunc);
-  if (!dn_good(p->min_depth) || !(p->min_depth >= 0.f)) return set_error(VDO_ERR_INVALID, "%s: min_depth %g must be finite and >= 0", who, (double)p->min_depth);
-  if (!dn_good(p->max_depth) || !(p->max_depth > p->min_depth)) return set_error(VDO_ERR_INVALID, "%s: max_depth %g must be finite and above min_depth %g", who, (double)p->max_depth, (double)p->min_depth);
+  if (!is_finite(p->voxel) || !(p->voxel > 0.f)) return set_error(VDO_ERR_INVALID, "%s: voxel %g must be positive and finite", who, (double)p->voxel);
+  int rc = check_intrinsics(who, "K", p->K);
+  if (rc != VDO_OK) return rc;
+  if (!is_finite(p->trunc) || !(p->trunc > 0.f)) return set_error(VDO_ERR_INVALID, "%s: trunc %g must be positive and finite", who, (double)p->trunc);
+  rc = check_depth_range(who, p->min_depth, p->max_depth);
+  if (rc != VDO_OK) return rc;
   if (p->max_weight < 1 || p->max_weight > 255) return set_error(VDO_ERR_INVALID, "%s: max_weight %d outside 1..255", who, p->max_weight);
   if (p->stage_points < 1) return set_error(VDO_ERR_INVALID, "%s: stage_points %d < 1", who, p->stage_points);
   for (int k = 0; k < 3; ++k) if (p->n[k] > kDnMaxSide) return set_error(VDO_ERR_UNSUPPORTED, "%s: n[%d] = %d exceeds 2^12", who, k, p->n[k]);
   const int64_t nvox = (int64_t)p->n[0] * p->n[1] * p->n[2];
   if (nvox > kDnMaxVoxels) return set_error(VDO_ERR_UNSUPPORTED, "%s: %d x %d x %d voxels exceed 2^31", who, p->n[0], p->n[1], p->n[2]);
-  if ((int64_t)width * height > kDnMaxPixels || width > kDnMaxImageSide || height > kDnMaxImageSide)
-    return set_error(VDO_ERR_UNSUPPORTED, "%s: width x height = %d x %d exceeds 2^26 pixels or 2^24 on a side", who, width, height);
-  int rc = dn_check_origin(who, "origin", p->origin, p->n);
+  rc = check_image_size(who, "width x height =", width, height);
+  if (rc != VDO_OK) return rc;
+  rc = dn_check_origin(who, "origin", p->origin, p->n);
   if (rc != VDO_OK) return rc;
   rc = ctx_bind(ctx);
   if (rc != VDO_OK) return rc;
@@ -273,8 +263,8 @@ extern "C" int vdo_dense_create(vdo_ctx* ctx, int width, int height, const vdo_d
                   hipMalloc((void**)&h->d_mask, npix * sizeof(int32_t)) == hipSuccess && hipMalloc((void**)&h->d_blk, nblk * sizeof(long long)) == hipSuccess &&
                   hipMalloc((void**)&h->d_cnt, (kDnTotal + 1) * sizeof(unsigned long long)) == hipSuccess && hipMalloc((void**)&h->d_xyz, sp * 3 * sizeof(float)) == hipSuccess &&
                   hipMalloc((void**)&h->d_grad, sp * 3 * sizeof(int32_t)) == hipSuccess && hipMalloc((void**)&h->d_wgt, sp * sizeof(int32_t)) == hipSuccess &&
-                  hipHostMalloc((void**)&h->h_cnt, (kDnTotal + 1) * sizeof(unsigned long long), hipHostMallocDefault) == hipSuccess && hipEventCreate(&h->ev0) == hipSuccess &&
-                  hipEventCreate(&h->ev1) == hipSuccess && hipMemsetAsync(h->d_vol, 0, (size_t)nvox * sizeof(uint32_t), ctx->stream) == hipSuccess &&
+                  hipHostMalloc((void**)&h->h_cnt, (kDnTotal + 1) * sizeof(unsigned long long), hipHostMallocDefault) == hipSuccess && h->tm.create() &&
+                  hipMemsetAsync(h->d_vol, 0, (size_t)nvox * sizeof(uint32_t), ctx->stream) == hipSuccess &&
                   hipStreamSynchronize(ctx->stream) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
@@ -303,42 +293,29 @@ extern "C" int vdo_dense_integrate(vdo_dense* h, const float* depth, int64_t dep
                                    int64_t out[3]) {
   static const char* who = "vdo_dense_integrate";
   if (!h) return set_error(VDO_ERR_INVALID, "%s: handle is null", who);
-  if (!depth) return set_error(VDO_ERR_INVALID, "%s: depth is null", who);
-  if (depth_stride_floats < h->W) return set_error(VDO_ERR_INVALID, "%s: depth_stride_floats %lld smaller than the width %d", who, (long long)depth_stride_floats, h->W);
-  if (mask && mask_stride_ints < h->W) return set_error(VDO_ERR_INVALID, "%s: mask_stride_ints %lld smaller than the width %d", who, (long long)mask_stride_ints, h->W);
+  int rc = check_depth_mask(who, h->W, depth, depth_stride_floats, mask, mask_stride_ints, false);
+  if (rc != VDO_OK) return rc;
   if (!T) return set_error(VDO_ERR_INVALID, "%s: T is null", who);
   if (!out) return set_error(VDO_ERR_INVALID, "%s: out is null", who);
-  const int rc = ctx_bind(h->ctx);
+  rc = ctx_bind(h->ctx);
   if (rc != VDO_OK) return rc;
-  const auto t0 = std::chrono::steady_clock::now();
   hipStream_t s = h->ctx->stream;
-  const int W = h->W, H = h->H;
-  const hipMemcpyKind kind = src_is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  hipEventRecord(h->ev0, s);
-  const float* d_depth = depth;
-  const int32_t* d_mask = mask;
-  if (!(src_is_device && depth_stride_floats == W)) {
-    hipMemcpy2DAsync(h->d_depth, W * sizeof(float), depth, (size_t)depth_stride_floats * sizeof(float), W * sizeof(float), H, kind, s);
-    d_depth = h->d_depth;
-  }
-  if (mask && !(src_is_device && mask_stride_ints == W)) {
-    hipMemcpy2DAsync(h->d_mask, W * sizeof(int32_t), mask, (size_t)mask_stride_ints * sizeof(int32_t), W * sizeof(int32_t), H, kind, s);
-    d_mask = h->d_mask;
-  }
+  const auto t0 = h->tm.begin(s);
+  const float* d_depth = stage_rows(s, h->d_depth, depth, depth_stride_floats, h->W, h->H, src_is_device);
+  const int32_t* d_mask = mask ? stage_rows(s, h->d_mask, mask, mask_stride_ints, h->W, h->H, src_is_device) : nullptr;
   return dn_integrate(who, h, d_depth, d_mask, T, out, t0);
 }
 
 extern "C" int vdo_dense_integrate_frame(vdo_dense* h, const vdo_frame_images* f, const float T[16], int64_t out[3]) {
   static const char* who = "vdo_dense_integrate_frame";
   if (!h) return set_error(VDO_ERR_INVALID, "%s: handle is null", who);
-  if (!f) return set_error(VDO_ERR_INVALID, "%s: frame is null", who);
-  if (f->w != h->W || f->h != h->H) return set_error(VDO_ERR_INVALID, "%s: frame is %d x %d, the mapper's images are %d x %d", who, f->w, f->h, h->W, h->H);
+  int rc = check_frame(who, f, h->W, h->H, "the mapper's");
+  if (rc != VDO_OK) return rc;
   if (!T) return set_error(VDO_ERR_INVALID, "%s: T is null", who);
   if (!out) return set_error(VDO_ERR_INVALID, "%s: out is null", who);
-  const int rc = ctx_bind(h->ctx);
+  rc = ctx_bind(h->ctx);
   if (rc != VDO_OK) return rc;
-  const auto t0 = std::chrono::steady_clock::now();
-  hipEventRecord(h->ev0, h->ctx->stream);
+  const auto t0 = h->tm.begin(h->ctx->stream);
   return dn_integrate(who, h, f->d_depth, f->d_mask, T, out, t0);
 }
 
@@ -350,13 +327,12 @@ extern "C" int vdo_dense_recenter(vdo_dense* h, const int32_t new_origin[3]) {
   if (rc != VDO_OK) return rc;
   rc = ctx_bind(h->ctx);
   if (rc != VDO_OK) return rc;
-  const auto t0 = std::chrono::steady_clock::now();
   hipStream_t s = h->ctx->stream;
   const int* n = h->a.n;
   int64_t d[3];
   bool all = false;
   for (int k = 0; k < 3; ++k) { d[k] = (int64_t)new_origin[k] - h->a.o[k]; all = all || d[k] >= n[k] || -d[k] >= n[k]; }
-  hipEventRecord(h->ev0, s);
+  const auto t0 = h->tm.begin(s);
   if (all) {
     hipMemsetAsync(h->d_vol, 0, (size_t)h->nvox * sizeof(uint32_t), s);
   } else {
@@ -368,15 +344,11 @@ extern "C" int vdo_dense_recenter(vdo_dense* h, const int32_t new_origin[3]) {
       hipLaunchKernelGGL(k_dn_clear, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, h->d_vol, n[0], n[1], n[2], k, dn_mod(g0, n[k]), len);
     }
   }
-  hipEventRecord(h->ev1, s);
-  hipError_t e = hipStreamSynchronize(s);
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e != hipSuccess) return dn_check_hip(who, e);
+  h->tm.mark_end(s);
+  rc = sync_check(who, s);
+  if (rc != VDO_OK) return rc;
   dn_set_origin(h, new_origin);
-  float dev_ms = 0.f;
-  hipEventElapsedTime(&dev_ms, h->ev0, h->ev1);
-  h->ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  h->ms[1] = dev_ms;
+  h->tm.finish(t0);
   return VDO_OK;
 }
 
@@ -392,9 +364,8 @@ extern "C" int vdo_dense_extract(vdo_dense* h, const int32_t lo[3], const int32_
   if (capacity > 0 && !grad) return set_error(VDO_ERR_INVALID, "%s: grad is null", who);
   if (capacity > 0 && !weight) return set_error(VDO_ERR_INVALID, "%s: weight is null", who);
   if (!count) return set_error(VDO_ERR_INVALID, "%s: count is null", who);
-  const int rc = ctx_bind(h->ctx);
+  int rc = ctx_bind(h->ctx);
   if (rc != VDO_OK) return rc;
-  const auto t0 = std::chrono::steady_clock::now();
   hipStream_t s = h->ctx->stream;
   DnBox bx;
   long long nbox = 1;
@@ -403,7 +374,7 @@ extern "C" int vdo_dense_extract(vdo_dense* h, const int32_t lo[3], const int32_
     bx.lo[k] = (int)a0; bx.b[k] = a1 > a0 ? (int)(a1 - a0) : 0;
     nbox *= bx.b[k];
   }
-  hipEventRecord(h->ev0, s);
+  const auto t0 = h->tm.begin(s);
   long long total = 0;
   if (nbox > 0) {
     const long long nblk = (nbox + 255) / 256;
@@ -411,9 +382,8 @@ extern "C" int vdo_dense_extract(vdo_dense* h, const int32_t lo[3], const int32_
                        (int32_t*)nullptr, (int32_t*)nullptr);
     hipLaunchKernelGGL(k_dn_scan, dim3(1), dim3(1024), 0, s, h->d_blk, nblk, h->d_cnt + kDnTotal);
     hipMemcpyAsync(h->h_cnt + kDnTotal, h->d_cnt + kDnTotal, sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
-    hipError_t e = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) return dn_check_hip(who, e);
+    rc = sync_check(who, s);
+    if (rc != VDO_OK) return rc;
     total = (long long)h->h_cnt[kDnTotal];
     const long long want = total < capacity ? total : capacity;
     // a device output is one window; a host output goes through the staging lists, stage_points at a time
@@ -425,20 +395,16 @@ extern "C" int vdo_dense_extract(vdo_dense* h, const int32_t lo[3], const int32_
         hipMemcpyAsync(xyz + 3 * base, h->d_xyz, (size_t)cap * 3 * sizeof(float), hipMemcpyDeviceToHost, s);
         hipMemcpyAsync(grad + 3 * base, h->d_grad, (size_t)cap * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s);
         hipMemcpyAsync(weight + base, h->d_wgt, (size_t)cap * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-        e = hipStreamSynchronize(s);                                         // the staging lists are free for the next window
-        if (e != hipSuccess) return dn_check_hip(who, e);
+        rc = check_hip(who, hipStreamSynchronize(s));                        // the staging lists are free for the next window
+        if (rc != VDO_OK) return rc;
       }
     }
   }
-  hipEventRecord(h->ev1, s);
-  hipError_t e = hipStreamSynchronize(s);
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e != hipSuccess) return dn_check_hip(who, e);
+  h->tm.mark_end(s);
+  rc = sync_check(who, s);
+  if (rc != VDO_OK) return rc;
   *count = total;
-  float dev_ms = 0.f;
-  hipEventElapsedTime(&dev_ms, h->ev0, h->ev1);
-  h->ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  h->ms[1] = dev_ms;
+  h->tm.finish(t0);
   return VDO_OK;
 }
 
@@ -450,7 +416,7 @@ extern "C" int vdo_dense_get_volume(vdo_dense* h, uint32_t* words, int32_t origi
     const int rc = ctx_bind(h->ctx);
     if (rc != VDO_OK) return rc;
     hipMemcpyAsync(words, h->d_vol, (size_t)h->nvox * sizeof(uint32_t), hipMemcpyDeviceToHost, h->ctx->stream);
-    const int rs = dn_check_hip(who, hipStreamSynchronize(h->ctx->stream));
+    const int rs = check_hip(who, hipStreamSynchronize(h->ctx->stream));
     if (rs != VDO_OK) return rs;
   }
   if (origin) for (int k = 0; k < 3; ++k) origin[k] = h->a.o[k];
@@ -464,7 +430,7 @@ extern "C" int vdo_dense_set_volume(vdo_dense* h, const uint32_t* words) {
   const int rc = ctx_bind(h->ctx);
   if (rc != VDO_OK) return rc;
   hipMemcpyAsync(h->d_vol, words, (size_t)h->nvox * sizeof(uint32_t), hipMemcpyHostToDevice, h->ctx->stream);
-  return dn_check_hip(who, hipStreamSynchronize(h->ctx->stream));
+  return check_hip(who, hipStreamSynchronize(h->ctx->stream));
 }
 
 extern "C" int vdo_dense_clear(vdo_dense* h) {
@@ -473,13 +439,11 @@ extern "C" int vdo_dense_clear(vdo_dense* h) {
   const int rc = ctx_bind(h->ctx);
   if (rc != VDO_OK) return rc;
   hipMemsetAsync(h->d_vol, 0, (size_t)h->nvox * sizeof(uint32_t), h->ctx->stream);
-  return dn_check_hip(who, hipStreamSynchronize(h->ctx->stream));
+  return check_hip(who, hipStreamSynchronize(h->ctx->stream));
 }
 
 extern "C" int vdo_dense_last_timing(vdo_dense* h, double ms[2]) {
-  if (!h || !ms) return set_error(VDO_ERR_INVALID, "vdo_dense_last_timing: %s is null", !h ? "handle" : "ms");
-  ms[0] = h->ms[0]; ms[1] = h->ms[1];
-  return VDO_OK;
+  return last_timing("vdo_dense_last_timing", h ? &h->tm : nullptr, ms);
 }
 
 extern "C" int vdo_dense_device_volume(vdo_dense* h, uint32_t** words) {

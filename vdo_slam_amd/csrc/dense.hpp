@@ -7,14 +7,13 @@
 
 #include "../../include/vdo_slam_hip.h"
 #include "ctx.hpp"
+#include "stage.hpp"
 
 namespace vdo {
 
 constexpr int kDnMaxSide = 1 << 12;
 constexpr int64_t kDnMaxVoxels = int64_t(1) << 31;
 constexpr int kDnMaxOrigin = 1 << 22;                                      // every |g| in use stays below it: (float)g + 0.5f is exact
-constexpr int64_t kDnMaxPixels = int64_t(1) << 26;
-constexpr int kDnMaxImageSide = 1 << 24;                                   // (float)(W - 1) is exact
 constexpr int kDnZ = 4;                                                    // z slots per workgroup of k_dn_integrate
 enum { kDnUpdated = 0, kDnMasked, kDnOccluded, kDnCounters = 4 };
 constexpr int kDnSlots = 1024;                                             // the counters of k_dn_integrate are kept kDnSlots times, 32 bytes apart; the host adds them up
@@ -44,8 +43,7 @@ struct vdo_dense {
   unsigned long long* d_cnt = nullptr;                    // [kDnSlots][kDnCounters], then the point count of the last extraction
   unsigned long long* h_cnt = nullptr;                    // pinned
   float* d_xyz = nullptr; int32_t* d_grad = nullptr; int32_t* d_wgt = nullptr;      // [stage_points] staging of host outputs
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  double ms[2] = {0, 0};
+  vdo::StageTimer tm;
 };
 
 namespace vdo {

@@ -19,12 +19,12 @@
 // loop still carries that bound as an explicit cap: on overrun the kernel raises a flag and returns, and the call answers VDO_ERR_INTERNAL.
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cstdint>
 
 #include "../../include/vdo_slam_hip.h"
 #include "ctx.hpp"
 #include "scan.hpp"
+#include "stage.hpp"
 
 namespace vdo {
 
@@ -51,8 +51,7 @@ struct vdo_labels {
   int32_t* d_blk = nullptr;                               // per 256 pixels: kept roots, then their exclusive scan
   int32_t* d_sel = nullptr;                               // [kSelSize]
   int32_t* h_sel = nullptr;                               // pinned, the first kSelHist of them
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  double ms[2] = {0, 0};
+  vdo::StageTimer tm;
   bool computed = false;
 };
 
@@ -314,15 +313,10 @@ __global__ __launch_bounds__(256) void k_lab_write(int n, const int32_t* __restr
   if ((threadIdx.x & 63) == 0 && c) atomicAdd(sel + kSelRemoved, c);
 }
 
-static int lab_check_hip(const char* who, hipError_t e) {
-  return e == hipSuccess ? VDO_OK : set_error(VDO_ERR_NO_DEVICE, "%s: %s", who, hipGetErrorString(e));
-}
-
 static void lab_free(vdo_labels* h) {
   hipFree(h->d_cls); hipFree(h->d_disp); hipFree(h->d_links); hipFree(h->d_parent); hipFree(h->d_area); hipFree(h->d_rank); hipFree(h->d_mask); hipFree(h->d_blk); hipFree(h->d_sel);
   if (h->h_sel) hipHostFree(h->h_sel);
-  if (h->ev0) hipEventDestroy(h->ev0);
-  if (h->ev1) hipEventDestroy(h->ev1);
+  h->tm.destroy();
   delete h;
 }
 
@@ -340,17 +334,13 @@ static void lab_components(vdo_labels* h, hipStream_t s, const uint8_t* cls, con
   hipLaunchKernelGGL(k_lab_flatten, dim3(nblk), dim3(256), 0, s, n, h->d_parent, h->d_area, h->d_sel);
 }
 
-static int lab_finish(const char* who, vdo_labels* h, std::chrono::steady_clock::time_point t0) {
+static int lab_finish(const char* who, vdo_labels* h, StageClock::time_point t0) {
   hipStream_t s = h->ctx->stream;
   hipMemcpyAsync(h->h_sel, h->d_sel, kSelHist * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-  hipError_t e = hipStreamSynchronize(s);
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e != hipSuccess) return lab_check_hip(who, e);
+  const int rc = sync_check(who, s);
+  if (rc != VDO_OK) return rc;
   if (h->h_sel[kSelOverrun]) return set_error(VDO_ERR_INTERNAL, "%s: a union-find walk passed its step bound of width x height", who);
-  float dev_ms = 0.f;
-  hipEventElapsedTime(&dev_ms, h->ev0, h->ev1);
-  h->ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  h->ms[1] = dev_ms;
+  h->tm.finish(t0);
   h->computed = true;
   return VDO_OK;
 }
@@ -380,8 +370,7 @@ extern "C" int vdo_labels_create(vdo_ctx* ctx, int width, int height, const vdo_
                   hipMalloc((void**)&h->d_parent, n * sizeof(int32_t)) == hipSuccess && hipMalloc((void**)&h->d_area, n * sizeof(int32_t)) == hipSuccess &&
                   hipMalloc((void**)&h->d_rank, n * sizeof(int32_t)) == hipSuccess && hipMalloc((void**)&h->d_mask, n * sizeof(int32_t)) == hipSuccess &&
                   hipMalloc((void**)&h->d_blk, nblk * sizeof(int32_t)) == hipSuccess && hipMalloc((void**)&h->d_sel, kSelSize * sizeof(int32_t)) == hipSuccess &&
-                  hipHostMalloc((void**)&h->h_sel, kSelHist * sizeof(int32_t), hipHostMallocDefault) == hipSuccess && hipEventCreate(&h->ev0) == hipSuccess &&
-                  hipEventCreate(&h->ev1) == hipSuccess;
+                  hipHostMalloc((void**)&h->h_sel, kSelHist * sizeof(int32_t), hipHostMallocDefault) == hipSuccess && h->tm.create();
   if (!ok) {
     (void)hipGetLastError();
     lab_free(h);
@@ -411,19 +400,12 @@ extern "C" int vdo_labels_compute(vdo_labels* h, const uint8_t* cls, int64_t cls
   if (!out) return set_error(VDO_ERR_INVALID, "%s: out is null", who);
   int rc = ctx_bind(h->ctx);
   if (rc != VDO_OK) return rc;
-  const auto t0 = std::chrono::steady_clock::now();
   hipStream_t s = h->ctx->stream;
   const int W = h->W, H = h->H, n = W * H, nblk = (n + 255) / 256;
-  hipEventRecord(h->ev0, s);
+  const auto t0 = h->tm.begin(s);
   // packed device images are read where they lie; anything else is brought to the handle's staging images
-  const hipMemcpyKind kind = src_is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  const uint8_t* d_cls = cls;
-  if (!(src_is_device && cls_stride == W)) { hipMemcpy2DAsync(h->d_cls, W, cls, (size_t)cls_stride, W, H, kind, s); d_cls = h->d_cls; }
-  const float* d_disp = gate ? disp : nullptr;
-  if (gate && !(src_is_device && disp_stride_floats == W)) {
-    hipMemcpy2DAsync(h->d_disp, W * sizeof(float), disp, (size_t)disp_stride_floats * sizeof(float), W * sizeof(float), H, kind, s);
-    d_disp = h->d_disp;
-  }
+  const uint8_t* d_cls = stage_rows(s, h->d_cls, cls, cls_stride, W, H, src_is_device);
+  const float* d_disp = gate ? stage_rows(s, h->d_disp, disp, disp_stride_floats, W, H, src_is_device) : nullptr;
   int32_t* d_mask = out_is_device ? mask : h->d_mask;
   lab_components<false>(h, s, d_cls, d_disp, h->p.connectivity, h->p.max_disp_diff);
   const int32_t *par = h->d_parent, *area = h->d_area;
@@ -438,7 +420,7 @@ extern "C" int vdo_labels_compute(vdo_labels* h, const uint8_t* cls, int64_t cls
   hipLaunchKernelGGL(k_lab_scan, dim3(1), dim3(1024), 0, s, h->d_blk, nblk, mn, mx, h->d_sel);
   hipLaunchKernelGGL(k_lab_number, dim3(nblk), dim3(256), 0, s, n, par, area, (const int32_t*)h->d_sel, (const int32_t*)h->d_blk, h->d_rank);
   hipLaunchKernelGGL(k_lab_write<false>, dim3(nblk), dim3(256), 0, s, n, par, area, (const int32_t*)h->d_rank, 0, d_mask, (float*)nullptr, h->d_sel);
-  hipEventRecord(h->ev1, s);
+  h->tm.mark_end(s);
   // the mask travels before the verdict is known; a walk past its bound (VDO_ERR_INTERNAL) cannot happen while the invariant holds
   if (!out_is_device) hipMemcpyAsync(mask, h->d_mask, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
   rc = lab_finish(who, h, t0);
@@ -456,16 +438,15 @@ extern "C" int vdo_labels_filter_speckles(vdo_labels* h, float* disparity256, in
   if (!n_removed) return set_error(VDO_ERR_INVALID, "%s: n_removed is null", who);
   int rc = ctx_bind(h->ctx);
   if (rc != VDO_OK) return rc;
-  const auto t0 = std::chrono::steady_clock::now();
   hipStream_t s = h->ctx->stream;
   const int n = h->W * h->H, nblk = (n + 255) / 256;
-  hipEventRecord(h->ev0, s);
+  const auto t0 = h->tm.begin(s);
   float* d = is_device ? disparity256 : h->d_disp;
   if (!is_device) hipMemcpyAsync(h->d_disp, disparity256, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s);
   lab_components<true>(h, s, nullptr, d, 4, max_diff);
   hipLaunchKernelGGL(k_lab_write<true>, dim3(nblk), dim3(256), 0, s, n, (const int32_t*)h->d_parent, (const int32_t*)h->d_area, (const int32_t*)h->d_rank, max_size,
                      (int32_t*)nullptr, d, h->d_sel);
-  hipEventRecord(h->ev1, s);
+  h->tm.mark_end(s);
   if (!is_device) hipMemcpyAsync(disparity256, h->d_disp, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s);
   rc = lab_finish(who, h, t0);
   if (rc != VDO_OK) return rc;
@@ -480,7 +461,7 @@ static int lab_fetch(const char* who, vdo_labels* h, const int32_t* dev, int32_t
   const int rc = ctx_bind(h->ctx);
   if (rc != VDO_OK) return rc;
   hipMemcpyAsync(out, dev, (size_t)h->W * h->H * sizeof(int32_t), hipMemcpyDeviceToHost, h->ctx->stream);
-  return lab_check_hip(who, hipStreamSynchronize(h->ctx->stream));
+  return check_hip(who, hipStreamSynchronize(h->ctx->stream));
 }
 
 extern "C" int vdo_labels_get_roots(vdo_labels* h, int32_t* out) { return lab_fetch("vdo_labels_get_roots", h, h ? h->d_parent : nullptr, out); }
@@ -488,9 +469,7 @@ extern "C" int vdo_labels_get_roots(vdo_labels* h, int32_t* out) { return lab_fe
 extern "C" int vdo_labels_get_areas(vdo_labels* h, int32_t* out) { return lab_fetch("vdo_labels_get_areas", h, h ? h->d_area : nullptr, out); }
 
 extern "C" int vdo_labels_last_timing(vdo_labels* h, double ms[2]) {
-  if (!h || !ms) return set_error(VDO_ERR_INVALID, "vdo_labels_last_timing: %s is null", !h ? "handle" : "ms");
-  ms[0] = h->ms[0]; ms[1] = h->ms[1];
-  return VDO_OK;
+  return last_timing("vdo_labels_last_timing", h ? &h->tm : nullptr, ms);
 }
 
 extern "C" int vdo_labels_device_images(vdo_labels* h, uint8_t** cls, int32_t** mask) {
@@ -507,8 +486,8 @@ extern "C" int vdo_labels_stage_classes(vdo_labels* h, const uint8_t* cls, int64
   if (cls_stride < h->W) return set_error(VDO_ERR_INVALID, "%s: cls_stride %lld smaller than the width %d", who, (long long)cls_stride, h->W);
   const int rc = ctx_bind(h->ctx);
   if (rc != VDO_OK) return rc;
-  hipMemcpy2DAsync(h->d_cls, h->W, cls, (size_t)cls_stride, h->W, h->H, hipMemcpyHostToDevice, h->ctx->stream);
-  const int rs = lab_check_hip(who, hipStreamSynchronize(h->ctx->stream));
+  stage_rows(h->ctx->stream, h->d_cls, cls, cls_stride, h->W, h->H, 0);
+  const int rs = check_hip(who, hipStreamSynchronize(h->ctx->stream));
   if (rs != VDO_OK) return rs;
   *cls_dev = h->d_cls;
   return VDO_OK;

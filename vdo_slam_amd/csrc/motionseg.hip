@@ -16,20 +16,18 @@
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
-#include <chrono>
 #include <cstdint>
 #include <cstring>
 
 #include "../../include/vdo_slam_hip.h"
 #include "ctx.hpp"
 #include "scan.hpp"
+#include "stage.hpp"
 
 namespace vdo {
 
 constexpr int kMsTW = 64, kMsTH = 16, kMsRMax = 7;                         // vote tile: 256 threads, 4 pixels each
 constexpr int kMsPitch = 80, kMsHH = kMsTH + 2 * kMsRMax;                  // LDS: 30 x 80 state bytes + 30 x 64 packed sums = 10080 bytes
-constexpr int64_t kMsMaxPixels = int64_t(1) << 26;
-constexpr int kMsMaxSide = 1 << 24;                                        // (float)(W - 1) and (float)x are exact
 enum { kMsMoving = 0, kMsStatic, kMsUnknown, kMsCounters = 4 };
 
 // what the kernels take by value: the camera, the weights, the thresholds and the first three rows of T
@@ -58,8 +56,7 @@ struct vdo_motionseg {
   int32_t* d_blk = nullptr;                               // per 256 grid positions: kept, then their exclusive scan
   int32_t* d_cnt = nullptr;                               // [kMsCounters]
   int32_t* h_cnt = nullptr;                               // pinned
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  double ms[2] = {0, 0};
+  vdo::StageTimer tm;
   bool computed = false;
   int smp_cap = -1;                                       // the grid size of the last ego-motion, -1 before the first
 };
@@ -201,21 +198,14 @@ __global__ __launch_bounds__(1024) void k_ms_scan(int32_t* __restrict__ blk, int
   if (threadIdx.x == 0) { n_out[0] = carry; n_out[1] = 0; }
 }
 
-static int ms_check_hip(const char* who, hipError_t e) {
-  return e == hipSuccess ? VDO_OK : set_error(VDO_ERR_NO_DEVICE, "%s: %s", who, hipGetErrorString(e));
-}
-
 static void ms_free(vdo_motionseg* h) {
   hipFree(h->d_state); hipFree(h->d_res); hipFree(h->d_cls); hipFree(h->d_disp1); hipFree(h->d_right); hipFree(h->d_disp0); hipFree(h->d_flow); hipFree(h->d_valid);
   hipFree(h->d_smp); hipFree(h->d_blk); hipFree(h->d_cnt);
   if (h->h_smp) hipHostFree(h->h_smp);
   if (h->h_cnt) hipHostFree(h->h_cnt);
-  if (h->ev0) hipEventDestroy(h->ev0);
-  if (h->ev1) hipEventDestroy(h->ev1);
+  h->tm.destroy();
   delete h;
 }
-
-static bool ms_good(float v) { return std::fabs(v) <= FLT_MAX; }
 
 // the images every entry reads, brought to where a kernel can read them: a packed (and, for the flow, 8-byte aligned) device image is read where
 // it lies, anything else goes to the handle's staging image
@@ -223,21 +213,8 @@ struct MsSources { const float* disp0; const float2* flow; const uint8_t* valid;
 static MsSources ms_stage(vdo_motionseg* h, hipStream_t s, const float* disp0, int64_t disp0_stride, const float* flow, int64_t flow_stride, const uint8_t* valid, int64_t valid_stride,
                           int src_is_device) {
   const int W = h->W, H = h->H;
-  const hipMemcpyKind kind = src_is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  MsSources o{disp0, (const float2*)flow, valid};
-  if (!(src_is_device && disp0_stride == W)) {
-    hipMemcpy2DAsync(h->d_disp0, W * sizeof(float), disp0, (size_t)disp0_stride * sizeof(float), W * sizeof(float), H, kind, s);
-    o.disp0 = h->d_disp0;
-  }
-  if (!(src_is_device && flow_stride == 2 * (int64_t)W && ((uintptr_t)flow & 7) == 0)) {
-    hipMemcpy2DAsync(h->d_flow, 2 * W * sizeof(float), flow, (size_t)flow_stride * sizeof(float), 2 * W * sizeof(float), H, kind, s);
-    o.flow = (const float2*)h->d_flow;
-  }
-  if (valid && !(src_is_device && valid_stride == W)) {
-    hipMemcpy2DAsync(h->d_valid, W, valid, (size_t)valid_stride, W, H, kind, s);
-    o.valid = h->d_valid;
-  }
-  return o;
+  return MsSources{stage_rows(s, h->d_disp0, disp0, disp0_stride, W, H, src_is_device), (const float2*)stage_rows(s, h->d_flow, flow, flow_stride, 2 * W, H, src_is_device, 8),
+                   valid ? stage_rows(s, h->d_valid, valid, valid_stride, W, H, src_is_device) : nullptr};
 }
 
 // the refusals the two entries share; 0 when the sources are in order
@@ -263,22 +240,21 @@ extern "C" int vdo_motionseg_create(vdo_ctx* ctx, int width, int height, const v
   if (!p) return set_error(VDO_ERR_INVALID, "%s: params is null", who);
   if (width < 1) return set_error(VDO_ERR_INVALID, "%s: width %d < 1", who, width);
   if (height < 1) return set_error(VDO_ERR_INVALID, "%s: height %d < 1", who, height);
-  for (int k = 0; k < 4; ++k) if (!ms_good(p->K[k])) return set_error(VDO_ERR_INVALID, "%s: K[%d] is not finite", who, k);
-  if (!(p->K[0] > 0.f) || !(p->K[1] > 0.f)) return set_error(VDO_ERR_INVALID, "%s: K: fx %g, fy %g must be positive", who, (double)p->K[0], (double)p->K[1]);
-  if (!ms_good(p->bf) || !(p->bf > 0.f)) return set_error(VDO_ERR_INVALID, "%s: bf %g must be positive and finite", who, (double)p->bf);
-  if (!ms_good(p->disp_unit) || !(p->disp_unit > 0.f)) return set_error(VDO_ERR_INVALID, "%s: disp_unit %g must be positive and finite", who, (double)p->disp_unit);
-  if (!ms_good(p->sigma_flow) || !(p->sigma_flow > 0.f)) return set_error(VDO_ERR_INVALID, "%s: sigma_flow %g must be positive and finite", who, (double)p->sigma_flow);
-  if (!ms_good(p->sigma_disp) || !(p->sigma_disp > 0.f)) return set_error(VDO_ERR_INVALID, "%s: sigma_disp %g must be positive and finite", who, (double)p->sigma_disp);
-  if (!ms_good(p->chi2) || !(p->chi2 >= 0.f)) return set_error(VDO_ERR_INVALID, "%s: chi2 %g must be finite and >= 0", who, (double)p->chi2);
-  if (!ms_good(p->min_disparity) || !(p->min_disparity >= 0.f)) return set_error(VDO_ERR_INVALID, "%s: min_disparity %g must be finite and >= 0", who, (double)p->min_disparity);
+  int rc = check_intrinsics(who, "K", p->K);
+  if (rc != VDO_OK) return rc;
+  if (!is_finite(p->bf) || !(p->bf > 0.f)) return set_error(VDO_ERR_INVALID, "%s: bf %g must be positive and finite", who, (double)p->bf);
+  if (!is_finite(p->disp_unit) || !(p->disp_unit > 0.f)) return set_error(VDO_ERR_INVALID, "%s: disp_unit %g must be positive and finite", who, (double)p->disp_unit);
+  if (!is_finite(p->sigma_flow) || !(p->sigma_flow > 0.f)) return set_error(VDO_ERR_INVALID, "%s: sigma_flow %g must be positive and finite", who, (double)p->sigma_flow);
+  if (!is_finite(p->sigma_disp) || !(p->sigma_disp > 0.f)) return set_error(VDO_ERR_INVALID, "%s: sigma_disp %g must be positive and finite", who, (double)p->sigma_disp);
+  if (!is_finite(p->chi2) || !(p->chi2 >= 0.f)) return set_error(VDO_ERR_INVALID, "%s: chi2 %g must be finite and >= 0", who, (double)p->chi2);
+  if (!is_finite(p->min_disparity) || !(p->min_disparity >= 0.f)) return set_error(VDO_ERR_INVALID, "%s: min_disparity %g must be finite and >= 0", who, (double)p->min_disparity);
   if (p->vote_radius < 0 || p->vote_radius > kMsRMax) return set_error(VDO_ERR_INVALID, "%s: vote_radius %d outside 0..%d", who, p->vote_radius, kMsRMax);
   if (p->vote_den < 1 || p->vote_den > 65535) return set_error(VDO_ERR_INVALID, "%s: vote_den %d outside 1..65535", who, p->vote_den);
   if (p->vote_num < 0 || p->vote_num >= p->vote_den) return set_error(VDO_ERR_INVALID, "%s: vote_num %d outside 0..vote_den-1 = %d", who, p->vote_num, p->vote_den - 1);
   if (p->min_known < 1) return set_error(VDO_ERR_INVALID, "%s: min_known %d < 1", who, p->min_known);
   if (p->class_value < 1 || p->class_value > 255) return set_error(VDO_ERR_INVALID, "%s: class_value %d outside 1..255", who, p->class_value);
-  if ((int64_t)width * height > kMsMaxPixels || width > kMsMaxSide || height > kMsMaxSide)
-    return set_error(VDO_ERR_UNSUPPORTED, "%s: width x height = %d x %d exceeds 2^26 pixels or 2^24 on a side", who, width, height);
-  int rc = ctx_bind(ctx);
+  rc = check_image_size(who, "width x height =", width, height);
+  if (rc == VDO_OK) rc = ctx_bind(ctx);
   if (rc != VDO_OK) return rc;
   vdo_motionseg* h = new vdo_motionseg;
   h->ctx = ctx; h->W = width; h->H = height; h->p = *p;
@@ -292,8 +268,7 @@ extern "C" int vdo_motionseg_create(vdo_ctx* ctx, int width, int height, const v
                   hipMalloc((void**)&h->d_disp0, n * sizeof(float)) == hipSuccess && hipMalloc((void**)&h->d_flow, 2 * n * sizeof(float)) == hipSuccess &&
                   hipMalloc((void**)&h->d_valid, n) == hipSuccess && hipMalloc((void**)&h->d_smp, smp) == hipSuccess && hipMalloc((void**)&h->d_blk, nblk * sizeof(int32_t)) == hipSuccess &&
                   hipMalloc((void**)&h->d_cnt, kMsCounters * sizeof(int32_t)) == hipSuccess && hipHostMalloc((void**)&h->h_smp, smp, hipHostMallocDefault) == hipSuccess &&
-                  hipHostMalloc((void**)&h->h_cnt, kMsCounters * sizeof(int32_t), hipHostMallocDefault) == hipSuccess && hipEventCreate(&h->ev0) == hipSuccess &&
-                  hipEventCreate(&h->ev1) == hipSuccess;
+                  hipHostMalloc((void**)&h->h_cnt, kMsCounters * sizeof(int32_t), hipHostMallocDefault) == hipSuccess && h->tm.create();
   if (!ok) {
     (void)hipGetLastError();
     ms_free(h);
@@ -325,7 +300,6 @@ extern "C" int vdo_motionseg_egomotion(vdo_motionseg* h, const float* disp0, int
   if (!out) return set_error(VDO_ERR_INVALID, "%s: out is null", who);
   rc = ctx_bind(h->ctx);
   if (rc != VDO_OK) return rc;
-  const auto t0 = std::chrono::steady_clock::now();
   hipStream_t s = h->ctx->stream;
   const int W = h->W, H = h->H;
   const int nx = step / 2 < W ? (W - 1 - step / 2) / step + 1 : 0, ny = step / 2 < H ? (H - 1 - step / 2) / step + 1 : 0;
@@ -333,21 +307,20 @@ extern "C" int vdo_motionseg_egomotion(vdo_motionseg* h, const float* disp0, int
   double* dX = (double*)(h->d_smp + 8);
   double* dUV = dX + 3 * (size_t)ngrid;
   int32_t n = 0;
-  hipEventRecord(h->ev0, s);
+  const auto t0 = h->tm.begin(s);
   if (ngrid > 0) {
     const MsSources src = ms_stage(h, s, disp0, disp0_stride_floats, flow, flow_stride_floats, flow_valid, flow_valid_stride, src_is_device);
     hipLaunchKernelGGL(k_ms_samples<false>, dim3(nblk), dim3(256), 0, s, h->a, src.disp0, src.flow, src.valid, W, H, step, nx, ngrid, h->d_blk, dX, dUV);
     hipLaunchKernelGGL(k_ms_scan, dim3(1), dim3(1024), 0, s, h->d_blk, nblk, (int32_t*)h->d_smp);
     hipLaunchKernelGGL(k_ms_samples<true>, dim3(nblk), dim3(256), 0, s, h->a, src.disp0, src.flow, src.valid, W, H, step, nx, ngrid, h->d_blk, dX, dUV);
-    hipEventRecord(h->ev1, s);
+    h->tm.mark_end(s);
     // one download: the count and both lists at the grid's capacity
     hipMemcpyAsync(h->h_smp, h->d_smp, 8 + (size_t)ngrid * 5 * sizeof(double), hipMemcpyDeviceToHost, s);
   } else {
-    hipEventRecord(h->ev1, s);
+    h->tm.mark_end(s);
   }
-  hipError_t e = hipStreamSynchronize(s);
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e != hipSuccess) return ms_check_hip(who, e);
+  rc = sync_check(who, s);
+  if (rc != VDO_OK) return rc;
   if (ngrid > 0) std::memcpy(&n, h->h_smp, sizeof n);
   else std::memset(h->h_smp, 0, 8);
   h->smp_cap = ngrid;
@@ -361,10 +334,7 @@ extern "C" int vdo_motionseg_egomotion(vdo_motionseg* h, const float* disp0, int
   const bool found = r.n_inliers >= min_inliers && r.best_iteration >= 0;
   for (int k = 0; k < 16; ++k) T[k] = found ? (float)r.T[k] : (k % 5 == 0 ? 1.f : 0.f);
   out[0] = n; out[1] = r.n_inliers; out[2] = r.iterations_run;
-  float dev_ms = 0.f;
-  hipEventElapsedTime(&dev_ms, h->ev0, h->ev1);
-  h->ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  h->ms[1] = dev_ms;
+  h->tm.finish(t0);
   return VDO_OK;
 }
 
@@ -381,37 +351,27 @@ extern "C" int vdo_motionseg_compute(vdo_motionseg* h, const float* disp0, int64
   if (!out) return set_error(VDO_ERR_INVALID, "%s: out is null", who);
   rc = ctx_bind(h->ctx);
   if (rc != VDO_OK) return rc;
-  const auto t0 = std::chrono::steady_clock::now();
   hipStream_t s = h->ctx->stream;
   const int W = h->W, H = h->H, n = W * H, nblk = (n + 255) / 256;
   const int tiles_x = (W + kMsTW - 1) / kMsTW, tiles_y = (H + kMsTH - 1) / kMsTH;
   MsArgs a = h->a;
   for (int k = 0; k < 12; ++k) a.T[k] = T[k];
-  hipEventRecord(h->ev0, s);
+  const auto t0 = h->tm.begin(s);
   const MsSources src = ms_stage(h, s, disp0, disp0_stride_floats, flow, flow_stride_floats, flow_valid, flow_valid_stride, src_is_device);
-  const float* d_disp1 = disp1;
-  if (!(src_is_device && disp1_stride_floats == W)) {
-    hipMemcpy2DAsync(h->d_disp1, W * sizeof(float), disp1, (size_t)disp1_stride_floats * sizeof(float), W * sizeof(float), H,
-                     src_is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s);
-    d_disp1 = h->d_disp1;
-  }
+  const float* d_disp1 = stage_rows(s, h->d_disp1, disp1, disp1_stride_floats, W, H, src_is_device);
   uint8_t* d_cls = out_is_device ? cls : h->d_cls;
   hipMemsetAsync(h->d_cnt, 0, kMsCounters * sizeof(int32_t), s);
   hipLaunchKernelGGL(k_ms_residual, dim3(nblk), dim3(256), 0, s, a, src.disp0, d_disp1, src.flow, src.valid, W, H, h->d_state, h->d_res, h->d_cnt);
   const vdo_motionseg_params& p = h->p;
   hipLaunchKernelGGL(k_ms_vote, dim3(tiles_x * tiles_y), dim3(256), 0, s, (const uint8_t*)h->d_state, W, H, tiles_x, p.vote_radius, p.vote_num, p.vote_den, p.min_known, p.class_value,
                      d_cls, h->d_cnt);
-  hipEventRecord(h->ev1, s);
+  h->tm.mark_end(s);
   if (!out_is_device) hipMemcpyAsync(cls, h->d_cls, (size_t)n, hipMemcpyDeviceToHost, s);
   hipMemcpyAsync(h->h_cnt, h->d_cnt, kMsCounters * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-  hipError_t e = hipStreamSynchronize(s);
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e != hipSuccess) return ms_check_hip(who, e);
+  rc = sync_check(who, s);
+  if (rc != VDO_OK) return rc;
   out[0] = h->h_cnt[kMsMoving]; out[1] = h->h_cnt[kMsStatic]; out[2] = h->h_cnt[kMsUnknown];
-  float dev_ms = 0.f;
-  hipEventElapsedTime(&dev_ms, h->ev0, h->ev1);
-  h->ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  h->ms[1] = dev_ms;
+  h->tm.finish(t0);
   h->computed = true;
   return VDO_OK;
 }
@@ -423,7 +383,7 @@ static int ms_fetch(const char* who, vdo_motionseg* h, const void* dev, size_t b
   const int rc = ctx_bind(h->ctx);
   if (rc != VDO_OK) return rc;
   hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, h->ctx->stream);
-  return ms_check_hip(who, hipStreamSynchronize(h->ctx->stream));
+  return check_hip(who, hipStreamSynchronize(h->ctx->stream));
 }
 
 extern "C" int vdo_motionseg_get_state(vdo_motionseg* h, uint8_t* out) { return ms_fetch("vdo_motionseg_get_state", h, h ? h->d_state : nullptr, h ? (size_t)h->W * h->H : 0, out); }
@@ -447,9 +407,7 @@ extern "C" int vdo_motionseg_get_samples(vdo_motionseg* h, double* X, double* uv
 }
 
 extern "C" int vdo_motionseg_last_timing(vdo_motionseg* h, double ms[2]) {
-  if (!h || !ms) return set_error(VDO_ERR_INVALID, "vdo_motionseg_last_timing: %s is null", !h ? "handle" : "ms");
-  ms[0] = h->ms[0]; ms[1] = h->ms[1];
-  return VDO_OK;
+  return last_timing("vdo_motionseg_last_timing", h ? &h->tm : nullptr, ms);
 }
 
 extern "C" int vdo_motionseg_device_images(vdo_motionseg* h, float** disp1, uint8_t** next_right, uint8_t** cls) {

@@ -18,7 +18,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
-#include <chrono>
 #include <climits>
 #include <cmath>
 #include <cstdint>
@@ -27,6 +26,7 @@
 #include "../../include/vdo_slam_hip.h"
 #include "ctx.hpp"
 #include "frame_images.hpp"
+#include "stage.hpp"
 #include "dense.hpp"
 
 namespace vdo {
@@ -188,39 +188,18 @@ struct vdo_objects {
   vdo::ObEntry* h_tab = nullptr;                          // pinned
   unsigned long long* d_cnt = nullptr;                    // [max_batch][kObSlots][2]
   unsigned long long* h_cnt = nullptr;                    // pinned
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  double ms[2] = {0, 0};
+  vdo::StageTimer tm;
 };
 
 namespace vdo {
-
-static int ob_check_hip(const char* who, hipError_t e) { return e == hipSuccess ? VDO_OK : set_error(VDO_ERR_NO_DEVICE, "%s: %s", who, hipGetErrorString(e)); }
-
-static bool ob_good(float v) { return std::fabs(v) <= FLT_MAX; }
 
 static void ob_free(vdo_objects* h) {
   hipFree(h->d_depth); hipFree(h->d_mask); hipFree(h->d_stats); hipFree(h->d_tab); hipFree(h->d_cnt);
   if (h->h_stats) hipHostFree(h->h_stats);
   if (h->h_tab) hipHostFree(h->h_tab);
   if (h->h_cnt) hipHostFree(h->h_cnt);
-  if (h->ev0) hipEventDestroy(h->ev0);
-  if (h->ev1) hipEventDestroy(h->ev1);
+  h->tm.destroy();
   delete h;
-}
-
-// What the entries check of the images before anything is queued
-static int ob_check_images(const char* who, const vdo_objects* h, const float* depth, int64_t ds, const int32_t* mask, int64_t ms) {
-  if (!depth) return set_error(VDO_ERR_INVALID, "%s: depth is null", who);
-  if (!mask) return set_error(VDO_ERR_INVALID, "%s: mask is null", who);
-  if (ds < h->W) return set_error(VDO_ERR_INVALID, "%s: depth_stride_floats %lld smaller than the width %d", who, (long long)ds, h->W);
-  if (ms < h->W) return set_error(VDO_ERR_INVALID, "%s: mask_stride_ints %lld smaller than the width %d", who, (long long)ms, h->W);
-  return VDO_OK;
-}
-
-static int ob_check_frame(const char* who, const vdo_objects* h, const vdo_frame_images* f) {
-  if (!f) return set_error(VDO_ERR_INVALID, "%s: frame is null", who);
-  if (f->w != h->W || f->h != h->H) return set_error(VDO_ERR_INVALID, "%s: frame is %d x %d, the stage's images are %d x %d", who, f->w, f->h, h->W, h->H);
-  return VDO_OK;
 }
 
 static int ob_check_batch(const char* who, const vdo_objects* h, int n, vdo_dense* const* maps, const int32_t* labels, const float* T, const int64_t* out) {
@@ -245,44 +224,23 @@ static int ob_check_batch(const char* who, const vdo_objects* h, int n, vdo_dens
   return VDO_OK;
 }
 
-// Packed device images from the caller's (ev0 is recorded first)
-static void ob_stage(vdo_objects* h, const float* depth, int64_t ds, const int32_t* mask, int64_t ms, int src_is_device, const float** d_depth, const int32_t** d_mask) {
-  hipStream_t s = h->ctx->stream;
-  const int W = h->W, H = h->H;
-  const hipMemcpyKind kind = src_is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  hipEventRecord(h->ev0, s);
-  *d_depth = depth; *d_mask = mask;
-  if (!(src_is_device && ds == W)) {
-    hipMemcpy2DAsync(h->d_depth, W * sizeof(float), depth, (size_t)ds * sizeof(float), W * sizeof(float), H, kind, s);
-    *d_depth = h->d_depth;
-  }
-  if (!(src_is_device && ms == W)) {
-    hipMemcpy2DAsync(h->d_mask, W * sizeof(int32_t), mask, (size_t)ms * sizeof(int32_t), W * sizeof(int32_t), H, kind, s);
-    *d_mask = h->d_mask;
-  }
-}
-
 // The stats pass and its download; the table is in h_stats afterwards
 static int ob_stats(const char* who, vdo_objects* h, const float* d_depth, const int32_t* d_mask) {
   hipStream_t s = h->ctx->stream;
   const int npix = h->W * h->H;
   hipLaunchKernelGGL(k_ob_stats_reset, dim3((h->rows + 255) / 256), dim3(256), 0, s, h->d_stats, h->rows, h->W, h->H);
   hipLaunchKernelGGL(k_ob_stats, dim3((npix + 255) / 256), dim3(256), 0, s, d_depth, d_mask, h->W, h->H, h->sa, h->d_stats);
-  hipEventRecord(h->ev1, s);
+  h->tm.mark_end(s);
   hipMemcpyAsync(h->h_stats, h->d_stats, (size_t)h->rows * kObRow * sizeof(long long), hipMemcpyDeviceToHost, s);
-  hipError_t e = hipStreamSynchronize(s);
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e != hipSuccess) return ob_check_hip(who, e);
+  const int rc = sync_check(who, s);
+  if (rc != VDO_OK) return rc;
   h->have_stats = true;
   return VDO_OK;
 }
 
-static void ob_finish(vdo_objects* h, std::chrono::steady_clock::time_point t0, int64_t* stats) {
+static void ob_finish(vdo_objects* h, StageClock::time_point t0, int64_t* stats) {
   if (stats) std::memcpy(stats, h->h_stats, (size_t)h->rows * kObRow * sizeof(long long));
-  float dev_ms = 0.f;
-  hipEventElapsedTime(&dev_ms, h->ev0, h->ev1);
-  h->ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  h->ms[1] = dev_ms;
+  h->tm.finish(t0);
 }
 
 // After the stats: the table of the objects that get work, one launch, the counts
@@ -307,11 +265,10 @@ static int ob_fuse(const char* who, vdo_objects* h, const float* d_depth, const 
   const int xblocks = (big[0] + 63) / 64;                                  // <= 64, times m <= 64
   const dim3 grid((unsigned)(xblocks * m), (big[1] + kObVpt - 1) / kObVpt, (big[2] + kDnZ - 1) / kDnZ);
   hipLaunchKernelGGL(k_ob_integrate<kObVpt>, grid, dim3(64, 1, kDnZ), 0, s, (const ObEntry*)h->d_tab, xblocks, d_depth, d_mask, h->W, h->H, h->d_cnt);
-  hipEventRecord(h->ev1, s);
+  h->tm.mark_end(s);
   hipMemcpyAsync(h->h_cnt, h->d_cnt, (size_t)n * kObSlots * 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
-  hipError_t e = hipStreamSynchronize(s);
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e != hipSuccess) return ob_check_hip(who, e);
+  const int rc = sync_check(who, s);
+  if (rc != VDO_OK) return rc;
   for (int i = 0; i < n; ++i)
     for (int k = 0; k < 2; ++k) {
       unsigned long long sum = 0;
@@ -332,14 +289,13 @@ extern "C" int vdo_objects_create(vdo_ctx* ctx, int width, int height, const vdo
   if (!p) return set_error(VDO_ERR_INVALID, "%s: params is null", who);
   if (width < 1) return set_error(VDO_ERR_INVALID, "%s: width %d < 1", who, width);
   if (height < 1) return set_error(VDO_ERR_INVALID, "%s: height %d < 1", who, height);
-  for (int k = 0; k < 4; ++k) if (!ob_good(p->K[k])) return set_error(VDO_ERR_INVALID, "%s: K[%d] is not finite", who, k);
-  if (!(p->K[0] > 0.f) || !(p->K[1] > 0.f)) return set_error(VDO_ERR_INVALID, "%s: K: fx %g, fy %g must be positive", who, (double)p->K[0], (double)p->K[1]);
-  if (!ob_good(p->min_depth) || !(p->min_depth >= 0.f)) return set_error(VDO_ERR_INVALID, "%s: min_depth %g must be finite and >= 0", who, (double)p->min_depth);
-  if (!ob_good(p->max_depth) || !(p->max_depth > p->min_depth)) return set_error(VDO_ERR_INVALID, "%s: max_depth %g must be finite and above min_depth %g", who, (double)p->max_depth, (double)p->min_depth);
+  int rc = check_intrinsics(who, "K", p->K);
+  if (rc == VDO_OK) rc = check_depth_range(who, p->min_depth, p->max_depth);
+  if (rc != VDO_OK) return rc;
   if (p->max_labels < 1 || p->max_labels > 1023) return set_error(VDO_ERR_INVALID, "%s: max_labels %d outside 1..1023", who, p->max_labels);
   if (p->max_batch < 1 || p->max_batch > 64) return set_error(VDO_ERR_INVALID, "%s: max_batch %d outside 1..64", who, p->max_batch);
-  if ((int64_t)width * height > kDnMaxPixels || width > kDnMaxImageSide || height > kDnMaxImageSide)
-    return set_error(VDO_ERR_UNSUPPORTED, "%s: width x height = %d x %d exceeds 2^26 pixels or 2^24 on a side", who, width, height);
+  rc = check_image_size(who, "width x height =", width, height);
+  if (rc != VDO_OK) return rc;
   {
     const double mx = (double)width + std::fabs((double)p->K[2]), my = (double)height + std::fabs((double)p->K[3]), m = mx > my ? mx : my;
     const double f = (double)(p->K[0] < p->K[1] ? p->K[0] : p->K[1]), r = m / f > 1.0 ? m / f : 1.0;
@@ -348,7 +304,7 @@ extern "C" int vdo_objects_create(vdo_ctx* ctx, int width, int height, const vdo
       return set_error(VDO_ERR_UNSUPPORTED, "%s: width * height * (max((w + |cx|, h + |cy|) / min(fx, fy), 1) * max_depth * 1024 + 1) = %g exceeds 2^62: a sum could leave int64", who,
                        (double)width * (double)height * term);
   }
-  int rc = ctx_bind(ctx);
+  rc = ctx_bind(ctx);
   if (rc != VDO_OK) return rc;
   vdo_objects* h = new vdo_objects;
   h->ctx = ctx; h->W = width; h->H = height; h->p = *p; h->rows = p->max_labels + 1;
@@ -358,7 +314,7 @@ extern "C" int vdo_objects_create(vdo_ctx* ctx, int width, int height, const vdo
   const bool ok = hipMalloc((void**)&h->d_depth, npix * sizeof(float)) == hipSuccess && hipMalloc((void**)&h->d_mask, npix * sizeof(int32_t)) == hipSuccess &&
                   hipMalloc((void**)&h->d_stats, sb) == hipSuccess && hipMalloc((void**)&h->d_tab, tb) == hipSuccess && hipMalloc((void**)&h->d_cnt, cb) == hipSuccess &&
                   hipHostMalloc((void**)&h->h_stats, sb, hipHostMallocDefault) == hipSuccess && hipHostMalloc((void**)&h->h_tab, tb, hipHostMallocDefault) == hipSuccess &&
-                  hipHostMalloc((void**)&h->h_cnt, cb, hipHostMallocDefault) == hipSuccess && hipEventCreate(&h->ev0) == hipSuccess && hipEventCreate(&h->ev1) == hipSuccess;
+                  hipHostMalloc((void**)&h->h_cnt, cb, hipHostMallocDefault) == hipSuccess && h->tm.create();
   if (!ok) {
     (void)hipGetLastError();
     ob_free(h);
@@ -378,13 +334,14 @@ extern "C" int vdo_objects_destroy(vdo_objects* h) {
 extern "C" int vdo_objects_stats(vdo_objects* h, const float* depth, int64_t depth_stride_floats, const int32_t* mask, int64_t mask_stride_ints, int src_is_device, int64_t* stats) {
   static const char* who = "vdo_objects_stats";
   if (!h) return set_error(VDO_ERR_INVALID, "%s: handle is null", who);
-  int rc = ob_check_images(who, h, depth, depth_stride_floats, mask, mask_stride_ints);
+  int rc = check_depth_mask(who, h->W, depth, depth_stride_floats, mask, mask_stride_ints, true);
   if (rc != VDO_OK) return rc;
   rc = ctx_bind(h->ctx);
   if (rc != VDO_OK) return rc;
-  const auto t0 = std::chrono::steady_clock::now();
-  const float* d_depth; const int32_t* d_mask;
-  ob_stage(h, depth, depth_stride_floats, mask, mask_stride_ints, src_is_device, &d_depth, &d_mask);
+  hipStream_t s = h->ctx->stream;
+  const auto t0 = h->tm.begin(s);
+  const float* d_depth = stage_rows(s, h->d_depth, depth, depth_stride_floats, h->W, h->H, src_is_device);
+  const int32_t* d_mask = stage_rows(s, h->d_mask, mask, mask_stride_ints, h->W, h->H, src_is_device);
   rc = ob_stats(who, h, d_depth, d_mask);
   if (rc != VDO_OK) return rc;
   ob_finish(h, t0, stats);
@@ -394,12 +351,11 @@ extern "C" int vdo_objects_stats(vdo_objects* h, const float* depth, int64_t dep
 extern "C" int vdo_objects_stats_frame(vdo_objects* h, const vdo_frame_images* f, int64_t* stats) {
   static const char* who = "vdo_objects_stats_frame";
   if (!h) return set_error(VDO_ERR_INVALID, "%s: handle is null", who);
-  int rc = ob_check_frame(who, h, f);
+  int rc = check_frame(who, f, h->W, h->H, "the stage's");
   if (rc != VDO_OK) return rc;
   rc = ctx_bind(h->ctx);
   if (rc != VDO_OK) return rc;
-  const auto t0 = std::chrono::steady_clock::now();
-  hipEventRecord(h->ev0, h->ctx->stream);
+  const auto t0 = h->tm.begin(h->ctx->stream);
   rc = ob_stats(who, h, f->d_depth, f->d_mask);
   if (rc != VDO_OK) return rc;
   ob_finish(h, t0, stats);
@@ -410,15 +366,16 @@ extern "C" int vdo_objects_integrate(vdo_objects* h, const float* depth, int64_t
                                      vdo_dense* const* maps, const int32_t* labels, const float* T, int64_t* out) {
   static const char* who = "vdo_objects_integrate";
   if (!h) return set_error(VDO_ERR_INVALID, "%s: handle is null", who);
-  int rc = ob_check_images(who, h, depth, depth_stride_floats, mask, mask_stride_ints);
+  int rc = check_depth_mask(who, h->W, depth, depth_stride_floats, mask, mask_stride_ints, true);
   if (rc != VDO_OK) return rc;
   rc = ob_check_batch(who, h, n, maps, labels, T, out);
   if (rc != VDO_OK) return rc;
   rc = ctx_bind(h->ctx);
   if (rc != VDO_OK) return rc;
-  const auto t0 = std::chrono::steady_clock::now();
-  const float* d_depth; const int32_t* d_mask;
-  ob_stage(h, depth, depth_stride_floats, mask, mask_stride_ints, src_is_device, &d_depth, &d_mask);
+  hipStream_t s = h->ctx->stream;
+  const auto t0 = h->tm.begin(s);
+  const float* d_depth = stage_rows(s, h->d_depth, depth, depth_stride_floats, h->W, h->H, src_is_device);
+  const int32_t* d_mask = stage_rows(s, h->d_mask, mask, mask_stride_ints, h->W, h->H, src_is_device);
   rc = ob_stats(who, h, d_depth, d_mask);
   if (rc == VDO_OK) rc = ob_fuse(who, h, d_depth, d_mask, n, maps, labels, T, out);
   if (rc != VDO_OK) return rc;
@@ -429,14 +386,13 @@ extern "C" int vdo_objects_integrate(vdo_objects* h, const float* depth, int64_t
 extern "C" int vdo_objects_integrate_frame(vdo_objects* h, const vdo_frame_images* f, int n, vdo_dense* const* maps, const int32_t* labels, const float* T, int64_t* out) {
   static const char* who = "vdo_objects_integrate_frame";
   if (!h) return set_error(VDO_ERR_INVALID, "%s: handle is null", who);
-  int rc = ob_check_frame(who, h, f);
+  int rc = check_frame(who, f, h->W, h->H, "the stage's");
   if (rc != VDO_OK) return rc;
   rc = ob_check_batch(who, h, n, maps, labels, T, out);
   if (rc != VDO_OK) return rc;
   rc = ctx_bind(h->ctx);
   if (rc != VDO_OK) return rc;
-  const auto t0 = std::chrono::steady_clock::now();
-  hipEventRecord(h->ev0, h->ctx->stream);
+  const auto t0 = h->tm.begin(h->ctx->stream);
   rc = ob_stats(who, h, f->d_depth, f->d_mask);
   if (rc == VDO_OK) rc = ob_fuse(who, h, f->d_depth, f->d_mask, n, maps, labels, T, out);
   if (rc != VDO_OK) return rc;
@@ -459,7 +415,5 @@ extern "C" int vdo_objects_last_stats(vdo_objects* h, int64_t* stats) {
 }
 
 extern "C" int vdo_objects_last_timing(vdo_objects* h, double ms[2]) {
-  if (!h || !ms) return set_error(VDO_ERR_INVALID, "vdo_objects_last_timing: %s is null", !h ? "handle" : "ms");
-  ms[0] = h->ms[0]; ms[1] = h->ms[1];
-  return VDO_OK;
+  return last_timing("vdo_objects_last_timing", h ? &h->tm : nullptr, ms);
 }

@@ -16,12 +16,12 @@
 //   k_flow_check     forward-backward check, validity image and the count of valid pixels (wave ballot, one integer atomic per wave).
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cstdint>
 
 #include "../../include/vdo_slam_hip.h"
 #include "census.hpp"
 #include "ctx.hpp"
+#include "stage.hpp"
 
 namespace vdo {
 
@@ -53,8 +53,7 @@ struct vdo_optflow {
   int* d_count = nullptr;
   int* h_count = nullptr;                               // pinned
   int32_t* d_mask = nullptr;                            // vdo_optflow_stage_mask, made on first use
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  double ms[2] = {0, 0};
+  vdo::StageTimer tm;
   bool computed = false;
 };
 
@@ -258,15 +257,10 @@ __global__ __launch_bounds__(256) void k_flow_check(const int2* __restrict__ F, 
   if ((threadIdx.x & 63) == 0 && count) atomicAdd(n_valid, count);
 }
 
-static int flow_check_hip(const char* who, hipError_t e) {
-  return e == hipSuccess ? VDO_OK : set_error(VDO_ERR_NO_DEVICE, "%s: %s", who, hipGetErrorString(e));
-}
-
 static void flow_free(vdo_optflow* h) {
   hipFree(h->d_pyr); hipFree(h->d_census); hipFree(h->d_level_flow); hipFree(h->d_raw); hipFree(h->d_flow); hipFree(h->d_valid); hipFree(h->d_count); hipFree(h->d_mask);
   if (h->h_count) hipHostFree(h->h_count);
-  if (h->ev0) hipEventDestroy(h->ev0);
-  if (h->ev1) hipEventDestroy(h->ev1);
+  h->tm.destroy();
   delete h;
 }
 
@@ -315,7 +309,7 @@ extern "C" int vdo_optflow_create(vdo_ctx* ctx, int width, int height, const vdo
                   hipMalloc((void**)&h->d_level_flow, 2 * (size_t)tot * sizeof(int2)) == hipSuccess && hipMalloc((void**)&h->d_raw, 2 * n1 * sizeof(int2)) == hipSuccess &&
                   hipMalloc((void**)&h->d_flow, 2 * n * sizeof(float)) == hipSuccess && hipMalloc((void**)&h->d_valid, n) == hipSuccess &&
                   hipMalloc((void**)&h->d_count, sizeof(int)) == hipSuccess && hipHostMalloc((void**)&h->h_count, sizeof(int), hipHostMallocDefault) == hipSuccess &&
-                  hipEventCreate(&h->ev0) == hipSuccess && hipEventCreate(&h->ev1) == hipSuccess;
+                  h->tm.create();
   if (!ok) {
     (void)hipGetLastError();
     flow_free(h);
@@ -344,12 +338,11 @@ extern "C" int vdo_optflow_compute(vdo_optflow* h, const uint8_t* im0, int64_t s
   if (!n_valid) return set_error(VDO_ERR_INVALID, "%s: n_valid is null", who);
   int rc = ctx_bind(h->ctx);
   if (rc != VDO_OK) return rc;
-  const auto t0 = std::chrono::steady_clock::now();
   hipStream_t s = h->ctx->stream;
   const FlowGeom& g = h->g;
   const int W = h->W, H = h->H, L = g.L, tot = g.tot;
   const size_t n_pix = (size_t)W * H;
-  hipEventRecord(h->ev0, s);
+  const auto t0 = h->tm.begin(s);
   // level 0 of the two pyramids is the pair, packed (a device pair that already lies there stays where it is)
   const hipMemcpyKind kind = src_is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   if (!(src_is_device && im0 == h->d_pyr && stride0 == W)) hipMemcpy2DAsync(h->d_pyr, W, im0, (size_t)stride0, W, H, kind, s);
@@ -381,20 +374,16 @@ extern "C" int vdo_optflow_compute(vdo_optflow* h, const uint8_t* im0, int64_t s
   }
   hipLaunchKernelGGL(k_flow_check, dim3((unsigned)((n_pix + 256 * kFlowCheckBatches - 1) / (256 * kFlowCheckBatches))), dim3(256), 0, s, (const int2*)h->d_level_flow, n_dir == 2 ? (const int2*)(h->d_level_flow + tot) : nullptr, W, H,
                      h->p.fb_max_diff, d_valid, h->d_count);
-  hipEventRecord(h->ev1, s);
+  h->tm.mark_end(s);
   hipMemcpyAsync(h->h_count, h->d_count, sizeof(int), hipMemcpyDeviceToHost, s);
   if (!out_is_device) {
     hipMemcpyAsync(flow, h->d_flow, 2 * n_pix * sizeof(float), hipMemcpyDeviceToHost, s);
     if (valid) hipMemcpyAsync(valid, h->d_valid, n_pix, hipMemcpyDeviceToHost, s);
   }
-  hipError_t e = hipStreamSynchronize(s);
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e != hipSuccess) return flow_check_hip(who, e);
+  rc = sync_check(who, s);
+  if (rc != VDO_OK) return rc;
   *n_valid = *h->h_count;
-  float dev_ms = 0.f;
-  hipEventElapsedTime(&dev_ms, h->ev0, h->ev1);
-  h->ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  h->ms[1] = dev_ms;
+  h->tm.finish(t0);
   h->computed = true;
   return VDO_OK;
 }
@@ -419,7 +408,7 @@ static int flow_fetch(const char* who, vdo_optflow* h, const char* sel_name, int
   if (rc != VDO_OK) return rc;
   const size_t first = (size_t)sel * h->g.tot + h->g.off[level], count = (size_t)h->g.W[level] * h->g.H[level];
   hipMemcpyAsync(out, (const char*)dev + first * elem, count * elem, hipMemcpyDeviceToHost, h->ctx->stream);
-  return flow_check_hip(who, hipStreamSynchronize(h->ctx->stream));
+  return check_hip(who, hipStreamSynchronize(h->ctx->stream));
 }
 
 extern "C" int vdo_optflow_get_pyramid(vdo_optflow* h, int which, int level, uint8_t* out) {
@@ -436,9 +425,7 @@ extern "C" int vdo_optflow_get_level_flow(vdo_optflow* h, int dir, int level, in
 }
 
 extern "C" int vdo_optflow_last_timing(vdo_optflow* h, double ms[2]) {
-  if (!h || !ms) return set_error(VDO_ERR_INVALID, "vdo_optflow_last_timing: %s is null", !h ? "handle" : "ms");
-  ms[0] = h->ms[0]; ms[1] = h->ms[1];
-  return VDO_OK;
+  return last_timing("vdo_optflow_last_timing", h ? &h->tm : nullptr, ms);
 }
 
 extern "C" int vdo_optflow_device_images(vdo_optflow* h, uint8_t** im0, uint8_t** im1, float** flow, uint8_t** valid) {
@@ -459,7 +446,7 @@ extern "C" int vdo_optflow_stage_mask(vdo_optflow* h, const int32_t* mask, int32
   const size_t n = (size_t)h->W * h->H;
   if (!h->d_mask && hipMalloc((void**)&h->d_mask, n * sizeof(int32_t)) != hipSuccess) { h->d_mask = nullptr; return set_error(VDO_ERR_OOM, "%s: device allocation failed", who); }
   hipMemcpyAsync(h->d_mask, mask, n * sizeof(int32_t), hipMemcpyHostToDevice, h->ctx->stream);
-  const int rs = flow_check_hip(who, hipStreamSynchronize(h->ctx->stream));
+  const int rs = check_hip(who, hipStreamSynchronize(h->ctx->stream));
   if (rs != VDO_OK) return rs;
   *mask_dev = h->d_mask;
   return VDO_OK;

@@ -20,12 +20,12 @@
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
-#include <chrono>
 #include <cmath>
 #include <cstdint>
 
 #include "../../include/vdo_slam_hip.h"
 #include "ctx.hpp"
+#include "stage.hpp"
 #include "dense.hpp"
 
 namespace vdo {
@@ -229,10 +229,6 @@ __global__ __launch_bounds__(256) void k_rc_march(RcArgs a, const uint32_t* __re
   }
 }
 
-static int rc_check_hip(const char* who, hipError_t e) { return e == hipSuccess ? VDO_OK : set_error(VDO_ERR_NO_DEVICE, "%s: %s", who, hipGetErrorString(e)); }
-
-static bool rc_good(float v) { return std::fabs(v) <= FLT_MAX; }
-
 }  // namespace vdo
 
 struct vdo_raycast {
@@ -244,8 +240,9 @@ struct vdo_raycast {
   uint8_t* d_grid = nullptr;                              // one byte per brick
   unsigned long long* d_cnt = nullptr;                    // [kRcSlots][kRcCounters]
   unsigned long long* h_cnt = nullptr;                    // pinned
-  hipEvent_t ev0 = nullptr, evg = nullptr, ev1 = nullptr;
-  double ms[2] = {0, 0}, grid_ms = 0;
+  vdo::StageTimer tm;
+  hipEvent_t evg = nullptr;                               // between the brick grid and the march
+  double grid_ms = 0;
 };
 
 using namespace vdo;
@@ -258,9 +255,8 @@ void vdo::rc_view_info(const vdo_raycast* view, int* W, int* H, float K[4], vdo_
 static void rc_free(vdo_raycast* h) {
   hipFree(h->d_stage); hipFree(h->d_grid); hipFree(h->d_cnt);
   if (h->h_cnt) hipHostFree(h->h_cnt);
-  if (h->ev0) hipEventDestroy(h->ev0);
+  h->tm.destroy();
   if (h->evg) hipEventDestroy(h->evg);
-  if (h->ev1) hipEventDestroy(h->ev1);
   delete h;
 }
 
@@ -271,15 +267,14 @@ extern "C" int vdo_raycast_create(vdo_dense* map, int width, int height, const v
   if (!p) return set_error(VDO_ERR_INVALID, "%s: params is null", who);
   if (width < 1) return set_error(VDO_ERR_INVALID, "%s: width %d < 1", who, width);
   if (height < 1) return set_error(VDO_ERR_INVALID, "%s: height %d < 1", who, height);
-  for (int k = 0; k < 4; ++k) if (!rc_good(p->K[k])) return set_error(VDO_ERR_INVALID, "%s: K[%d] is not finite", who, k);
-  if (!(p->K[0] > 0.f) || !(p->K[1] > 0.f)) return set_error(VDO_ERR_INVALID, "%s: K: fx %g, fy %g must be positive", who, (double)p->K[0], (double)p->K[1]);
-  if (!rc_good(p->near) || !(p->near >= 0.f)) return set_error(VDO_ERR_INVALID, "%s: near %g must be finite and >= 0", who, (double)p->near);
-  if (!rc_good(p->step) || !(p->step > 0.f)) return set_error(VDO_ERR_INVALID, "%s: step %g must be positive and finite", who, (double)p->step);
+  int rc = check_intrinsics(who, "K", p->K);
+  if (rc != VDO_OK) return rc;
+  if (!is_finite(p->near) || !(p->near >= 0.f)) return set_error(VDO_ERR_INVALID, "%s: near %g must be finite and >= 0", who, (double)p->near);
+  if (!is_finite(p->step) || !(p->step > 0.f)) return set_error(VDO_ERR_INVALID, "%s: step %g must be positive and finite", who, (double)p->step);
   if (p->n_steps < 1 || p->n_steps > kRcMaxSteps) return set_error(VDO_ERR_INVALID, "%s: n_steps %d outside 1..65536", who, p->n_steps);
   if (p->min_weight < 1 || p->min_weight > 255) return set_error(VDO_ERR_INVALID, "%s: min_weight %d outside 1..255", who, p->min_weight);
-  if ((int64_t)width * height > kDnMaxPixels || width > kDnMaxImageSide || height > kDnMaxImageSide)
-    return set_error(VDO_ERR_UNSUPPORTED, "%s: width x height = %d x %d exceeds 2^26 pixels or 2^24 on a side", who, width, height);
-  const int rc = ctx_bind(map->ctx);
+  rc = check_image_size(who, "width x height =", width, height);
+  if (rc == VDO_OK) rc = ctx_bind(map->ctx);
   if (rc != VDO_OK) return rc;
   vdo_raycast* h = new vdo_raycast;
   h->map = map;
@@ -291,8 +286,8 @@ extern "C" int vdo_raycast_create(vdo_dense* map, int width, int height, const v
   h->npix = (size_t)width * height;
   const bool ok = hipMalloc((void**)&h->d_stage, h->npix * 5 * sizeof(float)) == hipSuccess && hipMalloc((void**)&h->d_grid, h->grid_bytes) == hipSuccess &&
                   hipMalloc((void**)&h->d_cnt, kRcTotal * sizeof(unsigned long long)) == hipSuccess &&
-                  hipHostMalloc((void**)&h->h_cnt, kRcTotal * sizeof(unsigned long long), hipHostMallocDefault) == hipSuccess && hipEventCreate(&h->ev0) == hipSuccess &&
-                  hipEventCreate(&h->evg) == hipSuccess && hipEventCreate(&h->ev1) == hipSuccess;
+                  hipHostMalloc((void**)&h->h_cnt, kRcTotal * sizeof(unsigned long long), hipHostMallocDefault) == hipSuccess && h->tm.create() &&
+                  hipEventCreate(&h->evg) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
     rc_free(h);
@@ -320,9 +315,8 @@ extern "C" int vdo_raycast_render(vdo_raycast* h, const float T[16], float* dept
   if (!h) return set_error(VDO_ERR_INVALID, "%s: handle is null", who);
   if (!T) return set_error(VDO_ERR_INVALID, "%s: T is null", who);
   if (!out) return set_error(VDO_ERR_INVALID, "%s: out is null", who);
-  const int rc = ctx_bind(h->map->ctx);
+  int rc = ctx_bind(h->map->ctx);
   if (rc != VDO_OK) return rc;
-  const auto t0 = std::chrono::steady_clock::now();
   hipStream_t s = h->map->ctx->stream;
   RcArgs a = h->a;
   dn_centre(T, a.c);
@@ -335,7 +329,7 @@ extern "C" int vdo_raycast_render(vdo_raycast* h, const float T[16], float* dept
   float* o_depth = depth ? (out_is_device ? depth : h->d_stage) : nullptr;
   float* o_grad = grad ? (out_is_device ? grad : h->d_stage + np) : nullptr;
   int32_t* o_wgt = weight ? (out_is_device ? weight : (int32_t*)(h->d_stage + 4 * np)) : nullptr;
-  hipEventRecord(h->ev0, s);
+  const auto t0 = h->tm.begin(s);
   hipMemsetAsync(h->d_cnt, 0, kRcTotal * sizeof(unsigned long long), s);
   if (h->skip) {
     hipMemsetAsync(h->d_grid, 0, h->grid_bytes, s);
@@ -348,34 +342,27 @@ extern "C" int vdo_raycast_render(vdo_raycast* h, const float T[16], float* dept
   hipEventRecord(h->evg, s);
   const unsigned tiles = (unsigned)a.tiles_x * (unsigned)((a.H + 15) / 16);
   hipLaunchKernelGGL(k_rc_march, dim3(tiles), dim3(64, 4), 0, s, a, (const uint32_t*)h->map->d_vol, (const uint8_t*)(h->skip ? h->d_grid : nullptr), o_depth, o_grad, o_wgt, h->d_cnt);
-  hipEventRecord(h->ev1, s);
+  h->tm.mark_end(s);
   hipMemcpyAsync(h->h_cnt, h->d_cnt, kRcTotal * sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
   if (!out_is_device) {
     if (depth) hipMemcpyAsync(depth, o_depth, np * sizeof(float), hipMemcpyDeviceToHost, s);
     if (grad) hipMemcpyAsync(grad, o_grad, np * 3 * sizeof(float), hipMemcpyDeviceToHost, s);
     if (weight) hipMemcpyAsync(weight, o_wgt, np * sizeof(int32_t), hipMemcpyDeviceToHost, s);
   }
-  hipError_t e = hipStreamSynchronize(s);
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e != hipSuccess) return rc_check_hip(who, e);
+  rc = sync_check(who, s);
+  if (rc != VDO_OK) return rc;
   for (int k = 0; k < 3; ++k) {
     unsigned long long sum = 0;
     for (int slot = 0; slot < kRcSlots; ++slot) sum += h->h_cnt[slot * kRcCounters + k];
     out[k] = (int64_t)sum;
   }
-  float dev_ms = 0.f, grid_ms = 0.f;
-  hipEventElapsedTime(&dev_ms, h->ev0, h->ev1);
-  hipEventElapsedTime(&grid_ms, h->ev0, h->evg);
-  h->ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  h->ms[1] = dev_ms;
-  h->grid_ms = h->skip ? grid_ms : 0.0;
+  h->tm.finish(t0);
+  h->grid_ms = h->skip ? elapsed_ms(h->tm.ev0, h->evg) : 0.0;
   return VDO_OK;
 }
 
 extern "C" int vdo_raycast_last_timing(vdo_raycast* h, double ms[2]) {
-  if (!h || !ms) return set_error(VDO_ERR_INVALID, "vdo_raycast_last_timing: %s is null", !h ? "handle" : "ms");
-  ms[0] = h->ms[0]; ms[1] = h->ms[1];
-  return VDO_OK;
+  return last_timing("vdo_raycast_last_timing", h ? &h->tm : nullptr, ms);
 }
 
 extern "C" int vdo_raycast_grid_timing(vdo_raycast* h, double* ms) {

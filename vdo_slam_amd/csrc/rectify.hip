@@ -12,7 +12,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstdint>
 #include <cstring>
 #include <vector>
@@ -20,6 +19,7 @@
 #include "../../include/vdo_slam_hip.h"
 #include "ctx.hpp"
 #include "rectify_plan.hpp"
+#include "stage.hpp"
 
 namespace vdo {
 
@@ -51,8 +51,7 @@ struct vdo_rectify {
   std::vector<int32_t> map[vdo::kRectMaxCams];                      // host copies [H][W][2]
   std::vector<uint8_t> valid[vdo::kRectMaxCams];
   int32_t n_valid[vdo::kRectMaxCams] = {0, 0};
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  double ms[2] = {0, 0};
+  vdo::StageTimer tm;
 };
 
 namespace vdo {
@@ -118,17 +117,12 @@ __global__ __launch_bounds__(256) void k_rect_gate(const uint8_t* __restrict__ v
   if ((threadIdx.x & (warpSize - 1)) == 0 && b) atomicAdd(count, (int32_t)__popcll(b));
 }
 
-static int rect_check_hip(const char* who, hipError_t e) {
-  return e == hipSuccess ? VDO_OK : set_error(VDO_ERR_NO_DEVICE, "%s: %s", who, hipGetErrorString(e));
-}
-
 static void rect_free(vdo_rectify* h) {
   for (int c = 0; c < kRectMaxCams; ++c) { hipFree(h->d_map[c]); hipFree(h->d_valid[c]); }
   for (int k = 0; k < kRectMaxJobs; ++k) { hipFree(h->d_src[k]); hipFree(h->d_dst[k]); }
   hipFree(h->d_gate); hipFree(h->d_count);
   if (h->h_count) hipHostFree(h->h_count);
-  if (h->ev0) hipEventDestroy(h->ev0);
-  if (h->ev1) hipEventDestroy(h->ev1);
+  h->tm.destroy();
   delete h;
 }
 
@@ -155,7 +149,7 @@ static int rect_build(const char* who, vdo_ctx* ctx, vdo_rectify* h, vdo_rectify
     ok = hipMalloc((void**)&h->d_map[c], (size_t)H * Wp * 2 * sizeof(int32_t)) == hipSuccess && hipMalloc((void**)&h->d_valid[c], n) == hipSuccess;
   for (int k = 0; k < kRectMaxJobs && ok; ++k) ok = hipMalloc((void**)&h->d_src[k], h->stage_bytes) == hipSuccess && hipMalloc((void**)&h->d_dst[k], n) == hipSuccess;
   ok = ok && hipMalloc((void**)&h->d_gate, n * sizeof(float)) == hipSuccess && hipMalloc((void**)&h->d_count, sizeof(int32_t)) == hipSuccess &&
-       hipHostMalloc((void**)&h->h_count, sizeof(int32_t), hipHostMallocDefault) == hipSuccess && hipEventCreate(&h->ev0) == hipSuccess && hipEventCreate(&h->ev1) == hipSuccess;
+       hipHostMalloc((void**)&h->h_count, sizeof(int32_t), hipHostMallocDefault) == hipSuccess && h->tm.create();
   if (!ok) {
     (void)hipGetLastError();
     rect_free(h);
@@ -170,16 +164,9 @@ static int rect_build(const char* who, vdo_ctx* ctx, vdo_rectify* h, vdo_rectify
     if (e == hipSuccess) e = hipMemcpyAsync(h->d_valid[c], h->valid[c].data(), n, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);       // `padded` is reused by the next camera
   }
-  if (e != hipSuccess) { rect_free(h); return rect_check_hip(who, e); }
+  if (e != hipSuccess) { rect_free(h); return check_hip(who, e); }
   *out = h;
   return VDO_OK;
-}
-
-static void rect_finish_timing(vdo_rectify* h, std::chrono::steady_clock::time_point t0) {
-  float dev_ms = 0.f;
-  hipEventElapsedTime(&dev_ms, h->ev0, h->ev1);
-  h->ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  h->ms[1] = dev_ms;
 }
 
 }  // namespace vdo
@@ -274,10 +261,9 @@ extern "C" int vdo_rectify_compute(vdo_rectify* h, const vdo_rectify_job* jobs, 
   }
   int rc = ctx_bind(h->ctx);
   if (rc != VDO_OK) return rc;
-  const auto t0 = std::chrono::steady_clock::now();
   hipStream_t s = h->ctx->stream;
   const int W = h->W, H = h->H;
-  hipEventRecord(h->ev0, s);
+  const auto t0 = h->tm.begin(s);
   RectLaunch L{};
   for (int k = 0; k < n_jobs; ++k) {
     const vdo_rectify_job& j = jobs[k];
@@ -295,13 +281,12 @@ extern "C" int vdo_rectify_compute(vdo_rectify* h, const vdo_rectify_job* jobs, 
   }
   const dim3 grid(((W + 3) / 4 + kRectBX - 1) / kRectBX, (H + kRectBY - 1) / kRectBY, n_jobs);
   hipLaunchKernelGGL(k_rect_remap, grid, dim3(kRectBX, kRectBY), 0, s, L, W, H, h->Wp, border);
-  hipEventRecord(h->ev1, s);
+  h->tm.mark_end(s);
   if (!dst_is_device)
     for (int k = 0; k < n_jobs; ++k) hipMemcpy2DAsync(jobs[k].dst, (size_t)jobs[k].dst_stride, h->d_dst[k], W, W, H, hipMemcpyDeviceToHost, s);
-  hipError_t e = hipStreamSynchronize(s);
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e != hipSuccess) return rect_check_hip(who, e);
-  rect_finish_timing(h, t0);
+  rc = sync_check(who, s);
+  if (rc != VDO_OK) return rc;
+  h->tm.finish(t0);
   return VDO_OK;
 }
 
@@ -314,22 +299,20 @@ extern "C" int vdo_rectify_gate(vdo_rectify* h, int cam, float* image, int64_t s
   if (!n_cleared) return set_error(VDO_ERR_INVALID, "%s: n_cleared is null", who);
   int rc = ctx_bind(h->ctx);
   if (rc != VDO_OK) return rc;
-  const auto t0 = std::chrono::steady_clock::now();
   hipStream_t s = h->ctx->stream;
   const int W = h->W, H = h->H, n = W * H;
   const size_t rowb = (size_t)W * sizeof(float);
-  hipEventRecord(h->ev0, s);
+  const auto t0 = h->tm.begin(s);
   hipMemsetAsync(h->d_count, 0, sizeof(int32_t), s);
   float* d = image; int64_t stride = stride_floats;
   if (!is_device) { hipMemcpy2DAsync(h->d_gate, rowb, image, (size_t)stride_floats * sizeof(float), rowb, H, hipMemcpyHostToDevice, s); d = h->d_gate; stride = W; }
   hipLaunchKernelGGL(k_rect_gate, dim3((n + 255) / 256), dim3(256), 0, s, (const uint8_t*)h->d_valid[cam], W, H, d, stride, h->d_count);
-  hipEventRecord(h->ev1, s);
+  h->tm.mark_end(s);
   if (!is_device) hipMemcpy2DAsync(image, (size_t)stride_floats * sizeof(float), h->d_gate, rowb, rowb, H, hipMemcpyDeviceToHost, s);
   hipMemcpyAsync(h->h_count, h->d_count, sizeof(int32_t), hipMemcpyDeviceToHost, s);
-  hipError_t e = hipStreamSynchronize(s);
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e != hipSuccess) return rect_check_hip(who, e);
-  rect_finish_timing(h, t0);
+  rc = sync_check(who, s);
+  if (rc != VDO_OK) return rc;
+  h->tm.finish(t0);
   *n_cleared = *h->h_count;
   return VDO_OK;
 }
@@ -353,9 +336,7 @@ extern "C" int vdo_rectify_get_valid(vdo_rectify* h, int cam, uint8_t* valid, in
 }
 
 extern "C" int vdo_rectify_last_timing(vdo_rectify* h, double ms[2]) {
-  if (!h || !ms) return set_error(VDO_ERR_INVALID, "vdo_rectify_last_timing: %s is null", !h ? "handle" : "ms");
-  ms[0] = h->ms[0]; ms[1] = h->ms[1];
-  return VDO_OK;
+  return last_timing("vdo_rectify_last_timing", h ? &h->tm : nullptr, ms);
 }
 
 extern "C" int vdo_rectify_device_images(vdo_rectify* h, int k, uint8_t** src, uint8_t** dst) {
@@ -374,5 +355,5 @@ extern "C" int vdo_rectify_download_image(vdo_rectify* h, const uint8_t* image_d
   const int rc = ctx_bind(h->ctx);
   if (rc != VDO_OK) return rc;
   hipMemcpy2DAsync(out, h->W, image_dev, (size_t)stride, h->W, h->H, hipMemcpyDeviceToHost, h->ctx->stream);
-  return rect_check_hip(who, hipStreamSynchronize(h->ctx->stream));
+  return check_hip(who, hipStreamSynchronize(h->ctx->stream));
 }

@@ -17,7 +17,6 @@
 //                       of valid pixels (wave ballot, one integer atomic per wave).
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <climits>
 #include <cstdint>
 #include <type_traits>
@@ -25,6 +24,7 @@
 #include "../../include/vdo_slam_hip.h"
 #include "census.hpp"
 #include "ctx.hpp"
+#include "stage.hpp"
 
 struct vdo_stereo {
   vdo_ctx* ctx = nullptr;
@@ -39,8 +39,7 @@ struct vdo_stereo {
   int* d_count = nullptr;
   int* h_count = nullptr;                               // pinned
   float* d_flow = nullptr; int32_t* d_mask = nullptr;   // vdo_stereo_stage_frame, made on first use
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  double ms[2] = {0, 0};
+  vdo::StageTimer tm;
   bool computed = false;
 };
 
@@ -207,16 +206,11 @@ __global__ __launch_bounds__(256) void k_stereo_select(const uint16_t* __restric
   if ((threadIdx.x & 63) == 0 && m) atomicAdd(n_valid, (int)__popcll(m));
 }
 
-static int stereo_check_hip(const char* who, hipError_t e) {
-  return e == hipSuccess ? VDO_OK : set_error(VDO_ERR_NO_DEVICE, "%s: %s", who, hipGetErrorString(e));
-}
-
 static void stereo_free(vdo_stereo* h) {
   hipFree(h->d_left); hipFree(h->d_right); hipFree(h->d_census); hipFree(h->d_cost); hipFree(h->d_sum); hipFree(h->d_disp); hipFree(h->d_count);
   hipFree(h->d_flow); hipFree(h->d_mask);
   if (h->h_count) hipHostFree(h->h_count);
-  if (h->ev0) hipEventDestroy(h->ev0);
-  if (h->ev1) hipEventDestroy(h->ev1);
+  h->tm.destroy();
   delete h;
 }
 
@@ -249,7 +243,7 @@ extern "C" int vdo_stereo_create(vdo_ctx* ctx, int width, int height, const vdo_
                   hipMalloc((void**)&h->d_census, 2 * n * sizeof(uint64_t)) == hipSuccess && hipMalloc((void**)&h->d_cost, vol) == hipSuccess &&
                   hipMalloc((void**)&h->d_sum, vol * sizeof(uint16_t)) == hipSuccess && hipMalloc((void**)&h->d_disp, n * sizeof(float)) == hipSuccess &&
                   hipMalloc((void**)&h->d_count, sizeof(int)) == hipSuccess && hipHostMalloc((void**)&h->h_count, sizeof(int), hipHostMallocDefault) == hipSuccess &&
-                  hipEventCreate(&h->ev0) == hipSuccess && hipEventCreate(&h->ev1) == hipSuccess;
+                  h->tm.create();
   if (!ok) {
     (void)hipGetLastError();
     stereo_free(h);
@@ -286,15 +280,14 @@ extern "C" int vdo_stereo_compute(vdo_stereo* h, const uint8_t* left, int64_t le
   if (!n_valid) return set_error(VDO_ERR_INVALID, "%s: n_valid is null", who);
   int rc = ctx_bind(h->ctx);
   if (rc != VDO_OK) return rc;
-  const auto t0 = std::chrono::steady_clock::now();
   hipStream_t s = h->ctx->stream;
   const int W = h->W, H = h->H, D = h->p.max_disparity;
   const int64_t n_pix = (int64_t)W * H;
-  hipEventRecord(h->ev0, s);
+  const auto t0 = h->tm.begin(s);
   if (!src_is_device) {                                            // staged packed; a device pair is read where it is, with its strides
-    hipMemcpy2DAsync(h->d_left, W, left, (size_t)left_stride, W, H, hipMemcpyHostToDevice, s);
-    hipMemcpy2DAsync(h->d_right, W, right, (size_t)right_stride, W, H, hipMemcpyHostToDevice, s);
-    left = h->d_left; right = h->d_right; left_stride = right_stride = W;
+    left = stage_rows(s, h->d_left, left, left_stride, W, H, 0);
+    right = stage_rows(s, h->d_right, right, right_stride, W, H, 0);
+    left_stride = right_stride = W;
   }
   const int tiles_x = (W + kCensusTX - 1) / kCensusTX, tiles = tiles_x * ((H + kCensusTY - 1) / kCensusTY);
   hipLaunchKernelGGL(k_stereo_census, dim3(2 * tiles), dim3(256), 0, s, left, left_stride, right, right_stride, W, H, tiles_x, tiles, h->d_census);
@@ -309,17 +302,13 @@ extern "C" int vdo_stereo_compute(vdo_stereo* h, const uint8_t* left, int64_t le
   float* d_out = out_is_device ? disparity256 : h->d_disp;
   hipLaunchKernelGGL(k_stereo_select, dim3((unsigned)((n_pix + 255) / 256)), dim3(256), 0, s, (const uint16_t*)h->d_sum, W, n_pix, D, h->p.uniqueness, h->p.lr_max_diff,
                      h->p.subpixel, h->scale, d_out, h->d_count);
-  hipEventRecord(h->ev1, s);
+  h->tm.mark_end(s);
   hipMemcpyAsync(h->h_count, h->d_count, sizeof(int), hipMemcpyDeviceToHost, s);
   if (!out_is_device) hipMemcpyAsync(disparity256, h->d_disp, (size_t)n_pix * sizeof(float), hipMemcpyDeviceToHost, s);
-  hipError_t e = hipStreamSynchronize(s);
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e != hipSuccess) return stereo_check_hip(who, e);
+  rc = sync_check(who, s);
+  if (rc != VDO_OK) return rc;
   *n_valid = *h->h_count;
-  float dev_ms = 0.f;
-  hipEventElapsedTime(&dev_ms, h->ev0, h->ev1);
-  h->ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  h->ms[1] = dev_ms;
+  h->tm.finish(t0);
   h->computed = true;
   return VDO_OK;
 }
@@ -331,7 +320,7 @@ static int stereo_fetch(const char* who, vdo_stereo* h, const void* dev, void* o
   const int rc = ctx_bind(h->ctx);
   if (rc != VDO_OK) return rc;
   hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, h->ctx->stream);
-  return stereo_check_hip(who, hipStreamSynchronize(h->ctx->stream));
+  return check_hip(who, hipStreamSynchronize(h->ctx->stream));
 }
 
 extern "C" int vdo_stereo_get_census(vdo_stereo* h, int which, uint64_t* out) {
@@ -349,9 +338,7 @@ extern "C" int vdo_stereo_get_aggregated(vdo_stereo* h, uint16_t* out) {
 }
 
 extern "C" int vdo_stereo_last_timing(vdo_stereo* h, double ms[2]) {
-  if (!h || !ms) return set_error(VDO_ERR_INVALID, "vdo_stereo_last_timing: %s is null", !h ? "handle" : "ms");
-  ms[0] = h->ms[0]; ms[1] = h->ms[1];
-  return VDO_OK;
+  return last_timing("vdo_stereo_last_timing", h ? &h->tm : nullptr, ms);
 }
 
 extern "C" int vdo_stereo_device_images(vdo_stereo* h, uint8_t** left, uint8_t** right, float** disparity256) {
@@ -375,7 +362,7 @@ extern "C" int vdo_stereo_stage_frame(vdo_stereo* h, const float* flow, const in
   hipStream_t s = h->ctx->stream;
   hipMemcpyAsync(h->d_flow, flow, 2 * n * sizeof(float), hipMemcpyHostToDevice, s);
   hipMemcpyAsync(h->d_mask, mask, n * sizeof(int32_t), hipMemcpyHostToDevice, s);
-  const int rs = stereo_check_hip(who, hipStreamSynchronize(s));
+  const int rs = check_hip(who, hipStreamSynchronize(s));
   if (rs != VDO_OK) return rs;
   *flow_dev = h->d_flow; *mask_dev = h->d_mask;
   return VDO_OK;

@@ -16,30 +16,22 @@ class DenseParamsC(C.Structure):
                 ("max_depth", C.c_float), ("max_weight", C.c_int32), ("stage_points", C.c_int32)]
 
 
-_declared = False
-
-
 def _lib():
-    global _declared
-    L = K.lib()
-    if not _declared:
-        vp = C.c_void_p
-        L.vdo_dense_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(DenseParamsC), C.POINTER(vp)]
-        L.vdo_dense_destroy.argtypes = [vp]
-        L.vdo_dense_integrate.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.c_int, vp, vp]
-        L.vdo_dense_integrate_frame.argtypes = [vp, vp, vp, vp]
-        L.vdo_dense_recenter.argtypes = [vp, vp]
-        L.vdo_dense_extract.argtypes = [vp, vp, vp, C.c_int, C.c_int64, vp, vp, vp, C.c_int, vp]
-        L.vdo_dense_get_volume.argtypes = [vp, vp, vp]
-        L.vdo_dense_set_volume.argtypes = [vp, vp]
-        L.vdo_dense_last_timing.argtypes = [vp, K.c_double_p]
-        L.vdo_dense_device_volume.argtypes = [vp, C.POINTER(vp)]
-        L.vdo_dense_set_voxels_per_thread.argtypes = [vp, C.c_int]
-        L.vdo_dense_clear.argtypes = [vp]
-        for f in ("create", "destroy", "integrate", "integrate_frame", "recenter", "extract", "get_volume", "set_volume", "last_timing", "device_volume", "set_voxels_per_thread", "clear"):
-            getattr(L, "vdo_dense_" + f).restype = C.c_int
-        _declared = True
-    return L
+    vp = C.c_void_p
+    return K.declare(K.lib(), "vdo_dense_", {
+        "create": [vp, C.c_int, C.c_int, C.POINTER(DenseParamsC), C.POINTER(vp)],
+        "destroy": [vp],
+        "integrate": [vp, vp, C.c_int64, vp, C.c_int64, C.c_int, vp, vp],
+        "integrate_frame": [vp, vp, vp, vp],
+        "recenter": [vp, vp],
+        "extract": [vp, vp, vp, C.c_int, C.c_int64, vp, vp, vp, C.c_int, vp],
+        "get_volume": [vp, vp, vp],
+        "set_volume": [vp, vp],
+        "last_timing": [vp, K.c_double_p],
+        "device_volume": [vp, C.POINTER(vp)],
+        "set_voxels_per_thread": [vp, C.c_int],
+        "clear": [vp],
+    })
 
 
 def params(n, voxel, K4, origin=(0, 0, 0), trunc=None, min_depth=0.0, max_depth=40.0, max_weight=64, stage_points=1 << 20) -> DenseParamsC:
@@ -49,22 +41,12 @@ def params(n, voxel, K4, origin=(0, 0, 0), trunc=None, min_depth=0.0, max_depth=
                         float(min_depth), float(max_depth), int(max_weight), int(stage_points))
 
 
-def _rows(a, name, dtype, shape):
-    """A host image whose rows the C entry can read at their own stride: (array kept alive, address, stride in elements)"""
-    a = np.asarray(a)
-    if a.dtype != dtype or a.shape != shape:
-        raise ValueError(f"{name}: {a.dtype} {a.shape}, expected {np.dtype(dtype).name} {shape}")
-    if a.strides[1] != 4 or a.strides[0] < a.shape[1] * 4 or a.strides[0] % 4:
-        a = np.ascontiguousarray(a)
-    return a, a.ctypes.data, a.strides[0] // 4
-
-
-class DenseMapper:
+class DenseMapper(K.StageHandle):
     """``vdo_dense`` handle for an nx x ny x nz volume and width x height images; every device buffer is allocated here."""
+    _prefix = "vdo_dense_"
 
     def __init__(self, ctx, width, height, n, voxel, K4, **prm):
-        self._L = _lib()
-        self._h = C.c_void_p()
+        super().__init__(_lib())
         self.width, self.height = int(width), int(height)
         self.params = params(n, voxel, K4, **prm)
         self.n = tuple(self.params.n)
@@ -81,8 +63,8 @@ class DenseMapper:
 
     def integrate(self, depth, mask, T):
         """Host images (depth float32 [height, width] in metres, mask int32 [height, width] or None; row strides are honoured), T world -> camera."""
-        d, pd, sd = _rows(depth, "depth", np.float32, (self.height, self.width))
-        m, pm, sm = _rows(mask, "mask", np.int32, (self.height, self.width)) if mask is not None else (None, None, 0)
+        d, pd, sd = K.rows(depth, "depth", np.float32, (self.height, self.width))
+        m, pm, sm = K.rows(mask, "mask", np.int32, (self.height, self.width)) if mask is not None else (None, None, 0)
         return self.integrate_raw(pd, sd, pm, sm, False, T)
 
     def integrate_frame(self, frame_handle, T):
@@ -147,20 +129,6 @@ class DenseMapper:
 
     def set_voxels_per_thread(self, v):
         K.check(self._L.vdo_dense_set_voxels_per_thread(self._h, int(v)))
-
-    def timing(self):
-        """(wall ms of the call, device ms by events) of the last integrate, recenter or extract"""
-        ms = (C.c_double * 2)()
-        K.check(self._L.vdo_dense_last_timing(self._h, ms))
-        return ms[0], ms[1]
-
-    def close(self):
-        if self._h:
-            self._L.vdo_dense_destroy(self._h); self._h = C.c_void_p()
-
-    def __del__(self):
-        try: self.close()
-        except Exception: pass
 
 
 def camera_voxel(Tcw, voxel):

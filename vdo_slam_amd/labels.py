@@ -13,27 +13,19 @@ class LabelParamsC(C.Structure):
     _fields_ = [("connectivity", C.c_int32), ("max_disp_diff", C.c_int32), ("min_area", C.c_int32), ("max_labels", C.c_int32)]
 
 
-_declared = False
-
-
 def _lib():
-    global _declared
-    L = K.lib()
-    if not _declared:
-        vp = C.c_void_p
-        L.vdo_labels_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(LabelParamsC), C.POINTER(vp)]
-        L.vdo_labels_destroy.argtypes = [vp]
-        L.vdo_labels_compute.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.c_int, vp, C.c_int, K.c_int32_p]
-        L.vdo_labels_filter_speckles.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, K.c_int32_p]
-        L.vdo_labels_get_roots.argtypes = [vp, vp]
-        L.vdo_labels_get_areas.argtypes = [vp, vp]
-        L.vdo_labels_last_timing.argtypes = [vp, K.c_double_p]
-        L.vdo_labels_device_images.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
-        L.vdo_labels_stage_classes.argtypes = [vp, vp, C.c_int64, C.POINTER(vp)]
-        for f in ("create", "destroy", "compute", "filter_speckles", "get_roots", "get_areas", "last_timing", "device_images", "stage_classes"):
-            getattr(L, "vdo_labels_" + f).restype = C.c_int
-        _declared = True
-    return L
+    vp = C.c_void_p
+    return K.declare(K.lib(), "vdo_labels_", {
+        "create": [vp, C.c_int, C.c_int, C.POINTER(LabelParamsC), C.POINTER(vp)],
+        "destroy": [vp],
+        "compute": [vp, vp, C.c_int64, vp, C.c_int64, C.c_int, vp, C.c_int, K.c_int32_p],
+        "filter_speckles": [vp, vp, C.c_int, C.c_int, C.c_int, K.c_int32_p],
+        "get_roots": [vp, vp],
+        "get_areas": [vp, vp],
+        "last_timing": [vp, K.c_double_p],
+        "device_images": [vp, C.POINTER(vp), C.POINTER(vp)],
+        "stage_classes": [vp, vp, C.c_int64, C.POINTER(vp)],
+    })
 
 
 def params(connectivity=8, max_disp_diff=512, min_area=200, max_labels=1023) -> LabelParamsC:
@@ -41,12 +33,12 @@ def params(connectivity=8, max_disp_diff=512, min_area=200, max_labels=1023) -> 
     return LabelParamsC(int(connectivity), int(max_disp_diff), int(min_area), int(max_labels))
 
 
-class InstanceLabeler:
+class InstanceLabeler(K.StageHandle):
     """``vdo_labels`` handle for width x height images; every device buffer is allocated here."""
+    _prefix = "vdo_labels_"
 
     def __init__(self, ctx, width, height, **prm):
-        self._L = _lib()
-        self._h = C.c_void_p()
+        super().__init__(_lib())
         self.width, self.height = int(width), int(height)
         self.params = params(**prm)
         self._ctx = ctx
@@ -119,20 +111,6 @@ class InstanceLabeler:
         p = C.c_void_p()
         K.check(self._L.vdo_labels_stage_classes(self._h, cls.ctypes.data, self.width, C.byref(p)))
         return p.value
-
-    def timing(self):
-        """(wall ms of the call, device ms by events) of the last compute or filter"""
-        ms = (C.c_double * 2)()
-        K.check(self._L.vdo_labels_last_timing(self._h, ms))
-        return ms[0], ms[1]
-
-    def close(self):
-        if self._h:
-            self._L.vdo_labels_destroy(self._h); self._h = C.c_void_p()
-
-    def __del__(self):
-        try: self.close()
-        except Exception: pass
 
 
 def compute(ctx, cls, disp=None, **prm):

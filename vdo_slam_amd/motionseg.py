@@ -15,28 +15,19 @@ class MotionSegParamsC(C.Structure):
                 ("class_value", C.c_int32)]
 
 
-_declared = False
-c_float_p = C.POINTER(C.c_float)
-
-
 def _lib():
-    global _declared
-    L = K.lib()
-    if not _declared:
-        vp = C.c_void_p
-        L.vdo_motionseg_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(MotionSegParamsC), C.POINTER(vp)]
-        L.vdo_motionseg_destroy.argtypes = [vp]
-        L.vdo_motionseg_egomotion.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, vp, vp]
-        L.vdo_motionseg_compute.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, C.c_int, vp, vp, C.c_int, vp]
-        L.vdo_motionseg_get_state.argtypes = [vp, vp]
-        L.vdo_motionseg_get_residual.argtypes = [vp, vp]
-        L.vdo_motionseg_get_samples.argtypes = [vp, vp, vp, K.c_int32_p]
-        L.vdo_motionseg_last_timing.argtypes = [vp, K.c_double_p]
-        L.vdo_motionseg_device_images.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
-        for f in ("create", "destroy", "egomotion", "compute", "get_state", "get_residual", "get_samples", "last_timing", "device_images"):
-            getattr(L, "vdo_motionseg_" + f).restype = C.c_int
-        _declared = True
-    return L
+    vp = C.c_void_p
+    return K.declare(K.lib(), "vdo_motionseg_", {
+        "create": [vp, C.c_int, C.c_int, C.POINTER(MotionSegParamsC), C.POINTER(vp)],
+        "destroy": [vp],
+        "egomotion": [vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, vp, vp],
+        "compute": [vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, C.c_int, vp, vp, C.c_int, vp],
+        "get_state": [vp, vp],
+        "get_residual": [vp, vp],
+        "get_samples": [vp, vp, vp, K.c_int32_p],
+        "last_timing": [vp, K.c_double_p],
+        "device_images": [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)],
+    })
 
 
 def params(K4, bf, disp_unit, sigma_flow=0.5, sigma_disp=0.5, chi2=9.0, min_disparity=0.0, vote_radius=2, vote_num=1, vote_den=2, min_known=6,
@@ -46,23 +37,12 @@ def params(K4, bf, disp_unit, sigma_flow=0.5, sigma_disp=0.5, chi2=9.0, min_disp
                             int(vote_radius), int(vote_num), int(vote_den), int(min_known), int(class_value))
 
 
-def _rows(a, name, dtype, shape, unit):
-    """A host image whose rows the C entry can read at their own stride: (array kept alive, address, stride in elements)"""
-    a = np.asarray(a)
-    if a.dtype != dtype or a.shape != shape:
-        raise ValueError(f"{name}: {a.dtype} {a.shape}, expected {np.dtype(dtype).name} {shape}")
-    packed = a.strides[1:] == np.empty(shape, dtype).strides[1:]
-    if not packed or a.strides[0] < a.shape[1] * a.strides[1] or a.strides[0] % unit:
-        a = np.ascontiguousarray(a)
-    return a, a.ctypes.data, a.strides[0] // unit
-
-
-class MotionSegmenter:
+class MotionSegmenter(K.StageHandle):
     """``vdo_motionseg`` handle for width x height images; every device buffer is allocated here."""
+    _prefix = "vdo_motionseg_"
 
     def __init__(self, ctx, width, height, K4, bf, disp_unit, **prm):
-        self._L = _lib()
-        self._h = C.c_void_p()
+        super().__init__(_lib())
         self.width, self.height = int(width), int(height)
         self.params = params(K4, bf, disp_unit, **prm)
         self._ctx = ctx
@@ -80,8 +60,8 @@ class MotionSegmenter:
 
     def _sources(self, disp0, flow, flow_valid):
         H, W = self.height, self.width
-        keep = [_rows(disp0, "disp0", np.float32, (H, W), 4), _rows(flow, "flow", np.float32, (H, W, 2), 4)]
-        keep.append(_rows(flow_valid, "flow_valid", np.uint8, (H, W), 1) if flow_valid is not None else (None, None, 0))
+        keep = [K.rows(disp0, "disp0", np.float32, (H, W), 4), K.rows(flow, "flow", np.float32, (H, W, 2), 4)]
+        keep.append(K.rows(flow_valid, "flow_valid", np.uint8, (H, W), 1) if flow_valid is not None else (None, None, 0))
         return keep
 
     def egomotion(self, disp0, flow, flow_valid=None, **kw):
@@ -102,7 +82,7 @@ class MotionSegmenter:
     def compute(self, disp0, disp1, flow, flow_valid, T):
         """Host images -> (cls uint8 [height, width], (n_moving, n_static, n_unknown))."""
         (d0, p0, s0), (fl, pf, sf), (fv, pv, sv) = self._sources(disp0, flow, flow_valid)
-        d1, p1, s1 = _rows(disp1, "disp1", np.float32, (self.height, self.width), 4)
+        d1, p1, s1 = K.rows(disp1, "disp1", np.float32, (self.height, self.width), 4)
         cls = np.zeros((self.height, self.width), np.uint8)
         return cls, self.compute_raw(p0, s0, p1, s1, pf, sf, pv, sv, False, T, cls.ctypes.data, False)
 
@@ -131,20 +111,6 @@ class MotionSegmenter:
         p = [C.c_void_p() for _ in range(3)]
         K.check(self._L.vdo_motionseg_device_images(self._h, *[C.byref(x) for x in p]))
         return tuple(x.value for x in p)
-
-    def timing(self):
-        """(wall ms of the call, device ms by events) of the last compute or ego-motion"""
-        ms = (C.c_double * 2)()
-        K.check(self._L.vdo_motionseg_last_timing(self._h, ms))
-        return ms[0], ms[1]
-
-    def close(self):
-        if self._h:
-            self._L.vdo_motionseg_destroy(self._h); self._h = C.c_void_p()
-
-    def __del__(self):
-        try: self.close()
-        except Exception: pass
 
 
 def compute(ctx, disp0, disp1, flow, flow_valid, T, K4, bf, disp_unit, **prm):

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi as K
-from .dense import PLY_DTYPE, DenseMapper, _rows
+from .dense import PLY_DTYPE, DenseMapper
 
 STAT_COLS = 8            # count, x0, y0, x1, y1, sum qx, sum qy, sum qz (2^-10 m)
 
@@ -18,27 +18,19 @@ class ObjectsParamsC(C.Structure):
     _fields_ = [("K", C.c_float * 4), ("min_depth", C.c_float), ("max_depth", C.c_float), ("max_labels", C.c_int32), ("max_batch", C.c_int32)]
 
 
-_declared = False
-
-
 def _lib():
-    global _declared
-    L = K.lib()
-    if not _declared:
-        vp = C.c_void_p
-        L.vdo_objects_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(ObjectsParamsC), C.POINTER(vp)]
-        L.vdo_objects_destroy.argtypes = [vp]
-        L.vdo_objects_stats.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.c_int, vp]
-        L.vdo_objects_stats_frame.argtypes = [vp, vp, vp]
-        L.vdo_objects_integrate.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, vp, vp, vp, vp]
-        L.vdo_objects_integrate_frame.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
-        L.vdo_objects_set_cull.argtypes = [vp, C.c_int]
-        L.vdo_objects_last_stats.argtypes = [vp, vp]
-        L.vdo_objects_last_timing.argtypes = [vp, K.c_double_p]
-        for f in ("create", "destroy", "stats", "stats_frame", "integrate", "integrate_frame", "set_cull", "last_stats", "last_timing"):
-            getattr(L, "vdo_objects_" + f).restype = C.c_int
-        _declared = True
-    return L
+    vp = C.c_void_p
+    return K.declare(K.lib(), "vdo_objects_", {
+        "create": [vp, C.c_int, C.c_int, C.POINTER(ObjectsParamsC), C.POINTER(vp)],
+        "destroy": [vp],
+        "stats": [vp, vp, C.c_int64, vp, C.c_int64, C.c_int, vp],
+        "stats_frame": [vp, vp, vp],
+        "integrate": [vp, vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, vp, vp, vp, vp],
+        "integrate_frame": [vp, vp, C.c_int, vp, vp, vp, vp],
+        "set_cull": [vp, C.c_int],
+        "last_stats": [vp, vp],
+        "last_timing": [vp, K.c_double_p],
+    })
 
 
 def clear(mapper: DenseMapper):
@@ -46,12 +38,12 @@ def clear(mapper: DenseMapper):
     mapper.clear()
 
 
-class ObjectStage:
+class ObjectStage(K.StageHandle):
     """``vdo_objects`` handle for width x height images; it owns the tables, the counters and the image staging, and no volume."""
+    _prefix = "vdo_objects_"
 
     def __init__(self, ctx, width, height, K4, min_depth=0.0, max_depth=25.0, max_labels=1023, max_batch=16):
-        self._L = _lib()
-        self._h = C.c_void_p()
+        super().__init__(_lib())
         self.width, self.height, self.max_labels, self.max_batch = int(width), int(height), int(max_labels), int(max_batch)
         self.params = ObjectsParamsC((C.c_float * 4)(*[float(v) for v in K4]), float(min_depth), float(max_depth), int(max_labels), int(max_batch))
         self._ctx = ctx
@@ -67,8 +59,8 @@ class ObjectStage:
 
     def stats(self, depth, mask):
         """Host images (row strides are honoured) -> int64 [max_labels + 1, 8]"""
-        d, pd, sd = _rows(depth, "depth", np.float32, (self.height, self.width))
-        m, pm, sm = _rows(mask, "mask", np.int32, (self.height, self.width))
+        d, pd, sd = K.rows(depth, "depth", np.float32, (self.height, self.width))
+        m, pm, sm = K.rows(mask, "mask", np.int32, (self.height, self.width))
         return self.stats_raw(pd, sd, pm, sm, False)
 
     def stats_frame(self, frame_handle):
@@ -95,8 +87,8 @@ class ObjectStage:
 
     def integrate(self, depth, mask, maps, labels, T):
         """Host images; maps: DenseMapper objects, labels: their mask labels, T: [n, 4, 4] object frame -> camera"""
-        d, pd, sd = _rows(depth, "depth", np.float32, (self.height, self.width))
-        m, pm, sm = _rows(mask, "mask", np.int32, (self.height, self.width))
+        d, pd, sd = K.rows(depth, "depth", np.float32, (self.height, self.width))
+        m, pm, sm = K.rows(mask, "mask", np.int32, (self.height, self.width))
         return self.integrate_raw(pd, sd, pm, sm, False, maps, labels, T)
 
     def integrate_frame(self, frame_handle, maps, labels, T):
@@ -112,20 +104,6 @@ class ObjectStage:
         t = self._table()
         K.check(self._L.vdo_objects_last_stats(self._h, t.ctypes.data))
         return t
-
-    def timing(self):
-        """(wall ms of the call, device ms by events) of the last stats or integrate"""
-        ms = (C.c_double * 2)()
-        K.check(self._L.vdo_objects_last_timing(self._h, ms))
-        return ms[0], ms[1]
-
-    def close(self):
-        if self._h:
-            self._L.vdo_objects_destroy(self._h); self._h = C.c_void_p()
-
-    def __del__(self):
-        try: self.close()
-        except Exception: pass
 
 
 def mul44(A, B):

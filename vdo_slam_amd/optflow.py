@@ -14,27 +14,19 @@ class FlowParamsC(C.Structure):
                 ("fb_max_diff", C.c_int32), ("subpixel", C.c_int32)]
 
 
-_declared = False
-
-
 def _lib():
-    global _declared
-    L = K.lib()
-    if not _declared:
-        vp, ip = C.c_void_p, C.POINTER(C.c_int)
-        L.vdo_optflow_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(FlowParamsC), C.POINTER(vp)]
-        L.vdo_optflow_destroy.argtypes = [vp]
-        L.vdo_optflow_compute.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.c_int, vp, vp, C.c_int, K.c_int32_p]
-        L.vdo_optflow_level_size.argtypes = [vp, C.c_int, ip, ip]
-        L.vdo_optflow_get_pyramid.argtypes = [vp, C.c_int, C.c_int, vp]
-        L.vdo_optflow_get_census.argtypes = [vp, C.c_int, C.c_int, vp]
-        L.vdo_optflow_get_level_flow.argtypes = [vp, C.c_int, C.c_int, vp]
-        L.vdo_optflow_last_timing.argtypes = [vp, K.c_double_p]
-        L.vdo_optflow_device_images.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
-        for f in ("create", "destroy", "compute", "level_size", "get_pyramid", "get_census", "get_level_flow", "last_timing", "device_images"):
-            getattr(L, "vdo_optflow_" + f).restype = C.c_int
-        _declared = True
-    return L
+    vp, ip = C.c_void_p, C.POINTER(C.c_int)
+    return K.declare(K.lib(), "vdo_optflow_", {
+        "create": [vp, C.c_int, C.c_int, C.POINTER(FlowParamsC), C.POINTER(vp)],
+        "destroy": [vp],
+        "compute": [vp, vp, C.c_int64, vp, C.c_int64, C.c_int, vp, vp, C.c_int, K.c_int32_p],
+        "level_size": [vp, C.c_int, ip, ip],
+        "get_pyramid": [vp, C.c_int, C.c_int, vp],
+        "get_census": [vp, C.c_int, C.c_int, vp],
+        "get_level_flow": [vp, C.c_int, C.c_int, vp],
+        "last_timing": [vp, K.c_double_p],
+        "device_images": [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)],
+    })
 
 
 def params(levels=6, radius=2, window=2, median=True, fb_max_diff=1, subpixel=True) -> FlowParamsC:
@@ -42,12 +34,12 @@ def params(levels=6, radius=2, window=2, median=True, fb_max_diff=1, subpixel=Tr
     return FlowParamsC(int(levels), int(radius), int(window), int(median), int(fb_max_diff), int(subpixel))
 
 
-class FlowMatcher:
+class FlowMatcher(K.StageHandle):
     """``vdo_optflow`` handle for width x height images; every device buffer is allocated here."""
+    _prefix = "vdo_optflow_"
 
     def __init__(self, ctx, width, height, **prm):
-        self._L = _lib()
-        self._h = C.c_void_p()
+        super().__init__(_lib())
         self.width, self.height = int(width), int(height)
         self.params = params(**prm)
         self._ctx = ctx
@@ -102,20 +94,6 @@ class FlowMatcher:
         p = [C.c_void_p() for _ in range(4)]
         K.check(self._L.vdo_optflow_device_images(self._h, *[C.byref(x) for x in p]))
         return tuple(x.value for x in p)
-
-    def timing(self):
-        """(wall ms of the call, device ms by events) of the last compute"""
-        ms = (C.c_double * 2)()
-        K.check(self._L.vdo_optflow_last_timing(self._h, ms))
-        return ms[0], ms[1]
-
-    def close(self):
-        if self._h:
-            self._L.vdo_optflow_destroy(self._h); self._h = C.c_void_p()
-
-    def __del__(self):
-        try: self.close()
-        except Exception: pass
 
 
 def compute(ctx, im0, im1, **prm):

@@ -14,37 +14,29 @@ class RaycastParamsC(C.Structure):
     _fields_ = [("K", C.c_float * 4), ("near", C.c_float), ("step", C.c_float), ("n_steps", C.c_int32), ("min_weight", C.c_int32)]
 
 
-_declared = False
-
-
 def _lib():
-    global _declared
-    L = _dense._lib()
-    if not _declared:
-        vp = C.c_void_p
-        L.vdo_raycast_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(RaycastParamsC), C.POINTER(vp)]
-        L.vdo_raycast_destroy.argtypes = [vp]
-        L.vdo_raycast_render.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp]
-        L.vdo_raycast_set_skip.argtypes = [vp, C.c_int]
-        L.vdo_raycast_last_timing.argtypes = [vp, K.c_double_p]
-        L.vdo_raycast_grid_timing.argtypes = [vp, K.c_double_p]
-        for f in ("create", "destroy", "render", "set_skip", "last_timing", "grid_timing"):
-            getattr(L, "vdo_raycast_" + f).restype = C.c_int
-        _declared = True
-    return L
+    vp = C.c_void_p
+    return K.declare(_dense._lib(), "vdo_raycast_", {
+        "create": [vp, C.c_int, C.c_int, C.POINTER(RaycastParamsC), C.POINTER(vp)],
+        "destroy": [vp],
+        "render": [vp, vp, vp, vp, vp, C.c_int, vp],
+        "set_skip": [vp, C.c_int],
+        "last_timing": [vp, K.c_double_p],
+        "grid_timing": [vp, K.c_double_p],
+    })
 
 
 def params(K4, near, step, n_steps, min_weight=2) -> RaycastParamsC:
     return RaycastParamsC((C.c_float * 4)(*[float(v) for v in K4]), float(near), float(step), int(n_steps), int(min_weight))
 
 
-class Raycaster:
+class Raycaster(K.StageHandle):
     """``vdo_raycast`` handle: a width x height view of ``mapper`` (a ``dense.DenseMapper``) with intrinsics K4 = (fx, fy, cx, cy); sample k of a ray
     lies at z-depth ``near + k * step``, k < n_steps.  Every device buffer of the view is allocated here."""
+    _prefix = "vdo_raycast_"
 
     def __init__(self, mapper, width, height, K4, near, step, n_steps, min_weight=2):
-        self._L = _lib()
-        self._h = C.c_void_p()
+        super().__init__(_lib())
         self._mapper = mapper                                   # the view borrows the map: keep it alive
         self.width, self.height = int(width), int(height)
         self.params = params(K4, near, step, n_steps, min_weight)
@@ -74,19 +66,14 @@ class Raycaster:
 
     def timing(self):
         """(wall ms of the call, device ms by events, device ms of the occupancy-grid build) of the last render"""
-        ms = (C.c_double * 2)(); g = C.c_double()
-        K.check(self._L.vdo_raycast_last_timing(self._h, ms))
+        ms = super().timing()
+        g = C.c_double()
         K.check(self._L.vdo_raycast_grid_timing(self._h, C.byref(g)))
         return ms[0], ms[1], g.value
 
     def close(self):
-        if self._h:
-            self._L.vdo_raycast_destroy(self._h); self._h = C.c_void_p()
+        super().close()
         self._mapper = None
-
-    def __del__(self):
-        try: self.close()
-        except Exception: pass
 
 
 def normals(grad):

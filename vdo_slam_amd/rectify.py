@@ -22,29 +22,21 @@ class RectifyJobC(C.Structure):
                 ("nearest", C.c_int32), ("dst", C.c_void_p), ("dst_stride", C.c_int64)]
 
 
-_declared = False
-
-
 def _lib():
-    global _declared
-    L = K.lib()
-    if not _declared:
-        vp = C.c_void_p
-        L.vdo_rectify_plan.argtypes = [C.POINTER(RectifyParamsC), C.c_int, vp, vp, K.c_int32_p]
-        L.vdo_rectify_create.argtypes = [vp, C.POINTER(RectifyParamsC), C.POINTER(vp)]
-        L.vdo_rectify_create_from_maps.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp), K.c_int32_p, K.c_int32_p, C.POINTER(vp)]
-        L.vdo_rectify_destroy.argtypes = [vp]
-        L.vdo_rectify_compute.argtypes = [vp, C.POINTER(RectifyJobC), C.c_int, C.c_int, C.c_int, C.c_int]
-        L.vdo_rectify_gate.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int, K.c_int32_p]
-        L.vdo_rectify_get_map.argtypes = [vp, C.c_int, vp]
-        L.vdo_rectify_get_valid.argtypes = [vp, C.c_int, vp, K.c_int32_p]
-        L.vdo_rectify_last_timing.argtypes = [vp, K.c_double_p]
-        L.vdo_rectify_device_images.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp)]
-        L.vdo_rectify_download_image.argtypes = [vp, vp, C.c_int64, vp]
-        for f in ("download_image", "plan", "create", "create_from_maps", "destroy", "compute", "gate", "get_map", "get_valid", "last_timing", "device_images"):
-            getattr(L, "vdo_rectify_" + f).restype = C.c_int
-        _declared = True
-    return L
+    vp = C.c_void_p
+    return K.declare(K.lib(), "vdo_rectify_", {
+        "plan": [C.POINTER(RectifyParamsC), C.c_int, vp, vp, K.c_int32_p],
+        "create": [vp, C.POINTER(RectifyParamsC), C.POINTER(vp)],
+        "create_from_maps": [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp), K.c_int32_p, K.c_int32_p, C.POINTER(vp)],
+        "destroy": [vp],
+        "compute": [vp, C.POINTER(RectifyJobC), C.c_int, C.c_int, C.c_int, C.c_int],
+        "gate": [vp, C.c_int, vp, C.c_int64, C.c_int, K.c_int32_p],
+        "get_map": [vp, C.c_int, vp],
+        "get_valid": [vp, C.c_int, vp, K.c_int32_p],
+        "last_timing": [vp, K.c_double_p],
+        "device_images": [vp, C.c_int, C.POINTER(vp), C.POINTER(vp)],
+        "download_image": [vp, vp, C.c_int64, vp],
+    })
 
 
 def camera(K4, D=(0, 0, 0, 0, 0), R=(1, 0, 0, 0, 1, 0, 0, 0, 1), src_size=(0, 0)) -> dict:
@@ -88,13 +80,13 @@ def job(src, src_stride, channels, dst, dst_stride, cam=0, rgb_order=0, nearest=
     return RectifyJobC(C.c_void_p(src or None), int(src_stride), int(channels), int(rgb_order), int(cam), int(nearest), C.c_void_p(dst or None), int(dst_stride))
 
 
-class StereoRectifier:
+class StereoRectifier(K.StageHandle):
     """``vdo_rectify`` handle; every device buffer is allocated here.  Built from ``params(...)`` or, with ``maps=``, from ready-made maps
     (a list of int32 [H, W, 2] arrays) and ``src_sizes`` (a list of (Ws, Hs))."""
+    _prefix = "vdo_rectify_"
 
     def __init__(self, ctx, prm: RectifyParamsC = None, maps=None, src_sizes=None):
-        self._L = _lib()
-        self._h = C.c_void_p()
+        super().__init__(_lib())
         self._ctx = ctx
         if maps is not None:
             maps = [np.ascontiguousarray(m, np.int32) for m in maps]
@@ -173,17 +165,3 @@ class StereoRectifier:
         out = np.zeros((self.height, self.width), np.uint8)
         K.check(self._L.vdo_rectify_download_image(self._h, C.c_void_p(image_ptr or None), int(stride or self.width), out.ctypes.data))
         return out
-
-    def timing(self):
-        """(wall ms of the call, device ms by events) of the last compute or gate"""
-        ms = (C.c_double * 2)()
-        K.check(self._L.vdo_rectify_last_timing(self._h, ms))
-        return ms[0], ms[1]
-
-    def close(self):
-        if self._h:
-            self._L.vdo_rectify_destroy(self._h); self._h = C.c_void_p()
-
-    def __del__(self):
-        try: self.close()
-        except Exception: pass

@@ -14,26 +14,18 @@ class StereoParamsC(C.Structure):
                 ("uniqueness", C.c_int32), ("lr_max_diff", C.c_int32), ("subpixel", C.c_int32)]
 
 
-_declared = False
-
-
 def _lib():
-    global _declared
-    L = K.lib()
-    if not _declared:
-        vp = C.c_void_p
-        L.vdo_stereo_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(StereoParamsC), C.POINTER(vp)]
-        L.vdo_stereo_destroy.argtypes = [vp]
-        L.vdo_stereo_compute.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.c_int, vp, C.c_int, K.c_int32_p]
-        L.vdo_stereo_set_output_scale.argtypes = [vp, C.c_float]
-        L.vdo_stereo_get_census.argtypes = [vp, C.c_int, vp]
-        L.vdo_stereo_get_cost.argtypes = [vp, vp]
-        L.vdo_stereo_get_aggregated.argtypes = [vp, vp]
-        L.vdo_stereo_last_timing.argtypes = [vp, K.c_double_p]
-        for f in ("create", "destroy", "compute", "set_output_scale", "get_census", "get_cost", "get_aggregated", "last_timing"):
-            getattr(L, "vdo_stereo_" + f).restype = C.c_int
-        _declared = True
-    return L
+    vp = C.c_void_p
+    return K.declare(K.lib(), "vdo_stereo_", {
+        "create": [vp, C.c_int, C.c_int, C.POINTER(StereoParamsC), C.POINTER(vp)],
+        "destroy": [vp],
+        "compute": [vp, vp, C.c_int64, vp, C.c_int64, C.c_int, vp, C.c_int, K.c_int32_p],
+        "set_output_scale": [vp, C.c_float],
+        "get_census": [vp, C.c_int, vp],
+        "get_cost": [vp, vp],
+        "get_aggregated": [vp, vp],
+        "last_timing": [vp, K.c_double_p],
+    })
 
 
 def params(max_disparity=128, p1=10, p2=120, paths=8, uniqueness=5, lr_max_diff=1, subpixel=True) -> StereoParamsC:
@@ -41,12 +33,12 @@ def params(max_disparity=128, p1=10, p2=120, paths=8, uniqueness=5, lr_max_diff=
     return StereoParamsC(int(max_disparity), int(p1), int(p2), int(paths), int(uniqueness), int(lr_max_diff), int(bool(subpixel)))
 
 
-class StereoMatcher:
+class StereoMatcher(K.StageHandle):
     """``vdo_stereo`` handle for width x height images; every device buffer is allocated here."""
+    _prefix = "vdo_stereo_"
 
     def __init__(self, ctx, width, height, **prm):
-        self._L = _lib()
-        self._h = C.c_void_p()
+        super().__init__(_lib())
         self.width, self.height = int(width), int(height)
         self.params = params(**prm)
         self._ctx = ctx
@@ -91,19 +83,7 @@ class StereoMatcher:
         K.check(self._L.vdo_stereo_get_aggregated(self._h, out.ctypes.data))
         return out
 
-    def last_timing(self):
-        """(wall ms of the call, device ms by events) of the last compute"""
-        ms = (C.c_double * 2)()
-        K.check(self._L.vdo_stereo_last_timing(self._h, ms))
-        return ms[0], ms[1]
-
-    def close(self):
-        if self._h:
-            self._L.vdo_stereo_destroy(self._h); self._h = C.c_void_p()
-
-    def __del__(self):
-        try: self.close()
-        except Exception: pass
+    last_timing = K.StageHandle.timing      # (wall ms of the call, device ms by events) of the last compute
 
 
 def compute(ctx, left, right, **prm):
