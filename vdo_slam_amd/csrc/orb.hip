@@ -32,7 +32,7 @@
 namespace vdo {
 
 constexpr int kEdge = 19, kHalfPatch = 15, kPatch = 31;
-constexpr int kSpecCand = 24576;       // candidates fetched speculatively together with the header (typ. 10-15 k per KITTI frame)
+constexpr int kSpecCand = 24576;       // VDO_ORB_FUSED_ANGLE=1: candidates copied speculatively together with the header (typ. 10-15 k per KITTI frame)
 constexpr int kMaxCellDim = 68;        // hCell = ceil(height/nRows) < 60, +6 overlap
 static_assert(kMaxCellDim <= 128, "k_fast_cells packs cell-local coordinates in 7 bits");
 
@@ -365,6 +365,81 @@ __global__ __launch_bounds__(256) void k_compact_angle(const uint8_t* __restrict
   }
 }
 
+// The split form of k_compact_angle (default; VDO_ORB_FUSED_ANGLE=1 keeps the kernel above).  The host quadtrees read x, y and
+// resp only, so the angles need not stand between k_fast_cells and the host:
+//   k_compact  the same prefix over the cell counts and the same header, then x, y, resp, level of every candidate to the dense
+//              device arrays AND x, y, resp + the header to mapped pinned memory (hx / hy / hresp / hhdr: coalesced rows, written
+//              once) - no copy operation in front of the event the host waits for;
+//   k_angle    queued behind that event: the per-candidate loop of k_compact_angle (one wave per candidate, 31 rows over the
+//              lanes, the same integer moments and fast_atan2_dev) over the dense arrays.
+__global__ __launch_bounds__(256) void k_compact(const CellDesc* __restrict__ cells, const int* __restrict__ cnt, const int* __restrict__ cell_level,
+                                                 int* __restrict__ level_cnt, const uint32_t* __restrict__ pack, int ncells, int cell_cap,
+                                                 float* __restrict__ ox, float* __restrict__ oy, float* __restrict__ oresp, int* __restrict__ olevel,
+                                                 int* __restrict__ hhdr, float* __restrict__ hx, float* __restrict__ hy, float* __restrict__ hresp) {
+  const int cell = blockIdx.x;
+  const int n = min(cnt[cell], cell_cap);
+  const CellDesc C = cells[cell];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  __shared__ int s_part[4], s_lvl[17];
+  int a = 0;
+  for (int c = threadIdx.x; c < cell; c += 256) a += min(cnt[c], cell_cap);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) a += __shfl_down(a, off, 64);
+  if (lane == 0) s_part[wv] = a;
+  if (cell == 0 && threadIdx.x < 17) s_lvl[threadIdx.x] = 0;
+  __syncthreads();
+  const int base = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+  if (cell == 0) {
+    int mx = 0;
+    for (int c = threadIdx.x; c < ncells; c += 256) { const int r = cnt[c], v = min(r, cell_cap); if (v) atomicAdd(&s_lvl[cell_level[c]], v); mx = max(mx, r); }
+    atomicMax(&s_lvl[16], mx);
+    __syncthreads();
+    if (threadIdx.x < 16) level_cnt[threadIdx.x] = hhdr[threadIdx.x] = s_lvl[threadIdx.x];
+    if (threadIdx.x == 0) { int t = 0; for (int q = 0; q < 16; ++q) t += s_lvl[q]; level_cnt[16] = hhdr[16] = t; level_cnt[17] = hhdr[17] = s_lvl[16]; }
+  }
+  for (int k = threadIdx.x; k < n; k += 256) {       // (n <= cell_cap: base + k < ncells * cell_cap = dense_cap, the length of every row)
+    const uint32_t pk = pack[(size_t)cell * cell_cap + k];
+    const float x = (float)((int)(pk & 0x7f) + C.addx), y = (float)((int)((pk >> 7) & 0x7f) + C.addy), s = (float)(int)(pk >> 24);
+    const int o = base + k;
+    ox[o] = x; oy[o] = y; oresp[o] = s; olevel[o] = C.level;
+    hx[o] = x; hy[o] = y; hresp[o] = s;
+  }
+}
+
+// One wave per candidate as in k_compact_angle; a wave takes kAngChunk consecutive candidates and stores their angles with one
+// instruction (one contiguous write to the mapped row instead of kAngChunk single floats).  total = level_cnt[16] (k_compact).
+constexpr int kAngChunk = 8;
+__global__ __launch_bounds__(256) void k_angle(const uint8_t* __restrict__ pyr, const LevelDesc* __restrict__ levels, const int* __restrict__ level_cnt, UMax um,
+                                               const float* __restrict__ ox, const float* __restrict__ oy, const int* __restrict__ olevel,
+                                               float* __restrict__ oang, float* __restrict__ hang) {
+  const int total = level_cnt[16];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  for (int c0 = (blockIdx.x * 4 + wv) * kAngChunk; c0 < total; c0 += gridDim.x * 4 * kAngChunk) {
+    float mine = 0.f;
+    const int ce = min(c0 + kAngChunk, total);
+    for (int o = c0; o < ce; ++o) {
+      const int x = (int)ox[o], y = (int)oy[o];                 // integer-valued floats (k_compact)
+      const LevelDesc L = levels[olevel[o]];
+      const uint8_t* img = pyr + L.off_inner;
+      const int cx = x + (kEdge - 3), cy = y + (kEdge - 3);
+      int m10 = 0, m01 = 0;
+      if (lane < 31) {
+        const int v = lane - kHalfPatch;
+        const int d = um.v[v < 0 ? -v : v];
+        const uint8_t* row = img + (size_t)(cy + v) * L.bw + cx;
+        int rs = 0;
+        for (int u = -d; u <= d; ++u) { const int p = row[u]; m10 += u * p; rs += p; }
+        m01 = v * rs;
+      }
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) { m10 += __shfl_down(m10, off, 64); m01 += __shfl_down(m01, off, 64); }
+      const float ang = fast_atan2_dev((float)__shfl(m01, 0, 64), (float)__shfl(m10, 0, 64));
+      if (lane == o - c0) mine = ang;
+    }
+    if (c0 + lane < ce) { oang[c0 + lane] = mine; hang[c0 + lane] = mine; }
+  }
+}
+
 // ------------------------------------------------------------------------------------ K7
 // 7x7 Gaussian, sigma 2, 8-bit fixed-point separable (OpenCV 3.4.0 path), REFLECT_101 at the interior edge.
 struct Blur7 { int k[7]; };
@@ -654,9 +729,12 @@ struct vdo_orb {
   // and octaves in output order (pos_ready).  A new extraction clears both flags.
   bool desc_ready = false, pos_ready = false;
   float *m_x = nullptr, *m_y = nullptr; int32_t* m_oct = nullptr; int match_cap = 0;
-  // pinned staging: [32 ints: level counts, total, largest cell count][5][kSpecCand] — header and candidates arrive with ONE sync
-  float* h_pin = nullptr;
-  float* h_over = nullptr; size_t h_over_n = 0;      // overflow staging when a frame has more than kSpecCand candidates
+  // mapped pinned staging: [32 ints: level counts, total, largest cell count][4: x, y, resp, angle][dense_cap].  Split path (default): k_compact writes the
+  // header and the x / y / resp rows, k_angle the angle row, straight into it (d_pin: its device address).  VDO_ORB_FUSED_ANGLE=1
+  // (fused_angle, read in vdo_orb_create): k_compact_angle, then the header and the first kSpecCand columns of the rows are copied
+  // (all of them, in _end, for a frame with more candidates than that).
+  float* h_pin = nullptr; float* d_pin = nullptr;
+  bool fused_angle = false;
   // host view of the last extraction (pointers into the pinned staging)
   const float *hx = nullptr, *hy = nullptr, *hresp = nullptr, *hang = nullptr; std::vector<int> hlevel_cnt;
   int n_cand = 0;
@@ -666,6 +744,7 @@ struct vdo_orb {
   double ms_device = 0, ms_tree = 0;                  // last extraction: launch..sync, host quadtree
   bool begun = false;                                 // between vdo_orb_extract_begin and _end
   hipEvent_t ev_cand = nullptr;                       // candidates are on the host (the blur stage runs behind it)
+  hipEvent_t ev_ang = nullptr;                        // split path: their angles are on the host (k_angle runs behind ev_cand)
   std::chrono::steady_clock::time_point t_begin;
 };
 
@@ -692,7 +771,7 @@ extern "C" int vdo_orb_destroy(vdo_orb* o) {
   for (void* p : o->allocs) hipFree(p);
   if (o->h_pin) hipHostFree(o->h_pin);
   if (o->ev_cand) hipEventDestroy(o->ev_cand);
-  if (o->h_over) hipHostFree(o->h_over);
+  if (o->ev_ang) hipEventDestroy(o->ev_ang);
   delete o;
   return VDO_OK;
 }
@@ -871,16 +950,21 @@ extern "C" int vdo_orb_create(vdo_ctx* ctx, const vdo_orb_params* prm, int w, in
     o->d_y = o->d_x + (size_t)o->dense_cap; o->d_resp = o->d_x + 2 * (size_t)o->dense_cap; o->d_ang = o->d_x + 3 * (size_t)o->dense_cap;
     o->d_lvl = (int*)(o->d_x + 4 * (size_t)o->dense_cap);
   }
-  if (hipHostMalloc((void**)&o->h_pin, 4 * (32 + 5 * (size_t)kSpecCand)) != hipSuccess) o->h_pin = nullptr;
+  o->fused_angle = std::getenv("VDO_ORB_FUSED_ANGLE") != nullptr;
+  if (hipHostMalloc((void**)&o->h_pin, 4 * (32 + 4 * (size_t)o->dense_cap), hipHostMallocMapped) != hipSuccess) o->h_pin = nullptr;
+  if (o->h_pin && hipHostGetDevicePointer((void**)&o->d_pin, o->h_pin, 0) != hipSuccess) o->d_pin = nullptr;
   for (void* p : o->allocs) if (!p) { vdo_orb_destroy(o); return set_error(VDO_ERR_OOM, "hipMalloc failed"); }
-  if (!o->d_lvl || !o->h_pin) { vdo_orb_destroy(o); return set_error(VDO_ERR_OOM, "hipMalloc failed"); }
+  if (!o->d_lvl || !o->h_pin || !o->d_pin) { vdo_orb_destroy(o); return set_error(VDO_ERR_OOM, "hipMalloc failed"); }
   hipMemcpyAsync(o->d_levels, o->levels.data(), sizeof(LevelDesc) * NL, hipMemcpyHostToDevice, s);
   hipMemcpyAsync(o->d_cells, o->cells.data(), sizeof(CellDesc) * o->ncells, hipMemcpyHostToDevice, s);
   hipMemcpyAsync(o->d_cell_level, o->cell_level.data(), 4 * (size_t)o->ncells, hipMemcpyHostToDevice, s);
   static_assert(sizeof(kOrbPattern31) == sizeof(OrbPattern), "256 tests x 4 signed bytes");
   hipMemcpyAsync(o->d_pat, kOrbPattern31, sizeof(OrbPattern), hipMemcpyHostToDevice, s);
   if (hipStreamSynchronize(s) != hipSuccess) { vdo_orb_destroy(o); return set_error(VDO_ERR_NO_DEVICE, "orb upload failed"); }
-  if (hipEventCreateWithFlags(&o->ev_cand, hipEventDisableTiming) != hipSuccess) { vdo_orb_destroy(o); return set_error(VDO_ERR_NO_DEVICE, "hipEventCreate failed"); }
+  if (hipEventCreateWithFlags(&o->ev_cand, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&o->ev_ang, hipEventDisableTiming) != hipSuccess) {
+    vdo_orb_destroy(o);
+    return set_error(VDO_ERR_NO_DEVICE, "hipEventCreate failed");
+  }
   {
     const char* e = std::getenv("VDO_ORB_THREADS");
     const int nw = e ? std::atoi(e) : 3;
@@ -915,9 +999,26 @@ static int orb_device_stage(vdo_orb* o, const uint8_t* gray_dev, int stride) {
   }
   hipLaunchKernelGGL(k_fast_cells, dim3(o->ncells), dim3(256), 0, s, (const uint8_t*)o->d_pyr, (const LevelDesc*)o->d_levels, (const CellDesc*)o->d_cells,
                      o->prm.ini_th, o->prm.min_th, o->cell_cap, o->d_cnt, o->d_pack);
-  hipLaunchKernelGGL(k_compact_angle, dim3(o->ncells), dim3(256), 0, s, (const uint8_t*)o->d_pyr, (const LevelDesc*)o->d_levels, (const CellDesc*)o->d_cells,
-                     (const int*)o->d_cnt, (const int*)o->d_cell_level, o->d_level_cnt, (const uint32_t*)o->d_pack, o->ncells, o->cell_cap, o->um, o->d_x, o->d_y, o->d_resp, o->d_ang, o->d_lvl);
+  if (o->fused_angle) {
+    hipLaunchKernelGGL(k_compact_angle, dim3(o->ncells), dim3(256), 0, s, (const uint8_t*)o->d_pyr, (const LevelDesc*)o->d_levels, (const CellDesc*)o->d_cells,
+                       (const int*)o->d_cnt, (const int*)o->d_cell_level, o->d_level_cnt, (const uint32_t*)o->d_pack, o->ncells, o->cell_cap, o->um, o->d_x, o->d_y, o->d_resp, o->d_ang, o->d_lvl);
+  } else {
+    float* rows = o->d_pin + 32;
+    const size_t pitch = (size_t)o->dense_cap;
+    hipLaunchKernelGGL(k_compact, dim3(o->ncells), dim3(256), 0, s, (const CellDesc*)o->d_cells, (const int*)o->d_cnt, (const int*)o->d_cell_level, o->d_level_cnt,
+                       (const uint32_t*)o->d_pack, o->ncells, o->cell_cap, o->d_x, o->d_y, o->d_resp, o->d_lvl, (int*)o->d_pin, rows, rows + pitch, rows + 2 * pitch);
+  }
   return VDO_OK;
+}
+
+// Split path: K6 behind the event the host waits for; the angle row arrives under the quadtrees and is closed by ev_ang.
+static void orb_angle_stage(vdo_orb* o) {
+  hipStream_t s = o->ctx->stream;
+  // grid-stride over chunks of kAngChunk candidates per wave: 1024 workgroups take 32 k candidates per pass (a KITTI frame has 10-15 k)
+  const int chunks = (o->dense_cap + kAngChunk - 1) / kAngChunk;
+  hipLaunchKernelGGL(k_angle, dim3(std::max(1, std::min(1024, (chunks + 3) / 4))), dim3(256), 0, s, (const uint8_t*)o->d_pyr, (const LevelDesc*)o->d_levels,
+                     (const int*)o->d_level_cnt, o->um, (const float*)o->d_x, (const float*)o->d_y, (const int*)o->d_lvl, o->d_ang, o->d_pin + 32 + 3 * (size_t)o->dense_cap);
+  hipEventRecord(o->ev_ang, s);
 }
 
 // K7: the reference blurs every non-empty level (result unused there since BRIEF is commented out, F1).  Nothing downstream
@@ -953,13 +1054,17 @@ extern "C" int vdo_orb_extract_begin(vdo_orb* o, const uint8_t* gray, int stride
   o->t_begin = std::chrono::steady_clock::now();
   o->desc_ready = o->pos_ready = false;             // (the dense candidate arrays are overwritten from here on)
   orb_device_stage(o, src, sstride);
-  // candidates -> host: header (level counts + total) and the first kSpecCand columns of the 5 candidate rows
-  int* hdr = (int*)o->h_pin;
-  float* rows = o->h_pin + 32;
-  const int spec = std::min(kSpecCand, o->dense_cap);
-  hipMemcpyAsync(hdr, o->d_level_cnt, 4 * 32, hipMemcpyDeviceToHost, s);
-  hipMemcpy2DAsync(rows, 4 * (size_t)spec, o->d_x, 4 * (size_t)o->dense_cap, 4 * (size_t)spec, 5, hipMemcpyDeviceToHost, s);
-  hipEventRecord(o->ev_cand, s);
+  if (o->fused_angle) {
+    // candidates -> host: header (level counts + total) and the first kSpecCand columns of the 4 candidate rows the host reads
+    const int spec = std::min(kSpecCand, o->dense_cap);
+    hipMemcpyAsync(o->h_pin, o->d_level_cnt, 4 * 32, hipMemcpyDeviceToHost, s);
+    hipMemcpy2DAsync(o->h_pin + 32, 4 * (size_t)o->dense_cap, o->d_x, 4 * (size_t)o->dense_cap, 4 * (size_t)spec, 4, hipMemcpyDeviceToHost, s);
+    hipEventRecord(o->ev_cand, s);
+  } else {
+    // k_compact has written the header and the x / y / resp rows to the host itself; the angles follow behind the event
+    hipEventRecord(o->ev_cand, s);
+    orb_angle_stage(o);
+  }
   orb_blur_stage(o);
   o->begun = true;
   return VDO_OK;
@@ -979,8 +1084,8 @@ extern "C" int vdo_orb_extract_end(vdo_orb* o, vdo_keypoints* out) {
   hipStream_t s = o->ctx->stream;
   const auto t_begin = o->t_begin;
   int* hdr = (int*)o->h_pin;
-  float* rows = o->h_pin + 32;
-  const int spec = std::min(kSpecCand, o->dense_cap);
+  const float* rows = o->h_pin + 32;
+  const size_t pitch = (size_t)o->dense_cap;
   if (hipEventSynchronize(o->ev_cand) != hipSuccess) return set_error(VDO_ERR_NO_DEVICE, "orb device stage failed: %s", hipGetErrorString(hipGetLastError()));
   if (hdr[17] > o->cell_cap) {   // cannot happen (vdo_orb_create); k_fast_cells would have dropped the excess without a word
     o->hlevel_cnt.clear(); o->sel_dense.clear();
@@ -989,17 +1094,9 @@ extern "C" int vdo_orb_extract_end(vdo_orb* o, vdo_keypoints* out) {
   const int total = hdr[16];
   o->n_cand = total;
   o->hlevel_cnt.assign(hdr, hdr + 16);
-  size_t pitch = (size_t)spec;
-  if (total > spec) {           // rare: fetch everything into a (grown on demand) pinned overflow buffer
-    if (o->h_over_n < (size_t)total) {
-      if (o->h_over) hipHostFree(o->h_over);
-      o->h_over = nullptr; o->h_over_n = 0;
-      if (hipHostMalloc((void**)&o->h_over, 4 * 5 * (size_t)total) != hipSuccess) return set_error(VDO_ERR_OOM, "hipHostMalloc failed");
-      o->h_over_n = (size_t)total;
-    }
-    hipMemcpy2DAsync(o->h_over, 4 * (size_t)total, o->d_x, 4 * (size_t)o->dense_cap, 4 * (size_t)total, 5, hipMemcpyDeviceToHost, s);
+  if (o->fused_angle && total > kSpecCand) {           // rare: the speculative copy fell short, fetch all columns
+    hipMemcpy2DAsync(o->h_pin + 32, 4 * pitch, o->d_x, 4 * pitch, 4 * (size_t)total, 4, hipMemcpyDeviceToHost, s);
     if (hipStreamSynchronize(s) != hipSuccess) return set_error(VDO_ERR_NO_DEVICE, "orb D2H failed");
-    rows = o->h_over; pitch = (size_t)total;
   }
   o->hx = rows; o->hy = rows + pitch; o->hresp = rows + 2 * pitch; o->hang = rows + 3 * pitch;
   const auto t_dev = std::chrono::steady_clock::now();
@@ -1016,6 +1113,8 @@ extern "C" int vdo_orb_extract_end(vdo_orb* o, vdo_keypoints* out) {
   };
   if (o->pool) o->pool->run(NL, level_task);
   else for (int l = 0; l < NL; ++l) level_task(l);
+  // split path: the angle row was written under the quadtrees (o->hang and vdo_orb_get_candidates are valid from here on)
+  if (!o->fused_angle && hipEventSynchronize(o->ev_ang) != hipSuccess) return set_error(VDO_ERR_NO_DEVICE, "orb angle stage failed: %s", hipGetErrorString(hipGetLastError()));
   int n = 0;
   o->sel_dense.clear();
   for (int l = 0; l < NL; ++l) {

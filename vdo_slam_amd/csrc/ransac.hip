@@ -9,8 +9,12 @@
 //                  4th point picks among the <= 4 solutions
 //   k_ransac_vote  one workgroup per hypothesis: squared reprojection error of every correspondence, inlier count
 //                  and inlier bit-mask
-// and the host then replays the loop over the 500 counts (a better model shrinks the iteration budget), which
+//   k_ransac_records  one workgroup per problem: the hypotheses whose vote sets a record, in order, with their poses and
+//                  inlier masks, compactly into mapped pinned memory - all the host loop can ever look at
+// and the host then replays the loop over those records (a better model shrinks the iteration budget), which
 // yields exactly the model, inlier set and iteration count the sequential run would have produced.
+// (VDO_PNP_FULL_READBACK=1, or a problem with more than kRecCap records: votes, poses and masks of ALL hypotheses come back and the
+// loop runs over the 500 counts, as it did before the records kernel.)
 #include <algorithm>
 #include <cfloat>
 #include <chrono>
@@ -30,7 +34,7 @@
 namespace vdo {
 
 struct PnpDev {          // one problem inside the batch arrays
-  int n, n_hyp, pt_off, hyp_off, mask_off, mask_words, pad0, pad1;
+  int n, n_hyp, pt_off, hyp_off, mask_off, mask_words, rec_mask_off, pad1;      // rec_mask_off: first word of the problem's record mask rows (k_ransac_records)
   double K[4];
   double thr2;
 };
@@ -444,6 +448,50 @@ __global__ __launch_bounds__(256) void k_ransac_vote(const PnpDev* __restrict__ 
   if (threadIdx.x == 0) count[gh] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
 }
 
+// The records of one problem: hypothesis h sets a record iff it is valid and its vote exceeds max(3, every vote before it) - the test of the host loop
+// (`ok && cnt > max(max_good, 3)`, max_good being the vote of the last record) as an exclusive prefix maximum over the votes in hypothesis order; integer
+// work, order-exact.  Record r (< cap <= kRecCap) goes to rec_it / rec_vote / rec_pose / rec_mask of the problem, rec_cnt gets the count of ALL records
+// (more than cap: the host takes the full read-back).  The host loop stops at its shrinking budget; the records behind that point are simply not read.
+constexpr int kRecCap = 32;
+__global__ __launch_bounds__(256) void k_ransac_records(const PnpDev* __restrict__ probs, const double* __restrict__ hyp_pose, const int32_t* __restrict__ hyp_ok,
+                                                        const int32_t* __restrict__ count, const uint32_t* __restrict__ mask, int cap,
+                                                        int32_t* __restrict__ rec_cnt, int32_t* __restrict__ rec_it, int32_t* __restrict__ rec_vote,
+                                                        double* __restrict__ rec_pose, uint32_t* __restrict__ rec_mask) {
+  const PnpDev P = probs[blockIdx.x];
+  if (!P.n_hyp) return;
+  __shared__ int s_wmax[4], s_wcnt[4], s_it[kRecCap];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const size_t slot = (size_t)blockIdx.x * cap;
+  int run_max = 3, n_rec = 0;                       // (workgroup-uniform: every thread carries them over the 256-hypothesis chunks)
+  for (int h0 = 0; h0 < P.n_hyp; h0 += 256) {
+    const int h = h0 + threadIdx.x;
+    const int c = (h < P.n_hyp && hyp_ok[P.hyp_off + h]) ? count[P.hyp_off + h] : 0;
+    int m = c;                                       // inclusive maximum over the wave's lanes up to this one
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_up(m, off, 64); if (lane >= off) m = max(m, v); }
+    if (lane == 63) s_wmax[wv] = m;
+    __syncthreads();
+    int before = __shfl_up(m, 1, 64);
+    if (lane == 0) before = 0;
+    before = max(before, run_max);
+    for (int q = 0; q < wv; ++q) before = max(before, s_wmax[q]);
+    const bool rec = c > before;
+    const unsigned long long b = __ballot(rec);
+    if (lane == 0) s_wcnt[wv] = __popcll(b);
+    __syncthreads();
+    int rank = n_rec + __popcll(b & ((1ull << lane) - 1ull));
+    for (int q = 0; q < wv; ++q) rank += s_wcnt[q];
+    if (rec && rank < cap) { s_it[rank] = h; rec_it[slot + rank] = h; rec_vote[slot + rank] = c; }
+    run_max = max(max(run_max, max(s_wmax[0], s_wmax[1])), max(s_wmax[2], s_wmax[3]));
+    n_rec += s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
+    __syncthreads();                                 // (s_wmax / s_wcnt are rewritten by the next chunk; s_it is read below)
+  }
+  if (threadIdx.x == 0) rec_cnt[blockIdx.x] = n_rec;
+  const int nr = min(n_rec, cap), mw = P.mask_words;
+  for (int i = threadIdx.x; i < nr * 12; i += 256) { const int r = i / 12, q = i - 12 * r; rec_pose[12 * (slot + r) + q] = hyp_pose[12 * ((size_t)P.hyp_off + s_it[r]) + q]; }
+  for (int i = threadIdx.x; i < nr * mw; i += 256) { const int r = i / mw, w = i - mw * r; rec_mask[(size_t)P.rec_mask_off + (size_t)r * mw + w] = mask[(size_t)P.mask_off + (size_t)s_it[r] * mw + w]; }
+}
+
 // cv::RNG
 struct CvRng {
   uint64_t state;
@@ -491,8 +539,12 @@ static int pnp_ransac_impl(vdo_ctx* ctx, int n_problems, const vdo_pnp_problem* 
   static thread_local std::vector<int32_t> subsets;
   static thread_local std::vector<double> X, uv;
   hp.assign(n_problems, PnpDev{});
-  size_t tot_pts = 0, tot_hyp = 0, tot_words = 0;
+  size_t tot_pts = 0, tot_hyp = 0, tot_words = 0, tot_rec_words = 0;
   int max_hyp = 0;
+  // VDO_PNP_FULL_READBACK / VDO_PNP_RECORD_CAP (A/B switch and the test's way to the overflow path, read on every call as VDO_PNP_NO_GATE is: one process runs both paths)
+  bool records = std::getenv("VDO_PNP_FULL_READBACK") == nullptr;
+  int rec_cap = kRecCap;
+  if (const char* e = std::getenv("VDO_PNP_RECORD_CAP")) rec_cap = std::min(std::max(std::atoi(e), 1), kRecCap);
   for (int k = 0; k < n_problems; ++k) {
     const vdo_pnp_problem& p = probs[k];
     if (p.n < 0 || p.max_iterations < 0 || (p.n > 0 && (!p.X || !p.uv))) return set_error(VDO_ERR_INVALID, "pnp problem %d: bad fields", k);
@@ -501,6 +553,7 @@ static int pnp_ransac_impl(vdo_ctx* ctx, int n_problems, const vdo_pnp_problem* 
     d.pt_off = (int)tot_pts; d.hyp_off = (int)tot_hyp; d.mask_off = (int)tot_words; d.mask_words = (p.n + 63) / 64 * 2;
     std::memcpy(d.K, p.K, sizeof d.K);
     d.thr2 = p.reproj_threshold * p.reproj_threshold;
+    d.rec_mask_off = (int)tot_rec_words; tot_rec_words += (size_t)(d.n_hyp ? rec_cap : 0) * d.mask_words;
     tot_pts += p.n; tot_hyp += d.n_hyp; tot_words += (size_t)d.n_hyp * d.mask_words;
     max_hyp = std::max(max_hyp, d.n_hyp);
   }
@@ -547,7 +600,8 @@ static int pnp_ransac_impl(vdo_ctx* ctx, int n_problems, const vdo_pnp_problem* 
   }
   const double tr1 = g_pnp_trace.on ? pnp_now_us() : 0.0;
   Arena S(ctx);
-  if (!S.reserve(40 * tot_pts + 128 * tot_hyp + 4 * tot_words + sizeof(PnpDev) * (size_t)n_problems + 16 * 256 + 8192))
+  if (!S.reserve(40 * tot_pts + 128 * tot_hyp + 4 * tot_words + sizeof(PnpDev) * (size_t)n_problems + 16 * 256 + 8192 +
+                 (size_t)n_problems * (4 + (size_t)rec_cap * 104) + 4 * tot_rec_words))
     return set_error(VDO_ERR_OOM, "scratch arena: allocation failed");
   PnpDev* dprob = S.up(hp.data(), (size_t)n_problems);
   double *dX = S.up(X.data(), X.size()), *duv = S.up(uv.data(), uv.size());
@@ -563,36 +617,73 @@ static int pnp_ransac_impl(vdo_ctx* ctx, int n_problems, const vdo_pnp_problem* 
   if (grunert) hipLaunchKernelGGL(k_p3p_hyp, dim3((max_hyp + 63) / 64, n_problems), dim3(64), 0, S.stream(), (const PnpDev*)dprob, (const double*)dX, (const double*)duv, (const int32_t*)dsub, dpose, dok);
   else hipLaunchKernelGGL(k_ap3p_hyp, dim3((max_hyp + 63) / 64, n_problems), dim3(64), 0, S.stream(), (const PnpDev*)dprob, (const double*)dX, (const double*)duv, (const int32_t*)dsub, dpose, dok);
   hipLaunchKernelGGL(k_ransac_vote, dim3(max_hyp, n_problems), dim3(256), 0, S.stream(), (const PnpDev*)dprob, (const double*)dX, (const double*)duv, (const double*)dpose, (const int32_t*)dok, dcnt, dmask);
-  // (votes, poses and inlier masks of all hypotheses are read where they land in the pinned block: the replay touches a few rows)
-  const int32_t *cnt = S.down_view(dcnt, tot_hyp), *okv = S.down_view(dok, tot_hyp);
-  const double* pose = S.down_view(dpose, 12 * tot_hyp);
-  const uint32_t* mask = S.down_view(dmask, tot_words);
-  S.queue_downloads();
-  if (host_work) host_work(host_arg);                      // (the caller's own host work, under the two kernels and the copy back)
-  rc = S.finish("vdo_pnp_ransac_batch");
-  if (rc != VDO_OK) return rc;
-  if (!cnt || !okv || !pose || !mask) return set_error(VDO_ERR_OOM, "scratch arena exhausted");
+  // The records of every problem, written by k_ransac_records where the host reads them (Arena::out: mapped pinned memory, no copy operation) ...
+  const int32_t *rcnt = nullptr, *rit = nullptr, *rvote = nullptr; const double* rpose = nullptr; const uint32_t* rmask = nullptr;
+  if (records) {
+    const size_t nr = (size_t)n_problems * rec_cap;
+    int32_t *ocnt = S.out<int32_t>(n_problems), *oit = S.out<int32_t>(nr), *ovote = S.out<int32_t>(nr);
+    double* opose = S.out<double>(12 * nr);
+    uint32_t* omask = S.out<uint32_t>(tot_rec_words);
+    if (!ocnt || !oit || !ovote || !opose || !omask) return set_error(VDO_ERR_OOM, "scratch arena exhausted");
+    hipLaunchKernelGGL(k_ransac_records, dim3(n_problems), dim3(256), 0, S.stream(), (const PnpDev*)dprob, (const double*)dpose, (const int32_t*)dok, (const int32_t*)dcnt, (const uint32_t*)dmask,
+                       rec_cap, ocnt, oit, ovote, opose, omask);
+    rcnt = S.view(ocnt, n_problems); rit = S.view(oit, nr); rvote = S.view(ovote, nr); rpose = S.view(opose, 12 * nr); rmask = S.view(omask, tot_rec_words);
+    S.queue_downloads();
+    if (host_work) host_work(host_arg);                    // (the caller's own host work, under the three kernels)
+    rc = S.finish("vdo_pnp_ransac_batch");
+    if (rc != VDO_OK) return rc;
+    if (!rcnt || !rit || !rvote || !rpose || !rmask) return set_error(VDO_ERR_OOM, "scratch arena exhausted");
+    for (int k = 0; k < n_problems; ++k) if (hp[k].n_hyp && rcnt[k] > rec_cap) records = false;      // (not expected: a prefix maximum of 500 votes sets ~7 records)
+  }
+  // ... or, VDO_PNP_FULL_READBACK / more records than fit: votes, poses and inlier masks of all hypotheses, read where they land in the pinned block
+  const int32_t *cnt = nullptr, *okv = nullptr; const double* pose = nullptr; const uint32_t* mask = nullptr;
+  if (!records) {
+    cnt = S.down_view(dcnt, tot_hyp); okv = S.down_view(dok, tot_hyp);
+    pose = S.down_view(dpose, 12 * tot_hyp);
+    mask = S.down_view(dmask, tot_words);
+    S.queue_downloads();
+    if (host_work && !rcnt) host_work(host_arg);           // (the caller's own host work, under the two kernels and the copy back; it ran above if the records overflowed)
+    rc = S.finish("vdo_pnp_ransac_batch");
+    if (rc != VDO_OK) return rc;
+    if (!cnt || !okv || !pose || !mask) return set_error(VDO_ERR_OOM, "scratch arena exhausted");
+  }
+  static thread_local std::vector<const uint32_t*> win_row;      // the winner's inlier mask row of every problem (the flags below, the refit)
+  win_row.assign(n_problems, nullptr);
   const double tr2 = g_pnp_trace.on ? pnp_now_us() : 0.0;
   // replay of RANSACPointSetRegistrator::run over the precomputed votes
   for (int k = 0; k < n_problems; ++k) {
     const PnpDev& d = hp[k];
     if (!d.n_hyp) continue;
     int niters = d.n_hyp, max_good = 0, it = 0, bi = -1;
-    for (; it < niters; ++it) {
-      const int g = d.hyp_off + it;
-      if (!okv[g]) continue;
-      if (cnt[g] > std::max(max_good, 3)) {
-        max_good = cnt[g]; bi = it;
-        niters = ransac_update_iters(probs[k].confidence, (double)(d.n - cnt[g]) / d.n, 4, niters);
+    const double* Pz = nullptr;
+    if (records) {
+      // the same loop with its no-op iterations removed: only a record changes max_good, niters and bi, and a record at or behind the budget is never reached.
+      // The full loop leaves `it` at the first index >= niters: the budget, or the index behind the last record where the budget fell below it.
+      const size_t slot = (size_t)k * rec_cap;
+      int br = -1;
+      for (int q = 0; q < rcnt[k] && rit[slot + q] < niters; ++q) {
+        max_good = rvote[slot + q]; bi = rit[slot + q]; br = q;
+        niters = ransac_update_iters(probs[k].confidence, (double)(d.n - max_good) / d.n, 4, niters);
       }
+      it = std::max(niters, bi + 1);
+      if (br >= 0) { Pz = rpose + 12 * (slot + br); win_row[k] = rmask + (size_t)d.rec_mask_off + (size_t)br * d.mask_words; }
+    } else {
+      for (; it < niters; ++it) {
+        const int g = d.hyp_off + it;
+        if (!okv[g]) continue;
+        if (cnt[g] > std::max(max_good, 3)) {
+          max_good = cnt[g]; bi = it;
+          niters = ransac_update_iters(probs[k].confidence, (double)(d.n - cnt[g]) / d.n, 4, niters);
+        }
+      }
+      if (bi >= 0) { Pz = pose + 12 * ((size_t)d.hyp_off + bi); win_row[k] = mask + (size_t)d.mask_off + (size_t)bi * d.mask_words; }
     }
     vdo_pnp_result& r = results[k];
     r.iterations_run = it; r.best_iteration = bi; r.n_inliers = max_good;
     if (bi < 0) continue;
-    const double* Pz = pose + 12 * ((size_t)d.hyp_off + bi);
     for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) r.T[4 * i + j] = Pz[3 * i + j]; r.T[4 * i + 3] = Pz[9 + i]; }
     if (inlier_out && inlier_out[k]) {
-      const uint32_t* row = mask + (size_t)d.mask_off + (size_t)bi * d.mask_words;
+      const uint32_t* row = win_row[k];
       for (int i = 0; i < d.n; ++i) inlier_out[k][i] = (row[i >> 5] >> (i & 31)) & 1u;
     }
   }
@@ -608,11 +699,12 @@ static int pnp_ransac_impl(vdo_ctx* ctx, int n_problems, const vdo_pnp_problem* 
     }
   bool after_done = false;
   if (!todo.empty()) {
-    const PnpDev* hp_main = hp.data();               // (hp is thread_local: a pool thread naming it would see ITS OWN, empty, vector)
-    auto refit_one = [&, hp_main](int q) {
+    const PnpDev* hp_main = hp.data();               // (hp and win_row are thread_local: a pool thread naming them would see ITS OWN, empty, vectors)
+    const uint32_t* const* rows_main = win_row.data();
+    auto refit_one = [&, hp_main, rows_main](int q) {
       const int k = todo[q];
       const PnpDev& d = hp_main[k];
-      const uint32_t* row = mask + (size_t)d.mask_off + (size_t)results[k].best_iteration * d.mask_words;
+      const uint32_t* row = rows_main[k];
       thread_local std::vector<double> Xi, ui;
       thread_local epnp::Scratch scr;
       Xi.clear(); ui.clear();

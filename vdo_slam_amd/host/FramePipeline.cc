@@ -72,7 +72,7 @@ struct FramePipeline::StepState {
   vdo_keypoints kp;
   const int tag;                                        // frame id + 1: what orb_ready_ / objects_done_ / mask_final_ carry for this Step
   FrameCounts fc{};
-  bool orb_pending = false, tail_via_orb = false, k10_via_orb = false, fin_async = false, late_upload = false, up_async = false, static_async = false,
+  bool orb_pending = false, tail_via_orb = false, k10_via_orb = false, k9_via_orb = false, fin_async = false, late_upload = false, up_async = false, static_async = false,
        tail_async = false, tail_on_orb = false;
   bool orb_started = false;                             // the ORB thread has a job of this Step
   bool chain_open = false;                              // vdo_object_chain_begin without its end yet
@@ -105,7 +105,7 @@ FramePipeline::Switches FramePipeline::ReadSwitches() {
   Switches w;
   w.events = on("VDO_PIPE_EVENTS"); w.trace_slow = on("VDO_PIPE_TRACE_SLOW"); w.trace_obj = on("VDO_PIPE_TRACE_OBJ"); w.trace_batch = on("VDO_BATCH_TRACE");
   w.sync_upload = on("VDO_PIPE_SYNC_UPLOAD"); w.async_upload = !on("VDO_PIPE_NO_ASYNC_UPLOAD"); w.chain_split = !on("VDO_PIPE_NO_CHAIN_SPLIT");
-  w.fused_static = !on("VDO_PIPE_NO_FUSED_STATIC"); w.mm_overlap = !on("VDO_PIPE_NO_MM_OVERLAP"); w.cam_ahead = !on("VDO_PIPE_NO_CAM_AHEAD");
+  w.fused_static = !on("VDO_PIPE_NO_FUSED_STATIC"); w.k9_in_static = on("VDO_PIPE_K9_IN_STATIC"); w.mm_overlap = !on("VDO_PIPE_NO_MM_OVERLAP"); w.cam_ahead = !on("VDO_PIPE_NO_CAM_AHEAD");
   return w;
 }
 
@@ -295,6 +295,7 @@ int FramePipeline::Step(const uint8_t* d_gray, const float* d_depth_raw, const f
     } else if (StaticStage(s) != 0) return -1;
     if ((s.tail_on_orb || s.k10_via_orb) && worker_orb_->wait() != 0) return -1;
     if (s.k10_via_orb) s.fc.n_object_samples = s.n_tmp;
+    if (s.k9_via_orb) s.fc.n_static_new = s.n_new_s;
     mark(kEvStaticJoined);
     s.t.reset();
     // the object stage (results of the LMs, RenewFrameInfo of the objects, dynamic tracklets) ends in FinishObjects():
@@ -335,6 +336,7 @@ int FramePipeline::StartOrb(StepState& s) {
   s.orb_pending = worker_orb_ && !p_.use_sample_feature;
   s.tail_via_orb = s.orb_pending && pending_ && worker_;     // its job goes on with the tail of the last frame's object stage
   s.k10_via_orb = s.orb_pending && have_last_ && worker_;    // ... and ends with K10 of this frame, behind UpdateMask
+  s.k9_via_orb = s.k10_via_orb && !sw_.k9_in_static;         // ... next to K9: only a count comes of it here (FiltersOnOrb)
   if (s.orb_pending) {
     worker_orb_->run([this, sp = &s] { return OrbJob(*sp); });
     s.orb_started = true;
@@ -356,7 +358,7 @@ int FramePipeline::OrbJob(StepState& s) {
     if (rc2 != 0) rc = rc2;
   }
   // K10 reads the mask UpdateMask may repair: behind it
-  if (s.k10_via_orb && await_tag(mask_final_, s.tag) == s.tag && SampleObjectsOnOrb(s) != 0) rc = -1;
+  if (s.k10_via_orb && await_tag(mask_final_, s.tag) == s.tag && (s.k9_via_orb && rc == 0 ? FiltersOnOrb(s) : SampleObjectsOnOrb(s)) != 0) rc = -1;   // (no keypoints, no K9: the Step fails anyway)
   return rc;
 }
 
@@ -377,6 +379,22 @@ int FramePipeline::SampleObjectsOnOrb(StepState& s) {
   SizeSampleOutputs(tmp);
   VDO_TRY(vdo_frame_object_sample_on(ctx_orb_, s.cur, p_.th_depth_obj, 4, SampleCap(), tmp.x.data(), tmp.y.data(), tmp.cx.data(), tmp.cy.data(), tmp.fx.data(), tmp.fy.data(), tmp.d.data(),
                                      tmp.sem.data(), &s.n_tmp));
+  t.tick(kSecK10OnOrb);
+  return 0;
+}
+
+// K9 + K10 on the ORB thread's stream, one call and one synchronisation (vdo_frame_filters_on).  Once a last frame exists the renewal tops up from the ORB
+// keypoints themselves and K9's set feeds only fc.n_static_new, which nothing reads before the frame is committed: K9 and its round trip leave the static
+// stage - the helper thread's chain, which the camera stage of the next frame waits for - and join K10 here.  (VDO_PIPE_K9_IN_STATIC=1: K9 stays in the static stage.)
+// The keypoints are this thread's own (OrbJob); keep_ / flt_* are written here alone in such a Step, n_new_s is read after worker_orb_->wait().
+int FramePipeline::FiltersOnOrb(StepState& s) {
+  SecTimer t{ms_};
+  ObjSet& tmp = s.tmp;
+  SizeFilterOutputs(s.kp.n);
+  SizeSampleOutputs(tmp);
+  VDO_TRY(vdo_frame_filters_on(ctx_orb_, s.cur, s.kp.n, kx_.data(), ky_.data(), p_.th_depth_bg, 0, keep_.data(), flt_cx_.data(), flt_cy_.data(), flt_fx_.data(), flt_fy_.data(),
+                               flt_d_.data(), &s.n_new_s, p_.th_depth_obj, 4, SampleCap(), tmp.x.data(), tmp.y.data(), tmp.cx.data(), tmp.cy.data(), tmp.fx.data(), tmp.fy.data(),
+                               tmp.d.data(), tmp.sem.data(), &s.n_tmp));
   t.tick(kSecK10OnOrb);
   return 0;
 }
@@ -563,8 +581,10 @@ int FramePipeline::StaticStage(StepState& s) {
   VDO_TRY(vdo_propagate_static(s.cur, n_s, sta_.cx.data(), sta_.cy.data(), stat_depth_.data()));      // K11 (static), see IngestImages
   // K9 and the renewal as ONE round trip (vdo_static_stage): the renewal tops up from the ORB keypoints themselves, K9's outputs feed only fc.n_static_new
   // here - nothing is worth a synchronisation of its own.  Not where the renewal reads K9's set (UseSampleFeature) or where K10 shares K9's round trip.
-  const bool fused = !p_.use_sample_feature && s.k10_via_orb && sw_.fused_static;
-  if (fused) { if (JoinOrb(s) != 0) return -1; SizeFilterOutputs(s.kp.n); }
+  // Default where the ORB thread runs K10: K9 is its too (FiltersOnOrb), and the renewal below is all this stage sends.
+  const bool fused = !p_.use_sample_feature && s.k10_via_orb && !s.k9_via_orb && sw_.fused_static;
+  if (s.k9_via_orb) { if (JoinOrb(s) != 0) return -1; }
+  else if (fused) { if (JoinOrb(s) != 0) return -1; SizeFilterOutputs(s.kp.n); }
   else if (FrameFilters(s) != 0) return -1;
   t.tick(kSecK9K10); if (!fused) mark(kEvFilters);
   const int cs = p_.max_track_bg + 2;

@@ -141,12 +141,12 @@ class FramePipeline {
 
  private:
   // The environment switches of FramePipeline.cc, all read in one place, when the pipeline is built (ReadSwitches)
-  struct Switches { bool events, trace_slow, trace_obj, trace_batch, sync_upload, async_upload, chain_split, fused_static, mm_overlap, cam_ahead; };
+  struct Switches { bool events, trace_slow, trace_obj, trace_batch, sync_upload, async_upload, chain_split, fused_static, k9_in_static, mm_overlap, cam_ahead; };
   static Switches ReadSwitches();
   const Switches sw_ = ReadSwitches();
   // Step() is these stages, in this order, over one StepState (FramePipeline.cc): what a Step owns and shares with the helper and ORB threads
   struct StepState;
-  int StartOrb(StepState& s), OrbJob(StepState& s), SampleObjectsOnOrb(StepState& s), JoinOrb(StepState& s);      //  1. ORB on its own thread (OrbJob: extraction, then the
+  int StartOrb(StepState& s), OrbJob(StepState& s), SampleObjectsOnOrb(StepState& s), FiltersOnOrb(StepState& s), JoinOrb(StepState& s);      //  1. ORB on its own thread (OrbJob: extraction, then the
                                             //     last frame's tail, then K10) or its device stage queued.  (2. the last frame's object stage starts: in Step)
   int IngestImages(StepState& s);           //  3. images, K1
   int CameraAndLateUpload(StepState& s);    //  4. CameraStage unless it ran ahead; flow + mask of host inputs; keypoints where this thread makes them
