@@ -1131,6 +1131,60 @@ int vdo_dense_set_voxels_per_thread(vdo_dense* h, int voxels);
 /* Sets every word of the volume to 0 on the context's stream (host-synchronous) and leaves the origin alone: a retired handle is reused. */
 int vdo_dense_clear(vdo_dense* h);
 
+/* ---- Mesher: surface-nets triangles from a TSDF volume --------------------------------------------------------------------------------------
+ * New (the reference keeps no dense map): connected triangles from a vdo_dense - the static map or an object's volume -, in one-to-one relation with
+ * what Extract finds: one quad (two triangles) per sign-changing lattice edge, one vertex per cell at the mean of the cell's edge crossings.  No case
+ * table.  A vertex is fp32, one rounded operation per step in the order written, no contraction; everything else is integer.  The map is read only.
+ * Notation as above: the volume covers the global voxels o_a <= g_a < o_a + n_a, words t (int16) and w; a voxel is NEGATIVE iff t < 0 (t = 0 is
+ * positive).
+ *
+ * Cell.  Cell c has the 8 corner voxels c + {0,1}^3.  It is VALID iff all 8 corners are inside the VOLUME with w >= min_weight, ACTIVE iff it is
+ *   valid and its corners are not all of one sign.
+ * Vertex of an active cell.  Its 12 edges in this order: axis k = 0, 1, 2 with i = (k+1) % 3, j = (k+2) % 3; within an axis the lower corner offset
+ *   d_j = 0, 1 (outer), d_i = 0, 1 (inner).  Edge (a, b = a + e_k) crosses iff (ta < 0) != (tb < 0); then frac = (float)ta / (float)(ta - tb) (what
+ *   Extract computes) and the local point p is the corner offset as floats with (float)d_k + frac on axis k (d_k is 0).  s_c += p_c per coordinate
+ *   from 0.0f, in visiting order, crossing edges only; m their number (>= 3).  mean_c = s_c / (float)m; the coordinate
+ *   (((float)g_c + 0.5f) + mean_c) * voxel with g the cell's lower corner.
+ *   Per vertex also grad int32[3]: grad_k = the sum over the cell's four axis-k edges of t(b) - t(a), unnormalised, towards free space; weight
+ *   int32: the smallest of the 8 corner weights.
+ * Quad of a lattice edge (a, k) with a sign change: it uses the four cells a - d_i*e_i - d_j*e_j, which must ALL be valid (so their lower corners are
+ *   >= o, and both ends of the edge have w >= min_weight).  Vertex order (d_i, d_j) = (1,1), (0,1), (0,0), (1,0) when ta < 0, reversed when ta >= 0;
+ *   the triangles (v0, v1, v2) and (v0, v2, v3): counter-clockwise seen from free space.  The quad's CORNER BLOCK is the 3 x 3 x 2 corners its four
+ *   cells touch: a_i - 1 .. a_i + 1, a_j - 1 .. a_j + 1, a_k .. a_k + 1.
+ * Box and mode.  lo, hi: global voxels, clipped to the volume, as Extract takes them.  outside == 0: the quads whose corner block lies inside the
+ *   box and the vertices of the active cells whose 8 corners lie inside the box.  outside != 0: the quads of the volume whose corner block does NOT
+ *   lie inside the box, and the vertices of the active cells whose corners do not all lie inside the box shrunk by one voxel on every side - every
+ *   cell an outside quad uses is among them.  An empty box with outside set is the whole volume.  For any box the two modes partition the quads of
+ *   the whole volume exactly: a caller that meshes what STAYS with outside != 0 before a recentre and the whole volume at the end loses no quad at
+ *   a seam and doubles none.
+ * Order.  Vertices in the order z, y, x of the cell's lower corner (x fastest), numbered from 0 among the emitted ones; quads in the order z, y, x
+ *   of a, then k = 0, 1, 2; triangle indices int32 into that numbering.  A vertex need not be referenced by any triangle.
+ * No result depends on launch shape, schedule or the slot alignment of the cyclic volume. */
+typedef struct vdo_mesh vdo_mesh;
+typedef struct vdo_mesh_params {
+  int32_t n[3];                     /* 1..4096 each, nx * ny * nz <= 2^31: the mesher serves every map with no more voxels than that product */
+  int32_t stage_vertices;           /* >= 1: the vertices one window of a host output holds on the device (28 bytes each) */
+  int32_t stage_triangles;          /* >= 1: the triangles one window of a host output holds on the device (12 bytes each) */
+} vdo_mesh_params;
+/* ALL device memory is taken here (2 bits per cell, 16 bytes per 256 cells, the two staging windows); the other entries allocate nothing.  One mesher
+ * serves any vdo_dense of the same context whose nx * ny * nz fits: the static map and all object volumes can share one.  VDO_ERR_INVALID, the
+ * message naming the argument: a null pointer, a size or a window < 1.  VDO_ERR_UNSUPPORTED beyond the dense mapper's limits (a side above 2^12,
+ * more than 2^31 voxels).  VDO_ERR_OOM when the device has no room. */
+int vdo_mesh_create(vdo_ctx* ctx, const vdo_mesh_params* params, vdo_mesh** out);
+int vdo_mesh_destroy(vdo_mesh* h);
+/* The mesh of `map` for the box and mode, host-synchronous on the context's stream.  xyz [vertex_capacity][3], grad [vertex_capacity][3], weight
+ * [vertex_capacity], tri [triangle_capacity][3]: host pointers, or device pointers when out_is_device != 0 (a host output of any size goes through
+ * the staging windows); an output may be NULL when its capacity is 0.  counts (host): the total vertices and triangles, whatever the capacities;
+ * exactly the first min(capacity, count) of each are written, and indices always refer to the full numbering.  VDO_ERR_INVALID, the message naming
+ * the argument, and then NOTHING is written: a null handle, map, lo, hi or counts; min_weight < 1; a negative capacity; a null output with
+ * capacity > 0; a map of another context; a map with more voxels than the mesher.  VDO_ERR_UNSUPPORTED, nothing written, if a count would pass
+ * 2^31 - 1. */
+int vdo_mesh_extract(vdo_mesh* h, vdo_dense* map, const int32_t lo[3], const int32_t hi[3], int outside, int min_weight, int64_t vertex_capacity,
+                     float* xyz, int32_t* grad, int32_t* weight, int64_t triangle_capacity, int32_t* tri, int out_is_device, int64_t counts[2]);
+/* The last extract: ms[0] wall time of the call, ms[1] device time from the first kernel to the end of the last; 0, 0 after an extract that was
+ * refused with VDO_ERR_UNSUPPORTED or failed on the device (one refused with VDO_ERR_INVALID leaves the times of the call before it). */
+int vdo_mesh_last_timing(vdo_mesh* h, double ms[2]);
+
 /* ---- Object mapper: label statistics and a batched, label-selecting TSDF fusion -----------------------------------------------------------
  * New: the per-frame device stage of a volume per tracked object.  An object's volume is a plain vdo_dense in a frame of the object's own
  * (vdo_dense_extract, vdo_raycast_* and vdo_align_* work on it unchanged with T = Tcw * Two); a vdo_objects handle owns the label table, the

@@ -11,7 +11,7 @@
 //                        counts by wave ballot, summed over the workgroup in LDS, one 64-bit integer atomic per workgroup and counter on one of
 //                        1024 copies of the counters, which the host adds up.
 //   k_dn_clear           recenter: the slots of ONE leaving slab (a cyclic range on one axis, everything on the other two) are set to 0.
-//   k_dn_extract<FILL>   one thread per voxel of the box (x fastest), up to three points each: count per workgroup, k_dn_scan (one workgroup, 64-bit
+//   k_dn_extract<FILL>   one thread per voxel of the box (x fastest), up to three points each: count per workgroup, k_counts_scan of scan.hpp (one workgroup, 64-bit
 //                        carry), then the same kernel writes the points of a window [base, base + cap) of the visiting order.
 //
 // NO OUT-OF-RANGE ACCESS: the one gathered address comes from float compares against 0 and W - 1 / H - 1 made before any conversion to int (a NaN
@@ -151,22 +151,6 @@ __global__ __launch_bounds__(256) void k_dn_extract(DnArgs a, DnBox bx, long lon
     }
     ++pos;
   }
-}
-
-// exclusive scan of the workgroup counts (single workgroup) with a 64-bit carry; the total goes to total[0]
-__global__ __launch_bounds__(1024) void k_dn_scan(long long* __restrict__ blk, long long nblk, unsigned long long* __restrict__ total_out) {
-  __shared__ int lds[17];
-  long long carry = 0;
-  for (long long b0 = 0; b0 < nblk; b0 += 1024) {
-    const long long i = b0 + threadIdx.x;
-    const int v = i < nblk ? (int)blk[i] : 0;                                // <= 768 each, <= 786432 per round
-    int total;
-    const int ex = block_excl_scan(v, lds, &total);
-    if (i < nblk) blk[i] = carry + ex;
-    carry += total;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) total_out[0] = (unsigned long long)carry;
 }
 
 static void dn_free(vdo_dense* h) {
@@ -380,7 +364,7 @@ extern "C" int vdo_dense_extract(vdo_dense* h, const int32_t lo[3], const int32_
     const long long nblk = (nbox + 255) / 256;
     hipLaunchKernelGGL(k_dn_extract<false>, dim3((unsigned)nblk), dim3(256), 0, s, h->a, bx, nbox, min_weight, (const uint32_t*)h->d_vol, h->d_blk, 0LL, 0LL, (float*)nullptr,
                        (int32_t*)nullptr, (int32_t*)nullptr);
-    hipLaunchKernelGGL(k_dn_scan, dim3(1), dim3(1024), 0, s, h->d_blk, nblk, h->d_cnt + kDnTotal);
+    hipLaunchKernelGGL(k_counts_scan<1024>, dim3(1), dim3(1024), 0, s, h->d_blk, nblk, h->d_cnt + kDnTotal);
     hipMemcpyAsync(h->h_cnt + kDnTotal, h->d_cnt + kDnTotal, sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
     rc = sync_check(who, s);
     if (rc != VDO_OK) return rc;

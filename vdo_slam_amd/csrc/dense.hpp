@@ -17,7 +17,7 @@ constexpr int kDnMaxOrigin = 1 << 22;                                      // ev
 constexpr int kDnZ = 4;                                                    // z slots per workgroup of k_dn_integrate
 enum { kDnUpdated = 0, kDnMasked, kDnOccluded, kDnCounters = 4 };
 constexpr int kDnSlots = 1024;                                             // the counters of k_dn_integrate are kept kDnSlots times, 32 bytes apart; the host adds them up
-constexpr int kDnTotal = kDnSlots * kDnCounters;                           // then the point count of k_dn_scan
+constexpr int kDnTotal = kDnSlots * kDnCounters;                           // then the point count of k_counts_scan
 
 // what the kernels take by value
 struct DnArgs {

@@ -26,4 +26,22 @@ __device__ __forceinline__ int block_excl_scan(int v, int* lds, int* total) {
   return ex + lds[wv];
 }
 
+// exclusive scan of per-workgroup counts (single workgroup of THREADS, each count below 2^31 / THREADS) with a 64-bit carry; the total goes to
+// total_out[0].  The middle step of the ordered compactions of dense.hip and mesh.hip (a template, so that each of them launches its own copy)
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void k_counts_scan(long long* __restrict__ blk, long long nblk, unsigned long long* __restrict__ total_out) {
+  __shared__ int lds[17];
+  long long carry = 0;
+  for (long long b0 = 0; b0 < nblk; b0 += THREADS) {
+    const long long i = b0 + threadIdx.x;
+    const int v = i < nblk ? (int)blk[i] : 0;
+    int total;
+    const int ex = block_excl_scan(v, lds, &total);
+    if (i < nblk) blk[i] = carry + ex;
+    carry += total;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) total_out[0] = (unsigned long long)carry;
+}
+
 }  // namespace vdo

@@ -174,6 +174,9 @@ class FollowingMap:
         self.recenters = 0
         self.xyz, self.grad, self.wgt = [], [], []
 
+    def _before_move(self, origin, new_origin):
+        """Called once before every move of a started volume, the volume still at ``origin`` (mesh.FollowingMesh keeps its seam quads here)"""
+
     def _keep(self, lo, hi):
         xyz, grad, wgt, _ = self.mapper.extract(lo, hi, self.min_weight)
         self.xyz.append(xyz); self.grad.append(grad); self.wgt.append(wgt)
@@ -184,6 +187,7 @@ class FollowingMap:
         want = [c[a] - self.target[a] for a in range(3)]
         if not self.started or any(abs(c[a] - (o[a] + self.target[a])) > self.margin for a in range(3)):
             if self.started:
+                self._before_move(o, want)
                 for lo, hi in leaving_boxes(o, want, self.n):
                     self._keep(lo, hi)
                 self.recenters += 1

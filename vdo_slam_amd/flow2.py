@@ -29,6 +29,7 @@ class Flow2Batch:
         self._arr = arr
         self._h = C.c_void_p()
         K.check(K.lib().vdo_flow2_batch_create(ctx._h, len(self.problems), arr, C.byref(self._h)))
+        ctx._retain()                                 # vdo_flow2_batch_destroy waits on the context's stream: the context must outlive the batch (ba.Context)
 
     @classmethod
     def reserve(cls, ctx, capacities):
@@ -40,6 +41,7 @@ class Flow2Batch:
         self._h = C.c_void_p()
         caps = np.ascontiguousarray(capacities, dtype=np.int32)
         K.check(K.lib().vdo_flow2_batch_reserve(ctx._h, len(caps), K._ip(caps), C.byref(self._h)))
+        ctx._retain()
         return self
 
     def set(self, k, problem):
@@ -81,6 +83,7 @@ class Flow2Batch:
         if self._h:
             K.lib().vdo_flow2_batch_destroy(self._h)
             self._h = C.c_void_p()
+            self.ctx._release()
 
     def __del__(self):
         try:

@@ -2,7 +2,9 @@
 // fuses the frames (vdo_dense_integrate / vdo_dense_integrate_frame).
 #include "DenseMapper.h"
 
+#include <climits>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -16,9 +18,14 @@ static void die(const char* what) {   // (as MotionSegmenter.cc: a failure surfa
 
 DenseMapper::DenseMapper(vdo_ctx* ctx, int width, int height, const Settings& settings) : ctx_(ctx ? ctx : HostContext()), s_(settings), w_(width), h_px_(height) {
   if (vdo_dense_create(ctx_, width, height, &s_.params, &h_) != VDO_OK) die("vdo_dense_create");
+  if (s_.mesh) {
+    const vdo_mesh_params mp{{s_.params.n[0], s_.params.n[1], s_.params.n[2]}, 1 << 20, 1 << 21};
+    if (vdo_mesh_create(ctx_, &mp, &mesher_) != VDO_OK) { vdo_dense_destroy(h_); die("vdo_mesh_create"); }
+  }
 }
 
 DenseMapper::~DenseMapper() {
+  vdo_mesh_destroy(mesher_);
   vdo_align_destroy(align_);
   vdo_raycast_destroy(view_);                             // the view borrows the map
   vdo_dense_destroy(h_);
@@ -125,6 +132,31 @@ void DenseMapper::Append(const int32_t lo[3], const int32_t hi[3], Points& to) {
   if (vdo_dense_extract(h_, lo, hi, s_.minWeight, n, to.xyz.data() + 3 * at, to.grad.data() + 3 * at, to.weight.data() + at, 0, &n) != VDO_OK) die("vdo_dense_extract");
 }
 
+void DenseMapper::AppendMeshOf(vdo_mesh* mesher, vdo_dense* map, const int32_t lo[3], const int32_t hi[3], int outside, int min_weight, int64_t guess[2], Points& v,
+                               std::vector<int32_t>& tri) {
+  const size_t at = v.size(), tat = tri.size();
+  int64_t c[2] = {0, 0};
+  for (int pass = 0; pass < 2; ++pass) {
+    const size_t cv = (size_t)guess[0], ct = (size_t)guess[1];
+    v.xyz.resize(3 * (at + cv)); v.grad.resize(3 * (at + cv)); v.weight.resize(at + cv); tri.resize(tat + 3 * ct);
+    if (vdo_mesh_extract(mesher, map, lo, hi, outside, min_weight, guess[0], cv ? v.xyz.data() + 3 * at : nullptr, cv ? v.grad.data() + 3 * at : nullptr,
+                         cv ? v.weight.data() + at : nullptr, guess[1], ct ? tri.data() + tat : nullptr, 0, c) != VDO_OK)
+      die("vdo_mesh_extract");
+    const bool fits = c[0] <= guess[0] && c[1] <= guess[1];
+    if (c[0] > guess[0]) guess[0] = c[0] + c[0] / 4;                          // room for a surface that grows from call to call
+    if (c[1] > guess[1]) guess[1] = c[1] + c[1] / 4;
+    if (fits) break;
+  }
+  const size_t nv = (size_t)c[0], nt = (size_t)c[1];
+  if (at + nv > (size_t)INT32_MAX) throw std::runtime_error("VDO_SLAM::DenseMapper: the mesh passes 2^31 - 1 vertices");
+  v.xyz.resize(3 * (at + nv)); v.grad.resize(3 * (at + nv)); v.weight.resize(at + nv); tri.resize(tat + 3 * nt);
+  for (size_t i = tat; i < tri.size(); ++i) tri[i] += (int32_t)at;             // the piece's indices start at the running vertex count
+}
+
+void DenseMapper::AppendMesh(const int32_t lo[3], const int32_t hi[3], int outside, Points& v, std::vector<int32_t>& tri) {
+  AppendMeshOf(mesher_, h_, lo, hi, outside, s_.minWeight, meshGuess_, v, tri);
+}
+
 void DenseMapper::Follow(const float Tcw[16]) {
   const int32_t* n = s_.params.n;
   const double voxel = (double)s_.params.voxel;
@@ -142,6 +174,17 @@ void DenseMapper::Follow(const float Tcw[16]) {
     if (std::abs((long long)c[a] - ((long long)o[a] + target)) > s_.margin) move = true;
   }
   if (!move) return;
+  if (started_ && mesher_) {
+    // the staying box: what both the old and the new volume cover (empty after a move of n or more, and then everything is kept)
+    int32_t slo[3], shi[3];
+    bool none = false;
+    for (int a = 0; a < 3; ++a) {
+      slo[a] = o[a] > want[a] ? o[a] : want[a]; shi[a] = (o[a] < want[a] ? o[a] : want[a]) + n[a];
+      none = none || shi[a] <= slo[a];
+    }
+    if (none) for (int a = 0; a < 3; ++a) slo[a] = shi[a] = 0;
+    AppendMesh(slo, shi, 1, keptMeshV_, keptMeshT_);
+  }
   if (started_) {
     bool all = false;
     for (int a = 0; a < 3; ++a) all = all || std::abs((long long)want[a] - o[a]) >= n[a];
@@ -192,6 +235,49 @@ DenseMapper::Points DenseMapper::AllPoints() {
   return all;
 }
 
+void DenseMapper::Mesh(Points& v, std::vector<int32_t>& tri) {
+  if (!mesher_) throw std::runtime_error("VDO_SLAM::DenseMapper: Mesh without Dense.Mesh");
+  v = keptMeshV_; tri = keptMeshT_;
+  int32_t o[3];
+  origin(o);
+  const int32_t hi[3] = {o[0] + s_.params.n[0], o[1] + s_.params.n[1], o[2] + s_.params.n[2]};
+  AppendMesh(o, hi, 0, v, tri);
+}
+
+// one vertex record as SavePLY and SaveMeshPLY write it: x, y, z, the gradient normalised in double and narrowed (or 0), the weight
+static bool write_vertex(FILE* f, const DenseMapper::Points& p, size_t i) {
+  const double g[3] = {(double)p.grad[3 * i], (double)p.grad[3 * i + 1], (double)p.grad[3 * i + 2]};
+  const double len = std::sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
+  char rec[28];                                                            // (x86-64 is little-endian: the records are written as they lie)
+  float v[6] = {p.xyz[3 * i], p.xyz[3 * i + 1], p.xyz[3 * i + 2], 0.f, 0.f, 0.f};
+  if (len > 0) for (int k = 0; k < 3; ++k) v[3 + k] = (float)(g[k] / len);
+  std::memcpy(rec, v, 24); std::memcpy(rec + 24, &p.weight[i], 4);
+  return std::fwrite(rec, 1, 28, f) == 28;
+}
+
+bool DenseMapper::SaveMeshPLY(const std::string& path) {
+  Points v;
+  std::vector<int32_t> tri;
+  Mesh(v, tri);
+  return WriteMeshPLY(path, v, tri);
+}
+
+bool DenseMapper::WriteMeshPLY(const std::string& path, const Points& v, const std::vector<int32_t>& tri) {
+  FILE* f = std::fopen(path.c_str(), "wb");
+  if (!f) return false;
+  std::fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %zu\n", v.size());
+  std::fprintf(f, "property float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\nproperty float nz\nproperty int weight\n");
+  std::fprintf(f, "element face %zu\nproperty list uchar int vertex_indices\nend_header\n", tri.size() / 3);
+  bool ok = true;
+  for (size_t i = 0; i < v.size() && ok; ++i) ok = write_vertex(f, v, i);
+  for (size_t t = 0; t < tri.size() / 3 && ok; ++t) {
+    char rec[13] = {3};
+    std::memcpy(rec + 1, &tri[3 * t], 12);
+    ok = std::fwrite(rec, 1, 13, f) == 13;
+  }
+  return std::fclose(f) == 0 && ok;
+}
+
 bool DenseMapper::SavePLY(const std::string& path) {
   const Points all = AllPoints();
   FILE* f = std::fopen(path.c_str(), "wb");
@@ -199,15 +285,7 @@ bool DenseMapper::SavePLY(const std::string& path) {
   std::fprintf(f, "ply\nformat binary_little_endian 1.0\ncomment static scene, TSDF zero crossings\nelement vertex %zu\n", all.size());
   std::fprintf(f, "property float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\nproperty float nz\nproperty int weight\nend_header\n");
   bool ok = true;
-  for (size_t i = 0; i < all.size() && ok; ++i) {
-    const double g[3] = {(double)all.grad[3 * i], (double)all.grad[3 * i + 1], (double)all.grad[3 * i + 2]};
-    const double len = std::sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
-    char rec[28];                                                          // (x86-64 is little-endian: the records are written as they lie)
-    float v[6] = {all.xyz[3 * i], all.xyz[3 * i + 1], all.xyz[3 * i + 2], 0.f, 0.f, 0.f};
-    if (len > 0) for (int k = 0; k < 3; ++k) v[3 + k] = (float)(g[k] / len);
-    std::memcpy(rec, v, 24); std::memcpy(rec + 24, &all.weight[i], 4);
-    ok = std::fwrite(rec, 1, 28, f) == 28;
-  }
+  for (size_t i = 0; i < all.size() && ok; ++i) ok = write_vertex(f, all, i);
   return std::fclose(f) == 0 && ok;
 }
 

@@ -24,6 +24,8 @@ class DenseMapper {
     // gate on the distance between a point and its model point in metres (0: params.trunc), the sample stride, the smallest number of used samples
     // (0: a sixteenth of the sample grid, at least 6), and whether System fuses with the aligned pose.
     int alignIterations = 0; float alignMaxDist = 0.f; int alignSubsample = 1, alignMinPixels = 0; bool alignApply = false;
+    // Settings key Dense.Mesh (0): a mesher is made, and before the volume moves the quads that will not be wholly inside what stays are kept (Mesh below)
+    bool mesh = false;
   };
   // The settings error of the alignment fields ("" when in order): Iterations outside 0..64, MaxDist negative or not finite (0 stands for the default; the settings reader itself refuses a zero key), Subsample
   // outside 1..8, MinPixels below 6 (0 stands for the default).
@@ -62,6 +64,20 @@ class DenseMapper {
   // AllPoints() as a binary little-endian PLY: x, y, z, nx, ny, nz (float; the gradient normalised in double and narrowed, or 0) and weight (int).
   // False when the file cannot be written.
   bool SavePLY(const std::string& path);
+  // The surface as connected triangles (vdo_mesh_extract, surface nets): the pieces kept before the moves, then the whole current volume; tri holds
+  // 3 indices per triangle into v, every piece rebased by the number of vertices before it.  Pieces share no vertices; no quad is lost or doubled
+  // at a seam, whatever the direction of a move.  Throws std::runtime_error unless settings().mesh.
+  void Mesh(Points& v, std::vector<int32_t>& tri);
+  // Mesh() as a binary little-endian PLY: the vertices as SavePLY writes its points, then `face` as uchar int lists of 3.  False when the file
+  // cannot be written.
+  bool SaveMeshPLY(const std::string& path);
+  // The file SaveMeshPLY writes, for any mesh (ObjectMapper::SaveMeshes writes its models with it)
+  static bool WriteMeshPLY(const std::string& path, const Points& v, const std::vector<int32_t>& tri);
+  // The mesh of `map` for the box and mode (vdo_mesh_extract) appended to v and tri, the new indices rebased by the vertices already in v.  ONE
+  // extraction when the outputs fit `guess` (vertices, triangles: what the last call of this caller needed, kept up to date here), else a second
+  // one at the counts the first reported.
+  static void AppendMeshOf(vdo_mesh* mesher, vdo_dense* map, const int32_t lo[3], const int32_t hi[3], int outside, int min_weight, int64_t guess[2], Points& v,
+                           std::vector<int32_t>& tri);
   // What the map predicts a camera at Tcw (16 floats, world -> camera) would see (vdo_raycast_render): depth CV_32FC1 (metres, 0 without a surface),
   // normals CV_32FC3 (world frame, towards free space: the gradient normalised in double and narrowed, or 0, as SavePLY writes them) and, optionally,
   // weight CV_32SC1.  The view is made on first use at the mapper's image size and K with the settings' view fields; nothing of the map changes.
@@ -85,18 +101,23 @@ class DenseMapper {
  private:
   void Follow(const float Tcw[16]);
   void Append(const int32_t lo[3], const int32_t hi[3], Points& to);
+  void AppendMesh(const int32_t lo[3], const int32_t hi[3], int outside, Points& v, std::vector<int32_t>& tri);
   void EnsureView();
   void EnsureAligner(const float Tcw_init[16]);          // and renders the view at Tcw_init into its model
   vdo_ctx* ctx_ = nullptr;
   vdo_dense* h_ = nullptr;
   vdo_raycast* view_ = nullptr;                          // made by the first Render or Align; destroyed before the map
   vdo_align* align_ = nullptr;                           // made by the first Align; destroyed before the view
+  vdo_mesh* mesher_ = nullptr;                           // only with settings().mesh
   std::vector<float> grad_;                              // [h][w][3]: the gradient image of the last Render
   Settings s_;
   int w_, h_px_;
   bool started_ = false;
   int recenters_ = 0;
   Points kept_;
+  Points keptMeshV_;                                     // the mesh pieces kept before the moves
+  std::vector<int32_t> keptMeshT_;
+  int64_t meshGuess_[2] = {1 << 16, 1 << 17};            // the capacities the next mesh extraction tries first
 };
 
 }  // namespace VDO_SLAM

@@ -38,12 +38,24 @@ ObjectMapper::ObjectMapper(vdo_ctx* ctx, int width, int height, const Settings& 
   const vdo_objects_params op{{p.K[0], p.K[1], p.K[2], p.K[3]}, p.min_depth, p.max_depth, s_.maxLabels, s_.maxObjects};
   if (vdo_objects_create(ctx_, width, height, &op, &stage_) != VDO_OK) die("vdo_objects_create");
   stats_.assign((size_t)(s_.maxLabels + 1) * 8, 0);
+  if (s_.mesh) {
+    const vdo_mesh_params mp{{p.n[0], p.n[1], p.n[2]}, 1 << 18, 1 << 19};
+    if (vdo_mesh_create(ctx_, &mp, &mesher_) != VDO_OK) { vdo_objects_destroy(stage_); die("vdo_mesh_create"); }
+  }
 }
 
 ObjectMapper::~ObjectMapper() {
   for (Live& m : live_) pool_.push_back(m.slot);
   for (Slot& s : pool_) { vdo_raycast_destroy(s.view); vdo_dense_destroy(s.map); }      // the view borrows the map
+  vdo_mesh_destroy(mesher_);
   vdo_objects_destroy(stage_);
+}
+
+void ObjectMapper::ExtractMesh(vdo_dense* map, DenseMapper::Points& v, std::vector<int32_t>& tri) {
+  const vdo_dense_params& p = s_.params;
+  const int32_t lo[3] = {p.origin[0], p.origin[1], p.origin[2]}, hi[3] = {p.origin[0] + p.n[0], p.origin[1] + p.n[1], p.origin[2] + p.n[2]};
+  v = DenseMapper::Points(); tri.clear();
+  DenseMapper::AppendMeshOf(mesher_, map, lo, hi, 0, s_.minWeight, meshGuess_, v, tri);
 }
 
 void ObjectMapper::Extract(vdo_dense* map, DenseMapper::Points& to) {
@@ -70,6 +82,7 @@ void ObjectMapper::Flow(int f, const float Tcw[16], const std::vector<Motion>& m
       Model m;
       m.mod_label = gone.mod_label; m.live = false; m.frames = gone.frames; m.trajectory = std::move(gone.traj);
       Extract(gone.slot.map, m.points);
+      if (mesher_) ExtractMesh(gone.slot.map, m.mesh, m.tri);
       finished_.push_back(std::move(m));
     } else {
       ++dropped_;
@@ -170,9 +183,17 @@ std::vector<ObjectMapper::Model> ObjectMapper::Models() {
     Model m;
     m.mod_label = l.mod_label; m.live = true; m.frames = l.frames; m.trajectory = l.traj;
     Extract(l.slot.map, m.points);
+    if (mesher_) ExtractMesh(l.slot.map, m.mesh, m.tri);
     all.push_back(std::move(m));
   }
   return all;
+}
+
+bool ObjectMapper::SaveMeshes(const std::string& prefix) {
+  if (!mesher_) return false;
+  for (const Model& m : Models())
+    if (!DenseMapper::WriteMeshPLY(prefix + "_" + std::to_string(m.mod_label) + "_mesh.ply", m.mesh, m.tri)) return false;
+  return true;
 }
 
 bool ObjectMapper::SaveModels(const std::string& prefix) {

@@ -18,7 +18,8 @@ class ObjectMapper {
  public:
   // The settings file's Dense.Objects.* keys (System.h).  params: every object's volume (n, voxel, K, trunc, depth range, weight cap, stage_points;
   // the origin is set to -floor(n / 2) per axis here, so that a model's first centroid sits in the middle).
-  struct Settings { vdo_dense_params params{}; int maxObjects = 16, minPixels = 200, minFrames = 3, minWeight = 2, maxLabels = 1023; };
+  struct Settings { vdo_dense_params params{}; int maxObjects = 16, minPixels = 200, minFrames = 3, minWeight = 2, maxLabels = 1023; bool mesh = false; };
+  // (mesh: settings key Dense.Mesh - a mesher of the object volumes' size is made, and every model also carries its surface as triangles)
   // The settings error of the fields above ("" when in order): MaxObjects outside 1..64, MinPixels or MinFrames below 1, MinWeight outside 1..255
   static std::string Check(const Settings& s);
   // One tracked object of a frame: the unique tracking id, the label its pixels carry in the frame's mask, the world-frame motion from the last frame
@@ -26,7 +27,8 @@ class ObjectMapper {
   struct Motion { int mod_label = 0, sem_label = 0; double H[16] = {0}; };
   typedef std::array<double, 16> Pose;
   // A model as Models() reports it: points in the object frame (of a live model: what is in its volume now), the (frame, Two) rows
-  struct Model { int mod_label = 0; bool live = false; int frames = 0; DenseMapper::Points points; std::vector<std::pair<int, Pose> > trajectory; };
+  struct Model { int mod_label = 0; bool live = false; int frames = 0; DenseMapper::Points points; std::vector<std::pair<int, Pose> > trajectory;
+                 DenseMapper::Points mesh; std::vector<int32_t> tri; };      // with settings().mesh: the whole volume's mesh (vdo_mesh_extract), object frame
 
   // For width x height depth and mask images on `ctx` (HostContext() when null).  Throws std::runtime_error when the library refuses.
   ObjectMapper(vdo_ctx* ctx, int width, int height, const Settings& settings);
@@ -54,6 +56,9 @@ class ObjectMapper {
   // <prefix>_<mod_label>.ply per model in the object frame (the binary layout of DenseMapper::SavePLY) and <prefix>_poses.txt: frame, mod_label and
   // the 16 entries of Two per row, fixed with 9 digits (the row style of System::SaveResults).  False when a file cannot be written.
   bool SaveModels(const std::string& prefix);
+  // With settings().mesh: <prefix>_<mod_label>_mesh.ply per model in the object frame (the layout of DenseMapper::SaveMeshPLY) - a finished model as
+  // it was meshed when it was retired, a live one as its volume stands.  False without settings().mesh or when a file cannot be written.
+  bool SaveMeshes(const std::string& prefix);
   int dropped() const { return dropped_; }
   int skipped() const { return skipped_; }
   int live() const { return (int)live_.size(); }
@@ -66,9 +71,12 @@ class ObjectMapper {
   struct Live { int mod_label, sem_label, frames; Pose Two; std::vector<std::pair<int, Pose> > traj; Slot slot; };
   template <class Stats, class Integrate> void Flow(int f, const float Tcw[16], const std::vector<Motion>& motions, Stats stats, Integrate integrate);
   void Extract(vdo_dense* map, DenseMapper::Points& to);
+  void ExtractMesh(vdo_dense* map, DenseMapper::Points& v, std::vector<int32_t>& tri);
   int64_t Count(int sem) const { return sem >= 1 && sem <= s_.maxLabels ? stats_[(size_t)sem * 8] : 0; }
   vdo_ctx* ctx_ = nullptr;
   vdo_objects* stage_ = nullptr;
+  vdo_mesh* mesher_ = nullptr;                           // only with settings().mesh
+  int64_t meshGuess_[2] = {1 << 14, 1 << 15};
   Settings s_;
   int w_, h_px_;
   std::vector<int64_t> stats_;

@@ -271,6 +271,11 @@ std::string read_dense_settings(const std::string& path, const TrackingSettings&
   s.alignIterations = (int)al[0]; s.alignSubsample = (int)al[1]; s.alignMinPixels = (int)al[2]; s.alignApply = al[3] == 1; s.alignMaxDist = (float)max_dist;
   const std::string align_err = DenseMapper::CheckAlign(s);
   if (!align_err.empty()) return align_err;
+  // Dense.Mesh (0): 1 keeps the surface as triangles too (DenseMapper::Mesh, System::SaveDenseMesh)
+  const double mesh = get(raw, "Dense.Mesh", 0);
+  if (lists.count("Dense.Mesh") || (mesh != 0 && mesh != 1)) return "settings: Dense.Mesh must be 0 or 1";
+  s.mesh = mesh == 1;
+  ds.os.mesh = s.mesh;
   return read_dense_objects_settings(t, raw, lists, ds);
 }
 }  // namespace
@@ -905,10 +910,24 @@ bool System::SaveDenseMap(const std::string& path) {
   return true;
 }
 
+bool System::SaveDenseMesh(const std::string& path) {
+  DenseMapper* d = mpTracker->dense();
+  if (!d || !d->settings().mesh) { std::cerr << "VDO_SLAM::System::SaveDenseMesh: no mesh (the settings file has no Dense.VoxelSize with Dense.Mesh: 1)" << std::endl; return false; }
+  if (!d->SaveMeshPLY(path)) { std::cerr << "VDO_SLAM::System::SaveDenseMesh: cannot write " << path << std::endl; return false; }
+  return true;
+}
+
 bool System::SaveObjectMaps(const std::string& prefix) {
   ObjectMapper* o = mpTracker->objects();
   if (!o) { std::cerr << "VDO_SLAM::System::SaveObjectMaps: no object mapper (the settings file has no Dense.Objects.VoxelSize)" << std::endl; return false; }
   if (!o->SaveModels(prefix)) { std::cerr << "VDO_SLAM::System::SaveObjectMaps: cannot write " << prefix << "_*" << std::endl; return false; }
+  return true;
+}
+
+bool System::SaveObjectMeshes(const std::string& prefix) {
+  ObjectMapper* o = mpTracker->objects();
+  if (!o || !o->settings().mesh) { std::cerr << "VDO_SLAM::System::SaveObjectMeshes: no object meshes (the settings file has no Dense.Objects.VoxelSize with Dense.Mesh: 1)" << std::endl; return false; }
+  if (!o->SaveMeshes(prefix)) { std::cerr << "VDO_SLAM::System::SaveObjectMeshes: cannot write " << prefix << "_*_mesh.ply" << std::endl; return false; }
   return true;
 }
 
@@ -1179,6 +1198,18 @@ int host_settings_check_dense(const char* path, char* msg, int cap, double* out1
   }
   return err.empty() ? 0 : 1;
 }
+// the Dense.Mesh key as Tracking::Tracking reads it, without a GPU: 0 in order, 1 a settings error (text in msg), -2 no file.  out2 (may be null):
+// present (0 / 1: Dense.VoxelSize is in the file; the key is read only then), Mesh
+int host_settings_check_dense_mesh(const char* path, char* msg, int cap, double* out2) {
+  VDO_SLAM::TrackingSettings t{};
+  std::map<std::string, double> raw;
+  if (!VDO_SLAM::read_tracking_settings(path, t, &raw)) return -2;
+  VDO_SLAM::DenseSettings ds;
+  const std::string err = VDO_SLAM::read_dense_settings(path, t, raw, ds);
+  if (msg && cap > 0) std::snprintf(msg, (size_t)cap, "%s", err.c_str());
+  if (out2 && err.empty()) { out2[0] = ds.present ? 1 : 0; if (ds.present) out2[1] = ds.s.mesh ? 1 : 0; }
+  return err.empty() ? 0 : 1;
+}
 // the Dense.View.* keys as Tracking::Tracking reads them, without a GPU: 0 in order, 1 a settings error (text in msg), -2 no file.  out5 (may be null):
 // present (0 / 1: Dense.VoxelSize is in the file; the rest only then), Near, Step, MinWeight, the samples per ray
 int host_settings_check_dense_view(const char* path, char* msg, int cap, double* out5) {
@@ -1250,6 +1281,11 @@ int host_system_object_info(VDO_SLAM::System* s, int cap, long long* rows, long 
     for (int i = 0; i < n && i < cap; ++i) std::memcpy(rows + 4 * (size_t)i, r[i].data(), 4 * sizeof(long long));
     return n;
   } catch (const std::exception& e) { std::fprintf(stderr, "host_system_object_info: %s\n", e.what()); return -2; }
+}
+// System::SaveObjectMeshes: 0, -1 without an object mapper, without Dense.Mesh or when a file cannot be written
+int host_system_save_object_meshes(VDO_SLAM::System* s, const char* prefix) {
+  try { return s->SaveObjectMeshes(prefix) ? 0 : -1; }
+  catch (const std::exception& e) { std::fprintf(stderr, "host_system_save_object_meshes: %s\n", e.what()); return -1; }
 }
 // System::SaveObjectMaps: 0, -1 without an object mapper or when a file cannot be written
 int host_system_save_object_maps(VDO_SLAM::System* s, const char* prefix) {
@@ -1337,6 +1373,11 @@ int host_system_dense_info(VDO_SLAM::System* s, long long* info8) {
     for (int k = 0; k < 3; ++k) info8[5 + k] = s->tracker()->dense_counts()[k];
   } catch (const std::exception& e) { std::fprintf(stderr, "host_system_dense_info: %s\n", e.what()); return -1; }
   return 0;
+}
+// System::SaveDenseMesh: 0, -1 without a mapper, without Dense.Mesh or when the file cannot be written
+int host_system_save_dense_mesh(VDO_SLAM::System* s, const char* path) {
+  try { return s->SaveDenseMesh(path) ? 0 : -1; }
+  catch (const std::exception& e) { std::fprintf(stderr, "host_system_save_dense_mesh: %s\n", e.what()); return -1; }
 }
 // System::SaveDenseMap: 0, -1 without a mapper or when the file cannot be written
 int host_system_save_dense_map(VDO_SLAM::System* s, const char* path) {

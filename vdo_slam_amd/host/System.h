@@ -211,6 +211,13 @@ class System {
   // with Dense.Align.Apply, with those poses refined against the map itself, which the tracker never sees - and is not re-fused after a bundle adjustment; an edge between a leaving and a staying voxel can be lost when the volume moves towards a negative axis;
   // objects are left out of this map (their own models: SaveObjectMaps below); with semantic masks on the RGBD path parked instances are left out too.
   bool SaveDenseMap(const std::string& path);
+  // Settings key Dense.Mesh (0 or 1, default 0; read only with Dense.VoxelSize; another value is a settings error with every sensor).  With 1 the
+  // static map is also kept as connected triangles (vdo_mesh_extract, surface nets): before the volume moves, the quads that will not lie wholly
+  // inside what stays are kept on the host, so no quad is lost or doubled at a seam - the loss on moves towards a negative axis named above has no
+  // counterpart in the mesh.  SaveDenseMesh writes the kept pieces and the whole current volume as a binary little-endian PLY: the vertices as
+  // SaveDenseMap writes its points, then `face` as uchar int lists of 3; pieces share no vertices.  False without a mapper, without Dense.Mesh or when
+  // the file cannot be written.  Without the key no mesher is made and no frame does anything it did not do before.
+  bool SaveDenseMesh(const std::string& path);
   // What the dense map predicts a camera at Tcw (4 x 4 CV_32F, world -> camera) would see (DenseMapper::Render, vdo_raycast_render): depth CV_32FC1 in
   // metres, 0 where no surface is met, and normals CV_32FC3 in the world frame, towards free space, 0 where the surface has an unseen neighbour - at the
   // camera's image size and K.  Settings keys, all optional and read only with Dense.VoxelSize: Dense.View.Near (max(Dense.MinDepth, Dense.VoxelSize)),
@@ -243,6 +250,10 @@ class System {
   // SaveObjectMaps: <prefix>_<mod_label>.ply per finished and live model in the OBJECT frame and <prefix>_poses.txt (frame, mod_label, the 16
   // entries of Two); false without an object mapper or when a file cannot be written.
   bool SaveObjectMaps(const std::string& prefix);
+  // With Dense.Mesh: 1 the object mapper also meshes every model (whole volume; a model that is retired is meshed then, next to its points).
+  // SaveObjectMeshes writes <prefix>_<mod_label>_mesh.ply per finished and live model in the OBJECT frame, in the layout of SaveDenseMesh.  False
+  // without an object mapper, without Dense.Mesh or when a file cannot be written.
+  bool SaveObjectMeshes(const std::string& prefix);
   // What the model of the live object mod_label predicts a camera at Tcw (4 x 4 CV_32F, world -> camera) would see: depth CV_32FC1, normals CV_32FC3 in
   // the object frame.  False without an object mapper or a live model of that id.
   bool RenderObjectView(int mod_label, const cv::Mat& Tcw, cv::Mat& depth, cv::Mat& normals);

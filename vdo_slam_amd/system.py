@@ -282,6 +282,13 @@ class System:
         L.host_system_save_dense_map.argtypes = [C.c_void_p, C.c_char_p]
         return L.host_system_save_dense_map(self._h, str(path).encode()) == 0
 
+    def save_dense_mesh(self, path):
+        """System::SaveDenseMesh: the mesh pieces kept so far and the mesh of the whole volume as a binary little-endian PLY (``mesh.read_ply`` reads
+        it).  False without a mapper, without ``Dense.Mesh: 1`` or when the file cannot be written."""
+        L = self._L
+        L.host_system_save_dense_mesh.argtypes = [C.c_void_p, C.c_char_p]
+        return L.host_system_save_dense_mesh(self._h, str(path).encode()) == 0
+
     def render_dense_view(self, T):
         """System::RenderDenseView: what the dense map predicts a camera at T (4 x 4, world -> camera) would see, at the camera's image size:
         (depth [h, w] f32 in metres, normals [h, w, 3] f32), or None when the system has no mapper."""
@@ -363,6 +370,13 @@ class System:
         if n < 0:
             raise K.VdoError("System.object_info failed")
         return dict(models=[(int(r[0]), bool(r[1]), int(r[2]), int(r[3])) for r in rows[:min(n, cap)]], dropped=int(counts[0]), skipped=int(counts[1]))
+
+    def save_object_meshes(self, prefix):
+        """System::SaveObjectMeshes: <prefix>_<mod_label>_mesh.ply per model in the object frame (``mesh.read_ply`` reads them).  False without an
+        object mapper, without ``Dense.Mesh: 1`` or when a file cannot be written."""
+        L = self._L
+        L.host_system_save_object_meshes.argtypes = [C.c_void_p, C.c_char_p]
+        return L.host_system_save_object_meshes(self._h, str(prefix).encode()) == 0
 
     def save_object_maps(self, prefix):
         """System::SaveObjectMaps: <prefix>_<mod_label>.ply per model in the object frame and <prefix>_poses.txt.  False without an object mapper or
