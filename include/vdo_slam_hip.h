@@ -373,8 +373,19 @@ int vdo_orb_max_keypoints(const vdo_orb* orb, int* n);
 int vdo_orb_last_keypoints(const vdo_orb* orb, int* n);
 /* gray: 8-bit single channel, row stride `stride` bytes; host pointer unless src_is_device. */
 int vdo_orb_extract(vdo_orb* orb, const uint8_t* gray, int stride, int src_is_device, vdo_keypoints* out);
-/* The same in two halves: _begin queues the device stage (K3, K4, K6, K7 + the copy of the candidates) on the extractor's stream
- * and returns at once, _end waits for it and runs the quadtrees (K5) - a caller overlaps other work with the device stage. */
+/* The same in two halves: _begin queues the device stage (K3, K4, K5, K6, K7; the candidates and the ids of the selected ones are
+ * written to mapped host memory) on the extractor's stream and returns at once, _end waits for it and builds the keypoints - a
+ * caller overlaps other work with the device stage.
+ * K5, DistributeOctTree, runs on the device (k_quadtree: one workgroup per level, the host's list bit for bit and in its order)
+ * within these limits, all fixed before the launch: a level's quota N + 3 <= 1024 nodes (n_features up to about 4700 with the
+ * default pyramid) and no more initial column strips than that; a level's keypoint region below 65536 px on both sides; at most
+ * min(32768, cells of the level x candidates per cell) FAST candidates on the level; 48 rounds.  A level over the first two
+ * limits takes the host tree from the start; on any other limit its workgroup writes a status word and stops, and _end runs the
+ * host tree for that level - the results are the same either way.  With the device tree the angles of the returned keypoints are
+ * computed with their rows; the angle row of ALL candidates (vdo_orb_get_candidates, the descriptors) is computed when first asked for.
+ * Environment, read in vdo_orb_create: VDO_ORB_HOST_TREE=1
+ * keeps every level on the host tree (helper threads: VDO_ORB_THREADS, default 3; they are not started otherwise), as does
+ * VDO_ORB_FUSED_ANGLE=1; VDO_ORB_QT_NODE_CAP=n lowers the node limit (tests). */
 int vdo_orb_extract_begin(vdo_orb* orb, const uint8_t* gray, int stride, int src_is_device);
 int vdo_orb_extract_end(vdo_orb* orb, vdo_keypoints* out);
 /* K8 - rotated BRIEF, the `_descriptors` output of ORBextractor::operator() (computeOrbDescriptor src/ORBextractor.cc:97-136,
@@ -388,8 +399,13 @@ int vdo_orb_level_info(vdo_orb* orb, int level, int* w, int* h, int* n_features,
 int vdo_orb_get_pyramid(vdo_orb* orb, int level, uint8_t* out_bordered /* (w+38)*(h+38) */);
 int vdo_orb_get_blurred(vdo_orb* orb, int level, uint8_t* out /* w*h */);
 int vdo_orb_get_candidates(vdo_orb* orb, int level, float* x, float* y, float* response, float* angle, int cap, int* n);
-/* Wall time of the last vdo_orb_extract: ms[0] device stage launch .. candidates on the host, ms[1] host quadtree. */
+/* Wall time of the last vdo_orb_extract: ms[0] device stage launch .. candidates on the host (with the device tree: and the
+ * keypoint ids), ms[1] the rest of _end (host quadtrees, wait for the angles, keypoint rows). */
 int vdo_orb_last_timing(vdo_orb* orb, double ms[2]);
+/* Where K5 of `level` ran in the last extraction: *on_device 1 = k_quadtree, 0 = the host tree; *status 0, or why the level
+ * took the host tree: 1 over the node limit at create (or VDO_ORB_HOST_TREE / VDO_ORB_FUSED_ANGLE), 2 more candidates than
+ * the scratch holds, 3 more nodes than N + 3, 4 round limit, 5 a candidate outside the initial strips. */
+int vdo_orb_tree_info(vdo_orb* orb, int level, int* on_device, int* status);
 /* Kernel launches that build the pyramid of one image: 2 (levels 0-4 cascaded in LDS from the image, the rest from level 4;
  * 1 with <= 5 levels) - possible with <= 8 levels whose cascaded source windows fit the LDS buffers - or n_levels (level by
  * level; also forced by the environment variable VDO_ORB_PYRAMID_LAUNCHES). */

@@ -1,7 +1,8 @@
 // ORB front-end on gfx950 — replaces ORBextractor::operator() (reference src/ORBextractor.cc:1035-1110):
 //   K3 ComputePyramid          :1112-1137  cv::resize(INTER_LINEAR, 8u) from the previous level + REFLECT_101 border (19 px)
 //   K4 ComputeKeyPointsOctTree :754-818    cv::FAST(cell, thr=iniTh, NMS) with fallback minTh, per 30-px cell (+6 px overlap)
-//   K5 DistributeOctTree       :470-752    quadtree, best response per node      (host C++, sequential by nature)
+//   K5 DistributeOctTree       :470-752    quadtree, best response per node      (k_quadtree: one workgroup per level, rounds built from
+//                                          scans; QuadTree, host C++, is the fallback over its limits and under VDO_ORB_HOST_TREE=1)
 //   K6 IC_Angle                :66-93      31x31 circular patch moments + cv::fastAtan2
 //   K7 GaussianBlur 7x7 s=2    :1083-1084  executed by the reference although its consumer (BRIEF) is commented out
 //   K8 computeOrbDescriptor    :97-136     256 rotated pair tests on the blurred level (call site commented out :1083-1091;
@@ -409,6 +410,23 @@ __global__ __launch_bounds__(256) void k_compact(const CellDesc* __restrict__ ce
 // One wave per candidate as in k_compact_angle; a wave takes kAngChunk consecutive candidates and stores their angles with one
 // instruction (one contiguous write to the mapped row instead of kAngChunk single floats).  total = level_cnt[16] (k_compact).
 constexpr int kAngChunk = 8;
+// IC_Angle of the candidate at (x, y) of level L by one wave: 31 rows over the lanes, integer moments, fast_atan2_dev (every lane returns it)
+__device__ __forceinline__ float wave_ic_angle(const uint8_t* __restrict__ pyr, const LevelDesc& L, const UMax& um, int x, int y, int lane) {
+  const uint8_t* img = pyr + L.off_inner;
+  const int cx = x + (kEdge - 3), cy = y + (kEdge - 3);
+  int m10 = 0, m01 = 0;
+  if (lane < 31) {
+    const int v = lane - kHalfPatch;
+    const int d = um.v[v < 0 ? -v : v];
+    const uint8_t* row = img + (size_t)(cy + v) * L.bw + cx;
+    int rs = 0;
+    for (int u = -d; u <= d; ++u) { const int p = row[u]; m10 += u * p; rs += p; }
+    m01 = v * rs;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) { m10 += __shfl_down(m10, off, 64); m01 += __shfl_down(m01, off, 64); }
+  return fast_atan2_dev((float)__shfl(m01, 0, 64), (float)__shfl(m10, 0, 64));
+}
 __global__ __launch_bounds__(256) void k_angle(const uint8_t* __restrict__ pyr, const LevelDesc* __restrict__ levels, const int* __restrict__ level_cnt, UMax um,
                                                const float* __restrict__ ox, const float* __restrict__ oy, const int* __restrict__ olevel,
                                                float* __restrict__ oang, float* __restrict__ hang) {
@@ -420,20 +438,7 @@ __global__ __launch_bounds__(256) void k_angle(const uint8_t* __restrict__ pyr, 
     for (int o = c0; o < ce; ++o) {
       const int x = (int)ox[o], y = (int)oy[o];                 // integer-valued floats (k_compact)
       const LevelDesc L = levels[olevel[o]];
-      const uint8_t* img = pyr + L.off_inner;
-      const int cx = x + (kEdge - 3), cy = y + (kEdge - 3);
-      int m10 = 0, m01 = 0;
-      if (lane < 31) {
-        const int v = lane - kHalfPatch;
-        const int d = um.v[v < 0 ? -v : v];
-        const uint8_t* row = img + (size_t)(cy + v) * L.bw + cx;
-        int rs = 0;
-        for (int u = -d; u <= d; ++u) { const int p = row[u]; m10 += u * p; rs += p; }
-        m01 = v * rs;
-      }
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) { m10 += __shfl_down(m10, off, 64); m01 += __shfl_down(m01, off, 64); }
-      const float ang = fast_atan2_dev((float)__shfl(m01, 0, 64), (float)__shfl(m10, 0, 64));
+      const float ang = wave_ic_angle(pyr, L, um, x, y, lane);
       if (lane == o - c0) mine = ang;
     }
     if (c0 + lane < ce) { oang[c0 + lane] = mine; hang[c0 + lane] = mine; }
@@ -695,6 +700,357 @@ class QuadTree {
   }
 };
 
+// ------------------------------------------------------------------------- device: quadtree (K5)
+// k_quadtree: QuadTree::run above, one workgroup of kQtThreads per pyramid level, behind k_compact on the extractor's stream.  The
+// node list is an array in list order (LDS, two buffers); the keys are a permutation of the level's candidates (two buffers; LDS up to
+// kQtLdsKeys candidates, the level's global scratch above) in which every node owns the run [b, e), plus the list index of the owning
+// node per key.  One round =
+//   A  keys: quadrant of every key of an expandable node, exclusive prefix of the four quadrant counts (4 x 16 bit in one word)
+//      over the key positions -> P[k]; a node's child sizes are P[e] - P[b], a key's place in its child P[k] - P[b]: the stable
+//      4-way partition of every node at once;
+//   B  nodes: processing rank.  Full round: the expandable nodes in list order.  Final phase: by (size, creation id) descending,
+//      rank by counting (what the host's sort + walk from the back visits);
+//   C  prefix over the ranks of "non-empty children" -> how many are processed (final phase: up to the first prefix whose count
+//      reaches N), where each parent's children land (children of the LAST processed parent first, each n4..n1) and their creation ids;
+//   D  nodes: children and the untouched nodes (behind all children, old order) into the other node buffer;
+//   E  keys: scatter into the other key buffer.
+// Only integer arithmetic (the candidates' coordinates are integer-valued floats, so the host's float comparisons are integer comparisons
+// here; the strip of a key is the host's float division): the host's list, bit for bit.  Bounds fixed before the launch: kQtMaxRounds rounds,
+// N + 3 nodes (<= kQtMaxNodes), the level's share of the key scratch (<= kQtMaxCand keys: 16-bit quadrant counts).  On any of them the
+// workgroup writes a status word and stops; vdo_orb_extract_end then runs QuadTree::run for that level.  No workgroup waits for another.
+constexpr int kQtThreads = 1024, kQtMaxNodes = 1024, kQtLdsKeys = 4096, kQtMaxCand = 32768, kQtMaxRounds = 48;
+enum { kQtOk = 0, kQtHostLevel = 1, kQtCandOverflow = 2, kQtNodeOverflow = 3, kQtRoundCap = 4, kQtBadStrip = 5 };
+struct QtDesc {
+  int on_device;        // 0: the level takes the host tree (capacity, checked in vdo_orb_create)
+  int N, nIni, H;       // nfeat of the level, initial column strips, maxY - minY
+  int node_cap;         // N + 3
+  int cand_cap;         // keys the level's scratch holds
+  int koff;             // scratch offset of the level in keys
+  int out_off;          // first id of the level in the id rows (node_cap ids per level)
+  float hX;             // strip width, (float)(maxX - minX) / nIni as on the host
+  float scale;          // mvScaleFactor of the level
+  int pad[2];
+};
+typedef unsigned long long qt_u64;
+
+__device__ __forceinline__ int qt_field(qt_u64 v, int q) { return (int)((v >> (16 * q)) & 0xffffu); }
+__device__ __forceinline__ int qt_nchild(qt_u64 v) { return (qt_field(v, 0) != 0) + (qt_field(v, 1) != 0) + (qt_field(v, 2) != 0) + (qt_field(v, 3) != 0); }
+__device__ __forceinline__ int qt_nexp(qt_u64 v) { return (qt_field(v, 0) > 1) + (qt_field(v, 1) > 1) + (qt_field(v, 2) > 1) + (qt_field(v, 3) > 1); }
+
+// exclusive prefix of v over the workgroup's threads; total: the sum over all of them.  s_w: 16 words.
+__device__ __forceinline__ qt_u64 qt_block_scan(qt_u64 v, qt_u64* s_w, qt_u64& total) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  qt_u64 inc = v;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) { const qt_u64 u = __shfl_up(inc, off, 64); if (lane >= off) inc += u; }
+  __syncthreads();
+  if (lane == 63) s_w[wv] = inc;
+  __syncthreads();
+  qt_u64 base = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < kQtThreads / 64; ++w) { const qt_u64 p = s_w[w]; if (w < wv) base += p; tot += p; }
+  total = tot;
+  return base + inc - v;
+}
+
+__global__ __launch_bounds__(kQtThreads) void k_quadtree(const QtDesc* __restrict__ qd, const int* __restrict__ level_cnt,
+                                                         const float* __restrict__ ox, const float* __restrict__ oy, const float* __restrict__ oresp,
+                                                         uint32_t* wi, qt_u64* wp, int* __restrict__ dsel, int* __restrict__ dhdr,
+                                                         int* __restrict__ hsel, int* __restrict__ hhdr) {
+  __shared__ uint32_t s_nx[2][kQtMaxNodes], s_ny[2][kQtMaxNodes];     // x0 | x1 << 16, y0 | y1 << 16  (UL.x, UR.x, UL.y, BR.y)
+  __shared__ int s_b[2][kQtMaxNodes], s_e[2][kQtMaxNodes], s_cid[2][kQtMaxNodes];
+  __shared__ qt_u64 s_qc[kQtMaxNodes];                                // child sizes of an expandable node
+  __shared__ qt_u64 s_sc[kQtMaxNodes];                                // by rank: inclusive prefix of non-empty children | expandable children << 32
+  __shared__ int s_rank[kQtMaxNodes], s_order[kQtMaxNodes], s_nb[kQtMaxNodes];
+  __shared__ qt_u64 s_w[kQtThreads / 64];
+  __shared__ int s_m;
+  // the keys of a level with at most kQtLdsKeys candidates (otherwise the same arrays in the level's global scratch)
+  __shared__ uint32_t s_xy[kQtLdsKeys];
+  __shared__ uint16_t s_idx[2][kQtLdsKeys], s_kn[2][kQtLdsKeys];
+  __shared__ qt_u64 s_P[kQtLdsKeys + 1];
+  __shared__ uint8_t s_resp[kQtLdsKeys];                              // FAST scores are integers below 256
+  const int l = blockIdx.x, t = threadIdx.x;
+  const QtDesc D = qd[l];
+  auto finish = [&](int status, int count) { if (t == 0) { dhdr[l] = hhdr[l] = count; dhdr[16 + l] = hhdr[16 + l] = status; } };
+  if (!D.on_device) { finish(kQtHostLevel, 0); return; }
+  int pos = 0;
+  for (int q = 0; q < l; ++q) pos += level_cnt[q];
+  const int n = level_cnt[l];
+  if (n > D.cand_cap) { finish(kQtCandOverflow, 0); return; }
+  if (n <= 0) { finish(kQtOk, 0); return; }
+  const float *x = ox + pos, *y = oy + pos, *resp = oresp + pos;
+  const int KC = (n + kQtThreads - 1) / kQtThreads;
+  const int k0 = min(t * KC, n), k1 = min(k0 + KC, n);                // this thread's key positions
+  const int N = D.N, cap = D.node_cap;
+
+  // xy: x | y << 16 of candidate id (the candidates are integer-valued floats, k_compact: x < (float)m is the integer comparison);
+  // idA / idB: candidate ids in list order, two buffers; knA / knB: list index of the node that owns the key; P: n + 1 prefix words
+  const bool lds_keys = n <= kQtLdsKeys;
+  auto run = [&](uint32_t* xy, uint16_t* idA, uint16_t* idB, uint16_t* knA, uint16_t* knB, qt_u64* P) __attribute__((always_inline)) {
+    // initial nodes: stable bucket sort by column strip, four strips per pass; buffer 1 holds all nIni strips, buffer 0 the non-empty ones
+    {
+      int bad = 0;
+      for (int k = k0; k < k1; ++k) {
+        const float fx = x[k], fy = y[k];
+        const int s = (int)__fdiv_rn(fx, D.hX);
+        bad |= (s < 0 || s >= D.nIni || !(fx >= 0.f && fx < 65536.f && fy >= 0.f && fy < 65536.f));
+        xy[k] = (uint32_t)(int)fx | ((uint32_t)(int)fy << 16);
+        if (lds_keys) { const float r = resp[k]; bad |= !(r >= 0.f && r < 256.f); s_resp[k] = (uint8_t)(int)r; }
+      }
+      if (__syncthreads_or(bad)) { finish(kQtBadStrip, 0); return; }
+      int base = 0;
+      for (int g = 0; g < D.nIni; g += 4) {
+        qt_u64 a = 0;
+        for (int k = k0; k < k1; ++k) { const int s = (int)__fdiv_rn((float)(xy[k] & 0xffffu), D.hX) - g; if (s >= 0 && s < 4) a += 1ull << (16 * s); }
+        qt_u64 tot;
+        qt_u64 ex = qt_block_scan(a, s_w, tot);
+        int st[5];
+        st[0] = base;
+        for (int j = 0; j < 4; ++j) st[j + 1] = st[j] + qt_field(tot, j);
+        for (int k = k0; k < k1; ++k) {
+          const int s = (int)__fdiv_rn((float)(xy[k] & 0xffffu), D.hX) - g;
+          if (s < 0 || s >= 4) continue;
+          const int p = st[s] + qt_field(ex, s);
+          if ((unsigned)p < (unsigned)n) { idA[p] = (uint16_t)k; knA[p] = (uint16_t)(g + s); }
+          ex += 1ull << (16 * s);
+        }
+        if (t < 4 && g + t < D.nIni) {
+          const int i = g + t;
+          const int sx0 = (int)(D.hX * (float)i), sx1 = (int)(D.hX * (float)(i + 1));
+          s_nx[1][i] = (uint32_t)sx0 | ((uint32_t)sx1 << 16); s_ny[1][i] = (uint32_t)D.H << 16;
+          s_b[1][i] = st[t]; s_e[1][i] = st[t + 1];
+        }
+        base = st[4];
+      }
+      __syncthreads();
+    }
+    int count;
+    {
+      const int NC = (D.nIni + kQtThreads - 1) / kQtThreads;
+      const int i0 = min(t * NC, D.nIni), i1 = min(i0 + NC, D.nIni);
+      int a = 0;
+      for (int i = i0; i < i1; ++i) a += s_e[1][i] > s_b[1][i];
+      qt_u64 tot;
+      int ex = (int)qt_block_scan((qt_u64)a, s_w, tot);
+      count = (int)tot;
+      for (int i = i0; i < i1; ++i) {
+        s_nb[i] = ex;
+        if (s_e[1][i] > s_b[1][i]) { s_nx[0][ex] = s_nx[1][i]; s_ny[0][ex] = s_ny[1][i]; s_b[0][ex] = s_b[1][i]; s_e[0][ex] = s_e[1][i]; s_cid[0][ex] = i; ++ex; }
+      }
+      __syncthreads();
+      for (int k = k0; k < k1; ++k) knA[k] = (uint16_t)s_nb[knA[k]];
+      __syncthreads();
+    }
+    int c = 0, next_cid = D.nIni;
+    bool final_phase = false;
+    for (int round = 0;; ++round) {
+      if (round >= kQtMaxRounds) { finish(kQtRoundCap, 0); return; }
+      const int o = c ^ 1;
+      const uint16_t *idc = c ? idB : idA, *knc = c ? knB : knA;
+      uint16_t *ido = c ? idA : idB, *kno = c ? knA : knB;
+      // A
+      {
+        auto quadrant = [&](int k) {
+          const int i = knc[k];
+          if (s_e[c][i] - s_b[c][i] <= 1) return 4;
+          const uint32_t nx = s_nx[c][i], ny = s_ny[c][i];
+          const int x0 = (int)(nx & 0xffffu), x1 = (int)(nx >> 16), y0 = (int)(ny & 0xffffu), y1 = (int)(ny >> 16);
+          const int mx = x0 + ((x1 - x0 + 1) >> 1), my = y0 + ((y1 - y0 + 1) >> 1);      // x0 + ceil((x1 - x0) / 2)
+          const uint32_t v = xy[idc[k]];
+          const int kx = (int)(v & 0xffffu), ky = (int)(v >> 16);
+          return (kx < mx) ? ((ky < my) ? 0 : 2) : ((ky < my) ? 1 : 3);
+        };
+        qt_u64 a = 0;
+        uint32_t qs = 0;                                 // the quadrants of up to 8 keys, 4 bits each (more keys per thread: computed again)
+        for (int k = k0; k < k1; ++k) { const int q = quadrant(k); if (q < 4) a += 1ull << (16 * q); if (k - k0 < 8) qs |= (uint32_t)q << (4 * (k - k0)); }
+        qt_u64 tot;
+        qt_u64 ex = qt_block_scan(a, s_w, tot);
+        for (int k = k0; k < k1; ++k) { P[k] = ex; const int q = k - k0 < 8 ? (int)((qs >> (4 * (k - k0))) & 15u) : quadrant(k); if (q < 4) ex += 1ull << (16 * q); }
+        if (t == 0) P[n] = tot;
+        __syncthreads();
+      }
+      // B
+      const int NC = (count + kQtThreads - 1) / kQtThreads;
+      const int i0 = min(t * NC, count), i1 = min(i0 + NC, count);
+      int E;
+      {
+        int a = 0;
+        for (int i = i0; i < i1; ++i) {
+          const int b = s_b[c][i], e = s_e[c][i];
+          const bool ex = e - b > 1;
+          s_qc[i] = ex ? P[e] - P[b] : 0ull;
+          a += ex;
+        }
+        qt_u64 tot;
+        int r = (int)qt_block_scan((qt_u64)a, s_w, tot);
+        E = (int)tot;
+        if (!final_phase) {
+          for (int i = i0; i < i1; ++i) {
+            if (s_e[c][i] - s_b[c][i] <= 1) { s_rank[i] = -1; continue; }
+            s_rank[i] = r; s_order[r] = i; ++r;
+          }
+        } else {
+          // rank = the expandable nodes with a larger (size, creation id): the keys go to s_sc (free until C), every node's count is
+          // split over kQtThreads / count threads
+          for (int i = i0; i < i1; ++i) {
+            const int sz = s_e[c][i] - s_b[c][i];
+            s_sc[i] = sz > 1 ? ((qt_u64)sz << 32) | (uint32_t)s_cid[c][i] : 0ull;
+            s_rank[i] = sz > 1 ? 0 : -1;
+          }
+          __syncthreads();
+          const int G = max(1, kQtThreads / count), per = kQtThreads / G, part = t % G;
+          for (int i = t / G; i < count; i += per) {
+            const qt_u64 ki = s_sc[i];
+            if (!ki) continue;
+            int rk = 0;
+#pragma unroll 4
+            for (int j = part; j < count; j += G) rk += s_sc[j] > ki;
+            if (rk) atomicAdd(&s_rank[i], rk);
+          }
+          __syncthreads();
+          for (int i = i0; i < i1; ++i) if (s_rank[i] >= 0) s_order[s_rank[i]] = i;
+        }
+        if (t == 0) s_m = E;
+        __syncthreads();
+      }
+      // C
+      {
+        const int RC = (E + kQtThreads - 1) / kQtThreads;
+        const int r0 = min(t * RC, E), r1 = min(r0 + RC, E);
+        qt_u64 a = 0;
+        for (int r = r0; r < r1; ++r) { const qt_u64 qc = s_qc[s_order[r]]; a += (qt_u64)qt_nchild(qc) | ((qt_u64)qt_nexp(qc) << 32); }
+        qt_u64 tot;
+        qt_u64 ex = qt_block_scan(a, s_w, tot);
+        for (int r = r0; r < r1; ++r) {
+          const qt_u64 qc = s_qc[s_order[r]];
+          ex += (qt_u64)qt_nchild(qc) | ((qt_u64)qt_nexp(qc) << 32);
+          s_sc[r] = ex;
+          if (final_phase && count + (int)(ex & 0xffffffffu) - (r + 1) >= N) atomicMin(&s_m, r + 1);
+        }
+        __syncthreads();
+      }
+      const int m = s_m;
+      const int TC = m > 0 ? (int)(s_sc[m - 1] & 0xffffffffu) : 0, n_to_expand = m > 0 ? (int)(s_sc[m - 1] >> 32) : 0;
+      const int new_count = TC + count - m;
+      if (new_count > cap) { finish(kQtNodeOverflow, 0); return; }
+      // D
+      {
+        int a = 0;
+        for (int i = i0; i < i1; ++i) { const int rk = s_rank[i]; a += !(rk >= 0 && rk < m); }
+        qt_u64 tot;
+        int u = (int)qt_block_scan((qt_u64)a, s_w, tot);
+        for (int i = i0; i < i1; ++i) {
+          const int rk = s_rank[i];
+          if (!(rk >= 0 && rk < m)) {
+            const int p = TC + u++;
+            s_nx[o][p] = s_nx[c][i]; s_ny[o][p] = s_ny[c][i]; s_b[o][p] = s_b[c][i]; s_e[o][p] = s_e[c][i]; s_cid[o][p] = s_cid[c][i];
+            s_nb[i] = p;
+            continue;
+          }
+          const qt_u64 qc = s_qc[i];
+          const int incl = (int)(s_sc[rk] & 0xffffffffu), nch = qt_nchild(qc);
+          const int nbase = TC - incl;                  // the children of the parents processed later come first
+          s_nb[i] = nbase;
+          const uint32_t nx = s_nx[c][i], ny = s_ny[c][i];
+          const int x0 = (int)(nx & 0xffffu), x1 = (int)(nx >> 16), y0 = (int)(ny & 0xffffu), y1 = (int)(ny >> 16);
+          const int mx = x0 + ((x1 - x0 + 1) >> 1), my = y0 + ((y1 - y0 + 1) >> 1);
+          int b = s_b[c][i], made = 0;
+          for (int q = 0; q < 4; ++q) {
+            const int sz = qt_field(qc, q);
+            if (!sz) continue;
+            const int p = nbase + nch - 1 - made;       // n4..n1 in the list
+            s_nx[o][p] = (q & 1) ? ((uint32_t)mx | ((uint32_t)x1 << 16)) : ((uint32_t)x0 | ((uint32_t)mx << 16));
+            s_ny[o][p] = (q & 2) ? ((uint32_t)my | ((uint32_t)y1 << 16)) : ((uint32_t)y0 | ((uint32_t)my << 16));
+            s_b[o][p] = b; s_e[o][p] = b + sz; s_cid[o][p] = next_cid + incl - nch + made;
+            b += sz; ++made;
+          }
+        }
+        __syncthreads();
+      }
+      // E
+      for (int k = k0; k < k1; ++k) {
+        const int i = knc[k], rk = s_rank[i];
+        int nk = k, nn = s_nb[i];
+        if (rk >= 0 && rk < m) {
+          const qt_u64 qc = s_qc[i], pk = P[k], d = P[k + 1] - pk;
+          const int q = (d & 0xffffu) ? 0 : ((d >> 16) & 0xffffu) ? 1 : ((d >> 32) & 0xffffu) ? 2 : 3;
+          const int b = s_b[c][i];
+          int offq = 0, after = 0;
+          for (int j = 0; j < 4; ++j) { const int sz = qt_field(qc, j); if (j < q) offq += sz; else if (j > q) after += sz != 0; }
+          nk = b + offq + qt_field(pk, q) - qt_field(P[b], q);
+          nn += after;
+        }
+        if ((unsigned)nk < (unsigned)n) { ido[nk] = idc[k]; kno[nk] = (uint16_t)nn; }   // (always: a permutation of [0, n))
+      }
+      __syncthreads();
+      c = o; next_cid += TC;
+      const int prev = count;
+      count = new_count;
+      if (count >= N || count == prev) break;
+      if (!final_phase && count + 3 * n_to_expand > N) final_phase = true;
+    }
+    // one keypoint per node, list order: the largest response, the first of equals
+    const uint16_t* idc = c ? idB : idA;
+    for (int i = t; i < count; i += kQtThreads) {
+      const int b = s_b[c][i], e = s_e[c][i];
+      int best = idc[b];
+      if (lds_keys) {
+        int mr = s_resp[best];
+        for (int k = b + 1; k < e; ++k) { const int ki = idc[k], r = s_resp[ki]; if (r > mr) { best = ki; mr = r; } }
+      } else {
+        float mr = resp[best];
+        for (int k = b + 1; k < e; ++k) { const int ki = idc[k]; const float r = resp[ki]; if (r > mr) { best = ki; mr = r; } }
+      }
+      hsel[D.out_off + i] = best; dsel[D.out_off + i] = pos + best;
+    }
+    finish(kQtOk, count);
+  };
+  if (n <= kQtLdsKeys) run(s_xy, s_idx[0], s_idx[1], s_kn[0], s_kn[1], s_P);
+  else {
+    uint32_t* const w0 = wi + 3 * (size_t)D.koff;       // xy | ids (2 x 16 bit) | nodes (2 x 16 bit), cand_cap words each
+    uint16_t* const h0 = (uint16_t*)(w0 + D.cand_cap);
+    run(w0, h0, h0 + D.cand_cap, h0 + 2 * (size_t)D.cand_cap, h0 + 3 * (size_t)D.cand_cap, wp + D.koff + l);
+  }
+}
+
+// The rows of the keypoints k_quadtree selected, as vdo_orb_extract returns them (x, y in level-0 pixels, response, IC_Angle), straight to the mapped
+// block: half a wave per keypoint slot, one patch row per lane, all 31 bytes of the row loaded at once (the patch lies inside the bordered level).
+__global__ __launch_bounds__(256) void k_qt_rows(const QtDesc* __restrict__ qd, int n_levels, const int* __restrict__ dhdr, const int* __restrict__ dsel,
+                                                 const float* __restrict__ ox, const float* __restrict__ oy, const float* __restrict__ oresp,
+                                                 const uint8_t* __restrict__ pyr, const LevelDesc* __restrict__ levels, UMax um, float* __restrict__ hrows, int row_pitch) {
+  const int lane = threadIdx.x & 31;
+  const int slot = (blockIdx.x * 256 + threadIdx.x) >> 5;
+  int l = -1;
+  for (int q = 0; q < n_levels; ++q) { const int off = qd[q].out_off; if (qd[q].on_device && slot >= off && slot < off + qd[q].node_cap) l = q; }
+  const bool valid = l >= 0 && dhdr[16 + l] == kQtOk && slot - qd[l].out_off < dhdr[l];
+  int m10 = 0, m01 = 0, kx = 0, ky = 0, dense = 0;
+  if (valid) {
+    dense = dsel[slot];
+    kx = (int)ox[dense]; ky = (int)oy[dense];
+    if (lane < 31) {
+      const LevelDesc L = levels[l];
+      const int v = lane - kHalfPatch;
+      const int d = um.v[v < 0 ? -v : v];
+      const uint8_t* row = pyr + L.off_inner + (size_t)(ky + (kEdge - 3) + v) * L.bw + (kx + (kEdge - 3));
+      int px[kPatch];
+#pragma unroll
+      for (int u = 0; u < kPatch; ++u) px[u] = row[u - kHalfPatch];
+      int rs = 0;
+#pragma unroll
+      for (int u = 0; u < kPatch; ++u) { const int uu = u - kHalfPatch; const int p = (uu >= -d && uu <= d) ? px[u] : 0; m10 += uu * p; rs += p; }
+      m01 = v * rs;
+    }
+  }
+#pragma unroll
+  for (int off = 16; off > 0; off >>= 1) { m10 += __shfl_down(m10, off, 32); m01 += __shfl_down(m01, off, 32); }
+  if (valid && lane == 0) {
+    const float ang = fast_atan2_dev((float)m01, (float)m10);
+    float fx = (float)kx + (float)(kEdge - 3), fy = (float)ky + (float)(kEdge - 3);
+    if (l != 0) { const float sc = qd[l].scale; fx = fx * sc; fy = fy * sc; }
+    float* r = hrows + slot;
+    r[0] = fx; r[row_pitch] = fy; r[2 * (size_t)row_pitch] = oresp[dense]; r[3 * (size_t)row_pitch] = ang;
+  }
+}
 
 }  // namespace vdo
 
@@ -740,7 +1096,16 @@ struct vdo_orb {
   int n_cand = 0;
   QuadTree qt[16];                                    // one per level: buffers reused across frames
   std::vector<int> sel[16];
-  std::unique_ptr<LevelPool> pool;                    // helpers for the per-level quadtrees (VDO_ORB_THREADS, default 3)
+  std::unique_ptr<LevelPool> pool;                    // helpers for the per-level host quadtrees (VDO_ORB_THREADS, default 3); not started with the device tree
+  // device quadtree (k_quadtree; off with VDO_ORB_HOST_TREE=1 or VDO_ORB_FUSED_ANGLE=1).  The mapped block continues behind the four candidate rows with
+  // [16 keypoint counts][16 status words][qt_out ids: level-local candidate ids in list order, level l from qtd[l].out_off][4 rows of qt_out: x, y, response,
+  // angle of those keypoints as vdo_orb_extract returns them]; d_qsel / d_qhdr: ids and header resident, ids as dense candidate ids (what k_orb_desc /
+  // k_orb_match_pos index with).
+  bool dev_tree = false;
+  bool ang_queued = false;                            // k_angle of this extraction is on the stream (device tree: only once something asks for the angle row)
+  QtDesc qtd[16]; QtDesc* d_qtd = nullptr;
+  int qt_out = 0;
+  uint32_t* d_qt_i = nullptr; int *d_qsel = nullptr, *d_qhdr = nullptr; qt_u64* d_qt_p = nullptr;
   double ms_device = 0, ms_tree = 0;                  // last extraction: launch..sync, host quadtree
   bool begun = false;                                 // between vdo_orb_extract_begin and _end
   hipEvent_t ev_cand = nullptr;                       // candidates are on the host (the blur stage runs behind it)
@@ -951,7 +1316,46 @@ extern "C" int vdo_orb_create(vdo_ctx* ctx, const vdo_orb_params* prm, int w, in
     o->d_lvl = (int*)(o->d_x + 4 * (size_t)o->dense_cap);
   }
   o->fused_angle = std::getenv("VDO_ORB_FUSED_ANGLE") != nullptr;
-  if (hipHostMalloc((void**)&o->h_pin, 4 * (32 + 4 * (size_t)o->dense_cap), hipHostMallocMapped) != hipSuccess) o->h_pin = nullptr;
+  // K5 on the device unless VDO_ORB_HOST_TREE=1 (the A/B switch) or the fused path (its candidates reach the host by a copy).  A level takes the host
+  // tree when its node bound N + 3 exceeds kQtMaxNodes (VDO_ORB_QT_NODE_CAP lowers that, for the tests), when it has more initial strips than that bound,
+  // or when its region does not fit the 16-bit node coordinates.
+  {
+    const char* ht = std::getenv("VDO_ORB_HOST_TREE");
+    o->dev_tree = !o->fused_angle && !(ht && ht[0] && std::strcmp(ht, "0") != 0);
+    int node_cap_max = kQtMaxNodes;
+    if (const char* e = std::getenv("VDO_ORB_QT_NODE_CAP")) node_cap_max = std::max(0, std::min(kQtMaxNodes, std::atoi(e)));
+    int koff = 0, out_off = 0;
+    bool any = false;
+    for (int l = 0; l < 16; ++l) {
+      QtDesc& D = o->qtd[l];
+      D = QtDesc{};
+      if (l >= NL) continue;
+      const LevelDesc& L = o->levels[l];
+      const int minB = kEdge - 3, maxBX = L.w - kEdge + 3, maxBY = L.h - kEdge + 3;
+      int cells_l = 0;
+      for (int c : o->cell_level) cells_l += c == l;
+      D.N = o->nfeat[l]; D.H = maxBY - minB; D.nIni = 1; D.hX = 1.f; D.scale = o->scale[l];
+      if (cells_l) {                                   // (the same float arithmetic as QuadTree::run)
+        D.nIni = (int)std::round((float)(maxBX - minB) / (maxBY - minB));
+        D.hX = (float)(maxBX - minB) / D.nIni;
+      }
+      D.node_cap = D.N + 3;
+      D.cand_cap = (int)std::min<int64_t>((int64_t)cells_l * o->cell_cap, kQtMaxCand);
+      D.koff = koff; D.out_off = out_off;
+      D.on_device = o->dev_tree && D.node_cap <= node_cap_max && D.nIni <= D.node_cap && maxBX - minB < 65536 && maxBY - minB < 65536;
+      if (!D.on_device) { D.cand_cap = 0; D.node_cap = 0; }
+      any = any || D.on_device;
+      koff += D.cand_cap; out_off += D.node_cap;
+    }
+    o->dev_tree = any;
+    o->qt_out = out_off;
+    if (o->dev_tree) {
+      o->d_qtd = (QtDesc*)dev(sizeof(o->qtd));
+      o->d_qt_i = (uint32_t*)dev(4 * 3 * (size_t)koff); o->d_qt_p = (qt_u64*)dev(8 * ((size_t)koff + 16));
+      o->d_qsel = (int*)dev(4 * (size_t)out_off); o->d_qhdr = (int*)dev(4 * 32);
+    }
+  }
+  if (hipHostMalloc((void**)&o->h_pin, 4 * (32 + 4 * (size_t)o->dense_cap + 32 + 5 * (size_t)o->qt_out), hipHostMallocMapped) != hipSuccess) o->h_pin = nullptr;
   if (o->h_pin && hipHostGetDevicePointer((void**)&o->d_pin, o->h_pin, 0) != hipSuccess) o->d_pin = nullptr;
   for (void* p : o->allocs) if (!p) { vdo_orb_destroy(o); return set_error(VDO_ERR_OOM, "hipMalloc failed"); }
   if (!o->d_lvl || !o->h_pin || !o->d_pin) { vdo_orb_destroy(o); return set_error(VDO_ERR_OOM, "hipMalloc failed"); }
@@ -960,12 +1364,13 @@ extern "C" int vdo_orb_create(vdo_ctx* ctx, const vdo_orb_params* prm, int w, in
   hipMemcpyAsync(o->d_cell_level, o->cell_level.data(), 4 * (size_t)o->ncells, hipMemcpyHostToDevice, s);
   static_assert(sizeof(kOrbPattern31) == sizeof(OrbPattern), "256 tests x 4 signed bytes");
   hipMemcpyAsync(o->d_pat, kOrbPattern31, sizeof(OrbPattern), hipMemcpyHostToDevice, s);
+  if (o->dev_tree) hipMemcpyAsync(o->d_qtd, o->qtd, sizeof(o->qtd), hipMemcpyHostToDevice, s);
   if (hipStreamSynchronize(s) != hipSuccess) { vdo_orb_destroy(o); return set_error(VDO_ERR_NO_DEVICE, "orb upload failed"); }
   if (hipEventCreateWithFlags(&o->ev_cand, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&o->ev_ang, hipEventDisableTiming) != hipSuccess) {
     vdo_orb_destroy(o);
     return set_error(VDO_ERR_NO_DEVICE, "hipEventCreate failed");
   }
-  {
+  if (!o->dev_tree) {
     const char* e = std::getenv("VDO_ORB_THREADS");
     const int nw = e ? std::atoi(e) : 3;
     if (nw > 0) o->pool.reset(new LevelPool(std::min(nw, 15)));
@@ -1007,6 +1412,13 @@ static int orb_device_stage(vdo_orb* o, const uint8_t* gray_dev, int stride) {
     const size_t pitch = (size_t)o->dense_cap;
     hipLaunchKernelGGL(k_compact, dim3(o->ncells), dim3(256), 0, s, (const CellDesc*)o->d_cells, (const int*)o->d_cnt, (const int*)o->d_cell_level, o->d_level_cnt,
                        (const uint32_t*)o->d_pack, o->ncells, o->cell_cap, o->d_x, o->d_y, o->d_resp, o->d_lvl, (int*)o->d_pin, rows, rows + pitch, rows + 2 * pitch);
+    if (o->dev_tree) {
+      int* qh = (int*)(rows + 4 * pitch);
+      hipLaunchKernelGGL(k_quadtree, dim3(NL), dim3(kQtThreads), 0, s, (const QtDesc*)o->d_qtd, (const int*)o->d_level_cnt, (const float*)o->d_x, (const float*)o->d_y,
+                         (const float*)o->d_resp, o->d_qt_i, o->d_qt_p, o->d_qsel, o->d_qhdr, qh + 32, qh);
+      hipLaunchKernelGGL(k_qt_rows, dim3((o->qt_out + 7) / 8), dim3(256), 0, s, (const QtDesc*)o->d_qtd, NL, (const int*)o->d_qhdr, (const int*)o->d_qsel, (const float*)o->d_x,
+                         (const float*)o->d_y, (const float*)o->d_resp, (const uint8_t*)o->d_pyr, (const LevelDesc*)o->d_levels, o->um, (float*)(qh + 32 + o->qt_out), o->qt_out);
+    }
   }
   return VDO_OK;
 }
@@ -1019,6 +1431,15 @@ static void orb_angle_stage(vdo_orb* o) {
   hipLaunchKernelGGL(k_angle, dim3(std::max(1, std::min(1024, (chunks + 3) / 4))), dim3(256), 0, s, (const uint8_t*)o->d_pyr, (const LevelDesc*)o->d_levels,
                      (const int*)o->d_level_cnt, o->um, (const float*)o->d_x, (const float*)o->d_y, (const int*)o->d_lvl, o->d_ang, o->d_pin + 32 + 3 * (size_t)o->dense_cap);
   hipEventRecord(o->ev_ang, s);
+}
+
+// Device tree: no keypoint needs the angle row of all candidates (k_qt_rows computes the angles of the selected ones), and whatever the caller queues on the
+// extractor's stream next would wait behind k_angle.  So it runs on demand: for a level that took the host tree, vdo_orb_get_candidates and the descriptors
+// (k_orb_desc reads d_ang).  The pyramid and the dense candidate arrays stay resident until the next vdo_orb_extract_begin.
+static void orb_ensure_angles(vdo_orb* o) {
+  if (o->fused_angle || o->ang_queued) return;
+  orb_angle_stage(o);
+  o->ang_queued = true;
 }
 
 // K7: the reference blurs every non-empty level (result unused there since BRIEF is commented out, F1).  Nothing downstream
@@ -1061,9 +1482,11 @@ extern "C" int vdo_orb_extract_begin(vdo_orb* o, const uint8_t* gray, int stride
     hipMemcpy2DAsync(o->h_pin + 32, 4 * (size_t)o->dense_cap, o->d_x, 4 * (size_t)o->dense_cap, 4 * (size_t)spec, 4, hipMemcpyDeviceToHost, s);
     hipEventRecord(o->ev_cand, s);
   } else {
-    // k_compact has written the header and the x / y / resp rows to the host itself; the angles follow behind the event
+    // k_compact has written the header and the x / y / resp rows to the host itself (and k_quadtree, with the device tree, the keypoint ids);
+    // the angles of all candidates follow behind the event (device tree: on demand, orb_ensure_angles)
     hipEventRecord(o->ev_cand, s);
-    orb_angle_stage(o);
+    o->ang_queued = false;
+    if (!o->dev_tree) orb_ensure_angles(o);
   }
   orb_blur_stage(o);
   o->begun = true;
@@ -1106,21 +1529,43 @@ extern "C" int vdo_orb_extract_end(vdo_orb* o, vdo_keypoints* out) {
   lvl_pos[0] = 0;
   for (int l = 0; l < NL; ++l) lvl_pos[l + 1] = lvl_pos[l] + o->hlevel_cnt[l];
   const int minB = kEdge - 3;
+  const int* qh = (const int*)(rows + 4 * pitch);     // device tree: [16 counts][16 status][ids]
+  bool on_dev[16] = {};
+  bool all_dev = o->dev_tree;
+  for (int l = 0; l < NL; ++l) { on_dev[l] = o->dev_tree && qh[16 + l] == kQtOk && qh[l] >= 0 && qh[l] <= o->qtd[l].node_cap; all_dev = all_dev && on_dev[l]; }
   auto level_task = [&](int l) {
     const LevelDesc& L = o->levels[l];
     const int pos = lvl_pos[l];
+    if (on_dev[l]) {
+      const int* ids = qh + 32 + o->qtd[l].out_off;
+      o->sel[l].assign(ids, ids + qh[l]);
+      return;
+    }
     o->qt[l].run(o->hx + pos, o->hy + pos, o->hresp + pos, o->hlevel_cnt[l], minB, L.w - kEdge + 3, minB, L.h - kEdge + 3, o->nfeat[l], o->sel[l]);
   };
   if (o->pool) o->pool->run(NL, level_task);
   else for (int l = 0; l < NL; ++l) level_task(l);
   // split path: the angle row was written under the quadtrees (o->hang and vdo_orb_get_candidates are valid from here on)
-  if (!o->fused_angle && hipEventSynchronize(o->ev_ang) != hipSuccess) return set_error(VDO_ERR_NO_DEVICE, "orb angle stage failed: %s", hipGetErrorString(hipGetLastError()));
+  // (device tree: k_qt_rows has written the rows of its keypoints, angle included; the angle row of all candidates is waited for only by a level
+  //  that took the host tree, and by vdo_orb_get_candidates)
+  if (!all_dev) orb_ensure_angles(o);
+  if (!o->fused_angle && !all_dev && hipEventSynchronize(o->ev_ang) != hipSuccess) return set_error(VDO_ERR_NO_DEVICE, "orb angle stage failed: %s", hipGetErrorString(hipGetLastError()));
   int n = 0;
   o->sel_dense.clear();
   for (int l = 0; l < NL; ++l) {
     const int pos = lvl_pos[l];
     const float *cx = o->hx + pos, *cy = o->hy + pos, *cr = o->hresp + pos, *ca = o->hang + pos;
     const int patch = (int)(kPatch * o->scale[l]);
+    if (on_dev[l]) {
+      const int m = (int)o->sel[l].size();
+      if (n + m > out->capacity) return set_error(VDO_ERR_INVALID, "vdo_orb_extract: keypoint capacity %d too small", out->capacity);
+      const float* r = (const float*)(qh + 32 + o->qt_out) + o->qtd[l].out_off;
+      std::memcpy(out->x + n, r, 4 * (size_t)m); std::memcpy(out->y + n, r + o->qt_out, 4 * (size_t)m);
+      std::memcpy(out->response + n, r + 2 * (size_t)o->qt_out, 4 * (size_t)m); std::memcpy(out->angle + n, r + 3 * (size_t)o->qt_out, 4 * (size_t)m);
+      for (int k = 0; k < m; ++k) { o->sel_dense.push_back(pos + o->sel[l][k]); out->octave[n + k] = l; out->size[n + k] = (float)patch; }
+      n += m;
+      continue;
+    }
     for (int id : o->sel[l]) {
       o->sel_dense.push_back(pos + id);
       if (n >= out->capacity) return set_error(VDO_ERR_INVALID, "vdo_orb_extract: keypoint capacity %d too small", out->capacity);
@@ -1152,6 +1597,7 @@ static int orb_queue_descriptors(vdo_orb* o, int n) {
     o->allocs.push_back(ns); o->allocs.push_back(nd);
   }
   // the blurred levels of this extraction are queued on the same stream (orb_blur_stage), the dense candidate arrays are still resident
+  orb_ensure_angles(o);
   hipMemcpyAsync(o->d_sel, o->sel_dense.data(), 4 * (size_t)n, hipMemcpyHostToDevice, s);
   hipLaunchKernelGGL(k_orb_desc, dim3((n + 3) / 4), dim3(256), 0, s, (const uint8_t*)o->d_blur, (const LevelDesc*)o->d_levels, (const int*)o->d_sel, n,
                      (const float*)o->d_x, (const float*)o->d_y, (const float*)o->d_ang, (const int*)o->d_lvl, (const OrbPattern*)o->d_pat, o->d_desc);
@@ -1216,10 +1662,18 @@ int vdo::orb_match_view(vdo_orb* o, OrbMatchView* v) {
   return VDO_OK;
 }
 
-// Wall time of the last vdo_orb_extract: [0] launch of the device stage .. candidates on the host, [1] host quadtree (K5)
+// Wall time of the last vdo_orb_extract: [0] launch of the device stage .. candidates (device tree: and keypoint ids) on the host, [1] the rest of _end
 extern "C" int vdo_orb_last_timing(vdo_orb* o, double ms[2]) {
   if (!o || !ms) return set_error(VDO_ERR_INVALID, "null argument");
   ms[0] = o->ms_device; ms[1] = o->ms_tree;
+  return VDO_OK;
+}
+
+extern "C" int vdo_orb_tree_info(vdo_orb* o, int level, int* on_device, int* status) {
+  if (!o || !on_device || !status || level < 0 || level >= o->prm.n_levels) return set_error(VDO_ERR_INVALID, "vdo_orb_tree_info: bad argument");
+  if ((int)o->hlevel_cnt.size() != 16) return set_error(VDO_ERR_INVALID, "vdo_orb_tree_info: nothing extracted yet");
+  const int st = o->dev_tree ? ((const int*)(o->h_pin + 32 + 4 * (size_t)o->dense_cap))[16 + level] : (int)kQtHostLevel;
+  *on_device = st == kQtOk; *status = st;
   return VDO_OK;
 }
 
@@ -1261,6 +1715,13 @@ extern "C" int vdo_orb_get_candidates(vdo_orb* o, int level, float* x, float* y,
   for (int l = 0; l < level; ++l) pos += o->hlevel_cnt[l];
   const int cnt = o->hlevel_cnt[level];
   *n = cnt;
+  // (device tree: vdo_orb_extract_end has not waited for the angle row of all candidates)
+  if (angle && !o->fused_angle && !o->begun) {
+    const int rc = ctx_bind(o->ctx);
+    if (rc != VDO_OK) return rc;
+    orb_ensure_angles(o);
+  }
+  if (angle && !o->fused_angle && !o->begun && hipEventSynchronize(o->ev_ang) != hipSuccess) return set_error(VDO_ERR_NO_DEVICE, "orb angle stage failed: %s", hipGetErrorString(hipGetLastError()));
   for (int k = 0; k < cnt && k < cap; ++k) {
     if (x) x[k] = o->hx[pos + k];
     if (y) y[k] = o->hy[pos + k];
