@@ -1426,6 +1426,92 @@ int vdo_align_get_rows(vdo_align* h, float* rows);
 /* The last linearise or solve: ms[0] wall time of the call, ms[1] device time of its linearisations, first command to last kernel (events). */
 int vdo_align_last_timing(vdo_align* h, double ms[2]);
 
+/* ---- Colourer: fused RGB beside a TSDF volume ------------------------------------------------------------------------------------------
+ * New (the reference keeps no dense map): a colour per voxel of a vdo_dense - the static map or an object's volume -, fused per frame from the
+ * image the frame's depth belongs to, and read back at points (Sample) or along a depth image (Render).  A vdo_colour BORROWS its map: it uses the
+ * map's context, image size, K, depth range, voxel and origin, and is destroyed before it.  The geometry is fp32, one rounded operation per step in
+ * the order written, no contraction (/ and floorf correctly rounded); everything after it is integer; no result depends on workgroup shape, on the
+ * voxels a thread takes or on the schedule.  No float atomics.  The TSDF words are never read: no result depends on whether the same frame's
+ * vdo_dense_integrate ran before or after.
+ *
+ * Colour volume.  One 32-bit word per voxel in the map's slot layout (voxel g at slot g_a mod n_a per axis, x fastest, then y, then z): bits 0-7 R,
+ *   8-15 G, 16-23 B, 24-31 the colour weight cw.  cw == 0 is "no colour" and the whole word is then 0.
+ * Follow.  The handle remembers the map origin it last saw (at create: the map's).  EVERY entry that reads or writes the colour volume - integrate,
+ *   sample, render, get_volume, set_volume - first follows the map: if the map's origin differs from the remembered one by d, the slots whose global
+ *   voxel changes are set to 0 (per axis with d_a != 0 the leaving slab: the first d_a voxels when d_a > 0, the last -d_a when d_a < 0, whole on the
+ *   other two axes, one launch each) and no other word is touched; |d_a| >= n_a on any axis clears everything.  Only the difference since the last
+ *   entry counts: a map moved away and back between two entries clears nothing.
+ * Image.  uint8, `channels` 1 (grey, replicated), 3 or 4 (the fourth is ignored) per pixel, rows image_stride_bytes apart; rgb_order 0: R first,
+ *   1: B first.  A pack kernel writes one uint32 R | G << 8 | B << 16 per pixel into the handle's [H][W] image; the fusion reads that word.
+ * Integrate.  depth, mask, T and K as vdo_dense_integrate takes them; label an int.  Every voxel of the volume, from its own integer index:
+ *      the projection and the tests of vdo_dense_integrate up to and including "skip unless d finite, d > min_depth, d <= max_depth", the pixel
+ *      j = ((int)yq, (int)xq) the same bit for bit
+ *      m = mask != NULL ? mask(j) : 0
+ *      label == 0: skip if m != 0 (the static map);  label > 0: skip unless m == label (an object's volume);  label < 0: the mask is not read.
+ *                                  A voxel skipped here counts in out[1].
+ *      s = d - Zc;                 skip (counted in out[2]) if !(fabsf(s) <= band)
+ *      q_c the pixel's channel c;  c' = (2*(c*cw + q_c) + (cw+1)) / (2*(cw+1)) per channel (integers, all non-negative);  cw' = min(cw+1, max_weight)
+ *                                  counted in out[0]
+ *   The colour word is read only by the voxels that reach the last step, and stored only when it changed.  A skipped voxel keeps its word.
+ * Sample.  A world point p (3 floats), min_weight 1..255.  Per axis a:
+ *      u = p_a / voxel;  u = u - 0.5f;  b = floorf(u);  f = u - b;  fi = (int)floorf(f * 256.0f)        (0..256; 256 when u - b rounds up to 1)
+ *      no colour unless p_a is finite and -4194304.0f <= b <= 4194303.0f, compared as floats before any conversion to int
+ *   The corners g = b + {0,1}^3 with the axis weight 256 - fi for offset 0 and fi for offset 1.  A corner COUNTS iff o_a <= g_a < o_a + n_a on every
+ *   axis and its cw >= min_weight; its weight wgt is the product of its three axis weights.  Over the corners that count, in 64-bit integers:
+ *   S = sum wgt (at most 2^24), C_c = sum wgt * c_c.  S == 0: rgba = (0, 0, 0, 0).  Else c = (2*C_c + S) / (2*S) and
+ *   alpha = max(1, (255*S + (1 << 23)) >> 24): the share of the trilinear weight that had colour.
+ *   NO OUT-OF-RANGE READS: every index is built from slot coordinates tested against n.
+ * Render.  A depth image as vdo_raycast_render writes it (packed, z-depth, 0 for no surface) of any size, with the K = (fx, fy, cx, cy) and T it was
+ *   rendered at.  Per pixel (x, y) with depth finite and > 0: the world point c_a + depth * r_a from the raycaster's camera centre c of T and ray r
+ *   of the pixel (the point the aligner names), sampled as above.  Every other pixel is (0, 0, 0, 0). */
+typedef struct vdo_colour vdo_colour;
+typedef struct vdo_colour_params {
+  float band;                       /* metres; 0 < band <= the map's trunc */
+  int32_t max_weight;               /* 1..255 */
+  int32_t stage_points;             /* >= 1: the points (or pixels) one window of a host sample (or render) holds on the device (16 bytes each) */
+} vdo_colour_params;
+/* A colourer for `map`.  ALL device memory is taken here (the colour volume, 4 bytes per voxel, cleared; the packed image, 4 bytes per pixel, and the
+ * staging of a host image, 4 bytes per pixel; the counters; the window staging) - a host or strided depth and mask go through the MAP's staging
+ * images; the other entries allocate nothing.  VDO_ERR_INVALID, the message naming the argument: a null map, params or out; a parameter outside the
+ * range written beside it or not finite.  VDO_ERR_OOM when the device has no room. */
+int vdo_colour_create(vdo_dense* map, const vdo_colour_params* params, vdo_colour** out);
+int vdo_colour_destroy(vdo_colour* h);
+/* One frame, host-synchronous, on the map's context stream: follow, pack, one fusion kernel.  depth, mask, their strides and T as
+ * vdo_dense_integrate takes them; image: rows of `width` pixels of `channels` bytes, image_stride_bytes apart; all three images are host pointers,
+ * or device pointers when src_is_device != 0.  out (host): voxels updated, voxels skipped by the label rule, voxels skipped by the band rule.
+ * VDO_ERR_INVALID, the message naming the argument, and then NOTHING is written (the volume is not even followed): a null handle, depth, image, T or
+ * out; a depth or mask stride smaller than the width; image_stride_bytes smaller than width * channels; channels not 1, 3 or 4; rgb_order not 0
+ * or 1. */
+int vdo_colour_integrate(vdo_colour* h, const float* depth, int64_t depth_stride_floats, const int32_t* mask, int64_t mask_stride_ints, const uint8_t* image,
+                         int64_t image_stride_bytes, int channels, int rgb_order, int src_is_device, int label, const float T[16], int64_t out[3]);
+/* The same from the resident depth (after K1: metres) and mask of a vdo_frame_images of the map's image size, read where they lie and not written;
+ * image_is_device says where `image` lives.  Refusals as above, and a null frame or one of another size. */
+int vdo_colour_integrate_frame(vdo_colour* h, const vdo_frame_images* frame, const uint8_t* image, int64_t image_stride_bytes, int channels, int rgb_order,
+                               int image_is_device, int label, const float T[16], int64_t out[3]);
+/* The colour of the map at n world points: xyz float [n][3] in, rgba uint8 [n][4] out, both host pointers, or both device pointers when
+ * is_device != 0 (host points go through the stage_points window).  *n_coloured (host): the points with S != 0.  VDO_ERR_INVALID, the message
+ * naming the argument, and then NOTHING is written: a null handle or n_coloured; n < 0; a null xyz or rgba with n > 0; min_weight outside 1..255; a
+ * device rgba that is not 4-byte aligned (a point's four bytes are written as one word; a host rgba may lie anywhere). */
+int vdo_colour_sample(vdo_colour* h, int64_t n, const float* xyz, int min_weight, uint8_t* rgba, int is_device, int64_t* n_coloured);
+/* The colour image of a depth image: depth float [height][width] in, rgba uint8 [height][width][4] out, both packed, both host pointers (through
+ * the stage_points window) or both device pointers when is_device != 0.  K, T: host.  out (host): pixels coloured, pixels with depth but no colour.
+ * VDO_ERR_INVALID, the message naming the argument, and then NOTHING is written: a null handle, depth, K, T, rgba or out; a size < 1; a K that is
+ * not finite or has fx, fy <= 0; min_weight outside 1..255; a device rgba that is not 4-byte aligned.  VDO_ERR_UNSUPPORTED for an image over 2^26 pixels or 2^24 on a side.  A non-finite T
+ * is not refused: its points have no colour. */
+int vdo_colour_render(vdo_colour* h, const float* depth, int width, int height, const float K[4], const float T[16], int min_weight, uint8_t* rgba, int is_device,
+                      int64_t out[2]);
+/* Sets every colour word to 0 and remembers the map's present origin: a reused object handle after vdo_dense_clear. */
+int vdo_colour_clear(vdo_colour* h);
+/* Inspection, after following the map: the words in slot order (host, nx * ny * nz; may be NULL) and the origin (host; may be NULL; not both). */
+int vdo_colour_get_volume(vdo_colour* h, uint32_t* words, int32_t origin[3]);
+/* The reverse: nx * ny * nz host words in slot order replace the colour volume after it followed the map.  The caller keeps the format: cw = 0 only
+ * with the whole word 0. */
+int vdo_colour_set_volume(vdo_colour* h, const uint32_t* words);
+/* The y-consecutive voxels one thread of the fusion kernel takes: 1, 2, 4 (the default) or 8.  No result depends on it. */
+int vdo_colour_set_voxels_per_thread(vdo_colour* h, int voxels);
+/* The last integrate, sample or render: ms[0] wall time of the call, ms[1] device time from the first command to the end of the last kernel. */
+int vdo_colour_last_timing(vdo_colour* h, double ms[2]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,9 +22,22 @@ DenseMapper::DenseMapper(vdo_ctx* ctx, int width, int height, const Settings& se
     const vdo_mesh_params mp{{s_.params.n[0], s_.params.n[1], s_.params.n[2]}, 1 << 20, 1 << 21};
     if (vdo_mesh_create(ctx_, &mp, &mesher_) != VDO_OK) { vdo_dense_destroy(h_); die("vdo_mesh_create"); }
   }
+  if (s_.colour) {
+    if (s_.colourBand == 0.f) s_.colourBand = s_.params.trunc / 2.f;
+    if (s_.colourMaxWeight == 0) s_.colourMaxWeight = s_.params.max_weight;
+    const std::string err = CheckColour(s_);
+    const vdo_colour_params cp{s_.colourBand, s_.colourMaxWeight, 1 << 20};
+    if (!err.empty() || vdo_colour_create(h_, &cp, &colour_) != VDO_OK) {
+      vdo_mesh_destroy(mesher_); vdo_dense_destroy(h_);
+      if (!err.empty()) throw std::runtime_error("VDO_SLAM::DenseMapper: " + err);
+      die("vdo_colour_create");
+    }
+    kept_.coloured = keptMeshV_.coloured = true;            // what is copied from them and appended to carries colours, also while it is empty
+  }
 }
 
 DenseMapper::~DenseMapper() {
+  vdo_colour_destroy(colour_);                            // the colourer borrows the map
   vdo_mesh_destroy(mesher_);
   vdo_align_destroy(align_);
   vdo_raycast_destroy(view_);                             // the view borrows the map
@@ -55,6 +68,14 @@ std::string DenseMapper::CheckAlign(const Settings& s) {
   if (!std::isfinite(s.alignMaxDist) || !(s.alignMaxDist >= 0.f)) return "settings: Dense.Align.MaxDist must be finite and not negative (0 stands for Dense.Truncation)";
   if (s.alignSubsample < 1 || s.alignSubsample > 8) return "settings: Dense.Align.Subsample outside 1..8";
   if (s.alignMinPixels != 0 && s.alignMinPixels < 6) return "settings: Dense.Align.MinPixels must be at least 6";
+  return "";
+}
+
+std::string DenseMapper::CheckColour(const Settings& s) {
+  if (!std::isfinite(s.colourBand) || !(s.colourBand > 0.f)) return "settings: Dense.Colour.Band must be positive";
+  if (!(s.colourBand <= s.params.trunc)) return "settings: Dense.Colour.Band must not exceed Dense.Truncation";
+  if (s.colourMaxWeight < 1 || s.colourMaxWeight > 255) return "settings: Dense.Colour.MaxWeight outside 1..255";
+  if (s.colourMinWeight < 1 || s.colourMinWeight > 255) return "settings: Dense.Colour.MinWeight outside 1..255";
   return "";
 }
 
@@ -130,6 +151,17 @@ void DenseMapper::Append(const int32_t lo[3], const int32_t hi[3], Points& to) {
   const size_t at = to.size();
   to.xyz.resize(3 * (at + (size_t)n)); to.grad.resize(3 * (at + (size_t)n)); to.weight.resize(at + (size_t)n);
   if (vdo_dense_extract(h_, lo, hi, s_.minWeight, n, to.xyz.data() + 3 * at, to.grad.data() + 3 * at, to.weight.data() + at, 0, &n) != VDO_OK) die("vdo_dense_extract");
+  Colour(to, at);
+}
+
+void DenseMapper::Colour(Points& p, size_t from) {
+  if (!colour_) return;
+  p.coloured = true;
+  const size_t n = p.size();
+  p.rgba.resize(4 * n);
+  if (n == from) return;
+  int64_t coloured = 0;
+  if (vdo_colour_sample(colour_, (int64_t)(n - from), p.xyz.data() + 3 * from, s_.colourMinWeight, p.rgba.data() + 4 * from, 0, &coloured) != VDO_OK) die("vdo_colour_sample");
 }
 
 void DenseMapper::AppendMeshOf(vdo_mesh* mesher, vdo_dense* map, const int32_t lo[3], const int32_t hi[3], int outside, int min_weight, int64_t guess[2], Points& v,
@@ -154,7 +186,9 @@ void DenseMapper::AppendMeshOf(vdo_mesh* mesher, vdo_dense* map, const int32_t l
 }
 
 void DenseMapper::AppendMesh(const int32_t lo[3], const int32_t hi[3], int outside, Points& v, std::vector<int32_t>& tri) {
+  const size_t at = v.size();
   AppendMeshOf(mesher_, h_, lo, hi, outside, s_.minWeight, meshGuess_, v, tri);
+  Colour(v, at);
 }
 
 void DenseMapper::Follow(const float Tcw[16]) {
@@ -211,6 +245,7 @@ void DenseMapper::FuseFrame(const vdo_frame_images* frame, const float Tcw[16], 
   Follow(Tcw);
   int64_t out[3] = {0, 0, 0};
   if (vdo_dense_integrate_frame(h_, frame, Tcw, out) != VDO_OK) die("vdo_dense_integrate_frame");
+  lastFrame_ = frame;
   if (counts) for (int k = 0; k < 3; ++k) counts[k] = out[k];
 }
 
@@ -223,7 +258,25 @@ void DenseMapper::Fuse(const cv::Mat& depth, const cv::Mat& mask, const float Tc
   if (vdo_dense_integrate(h_, (const float*)depth.data, (int64_t)(depth.step / 4), mask.empty() ? nullptr : (const int32_t*)mask.data, mask.empty() ? 0 : (int64_t)(mask.step / 4), 0, Tcw,
                           out) != VDO_OK)
     die("vdo_dense_integrate");
+  lastFrame_ = nullptr;
   if (counts) for (int k = 0; k < 3; ++k) counts[k] = out[k];
+}
+
+void DenseMapper::FuseColour(const Image& im, const float Tcw[16], int64_t counts[3]) {
+  if (!colour_) throw std::runtime_error("VDO_SLAM::DenseMapper: FuseColour without Dense.Colour");
+  if (!lastFrame_) throw std::runtime_error("VDO_SLAM::DenseMapper: FuseColour follows a FuseFrame");
+  int64_t out[3] = {0, 0, 0};
+  if (vdo_colour_integrate_frame(colour_, lastFrame_, im.data, im.step, im.channels, im.bgr ? 1 : 0, im.device ? 1 : 0, 0, Tcw, out) != VDO_OK) die("vdo_colour_integrate_frame");
+  if (counts) for (int k = 0; k < 3; ++k) counts[k] = out[k];
+}
+
+void DenseMapper::RenderColour(const float Tcw[16], cv::Mat& rgba) {
+  if (!colour_) throw std::runtime_error("VDO_SLAM::DenseMapper: RenderColour without Dense.Colour");
+  cv::Mat depth, normals;
+  Render(Tcw, depth, normals);
+  rgba.create(h_px_, w_, cv::CV_8UC4);
+  int64_t out[2] = {0, 0};
+  if (vdo_colour_render(colour_, (const float*)depth.data, w_, h_px_, s_.params.K, Tcw, s_.colourMinWeight, rgba.data, 0, out) != VDO_OK) die("vdo_colour_render");
 }
 
 DenseMapper::Points DenseMapper::AllPoints() {
@@ -244,16 +297,22 @@ void DenseMapper::Mesh(Points& v, std::vector<int32_t>& tri) {
   AppendMesh(o, hi, 0, v, tri);
 }
 
-// one vertex record as SavePLY and SaveMeshPLY write it: x, y, z, the gradient normalised in double and narrowed (or 0), the weight
-static bool write_vertex(FILE* f, const DenseMapper::Points& p, size_t i) {
+// one vertex record as SavePLY and SaveMeshPLY write it: x, y, z, the gradient normalised in double and narrowed (or 0), the weight and, when the
+// points carry colours (the caller decides, once per file), red, green, blue, alpha
+static bool write_vertex(FILE* f, const DenseMapper::Points& p, size_t i, bool coloured) {
   const double g[3] = {(double)p.grad[3 * i], (double)p.grad[3 * i + 1], (double)p.grad[3 * i + 2]};
   const double len = std::sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
-  char rec[28];                                                            // (x86-64 is little-endian: the records are written as they lie)
+  char rec[32];                                                            // (x86-64 is little-endian: the records are written as they lie)
   float v[6] = {p.xyz[3 * i], p.xyz[3 * i + 1], p.xyz[3 * i + 2], 0.f, 0.f, 0.f};
   if (len > 0) for (int k = 0; k < 3; ++k) v[3 + k] = (float)(g[k] / len);
   std::memcpy(rec, v, 24); std::memcpy(rec + 24, &p.weight[i], 4);
-  return std::fwrite(rec, 1, 28, f) == 28;
+  if (coloured) std::memcpy(rec + 28, &p.rgba[4 * i], 4);
+  const size_t len_rec = coloured ? 32 : 28;
+  return std::fwrite(rec, 1, len_rec, f) == len_rec;
 }
+
+static const char* kVertexProperties = "property float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\nproperty float nz\nproperty int weight\n";
+static const char* kColourProperties = "property uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\n";
 
 bool DenseMapper::SaveMeshPLY(const std::string& path) {
   Points v;
@@ -263,13 +322,14 @@ bool DenseMapper::SaveMeshPLY(const std::string& path) {
 }
 
 bool DenseMapper::WriteMeshPLY(const std::string& path, const Points& v, const std::vector<int32_t>& tri) {
+  if (v.coloured && v.rgba.size() != 4 * v.size()) return false;
   FILE* f = std::fopen(path.c_str(), "wb");
   if (!f) return false;
   std::fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %zu\n", v.size());
-  std::fprintf(f, "property float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\nproperty float nz\nproperty int weight\n");
+  std::fprintf(f, "%s%s", kVertexProperties, v.coloured ? kColourProperties : "");
   std::fprintf(f, "element face %zu\nproperty list uchar int vertex_indices\nend_header\n", tri.size() / 3);
   bool ok = true;
-  for (size_t i = 0; i < v.size() && ok; ++i) ok = write_vertex(f, v, i);
+  for (size_t i = 0; i < v.size() && ok; ++i) ok = write_vertex(f, v, i, v.coloured);
   for (size_t t = 0; t < tri.size() / 3 && ok; ++t) {
     char rec[13] = {3};
     std::memcpy(rec + 1, &tri[3 * t], 12);
@@ -280,12 +340,13 @@ bool DenseMapper::WriteMeshPLY(const std::string& path, const Points& v, const s
 
 bool DenseMapper::SavePLY(const std::string& path) {
   const Points all = AllPoints();
+  if (all.coloured && all.rgba.size() != 4 * all.size()) return false;
   FILE* f = std::fopen(path.c_str(), "wb");
   if (!f) return false;
   std::fprintf(f, "ply\nformat binary_little_endian 1.0\ncomment static scene, TSDF zero crossings\nelement vertex %zu\n", all.size());
-  std::fprintf(f, "property float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\nproperty float nz\nproperty int weight\nend_header\n");
+  std::fprintf(f, "%s%send_header\n", kVertexProperties, all.coloured ? kColourProperties : "");
   bool ok = true;
-  for (size_t i = 0; i < all.size() && ok; ++i) ok = write_vertex(f, all, i);
+  for (size_t i = 0; i < all.size() && ok; ++i) ok = write_vertex(f, all, i, all.coloured);
   return std::fclose(f) == 0 && ok;
 }
 

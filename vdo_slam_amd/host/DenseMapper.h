@@ -26,7 +26,13 @@ class DenseMapper {
     int alignIterations = 0; float alignMaxDist = 0.f; int alignSubsample = 1, alignMinPixels = 0; bool alignApply = false;
     // Settings key Dense.Mesh (0): a mesher is made, and before the volume moves the quads that will not be wholly inside what stays are kept (Mesh below)
     bool mesh = false;
+    // Settings keys Dense.Colour (0), Dense.Colour.Band (params.trunc / 2), Dense.Colour.MaxWeight (params.max_weight), Dense.Colour.MinWeight (1): a
+    // colourer is made beside the volume (vdo_colour_*), FuseColour fuses a frame's image, and every Points this class hands out carries rgba.
+    // colourBand == 0 and colourMaxWeight == 0 stand for the defaults.
+    bool colour = false; float colourBand = 0.f; int colourMaxWeight = 0, colourMinWeight = 1;
   };
+  // The settings error of the colour fields ("" when in order): Band not positive, not finite or above params.trunc; MaxWeight, MinWeight outside 1..255
+  static std::string CheckColour(const Settings& s);
   // The settings error of the alignment fields ("" when in order): Iterations outside 0..64, MaxDist negative or not finite (0 stands for the default; the settings reader itself refuses a zero key), Subsample
   // outside 1..8, MinPixels below 6 (0 stands for the default).
   static std::string CheckAlign(const Settings& s);
@@ -44,8 +50,12 @@ class DenseMapper {
     s.margin = 128 / 8;
     return s;
   }
-  // The surface points kept on the host: xyz [n][3], the unnormalised integer gradient [n][3], the weight [n]
-  struct Points { std::vector<float> xyz; std::vector<int32_t> grad, weight; size_t size() const { return weight.size(); } };
+  // The surface points kept on the host: xyz [n][3], the unnormalised integer gradient [n][3], the weight [n] and, with settings().colour, the colour
+  // [n][4] (red, green, blue, alpha; alpha 0: no colour was fused there) - `coloured` says whether the points carry colours at all (also when there
+  // are none); rgba stays empty and coloured false when colour is off
+  struct Points { std::vector<float> xyz; std::vector<int32_t> grad, weight; std::vector<uint8_t> rgba; bool coloured = false; size_t size() const { return weight.size(); } };
+  // An image FuseColour reads: uint8, 1 (grey), 3 or 4 channels per pixel, rows `step` bytes apart, R first unless bgr; a host or a device pointer
+  struct Image { const uint8_t* data; int64_t step; int channels; bool bgr; bool device; };
 
   // A mapper for width x height depth and mask images on `ctx` (HostContext() when null).  Throws std::runtime_error when the library refuses.
   DenseMapper(vdo_ctx* ctx, int width, int height, const Settings& settings);
@@ -59,10 +69,17 @@ class DenseMapper {
   // Tcw (16 floats, world -> camera).  counts (optional): updated, masked and occluded voxels.
   void FuseFrame(const vdo_frame_images* frame, const float Tcw[16], int64_t counts[3] = nullptr);
   void Fuse(const cv::Mat& depth, const cv::Mat& mask, const float Tcw[16], int64_t counts[3] = nullptr);
+  // The colour of the frame the last FuseFrame fused, with the same pose (vdo_colour_integrate_frame, label 0: the pixels the geometry left out are
+  // left out here).  The image has the mapper's size.  counts (optional): voxels updated, skipped by the mask, skipped as outside the band.  Throws
+  // std::runtime_error unless settings().colour and the last frame came through FuseFrame (Fuse keeps nothing of its cv::Mats).
+  void FuseColour(const Image& image, const float Tcw[16], int64_t counts[3] = nullptr);
+  // What the map predicts a camera at Tcw would see, in colour: Render's depth image, then the colour of its points (vdo_colour_render) as CV_8UC4
+  // (red, green, blue, alpha; 0 without a surface or a colour).  Throws std::runtime_error unless settings().colour.
+  void RenderColour(const float Tcw[16], cv::Mat& rgba);
   // kept() followed by what is in the volume now (neither is changed)
   Points AllPoints();
-  // AllPoints() as a binary little-endian PLY: x, y, z, nx, ny, nz (float; the gradient normalised in double and narrowed, or 0) and weight (int).
-  // False when the file cannot be written.
+  // AllPoints() as a binary little-endian PLY: x, y, z, nx, ny, nz (float; the gradient normalised in double and narrowed, or 0) and weight (int);
+  // with settings().colour also red, green, blue, alpha (uchar).  False when the file cannot be written.
   bool SavePLY(const std::string& path);
   // The surface as connected triangles (vdo_mesh_extract, surface nets): the pieces kept before the moves, then the whole current volume; tri holds
   // 3 indices per triangle into v, every piece rebased by the number of vertices before it.  Pieces share no vertices; no quad is lost or doubled
@@ -71,7 +88,8 @@ class DenseMapper {
   // Mesh() as a binary little-endian PLY: the vertices as SavePLY writes its points, then `face` as uchar int lists of 3.  False when the file
   // cannot be written.
   bool SaveMeshPLY(const std::string& path);
-  // The file SaveMeshPLY writes, for any mesh (ObjectMapper::SaveMeshes writes its models with it)
+  // The file SaveMeshPLY writes, for any mesh (ObjectMapper::SaveMeshes writes its models with it); the four uchar colour properties iff v.coloured -
+  // decided once for the header and every record; false, nothing written, if v.rgba does not then hold four bytes per vertex
   static bool WriteMeshPLY(const std::string& path, const Points& v, const std::vector<int32_t>& tri);
   // The mesh of `map` for the box and mode (vdo_mesh_extract) appended to v and tri, the new indices rebased by the vertices already in v.  ONE
   // extraction when the outputs fit `guess` (vertices, triangles: what the last call of this caller needed, kept up to date here), else a second
@@ -102,6 +120,7 @@ class DenseMapper {
   void Follow(const float Tcw[16]);
   void Append(const int32_t lo[3], const int32_t hi[3], Points& to);
   void AppendMesh(const int32_t lo[3], const int32_t hi[3], int outside, Points& v, std::vector<int32_t>& tri);
+  void Colour(Points& p, size_t from);                   // with a colourer: p.rgba of the points from `from` on, sampled from the volume as it is now
   void EnsureView();
   void EnsureAligner(const float Tcw_init[16]);          // and renders the view at Tcw_init into its model
   vdo_ctx* ctx_ = nullptr;
@@ -109,6 +128,8 @@ class DenseMapper {
   vdo_raycast* view_ = nullptr;                          // made by the first Render or Align; destroyed before the map
   vdo_align* align_ = nullptr;                           // made by the first Align; destroyed before the view
   vdo_mesh* mesher_ = nullptr;                           // only with settings().mesh
+  vdo_colour* colour_ = nullptr;                         // only with settings().colour; borrows the map: destroyed before it
+  const vdo_frame_images* lastFrame_ = nullptr;          // what the last FuseFrame fused; null after Fuse
   std::vector<float> grad_;                              // [h][w][3]: the gradient image of the last Render
   Settings s_;
   int w_, h_px_;

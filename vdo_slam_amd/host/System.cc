@@ -276,6 +276,18 @@ std::string read_dense_settings(const std::string& path, const TrackingSettings&
   if (lists.count("Dense.Mesh") || (mesh != 0 && mesh != 1)) return "settings: Dense.Mesh must be 0 or 1";
   s.mesh = mesh == 1;
   ds.os.mesh = s.mesh;
+  // Dense.Colour (0): 1 fuses every frame's image beside the geometry (DenseMapper::FuseColour); Dense.Colour.Band, .MaxWeight, .MinWeight
+  const double colour = get(raw, "Dense.Colour", 0);
+  if (lists.count("Dense.Colour") || (colour != 0 && colour != 1)) return "settings: Dense.Colour must be 0 or 1";
+  s.colour = colour == 1;
+  const double band = get(raw, "Dense.Colour.Band", (double)(p.trunc / 2.f));
+  if (lists.count("Dense.Colour.Band") || !std::isfinite(band) || !(band > 0) || !((float)band > 0)) return "settings: Dense.Colour.Band must be positive";
+  const double cw[2] = {get(raw, "Dense.Colour.MaxWeight", p.max_weight), get(raw, "Dense.Colour.MinWeight", 1)};
+  static const char* cw_keys[2] = {"MaxWeight", "MinWeight"};
+  for (int k = 0; k < 2; ++k) if (lists.count(std::string("Dense.Colour.") + cw_keys[k]) || !whole(cw[k])) return std::string("settings: Dense.Colour.") + cw_keys[k] + " must be a whole number";
+  s.colourBand = (float)band; s.colourMaxWeight = (int)cw[0]; s.colourMinWeight = (int)cw[1];
+  const std::string colour_err = DenseMapper::CheckColour(s);
+  if (!colour_err.empty()) return colour_err;
   return read_dense_objects_settings(t, raw, lists, ds);
 }
 }  // namespace
@@ -437,6 +449,7 @@ cv::Mat Tracking::GrabImageRGBD(const cv::Mat& imRGB, cv::Mat& imD, const cv::Ma
   if (fc.n_recovered_masks > 0) pipe_->DownloadMask((int32_t*)maskSEM.data);      // UpdateMask writes through the shared header (Tracking.cc:3049-3068)
   if (trace_slow && since(t_call) > 5.0)
     std::fprintf(stderr, "[slow TrackRGBD f=%d] pre %.2f step %.2f depth %.2f mask(%d) %.2f ms\n", f_id, ms_pre, ms_step, ms_depth, fc.n_recovered_masks, since(t_call));
+  colour_src_ = DenseMapper::Image{imRGB.data, (int64_t)imRGB.step, imRGB.channels(), !mbRGB, false};      // the image as it was handed in
   return FinishFrame(mTcw_gt, t_call);
 }
 
@@ -523,6 +536,7 @@ cv::Mat Tracking::GrabStereoFrame(const char* who, const cv::Mat& imLeft, const 
   FrameCounts fc{};
   if (pipe_->StepDevice(d_gray, d_disp, d_flow, d_mask, false, &fc) != 0) return cv::Mat();
   if (maskSEM && fc.n_recovered_masks > 0) pipe_->DownloadMask((int32_t*)maskSEM->data);      // UpdateMask writes through the shared header, as in GrabImageRGBD
+  colour_src_ = DenseMapper::Image{d_gray, (int64_t)W, 1, false, true};            // the left grey image where the matcher keeps it
   return FinishFrame(mTcw_gt, t_call);
 }
 
@@ -590,6 +604,7 @@ cv::Mat Tracking::GrabRawStereoFrame(const char* who, const cv::Mat& imLeft, con
   FrameCounts fc{};
   if (pipe_->StepDevice(d_gray, d_disp, d_flow, d_mask, false, &fc) != 0) return cv::Mat();
   if (maskSEM && fc.n_recovered_masks > 0) pipe_->DownloadMask((int32_t*)maskSEM->data);
+  colour_src_ = DenseMapper::Image{d_gray, (int64_t)pipe_->params().width, 1, false, true};      // the rectified left grey image
   return FinishFrame(mTcw_gt, t_call);
 }
 
@@ -676,6 +691,7 @@ cv::Mat Tracking::GrabImageStereoVideo(const cv::Mat& imLeft, const cv::Mat& imR
   pipe_->SetObjectGate(labels.data(), (int)labels.size());
   FrameCounts fc{};
   if (pipe_->StepDevice(d_gray, d_disp, d_flow, d_mask, false, &fc) != 0) return cv::Mat();
+  colour_src_ = DenseMapper::Image{d_gray, (int64_t)pipe_->params().width, 1, false, true};      // the left grey image of the video entry
   return FinishFrame(mTcw_gt, t_call);
 }
 
@@ -714,6 +730,8 @@ cv::Mat Tracking::FinishFrame(const cv::Mat& mTcw_gt, std::chrono::steady_clock:
       if (dense_->settings().alignApply && dense_align_.status == 0) std::memcpy(dense_fused_, aligned, sizeof dense_fused_);
     }
     dense_->FuseFrame(pipe_->LastImages(), dense_fused_, dense_counts_);
+    // the colour of the same frame, with the pose its geometry was fused with (Dense.Colour: 1)
+    if (dense_->settings().colour) dense_->FuseColour(colour_src_, dense_fused_, colour_counts_);
     // the object models: the same images and pose, and the motions of the step that made them (FramePipeline::FinishObjects: mod_label, the label in
     // the repaired mask, the world-frame motion from the last frame).  With deferred objects the motions at hand are the last frame's: nothing is fused.
     if (objects_ && !pipe_->params().defer_objects) {
@@ -790,6 +808,7 @@ cv::Mat Tracking::GrabFilesRGBD(const std::string& rgbPath, const std::string& d
   const bool metric = mTestData != OMD && mTestData != KITTI;
   FrameCounts fc{};
   if (pipe_->StepDevice(d_gray, d_depth, d_flow, d_mask, metric, &fc) != 0) return cv::Mat();
+  colour_src_ = DenseMapper::Image{d_gray, (int64_t)pipe_->params().width, 1, false, true};      // the grey image the ingest stage decoded on the device
   return FinishFrame(mTcw_gt, t_call);
 }
 
@@ -956,6 +975,16 @@ bool System::RenderDenseView(const cv::Mat& Tcw, cv::Mat& depth, cv::Mat& normal
   float T[16];
   for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) T[4 * r + c] = Tcw.at<float>(r, c);
   d->Render(T, depth, normals);
+  return true;
+}
+
+bool System::RenderDenseColour(const cv::Mat& Tcw, cv::Mat& rgba) {
+  DenseMapper* d = mpTracker->dense();
+  if (!d || !d->settings().colour) return false;
+  if (Tcw.rows != 4 || Tcw.cols != 4 || Tcw.type() != cv::CV_32FC1) throw std::runtime_error("VDO_SLAM::System::RenderDenseColour: Tcw must be a 4 x 4 CV_32F matrix");
+  float T[16];
+  for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) T[4 * r + c] = Tcw.at<float>(r, c);
+  d->RenderColour(T, rgba);
   return true;
 }
 
@@ -1210,6 +1239,21 @@ int host_settings_check_dense_mesh(const char* path, char* msg, int cap, double*
   if (out2 && err.empty()) { out2[0] = ds.present ? 1 : 0; if (ds.present) out2[1] = ds.s.mesh ? 1 : 0; }
   return err.empty() ? 0 : 1;
 }
+// the Dense.Colour* keys as Tracking::Tracking reads them, without a GPU: 0 in order, 1 a settings error (text in msg), -2 no file.  out5 (may be null):
+// present (0 / 1: Dense.VoxelSize is in the file; the keys are read only then), Colour, Band, MaxWeight, MinWeight
+int host_settings_check_dense_colour(const char* path, char* msg, int cap, double* out5) {
+  VDO_SLAM::TrackingSettings t{};
+  std::map<std::string, double> raw;
+  if (!VDO_SLAM::read_tracking_settings(path, t, &raw)) return -2;
+  VDO_SLAM::DenseSettings ds;
+  const std::string err = VDO_SLAM::read_dense_settings(path, t, raw, ds);
+  if (msg && cap > 0) std::snprintf(msg, (size_t)cap, "%s", err.c_str());
+  if (out5 && err.empty()) {
+    out5[0] = ds.present ? 1 : 0;
+    if (ds.present) { out5[1] = ds.s.colour ? 1 : 0; out5[2] = ds.s.colourBand; out5[3] = ds.s.colourMaxWeight; out5[4] = ds.s.colourMinWeight; }
+  }
+  return err.empty() ? 0 : 1;
+}
 // the Dense.View.* keys as Tracking::Tracking reads them, without a GPU: 0 in order, 1 a settings error (text in msg), -2 no file.  out5 (may be null):
 // present (0 / 1: Dense.VoxelSize is in the file; the rest only then), Near, Step, MinWeight, the samples per ray
 int host_settings_check_dense_view(const char* path, char* msg, int cap, double* out5) {
@@ -1359,6 +1403,30 @@ int host_system_render_dense_view(VDO_SLAM::System* s, const float* Tcw, int* wh
     std::memcpy(depth, D.data, D.total() * sizeof(float));
     std::memcpy(normals, N.data, N.total() * 3 * sizeof(float));
   } catch (const std::exception& e) { std::fprintf(stderr, "host_system_render_dense_view: %s\n", e.what()); return -1; }
+  return 0;
+}
+// The colour stage of a System with Dense.Colour: 1.  counts3: the voxels the last frame coloured, skipped by the mask and skipped as outside the band
+// (Tracking::dense_colour_counts).  0, 1 without a mapper or without Dense.Colour (nothing is written), -1 on a failure
+int host_system_dense_colour_counts(VDO_SLAM::System* s, long long* counts3) {
+  try {
+    VDO_SLAM::DenseMapper* d = s->tracker()->dense();
+    if (!d || !d->settings().colour) return 1;
+    for (int k = 0; k < 3; ++k) counts3[k] = s->tracker()->dense_colour_counts()[k];
+  } catch (const std::exception& e) { std::fprintf(stderr, "host_system_dense_colour_counts: %s\n", e.what()); return -1; }
+  return 0;
+}
+// System::RenderDenseColour: Tcw [16] world -> camera; rgba [Camera.height][Camera.width][4] uint8; wh2 (may be null) receives Camera.width and
+// Camera.height, and with rgba null nothing else happens.  0, 1 without a mapper or without Dense.Colour (nothing is written), -1 on a failure
+int host_system_render_dense_colour(VDO_SLAM::System* s, const float* Tcw, int* wh2, unsigned char* rgba) {
+  try {
+    VDO_SLAM::DenseMapper* d = s->tracker()->dense();
+    if (!d || !d->settings().colour) return 1;
+    if (wh2) { wh2[0] = d->width(); wh2[1] = d->height(); }
+    if (!rgba) return 0;
+    cv::Mat T(4, 4, cv::CV_32FC1, (void*)Tcw), C;
+    if (!s->RenderDenseColour(T, C)) return 1;
+    std::memcpy(rgba, C.data, C.total() * 4);
+  } catch (const std::exception& e) { std::fprintf(stderr, "host_system_render_dense_colour: %s\n", e.what()); return -1; }
   return 0;
 }
 // the dense map of a System with Dense.* keys.  info8: the origin (3), the recentrings so far, the points kept on the host, and the updated, masked

@@ -71,6 +71,7 @@ class Tracking {
   // after the pose is known: the frame's resident depth and mask with that pose, on a context of its own.
   DenseMapper* dense() { return dense_.get(); }
   const int64_t* dense_counts() const { return dense_counts_; }      // updated, masked and occluded voxels of the last frame
+  const int64_t* dense_colour_counts() const { return colour_counts_; }      // Dense.Colour: voxels coloured, skipped by the mask, outside the band in the last frame
   // With Dense.Align.Iterations > 0: the alignment of the last frame against the map, made at the tracker's pose before the frame was fused
   // (null otherwise, and before the first frame), and the pose the frame was fused with
   const vdo_align_report* dense_alignment() const { return dense_align_valid_ ? &dense_align_ : nullptr; }
@@ -138,6 +139,8 @@ class Tracking {
   vdo_ctx* ctx_dense_ = nullptr;                         // its context (made only with the mapper)
   std::unique_ptr<ObjectMapper> objects_;                // Dense.Objects.VoxelSize present as well: a volume per tracked object, on ctx_dense_
   int64_t dense_counts_[3] = {0, 0, 0};
+  DenseMapper::Image colour_src_{};                      // Dense.Colour: the image of the frame in hand, set by every Grab* entry before FinishFrame
+  int64_t colour_counts_[3] = {0, 0, 0};                 // voxels coloured, skipped by the mask, skipped as outside the band in the last frame
   vdo_align_report dense_align_{};                       // Dense.Align.Iterations > 0: the last frame against the map
   bool dense_align_valid_ = false;
   long long dense_align_count_ = 0;
@@ -225,6 +228,17 @@ class System {
   // a ray has ceil((Dense.MaxDepth - Near) / Step) + 1 samples, at most 65536.  A non-finite value, Step <= 0, Near < 0, Near >= Dense.MaxDepth or too
   // many samples is a settings error.  False without a mapper; nothing of the map or of the tracker changes.
   bool RenderDenseView(const cv::Mat& Tcw, cv::Mat& depth, cv::Mat& normals);
+  // A coloured dense map.  Settings keys, all optional and read only with Dense.VoxelSize: Dense.Colour (0 or 1, default 0; another value is a settings
+  // error with every sensor); Dense.Colour.Band (Dense.Truncation / 2; positive, at most Dense.Truncation), the distance in metres of z-depth from the
+  // measured surface within which a voxel takes the pixel's colour; Dense.Colour.MaxWeight (Dense.MaxWeight; 1..255), the cap of the running mean's
+  // weight; Dense.Colour.MinWeight (1; 1..255), the smallest colour weight of a voxel that counts when a colour is read.  With Dense.Colour: 1 every
+  // Track* entry fuses its image after the frame's geometry, with the same pose: TrackRGBD the image it was handed (Camera.RGB says which channel
+  // comes first), the stereo entries the left grey image, the files entry the grey image decoded on the device.  SaveDenseMap and SaveDenseMesh then
+  // write red, green, blue, alpha (uchar) after weight; alpha is the share of the trilinear weight that had colour, 0 where none was fused.  What
+  // leaves the volume is coloured before it leaves.  The object models stay uncoloured.  Without the key every file keeps today's bytes.
+  // RenderDenseColour: RenderDenseView's depth image at Tcw, then the colour of its points as CV_8UC4 (red, green, blue, alpha).  False without a
+  // mapper or without Dense.Colour.
+  bool RenderDenseColour(const cv::Mat& Tcw, cv::Mat& rgba);
   // How far a pose is from the geometry in the map (DenseMapper::Align, vdo_align_solve): imD (CV_32FC1 metres) and mask (CV_32SC1 or empty) of the
   // camera's image size are aligned by point-to-plane ICP against the map's view at Tcw (4 x 4 CV_32F, world -> camera); Tcw_out receives the refined
   // pose (Tcw itself unless LastDenseAlignment's status is 0).  False without a mapper; nothing of the map or of the tracker changes.  Settings keys,

@@ -304,6 +304,33 @@ class System:
             raise K.VdoError("System.render_dense_view failed")
         return d, n
 
+    def dense_colour_counts(self):
+        """With ``Dense.Colour: 1``: the voxels the last frame (coloured, skipped by the mask, skipped as outside the band); None without a mapper or
+        without the key."""
+        L = self._L
+        L.host_system_dense_colour_counts.argtypes = [C.c_void_p, C.c_void_p]
+        out = np.zeros(3, np.int64)
+        rc = L.host_system_dense_colour_counts(self._h, _ptr(out))
+        if rc == 1:
+            return None
+        if rc != 0:
+            raise K.VdoError("System.dense_colour_counts failed")
+        return tuple(int(v) for v in out)
+
+    def render_dense_colour(self, T):
+        """System::RenderDenseColour: the colour image that belongs to ``render_dense_view(T)``'s depth image: rgba [h, w, 4] uint8 (alpha 0 where there
+        is no surface or no colour), or None when the system has no mapper or no ``Dense.Colour: 1``."""
+        L = self._L
+        L.host_system_render_dense_colour.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        Tc = np.ascontiguousarray(np.asarray(T, np.float32).reshape(16))
+        wh = np.zeros(2, np.int32)
+        if L.host_system_render_dense_colour(self._h, _ptr(Tc), _ptr(wh), None) == 1:
+            return None
+        rgba = np.zeros((int(wh[1]), int(wh[0]), 4), np.uint8)
+        if L.host_system_render_dense_colour(self._h, _ptr(Tc), _ptr(wh), _ptr(rgba)) != 0:
+            raise K.VdoError("System.render_dense_colour failed")
+        return rgba
+
     @staticmethod
     def _align_report(r):
         return dict(iterations=int(r[0]), status=int(r[1]), used=int(r[2]), rms_first=float(r[3]), rms_last=float(r[4]), xi=r[5:11].copy())
