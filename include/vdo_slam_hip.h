@@ -1512,6 +1512,66 @@ int vdo_colour_set_voxels_per_thread(vdo_colour* h, int voxels);
 /* The last integrate, sample or render: ms[0] wall time of the call, ms[1] device time from the first command to the end of the last kernel. */
 int vdo_colour_last_timing(vdo_colour* h, double ms[2]);
 
+/* ---- Distance field: exact Euclidean clearance from a TSDF volume ------------------------------------------------------------------------
+ * New (the reference keeps no dense map): how far a voxel of a vdo_dense - the static map or an object's volume - is from the mapped surface, as
+ * the exact squared Euclidean distance, in voxels, to the nearest voxel at a zero crossing, and whether the voxel is free, inside or unknown.  The
+ * TSDF itself cannot say: it is truncated, projective and 0 where nothing was seen.  Integer from end to end; the map is read only.  Notation as
+ * above: the volume covers the global voxels o_a <= g_a < o_a + n_a, words t (int16) and w, cyclic slots.
+ *
+ * Valid, site, state.  min_weight 1..255.  A voxel is VALID iff w >= min_weight.  A valid voxel a is a SITE iff some 6-neighbour b = a +- e_k lies
+ *   inside the VOLUME (not the box), is valid, and (ta < 0) != (tb < 0): the two ends of exactly the lattice edges Extract and the Mesher call
+ *   crossings.  The STATE of a voxel: 0 unknown (not valid), 1 free (valid, t >= 0), 2 inside (valid, t < 0).
+ * Field.  A box [lo, hi) in global voxels, clipped to the volume, as Extract takes it; radius R 1..8191 voxels.  One uint32 per voxel of the CLIPPED
+ *   box in the order z, y, x (x fastest) - box order, not slot order: the field does not wrap.
+ *      bits 0-27   d2: the smallest dx^2 + dy^2 + dz^2 (voxels^2) to a site INSIDE THE BOX if that is <= R^2, else FAR = 0x0FFFFFFF
+ *      bits 28-29  the state
+ *      bits 30-31  0
+ *   d2 is exact: d2 == 0 iff the voxel is a site; d2 == R^2 is kept, R^2 + 1 is FAR.  Only the distance is stored, so ties between sites cannot
+ *   show.  Sites outside the box do not count: a caller that wants the field exact up to R in a region pads its box by R.  3 * 4095^2 < 2^26 and
+ *   8191^2 < 2^27: nothing overflows the 28 bits, and R >= 7093 caps nothing.
+ * Snapshot.  The handle keeps the last field on the device with its clipped box in GLOBAL voxels and the map's voxel size.  Later integrations or
+ *   moves of the map do not touch it; a sample after a recentre still names the right voxel.  An empty box, or one outside the volume, gives an
+ *   empty snapshot: counts (0, 0, 0), and every sample is outside.
+ * Sample.  A world point p (3 floats).  Per axis a:
+ *      u = p_a / voxel;  b = floorf(u)                          (one rounded operation per step, no contraction)
+ *      outside unless p_a is finite and -4194304.0f <= b <= 4194303.0f, compared as floats before any conversion to int;  then g_a = (int)b
+ *   The result is the field word of g if g lies in the snapshot's box, else VDO_DISTANCE_OUTSIDE.  NO OUT-OF-RANGE READS: no address is formed
+ *   before the compares have passed.
+ * No result depends on launch shape, method, schedule or the slot alignment of the cyclic volume. */
+#define VDO_DISTANCE_FAR 0x0FFFFFFFu
+#define VDO_DISTANCE_OUTSIDE 0xFFFFFFFFu
+#define VDO_DISTANCE_WINDOW 262144     /* the points one window of a host sample holds on the device (16 bytes each) */
+typedef struct vdo_distance vdo_distance;
+typedef struct vdo_distance_params {
+  int32_t n[3];                     /* 1..4096 each, nx * ny * nz <= 2^31: the handle serves every clipped box with no more voxels than that product */
+} vdo_distance_params;
+/* ALL device memory is taken here (the field and one buffer of the same size for the passes, 4 bytes per voxel each; one site bit per voxel; the
+ * counters; the sample window); the other entries allocate nothing.  One handle serves any vdo_dense of the same context: the static map and all
+ * object volumes can share one.  VDO_ERR_INVALID, the message naming the argument: a null pointer, a size < 1.  VDO_ERR_UNSUPPORTED beyond the dense
+ * mapper's limits (a side above 2^12, more than 2^31 voxels).  VDO_ERR_OOM when the device has no room. */
+int vdo_distance_create(vdo_ctx* ctx, const vdo_distance_params* params, vdo_distance** out);
+int vdo_distance_destroy(vdo_distance* h);
+/* The field of `map` for the box, host-synchronous on the context's stream; it becomes the snapshot.  counts (host): sites in the box, voxels with
+ * d2 != FAR, voxels of the clipped box.  VDO_ERR_INVALID, the message naming the argument, and then NOTHING is written and the previous snapshot
+ * stays: a null handle, map, lo, hi or counts; min_weight outside 1..255; radius outside 1..8191; a map of another context; a clipped box with more
+ * voxels than the handle holds. */
+int vdo_distance_compute(vdo_distance* h, vdo_dense* map, const int32_t lo[3], const int32_t hi[3], int min_weight, int radius, int64_t counts[3]);
+/* The snapshot, a plain copy: its words (host, or device when out_is_device != 0; may be NULL) and its clipped box (host; each may be NULL; an empty
+ * snapshot has lo = hi = 0).  VDO_ERR_INVALID for a null handle and before the first compute. */
+int vdo_distance_get(vdo_distance* h, uint32_t* words, int out_is_device, int32_t lo[3], int32_t hi[3]);
+/* The snapshot at n world points: xyz float [n][3] in, words uint32 [n] out, both host pointers (through the window of VDO_DISTANCE_WINDOW points) or
+ * both device pointers when is_device != 0.  *n_inside (host): the points that fell inside the box.  Before the first compute every point is
+ * outside.  VDO_ERR_INVALID, the message naming the argument, and then NOTHING is written: a null handle or n_inside; n < 0; a null xyz or words
+ * with n > 0. */
+int vdo_distance_sample(vdo_distance* h, int64_t n, const float* xyz, uint32_t* words, int is_device, int64_t* n_inside);
+/* The snapshot where it lives (a device pointer owned by the handle, valid until the next compute). */
+int vdo_distance_device_field(vdo_distance* h, uint32_t** words);
+/* How the y and z passes find their minima: 1 a windowed minimum over |q - p| <= R, 2 the lower envelope of parabolas, 0 (the default) the
+ * handle's own choice between them.  No result depends on it.  VDO_ERR_INVALID for another value. */
+int vdo_distance_set_method(vdo_distance* h, int method);
+/* The last compute or sample: ms[0] wall time of the call, ms[1] device time from the first command to the end of the last kernel. */
+int vdo_distance_last_timing(vdo_distance* h, double ms[2]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,9 +34,20 @@ DenseMapper::DenseMapper(vdo_ctx* ctx, int width, int height, const Settings& se
     }
     kept_.coloured = keptMeshV_.coloured = true;            // what is copied from them and appended to carries colours, also while it is empty
   }
+  if (s_.distance) {
+    if (s_.distanceMinWeight == 0) s_.distanceMinWeight = s_.minWeight;
+    const std::string err = CheckDistance(s_);
+    const vdo_distance_params dp{{s_.params.n[0], s_.params.n[1], s_.params.n[2]}};
+    if (!err.empty() || vdo_distance_create(ctx_, &dp, &dist_) != VDO_OK) {
+      vdo_colour_destroy(colour_); vdo_mesh_destroy(mesher_); vdo_dense_destroy(h_);
+      if (!err.empty()) throw std::runtime_error("VDO_SLAM::DenseMapper: " + err);
+      die("vdo_distance_create");
+    }
+  }
 }
 
 DenseMapper::~DenseMapper() {
+  vdo_distance_destroy(dist_);
   vdo_colour_destroy(colour_);                            // the colourer borrows the map
   vdo_mesh_destroy(mesher_);
   vdo_align_destroy(align_);
@@ -77,6 +88,43 @@ std::string DenseMapper::CheckColour(const Settings& s) {
   if (s.colourMaxWeight < 1 || s.colourMaxWeight > 255) return "settings: Dense.Colour.MaxWeight outside 1..255";
   if (s.colourMinWeight < 1 || s.colourMinWeight > 255) return "settings: Dense.Colour.MinWeight outside 1..255";
   return "";
+}
+
+int DenseMapper::DistanceRadiusVoxels(const Settings& s) {
+  if (!std::isfinite(s.distanceRadius) || !(s.distanceRadius > 0.f)) return 0;
+  const double v = std::ceil((double)s.distanceRadius / (double)s.params.voxel);
+  return v >= 1.0 && v <= 8191.0 ? (int)v : 0;
+}
+
+std::string DenseMapper::CheckDistance(const Settings& s) {
+  if (!std::isfinite(s.distanceRadius) || !(s.distanceRadius > 0.f)) return "settings: Dense.Distance.Radius must be positive";
+  if (DistanceRadiusVoxels(s) == 0) return "settings: Dense.Distance.Radius outside 1..8191 voxels of Dense.VoxelSize";
+  if (s.distanceMinWeight != 0 && (s.distanceMinWeight < 1 || s.distanceMinWeight > 255)) return "settings: Dense.Distance.MinWeight outside 1..255";
+  return "";
+}
+
+void DenseMapper::Distance(const int32_t lo[3], const int32_t hi[3], int64_t counts[3]) {
+  if (!dist_) throw std::runtime_error("VDO_SLAM::DenseMapper: Distance without Dense.Distance");
+  const bool whole = !lo && !hi;
+  int32_t o[3], wlo[3], whi[3];
+  if (whole) {
+    origin(o);
+    for (int a = 0; a < 3; ++a) { wlo[a] = o[a]; whi[a] = o[a] + s_.params.n[a]; }
+  } else if (!lo || !hi) {
+    throw std::runtime_error("VDO_SLAM::DenseMapper: Distance takes both corners of a box or neither");
+  }
+  int64_t out[3] = {0, 0, 0};
+  if (vdo_distance_compute(dist_, h_, whole ? wlo : lo, whole ? whi : hi, s_.distanceMinWeight, DistanceRadiusVoxels(s_), out) != VDO_OK) die("vdo_distance_compute");
+  ++distComputes_;
+  distGeneration_ = whole ? generation_ : 0;
+  if (counts) for (int k = 0; k < 3; ++k) counts[k] = out[k];
+}
+
+void DenseMapper::Clearance(const float* xyz, int64_t n, uint32_t* words) {
+  if (!dist_) throw std::runtime_error("VDO_SLAM::DenseMapper: Clearance without Dense.Distance");
+  if (distGeneration_ != generation_) Distance(nullptr, nullptr);
+  int64_t inside = 0;
+  if (vdo_distance_sample(dist_, n, xyz, words, 0, &inside) != VDO_OK) die("vdo_distance_sample");
 }
 
 int DenseMapper::AlignMinPixels(const Settings& s, int width, int height) {
@@ -239,12 +287,14 @@ void DenseMapper::Follow(const float Tcw[16]) {
   }
   if (vdo_dense_recenter(h_, want) != VDO_OK) die("vdo_dense_recenter");
   started_ = true;
+  ++generation_;
 }
 
 void DenseMapper::FuseFrame(const vdo_frame_images* frame, const float Tcw[16], int64_t counts[3]) {
   Follow(Tcw);
   int64_t out[3] = {0, 0, 0};
   if (vdo_dense_integrate_frame(h_, frame, Tcw, out) != VDO_OK) die("vdo_dense_integrate_frame");
+  ++generation_;
   lastFrame_ = frame;
   if (counts) for (int k = 0; k < 3; ++k) counts[k] = out[k];
 }
@@ -258,6 +308,7 @@ void DenseMapper::Fuse(const cv::Mat& depth, const cv::Mat& mask, const float Tc
   if (vdo_dense_integrate(h_, (const float*)depth.data, (int64_t)(depth.step / 4), mask.empty() ? nullptr : (const int32_t*)mask.data, mask.empty() ? 0 : (int64_t)(mask.step / 4), 0, Tcw,
                           out) != VDO_OK)
     die("vdo_dense_integrate");
+  ++generation_;
   lastFrame_ = nullptr;
   if (counts) for (int k = 0; k < 3; ++k) counts[k] = out[k];
 }

@@ -30,7 +30,15 @@ class DenseMapper {
     // colourer is made beside the volume (vdo_colour_*), FuseColour fuses a frame's image, and every Points this class hands out carries rgba.
     // colourBand == 0 and colourMaxWeight == 0 stand for the defaults.
     bool colour = false; float colourBand = 0.f; int colourMaxWeight = 0, colourMinWeight = 1;
+    // Settings keys Dense.Distance (0), Dense.Distance.Radius (2.0 metres), Dense.Distance.MinWeight (minWeight; 0 stands for it): a distance field
+    // of the volume's size is made (vdo_distance_*) and Distance and Clearance serve it.  Nothing runs per frame.
+    bool distance = false; float distanceRadius = 2.f; int distanceMinWeight = 0;
   };
+  // The radius in voxels: ceil(distanceRadius / voxel) in double; 0 when that is not a number in 1..8191
+  static int DistanceRadiusVoxels(const Settings& s);
+  // The settings error of the distance fields ("" when in order): Radius not positive or not finite, or outside 1..8191 voxels; MinWeight outside
+  // 1..255 (0 stands for minWeight)
+  static std::string CheckDistance(const Settings& s);
   // The settings error of the colour fields ("" when in order): Band not positive, not finite or above params.trunc; MaxWeight, MinWeight outside 1..255
   static std::string CheckColour(const Settings& s);
   // The settings error of the alignment fields ("" when in order): Iterations outside 0..64, MaxDist negative or not finite (0 stands for the default; the settings reader itself refuses a zero key), Subsample
@@ -108,6 +116,15 @@ class DenseMapper {
   // the map changes.
   void Align(const cv::Mat& depth, const cv::Mat& mask, const float Tcw_init[16], float Tcw_out[16], vdo_align_report* report = nullptr);
   void AlignFrame(const vdo_frame_images* frame, const float Tcw_init[16], float Tcw_out[16], vdo_align_report* report = nullptr);
+  // The distance field of the box [lo, hi) (global voxels, clipped to the volume; both null: the whole current volume) with the settings' radius and
+  // weight (vdo_distance_compute); it becomes the snapshot Clearance samples until the map changes.  counts (optional): sites, voxels within the
+  // radius, voxels of the clipped box.  Throws std::runtime_error unless settings().distance.
+  void Distance(const int32_t lo[3], const int32_t hi[3], int64_t counts[3] = nullptr);
+  // The field words (include/vdo_slam_hip.h, "Distance field") of n world points xyz [n][3].  The whole current volume's field is computed first if
+  // the map was fused or moved since the last whole-volume field (a generation counter that Fuse, FuseFrame and a move bump), or if the snapshot is
+  // a box of Distance's; two calls with nothing in between compute once.  Throws std::runtime_error unless settings().distance.
+  void Clearance(const float* xyz, int64_t n, uint32_t* words);
+  int distanceComputes() const { return distComputes_; } // the fields computed so far
   const Points& kept() const { return kept_; }
   int recenters() const { return recenters_; }
   void origin(int32_t out[3]) const;
@@ -129,6 +146,9 @@ class DenseMapper {
   vdo_align* align_ = nullptr;                           // made by the first Align; destroyed before the view
   vdo_mesh* mesher_ = nullptr;                           // only with settings().mesh
   vdo_colour* colour_ = nullptr;                         // only with settings().colour; borrows the map: destroyed before it
+  vdo_distance* dist_ = nullptr;                         // only with settings().distance; destroyed before the map
+  uint64_t generation_ = 1, distGeneration_ = 0;         // bumped by every fusion and move; the generation the whole-volume field was computed at (0: none)
+  int distComputes_ = 0;
   const vdo_frame_images* lastFrame_ = nullptr;          // what the last FuseFrame fused; null after Fuse
   std::vector<float> grad_;                              // [h][w][3]: the gradient image of the last Render
   Settings s_;

@@ -62,6 +62,12 @@ class ObjectMapper {
   int dropped() const { return dropped_; }
   int skipped() const { return skipped_; }
   int live() const { return (int)live_.size(); }
+  // (mod_label, Two) of every live model, in their order; nothing is extracted
+  std::vector<std::pair<int, Pose> > LivePoses() const {
+    std::vector<std::pair<int, Pose> > out;
+    for (const Live& l : live_) out.emplace_back(l.mod_label, l.Two);
+    return out;
+  }
   const int64_t* last_stats() const { return stats_.data(); }     // [(maxLabels + 1)][8] of the last frame
   vdo_objects* handle() { return stage_; }
   const Settings& settings() const { return s_; }

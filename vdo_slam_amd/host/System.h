@@ -239,6 +239,17 @@ class System {
   // RenderDenseColour: RenderDenseView's depth image at Tcw, then the colour of its points as CV_8UC4 (red, green, blue, alpha).  False without a
   // mapper or without Dense.Colour.
   bool RenderDenseColour(const cv::Mat& Tcw, cv::Mat& rgba);
+  // How much room a point has to the static scene (DenseMapper::Clearance, vdo_distance_*): the exact Euclidean distance to the nearest voxel at a zero
+  // crossing of the map.  Settings keys, all optional and read only with Dense.VoxelSize: Dense.Distance (0 or 1, default 0; another value is a
+  // settings error with every sensor); Dense.Distance.Radius (2.0 metres; positive and finite, ceil(Radius / Dense.VoxelSize) in 1..8191 voxels), the
+  // distance beyond which a point is simply far; Dense.Distance.MinWeight (Dense.MinWeight; 1..255), the smallest weight of a voxel that counts.
+  // Nothing runs per frame: the field of the whole current volume is computed when a query finds the map fused or moved since the last one.
+  // DenseClearance: points n x 3 CV_32F in the world frame; metres CV_32FC1 n x 1, the distance (+inf beyond the radius, NaN for a point outside the
+  // volume); state CV_8UC1 n x 1, 0 unknown, 1 free, 2 inside a surface, 255 outside the volume.  False without a mapper or without Dense.Distance.
+  bool DenseClearance(const cv::Mat& points, cv::Mat& metres, cv::Mat& state);
+  // For every live model of the object mapper: (mod_label, the clearance in metres at the world position of the model's origin - the translation of
+  // its current Two), in the models' order.  False without Dense.Distance or without an object mapper.
+  bool ObjectClearances(std::vector<std::pair<int, float> >& out);
   // How far a pose is from the geometry in the map (DenseMapper::Align, vdo_align_solve): imD (CV_32FC1 metres) and mask (CV_32SC1 or empty) of the
   // camera's image size are aligned by point-to-plane ICP against the map's view at Tcw (4 x 4 CV_32F, world -> camera); Tcw_out receives the refined
   // pose (Tcw itself unless LastDenseAlignment's status is 0).  False without a mapper; nothing of the map or of the tracker changes.  Settings keys,

@@ -331,6 +331,36 @@ class System:
             raise K.VdoError("System.render_dense_colour failed")
         return rgba
 
+    def dense_clearance(self, points):
+        """System::DenseClearance with ``Dense.Distance: 1``: how much room world points [n, 3] have to the static scene -> (metres float32 [n]: the
+        exact Euclidean distance to the nearest voxel at a zero crossing, +inf beyond ``Dense.Distance.Radius``, NaN outside the volume; state uint8 [n]:
+        0 unknown, 1 free, 2 inside, 255 outside the volume), or None when the system has no mapper or no ``Dense.Distance: 1``.  The field is computed
+        when the map was fused or moved since the last query; ``self.distance_computes`` is the number of fields computed so far."""
+        L = self._L
+        L.host_system_dense_clearance.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        p = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))
+        m = np.zeros(len(p), np.float32); st = np.zeros(len(p), np.uint8); computes = np.zeros(1, np.int64)
+        rc = L.host_system_dense_clearance(self._h, len(p), _ptr(p), _ptr(m), _ptr(st), _ptr(computes))
+        if rc == 1:
+            return None
+        if rc != 0:
+            raise K.VdoError("System.dense_clearance failed")
+        self.distance_computes = int(computes[0])
+        return m, st
+
+    def object_clearances(self):
+        """System::ObjectClearances: [(mod_label, metres)] for every live object model - the clearance at the world position of the model's origin -, or
+        None without ``Dense.Distance: 1`` or without an object mapper."""
+        L = self._L
+        L.host_system_object_clearances.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        labels = np.zeros(64, np.int32); m = np.zeros(64, np.float32); count = np.zeros(1, np.int32)
+        rc = L.host_system_object_clearances(self._h, 64, _ptr(labels), _ptr(m), _ptr(count))
+        if rc == 1:
+            return None
+        if rc != 0:
+            raise K.VdoError("System.object_clearances failed")
+        return [(int(labels[i]), m[i]) for i in range(min(64, int(count[0])))]
+
     @staticmethod
     def _align_report(r):
         return dict(iterations=int(r[0]), status=int(r[1]), used=int(r[2]), rms_first=float(r[3]), rms_last=float(r[4]), xi=r[5:11].copy())
