@@ -9,12 +9,12 @@
 //                        test - a shell of 2 * band around the surfaces against the whole frustum -, so the colour word is NOT loaded up front as
 //                        k_dn_integrate loads its TSDF word: only a voxel that reaches the running mean reads it, and writes it only when it changed.
 //                        The three counts as there: wave ballots, LDS, one 64-bit integer atomic per workgroup and counter on one of 1024 copies.
-//   k_cl_clear           follow: the slots of ONE leaving slab are set to 0 (the rule and the shape of k_dn_clear).
+//   (follow)             dense.hip's dn_queue_move on the colour words: the mapper's own rule and its k_dn_clear.
 //   k_cl_sample          one thread per point: up to eight gathered words, integer trilinear weights.
 //   k_cl_render          one thread per pixel of a window of a depth image: the raycaster's point, then the same sample.
 //
 // NO OUT-OF-RANGE ACCESS: the gathered pixel comes from float compares against 0 and W - 1 / H - 1 made before any conversion to int (a NaN fails
-// them); a sample's base cell is converted to int only after float compares against +-2^22, and a corner is turned into slots only after its integer
+// them); a sample's base cell is converted to int only after dn_indexable, and a corner is turned into slots only after its integer
 // tests against o and o + n; a point or pixel is read and written only inside its window.
 #include <hip/hip_runtime.h>
 
@@ -121,18 +121,6 @@ __global__ __launch_bounds__(256) void k_cl_integrate(DnArgs a, ClFuse cf, const
   }
 }
 
-// the slab of `len` slots from slot s0 on (cyclic) on `axis`, whole on the other two axes
-__global__ __launch_bounds__(256) void k_cl_clear(uint32_t* __restrict__ col, int nx, int ny, int nz, int axis, int s0, int len) {
-  const int lx = axis == 0 ? len : nx, ly = axis == 1 ? len : ny, lz = axis == 2 ? len : nz;
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (long long)lx * ly * lz) return;
-  int x = (int)(i % lx), y = (int)((i / lx) % ly), z = (int)(i / ((long long)lx * ly));
-  if (axis == 0) { x += s0; if (x >= nx) x -= nx; }
-  if (axis == 1) { y += s0; if (y >= ny) y -= ny; }
-  if (axis == 2) { z += s0; if (z >= nz) z -= nz; }
-  col[((size_t)z * ny + y) * nx + x] = 0u;
-}
-
 // the colour of the world point p: R | G << 8 | B << 16 | alpha << 24, 0 when no corner counts
 __device__ __forceinline__ uint32_t cl_sample(const ClVol& v, const uint32_t* __restrict__ col, const float p[3], int min_w) {
   int b[3], fi[3];
@@ -141,7 +129,7 @@ __device__ __forceinline__ uint32_t cl_sample(const ClVol& v, const uint32_t* __
     float u = p[k] / v.voxel;
     u = u - 0.5f;
     const float fl = floorf(u), f = u - fl;
-    if (!(dn_finite(p[k]) && fl >= -4194304.0f && fl <= 4194303.0f)) return 0u;
+    if (!dn_indexable(p[k], fl)) return 0u;
     b[k] = (int)fl; fi[k] = (int)floorf(f * 256.0f);
   }
   // per axis and offset: the slot, or -1 outside the volume, and the axis weight
@@ -152,7 +140,7 @@ __device__ __forceinline__ uint32_t cl_sample(const ClVol& v, const uint32_t* __
     for (int d = 0; d < 2; ++d) {
       const int g = b[k] + d;
       int s = -1;
-      if (g >= v.o[k] && g < v.o[k] + v.n[k]) { s = v.om[k] + (g - v.o[k]); if (s >= v.n[k]) s -= v.n[k]; }
+      if (g >= v.o[k] && g < v.o[k] + v.n[k]) s = dn_slot(g - v.o[k], v.om[k], v.n[k]);
       slot[k][d] = s; aw[k][d] = d ? fi[k] : 256 - fi[k];
     }
   long long S = 0, C[3] = {0, 0, 0};
@@ -239,8 +227,7 @@ struct vdo_colour {
   uint32_t* d_col = nullptr;                              // [nz][ny][nx] words in slot order
   uint32_t* d_img = nullptr;                              // [H][W] packed R | G << 8 | B << 16
   uint8_t* d_src = nullptr;                               // [H][W * 4] staging of a host image
-  unsigned long long* d_cnt = nullptr;                    // [kDnSlots][kDnCounters]
-  unsigned long long* h_cnt = nullptr;                    // pinned
+  vdo::SlotCounts cnt;                                    // [kDnSlots][kDnCounters]
   float* d_xyz = nullptr;                                 // [stage_points][3]: a window of host points, or [stage_points] of a host depth image
   uint32_t* d_rgba = nullptr;                             // [stage_points]
   vdo::StageTimer tm;
@@ -249,34 +236,16 @@ struct vdo_colour {
 using namespace vdo;
 
 static void cl_free(vdo_colour* h) {
-  hipFree(h->d_col); hipFree(h->d_img); hipFree(h->d_src); hipFree(h->d_cnt); hipFree(h->d_xyz); hipFree(h->d_rgba);
-  if (h->h_cnt) hipHostFree(h->h_cnt);
+  hipFree(h->d_col); hipFree(h->d_img); hipFree(h->d_src); hipFree(h->d_xyz); hipFree(h->d_rgba);
+  h->cnt.destroy();
   h->tm.destroy();
   delete h;
 }
 
-static int cl_mod(int g, int n) { const int m = g % n; return m < 0 ? m + n : m; }
-
 // Queues what brings the colour volume to the map's present origin: nothing when it has not moved
 static void cl_follow(vdo_colour* h, hipStream_t s) {
-  const int* n = h->map->a.n;
-  const int* mo = h->map->a.o;
-  int64_t d[3];
-  bool all = false, any = false;
-  for (int k = 0; k < 3; ++k) { d[k] = (int64_t)mo[k] - h->o[k]; all = all || d[k] >= n[k] || -d[k] >= n[k]; any = any || d[k] != 0; }
-  if (!any) return;
-  if (all) {
-    hipMemsetAsync(h->d_col, 0, (size_t)h->map->nvox * sizeof(uint32_t), s);
-  } else {
-    for (int k = 0; k < 3; ++k) {
-      if (d[k] == 0) continue;
-      // leaving: the first d voxels of the axis when the volume moved up, the last -d when it moved down
-      const int len = (int)(d[k] > 0 ? d[k] : -d[k]), g0 = d[k] > 0 ? h->o[k] : h->o[k] + n[k] - len;
-      const long long cells = (long long)len * (h->map->nvox / n[k]);
-      hipLaunchKernelGGL(k_cl_clear, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, h->d_col, n[0], n[1], n[2], k, cl_mod(g0, n[k]), len);
-    }
-  }
-  for (int k = 0; k < 3; ++k) h->o[k] = mo[k];
+  dn_queue_move(s, h->d_col, h->map->a.n, h->map->nvox, h->o, h->map->a.o);
+  for (int k = 0; k < 3; ++k) h->o[k] = h->map->a.o[k];
 }
 
 static ClVol cl_vol(const vdo_colour* h) {
@@ -284,13 +253,6 @@ static ClVol cl_vol(const vdo_colour* h) {
   v.voxel = h->map->a.voxel;
   for (int k = 0; k < 3; ++k) { v.n[k] = h->map->a.n[k]; v.o[k] = h->map->a.o[k]; v.om[k] = h->map->a.om[k]; }
   return v;
-}
-
-// the sum of counter k over its copies, after the download
-static int64_t cl_sum(const vdo_colour* h, int k) {
-  unsigned long long sum = 0;
-  for (int slot = 0; slot < kDnSlots; ++slot) sum += h->h_cnt[slot * kDnCounters + k];
-  return (int64_t)sum;
 }
 
 static int cl_check_image(const char* who, int W, const uint8_t* image, int64_t stride, int channels, int rgb_order) {
@@ -304,7 +266,7 @@ static int cl_check_image(const char* who, int W, const uint8_t* image, int64_t 
 template <int VPT>
 static void cl_launch_integrate(vdo_colour* h, hipStream_t s, const DnArgs& a, const ClFuse& cf, const float* depth, const int32_t* mask) {
   const dim3 grid((a.n[0] + 63) / 64, (a.n[1] + VPT - 1) / VPT, (a.n[2] + kDnZ - 1) / kDnZ);
-  hipLaunchKernelGGL(k_cl_integrate<VPT>, grid, dim3(64, 1, kDnZ), 0, s, a, cf, depth, mask, (const uint32_t*)h->d_img, h->map->W, h->map->H, h->d_col, h->d_cnt);
+  hipLaunchKernelGGL(k_cl_integrate<VPT>, grid, dim3(64, 1, kDnZ), 0, s, a, cf, depth, mask, (const uint32_t*)h->d_img, h->map->W, h->map->H, h->d_col, h->cnt.d);
 }
 
 // what the two integrate entries share, from the follow on; depth and mask are packed device images
@@ -322,7 +284,7 @@ static int cl_integrate(const char* who, vdo_colour* h, const float* d_depth, co
   DnArgs a = h->map->a;
   for (int k = 0; k < 12; ++k) a.T[k] = T[k];
   const ClFuse cf{h->p.band, h->p.max_weight, label};
-  hipMemsetAsync(h->d_cnt, 0, kDnTotal * sizeof(unsigned long long), s);
+  h->cnt.zero(s);
   switch (h->vpt) {
     case 1: cl_launch_integrate<1>(h, s, a, cf, d_depth, d_mask); break;
     case 2: cl_launch_integrate<2>(h, s, a, cf, d_depth, d_mask); break;
@@ -330,10 +292,10 @@ static int cl_integrate(const char* who, vdo_colour* h, const float* d_depth, co
     default: cl_launch_integrate<4>(h, s, a, cf, d_depth, d_mask); break;
   }
   h->tm.mark_end(s);
-  hipMemcpyAsync(h->h_cnt, h->d_cnt, kDnTotal * sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
+  h->cnt.download(s);
   const int rc = sync_check(who, s);
   if (rc != VDO_OK) return rc;
-  for (int k = 0; k < 3; ++k) out[k] = cl_sum(h, k);
+  for (int k = 0; k < 3; ++k) out[k] = h->cnt.sum(k);
   h->tm.finish(t0);
   return VDO_OK;
 }
@@ -354,9 +316,8 @@ extern "C" int vdo_colour_create(vdo_dense* map, const vdo_colour_params* p, vdo
   for (int k = 0; k < 3; ++k) h->o[k] = map->a.o[k];
   const size_t npix = (size_t)map->W * map->H, sp = (size_t)p->stage_points, nvox = (size_t)map->nvox;
   const bool ok = hipMalloc((void**)&h->d_col, nvox * sizeof(uint32_t)) == hipSuccess && hipMalloc((void**)&h->d_img, npix * sizeof(uint32_t)) == hipSuccess &&
-                  hipMalloc((void**)&h->d_src, npix * 4) == hipSuccess && hipMalloc((void**)&h->d_cnt, kDnTotal * sizeof(unsigned long long)) == hipSuccess &&
-                  hipMalloc((void**)&h->d_xyz, sp * 3 * sizeof(float)) == hipSuccess && hipMalloc((void**)&h->d_rgba, sp * sizeof(uint32_t)) == hipSuccess &&
-                  hipHostMalloc((void**)&h->h_cnt, kDnTotal * sizeof(unsigned long long), hipHostMallocDefault) == hipSuccess && h->tm.create() &&
+                  hipMalloc((void**)&h->d_src, npix * 4) == hipSuccess && h->cnt.create(kDnSlots, kDnCounters) &&
+                  hipMalloc((void**)&h->d_xyz, sp * 3 * sizeof(float)) == hipSuccess && hipMalloc((void**)&h->d_rgba, sp * sizeof(uint32_t)) == hipSuccess && h->tm.create() &&
                   hipMemsetAsync(h->d_col, 0, nvox * sizeof(uint32_t), map->ctx->stream) == hipSuccess && hipStreamSynchronize(map->ctx->stream) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
@@ -430,7 +391,7 @@ extern "C" int vdo_colour_sample(vdo_colour* h, int64_t n, const float* xyz, int
   const auto t0 = h->tm.begin(s);
   cl_follow(h, s);
   const ClVol v = cl_vol(h);
-  hipMemsetAsync(h->d_cnt, 0, kDnTotal * sizeof(unsigned long long), s);
+  h->cnt.zero(s);
   // a device output in windows of 2^30 points, a host output through the staging lists, stage_points at a time
   const long long window = is_device ? kClMaxWindow : (long long)h->stage_points;
   for (long long base = 0; base < n; base += window) {
@@ -441,7 +402,7 @@ extern "C" int vdo_colour_sample(vdo_colour* h, int64_t n, const float* xyz, int
       hipMemcpyAsync(h->d_xyz, xyz + 3 * base, (size_t)cap * 3 * sizeof(float), hipMemcpyHostToDevice, s);
       i_xyz = h->d_xyz; o_rgba = h->d_rgba;
     }
-    hipLaunchKernelGGL(k_cl_sample, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, s, v, (const uint32_t*)h->d_col, cap, i_xyz, min_weight, o_rgba, h->d_cnt);
+    hipLaunchKernelGGL(k_cl_sample, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, s, v, (const uint32_t*)h->d_col, cap, i_xyz, min_weight, o_rgba, h->cnt.d);
     if (!is_device) {
       hipMemcpyAsync(rgba + 4 * base, h->d_rgba, (size_t)cap * 4, hipMemcpyDeviceToHost, s);
       rc = check_hip(who, hipStreamSynchronize(s));                          // the staging lists are free for the next window
@@ -449,10 +410,10 @@ extern "C" int vdo_colour_sample(vdo_colour* h, int64_t n, const float* xyz, int
     }
   }
   h->tm.mark_end(s);
-  hipMemcpyAsync(h->h_cnt, h->d_cnt, kDnTotal * sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
+  h->cnt.download(s);
   rc = sync_check(who, s);
   if (rc != VDO_OK) return rc;
-  *n_coloured = cl_sum(h, 0);
+  *n_coloured = h->cnt.sum(0);
   h->tm.finish(t0);
   return VDO_OK;
 }
@@ -483,7 +444,7 @@ extern "C" int vdo_colour_render(vdo_colour* h, const float* depth, int width, i
   vw.fx = K[0]; vw.fy = K[1]; vw.cx = K[2]; vw.cy = K[3]; vw.W = width;
   dn_centre(T, vw.c);
   for (int k = 0; k < 3; ++k) { vw.R[k] = T[k]; vw.R[3 + k] = T[4 + k]; vw.R[6 + k] = T[8 + k]; }
-  hipMemsetAsync(h->d_cnt, 0, kDnTotal * sizeof(unsigned long long), s);
+  h->cnt.zero(s);
   const int npix = width * height;                                           // at most 2^26
   const int window = is_device ? npix : (int)(h->stage_points < npix ? h->stage_points : npix);
   for (int base = 0; base < npix; base += window) {
@@ -494,7 +455,7 @@ extern "C" int vdo_colour_render(vdo_colour* h, const float* depth, int width, i
       hipMemcpyAsync(h->d_xyz, depth + base, (size_t)cap * sizeof(float), hipMemcpyHostToDevice, s);
       i_depth = h->d_xyz; o_rgba = h->d_rgba;
     }
-    hipLaunchKernelGGL(k_cl_render, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, s, v, vw, (const uint32_t*)h->d_col, base, cap, i_depth, min_weight, o_rgba, h->d_cnt);
+    hipLaunchKernelGGL(k_cl_render, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, s, v, vw, (const uint32_t*)h->d_col, base, cap, i_depth, min_weight, o_rgba, h->cnt.d);
     if (!is_device) {
       hipMemcpyAsync(rgba + 4 * (size_t)base, h->d_rgba, (size_t)cap * 4, hipMemcpyDeviceToHost, s);
       rc = check_hip(who, hipStreamSynchronize(s));
@@ -502,10 +463,10 @@ extern "C" int vdo_colour_render(vdo_colour* h, const float* depth, int width, i
     }
   }
   h->tm.mark_end(s);
-  hipMemcpyAsync(h->h_cnt, h->d_cnt, kDnTotal * sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
+  h->cnt.download(s);
   rc = sync_check(who, s);
   if (rc != VDO_OK) return rc;
-  out[0] = cl_sum(h, 0); out[1] = cl_sum(h, 1);
+  out[0] = h->cnt.sum(0); out[1] = h->cnt.sum(1);
   h->tm.finish(t0);
   return VDO_OK;
 }

@@ -93,13 +93,11 @@ __global__ __launch_bounds__(256) void k_dn_clear(uint32_t* __restrict__ vol, in
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= (long long)lx * ly * lz) return;
   int x = (int)(i % lx), y = (int)((i / lx) % ly), z = (int)(i / ((long long)lx * ly));
-  if (axis == 0) { x += s0; if (x >= nx) x -= nx; }
-  if (axis == 1) { y += s0; if (y >= ny) y -= ny; }
-  if (axis == 2) { z += s0; if (z >= nz) z -= nz; }
+  if (axis == 0) x = dn_slot(x, s0, nx);
+  if (axis == 1) y = dn_slot(y, s0, ny);
+  if (axis == 2) z = dn_slot(z, s0, nz);
   vol[((size_t)z * ny + y) * nx + x] = 0u;
 }
-
-struct DnBox { int lo[3], b[3]; };                                           // the clipped box: its first global voxel and its size (all > 0)
 
 // Voxel i of the box in the visiting order (x fastest): its points on axes 0, 1, 2.  !FILL: the workgroup's number of points.  FILL: the points
 // whose place in the visiting order lies in [base, base + cap) are written at place - base.
@@ -115,15 +113,15 @@ __global__ __launch_bounds__(256) void k_dn_extract(DnArgs a, DnBox bx, long lon
     int s[3];
     for (int k = 0; k < 3; ++k) { s[k] = g[k] % a.n[k]; if (s[k] < 0) s[k] += a.n[k]; }
     const uint32_t w0 = vol[((size_t)s[2] * a.n[1] + s[1]) * a.n[0] + s[0]];
-    ta = (int)(int16_t)(w0 & 0xffffu); wa = (int)(w0 >> 16);
+    ta = (int)(int16_t)(w0 & 0xffffu); wa = dn_weight(w0);                   // dn_tsdf, spelled out here and for tb: the call changes the kernel's instructions
     all_in = true;
     for (int k = 0; k < 3; ++k) {
       const bool inside = g[k] + 1 < a.o[k] + a.n[k];
       if (inside) {
         int t[3] = {s[0], s[1], s[2]};
-        t[k] = s[k] + 1 == a.n[k] ? 0 : s[k] + 1;
+        t[k] = dn_next(s[k], a.n[k]);
         const uint32_t w1 = vol[((size_t)t[2] * a.n[1] + t[1]) * a.n[0] + t[0]];
-        tb[k] = (int)(int16_t)(w1 & 0xffffu); wb[k] = (int)(w1 >> 16);
+        tb[k] = (int)(int16_t)(w1 & 0xffffu); wb[k] = dn_weight(w1);
       }
       const bool usable = inside && wb[k] >= min_w;
       all_in = all_in && usable;
@@ -154,13 +152,20 @@ __global__ __launch_bounds__(256) void k_dn_extract(DnArgs a, DnBox bx, long lon
 }
 
 static void dn_free(vdo_dense* h) {
-  hipFree(h->d_vol); hipFree(h->d_depth); hipFree(h->d_mask); hipFree(h->d_blk); hipFree(h->d_cnt); hipFree(h->d_xyz); hipFree(h->d_grad); hipFree(h->d_wgt);
-  if (h->h_cnt) hipHostFree(h->h_cnt);
+  hipFree(h->d_vol); hipFree(h->d_depth); hipFree(h->d_mask); hipFree(h->d_blk); hipFree(h->d_xyz); hipFree(h->d_grad); hipFree(h->d_wgt);
+  h->cnt.destroy();
   h->tm.destroy();
   delete h;
 }
 
-static int dn_mod(int g, int n) { const int m = g % n; return m < 0 ? m + n : m; }
+void dn_queue_move(hipStream_t s, uint32_t* words, const int n[3], int64_t nvox, const int from[3], const int to[3]) {
+  const DnMove m = dn_move(n, from, to);
+  if (m.all) hipMemsetAsync(words, 0, (size_t)nvox * sizeof(uint32_t), s);
+  for (int i = 0; i < m.slabs; ++i) {
+    const long long cells = (long long)m.slab[i].len * (nvox / n[m.slab[i].axis]);
+    hipLaunchKernelGGL(k_dn_clear, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, words, n[0], n[1], n[2], m.slab[i].axis, m.slab[i].s0, m.slab[i].len);
+  }
+}
 
 // an origin whose volume stays inside (-2^22, 2^22) on every axis; 0 when it does
 static int dn_check_origin(const char* who, const char* name, const int32_t o[3], const int32_t n[3]) {
@@ -177,7 +182,7 @@ static void dn_set_origin(vdo_dense* h, const int32_t o[3]) {
 template <int VPT>
 static void dn_launch_integrate(vdo_dense* h, hipStream_t s, const DnArgs& a, const float* depth, const int32_t* mask) {
   const dim3 grid((a.n[0] + 63) / 64, (a.n[1] + VPT - 1) / VPT, (a.n[2] + kDnZ - 1) / kDnZ);
-  hipLaunchKernelGGL(k_dn_integrate<VPT>, grid, dim3(64, 1, kDnZ), 0, s, a, depth, mask, h->W, h->H, h->d_vol, h->d_cnt);
+  hipLaunchKernelGGL(k_dn_integrate<VPT>, grid, dim3(64, 1, kDnZ), 0, s, a, depth, mask, h->W, h->H, h->d_vol, h->cnt.d);
 }
 
 // the launch, the download of the counts and the timing the two integrate entries share; depth and mask are packed device images
@@ -185,7 +190,7 @@ static int dn_integrate(const char* who, vdo_dense* h, const float* d_depth, con
   hipStream_t s = h->ctx->stream;
   DnArgs a = h->a;
   for (int k = 0; k < 12; ++k) a.T[k] = T[k];
-  hipMemsetAsync(h->d_cnt, 0, kDnTotal * sizeof(unsigned long long), s);
+  h->cnt.zero(s);
   switch (h->vpt) {
     case 1: dn_launch_integrate<1>(h, s, a, d_depth, d_mask); break;
     case 2: dn_launch_integrate<2>(h, s, a, d_depth, d_mask); break;
@@ -193,14 +198,10 @@ static int dn_integrate(const char* who, vdo_dense* h, const float* d_depth, con
     default: dn_launch_integrate<4>(h, s, a, d_depth, d_mask); break;
   }
   h->tm.mark_end(s);
-  hipMemcpyAsync(h->h_cnt, h->d_cnt, kDnTotal * sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
+  h->cnt.download(s);
   const int rc = sync_check(who, s);
   if (rc != VDO_OK) return rc;
-  for (int k = 0; k < 3; ++k) {
-    unsigned long long sum = 0;
-    for (int slot = 0; slot < kDnSlots; ++slot) sum += h->h_cnt[slot * kDnCounters + k];
-    out[k] = (int64_t)sum;
-  }
+  for (int k = 0; k < 3; ++k) out[k] = h->cnt.sum(k);
   h->tm.finish(t0);
   return VDO_OK;
 }
@@ -216,19 +217,19 @@ extern "C" int vdo_dense_create(vdo_ctx* ctx, int width, int height, const vdo_d
   if (!p) return set_error(VDO_ERR_INVALID, "%s: params is null", who);
   if (width < 1) return set_error(VDO_ERR_INVALID, "%s: width %d < 1", who, width);
   if (height < 1) return set_error(VDO_ERR_INVALID, "%s: height %d < 1", who, height);
-  for (int k = 0; k < 3; ++k) if (p->n[k] < 1) return set_error(VDO_ERR_INVALID, "%s: n[%d] = %d < 1", who, k, p->n[k]);
+  int rc = dn_check_sides(who, p->n);
+  if (rc != VDO_OK) return rc;
   if (!is_finite(p->voxel) || !(p->voxel > 0.f)) return set_error(VDO_ERR_INVALID, "%s: voxel %g must be positive and finite", who, (double)p->voxel);
-  int rc = check_intrinsics(who, "K", p->K);
+  rc = check_intrinsics(who, "K", p->K);
   if (rc != VDO_OK) return rc;
   if (!is_finite(p->trunc) || !(p->trunc > 0.f)) return set_error(VDO_ERR_INVALID, "%s: trunc %g must be positive and finite", who, (double)p->trunc);
   rc = check_depth_range(who, p->min_depth, p->max_depth);
   if (rc != VDO_OK) return rc;
   if (p->max_weight < 1 || p->max_weight > 255) return set_error(VDO_ERR_INVALID, "%s: max_weight %d outside 1..255", who, p->max_weight);
   if (p->stage_points < 1) return set_error(VDO_ERR_INVALID, "%s: stage_points %d < 1", who, p->stage_points);
-  for (int k = 0; k < 3; ++k) if (p->n[k] > kDnMaxSide) return set_error(VDO_ERR_UNSUPPORTED, "%s: n[%d] = %d exceeds 2^12", who, k, p->n[k]);
-  const int64_t nvox = (int64_t)p->n[0] * p->n[1] * p->n[2];
-  if (nvox > kDnMaxVoxels) return set_error(VDO_ERR_UNSUPPORTED, "%s: %d x %d x %d voxels exceed 2^31", who, p->n[0], p->n[1], p->n[2]);
-  rc = check_image_size(who, "width x height =", width, height);
+  int64_t nvox;
+  rc = dn_check_size(who, p->n, &nvox);
+  if (rc == VDO_OK) rc = check_image_size(who, "width x height =", width, height);
   if (rc != VDO_OK) return rc;
   rc = dn_check_origin(who, "origin", p->origin, p->n);
   if (rc != VDO_OK) return rc;
@@ -245,9 +246,8 @@ extern "C" int vdo_dense_create(vdo_ctx* ctx, int width, int height, const vdo_d
   const size_t npix = (size_t)width * height, nblk = (size_t)((nvox + 255) / 256), sp = (size_t)p->stage_points;
   const bool ok = hipMalloc((void**)&h->d_vol, (size_t)nvox * sizeof(uint32_t)) == hipSuccess && hipMalloc((void**)&h->d_depth, npix * sizeof(float)) == hipSuccess &&
                   hipMalloc((void**)&h->d_mask, npix * sizeof(int32_t)) == hipSuccess && hipMalloc((void**)&h->d_blk, nblk * sizeof(long long)) == hipSuccess &&
-                  hipMalloc((void**)&h->d_cnt, (kDnTotal + 1) * sizeof(unsigned long long)) == hipSuccess && hipMalloc((void**)&h->d_xyz, sp * 3 * sizeof(float)) == hipSuccess &&
-                  hipMalloc((void**)&h->d_grad, sp * 3 * sizeof(int32_t)) == hipSuccess && hipMalloc((void**)&h->d_wgt, sp * sizeof(int32_t)) == hipSuccess &&
-                  hipHostMalloc((void**)&h->h_cnt, (kDnTotal + 1) * sizeof(unsigned long long), hipHostMallocDefault) == hipSuccess && h->tm.create() &&
+                  h->cnt.create(kDnSlots, kDnCounters) && hipMalloc((void**)&h->d_xyz, sp * 3 * sizeof(float)) == hipSuccess &&
+                  hipMalloc((void**)&h->d_grad, sp * 3 * sizeof(int32_t)) == hipSuccess && hipMalloc((void**)&h->d_wgt, sp * sizeof(int32_t)) == hipSuccess && h->tm.create() &&
                   hipMemsetAsync(h->d_vol, 0, (size_t)nvox * sizeof(uint32_t), ctx->stream) == hipSuccess &&
                   hipStreamSynchronize(ctx->stream) == hipSuccess;
   if (!ok) {
@@ -312,22 +312,8 @@ extern "C" int vdo_dense_recenter(vdo_dense* h, const int32_t new_origin[3]) {
   rc = ctx_bind(h->ctx);
   if (rc != VDO_OK) return rc;
   hipStream_t s = h->ctx->stream;
-  const int* n = h->a.n;
-  int64_t d[3];
-  bool all = false;
-  for (int k = 0; k < 3; ++k) { d[k] = (int64_t)new_origin[k] - h->a.o[k]; all = all || d[k] >= n[k] || -d[k] >= n[k]; }
   const auto t0 = h->tm.begin(s);
-  if (all) {
-    hipMemsetAsync(h->d_vol, 0, (size_t)h->nvox * sizeof(uint32_t), s);
-  } else {
-    for (int k = 0; k < 3; ++k) {
-      if (d[k] == 0) continue;
-      // leaving: the first d voxels of the axis when the volume moves up, the last -d when it moves down
-      const int len = (int)(d[k] > 0 ? d[k] : -d[k]), g0 = d[k] > 0 ? h->a.o[k] : h->a.o[k] + n[k] - len;
-      const long long cells = (long long)len * (h->nvox / n[k]);
-      hipLaunchKernelGGL(k_dn_clear, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, h->d_vol, n[0], n[1], n[2], k, dn_mod(g0, n[k]), len);
-    }
-  }
+  dn_queue_move(s, h->d_vol, h->a.n, h->nvox, h->a.o, new_origin);
   h->tm.mark_end(s);
   rc = sync_check(who, s);
   if (rc != VDO_OK) return rc;
@@ -351,24 +337,21 @@ extern "C" int vdo_dense_extract(vdo_dense* h, const int32_t lo[3], const int32_
   int rc = ctx_bind(h->ctx);
   if (rc != VDO_OK) return rc;
   hipStream_t s = h->ctx->stream;
-  DnBox bx;
-  long long nbox = 1;
-  for (int k = 0; k < 3; ++k) {
-    const int64_t a0 = lo[k] > h->a.o[k] ? lo[k] : h->a.o[k], a1 = hi[k] < (int64_t)h->a.o[k] + h->a.n[k] ? hi[k] : (int64_t)h->a.o[k] + h->a.n[k];
-    bx.lo[k] = (int)a0; bx.b[k] = a1 > a0 ? (int)(a1 - a0) : 0;
-    nbox *= bx.b[k];
-  }
+  const DnClip clip = dn_clip(h, lo, hi);
+  const DnBox& bx = clip.box;
+  const long long nbox = clip.voxels();
+  unsigned long long* d_total = h->cnt.d + h->cnt.words();                    // the spare word
   const auto t0 = h->tm.begin(s);
   long long total = 0;
   if (nbox > 0) {
     const long long nblk = (nbox + 255) / 256;
     hipLaunchKernelGGL(k_dn_extract<false>, dim3((unsigned)nblk), dim3(256), 0, s, h->a, bx, nbox, min_weight, (const uint32_t*)h->d_vol, h->d_blk, 0LL, 0LL, (float*)nullptr,
                        (int32_t*)nullptr, (int32_t*)nullptr);
-    hipLaunchKernelGGL(k_counts_scan<1024>, dim3(1), dim3(1024), 0, s, h->d_blk, nblk, h->d_cnt + kDnTotal);
-    hipMemcpyAsync(h->h_cnt + kDnTotal, h->d_cnt + kDnTotal, sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
+    hipLaunchKernelGGL(k_counts_scan<1024>, dim3(1), dim3(1024), 0, s, h->d_blk, nblk, d_total);
+    hipMemcpyAsync(h->cnt.h + h->cnt.words(), d_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
     rc = sync_check(who, s);
     if (rc != VDO_OK) return rc;
-    total = (long long)h->h_cnt[kDnTotal];
+    total = (long long)h->cnt.h[h->cnt.words()];
     const long long want = total < capacity ? total : capacity;
     // a device output is one window; a host output goes through the staging lists, stage_points at a time
     for (long long base = 0; base < want; base += out_is_device ? want : h->stage_points) {

@@ -32,8 +32,6 @@
 
 namespace vdo {
 
-typedef unsigned long long u64;
-
 constexpr uint32_t kDtFar = VDO_DISTANCE_FAR, kDtState = 0x30000000u;
 constexpr int kDtRows = 192;                                               // the most rows of the LDS tile of k_dt_axis_win: 48 KiB
 constexpr int kDtMinTile = 32;                                             // the fewest rows of a tile that are not halo
@@ -63,25 +61,16 @@ __device__ __forceinline__ void dt_count(int v, int which, u64* __restrict__ cnt
   }
 }
 
-// the word of the voxel at local (x, y, z), each inside [0, n)
-__device__ __forceinline__ uint32_t dt_word(const DtArgs& a, const uint32_t* __restrict__ vol, int x, int y, int z) {
-  int sx = a.om[0] + x, sy = a.om[1] + y, sz = a.om[2] + z;
-  if (sx >= a.n[0]) sx -= a.n[0];
-  if (sy >= a.n[1]) sy -= a.n[1];
-  if (sz >= a.n[2]) sz -= a.n[2];
-  return vol[((size_t)sz * a.n[1] + sy) * a.n[0] + sx];
-}
-
 __global__ __launch_bounds__(256) void k_dt_sites(DtArgs a, const uint32_t* __restrict__ vol, u64* __restrict__ bits, uint32_t* __restrict__ field, u64* __restrict__ cnt) {
   const unsigned i = blockIdx.x * 256u + threadIdx.x;
   bool site = false;
   if (i < a.nbox) {
     const unsigned bx = (unsigned)a.b[0], by = (unsigned)a.b[1], r = i / bx, z = r / by;
     const int l[3] = {a.blo[0] + (int)(i - r * bx), a.blo[1] + (int)(r - z * by), a.blo[2] + (int)z};
-    const uint32_t v = dt_word(a, vol, l[0], l[1], l[2]);
+    const uint32_t v = dn_word(vol, a.n, a.om, l[0], l[1], l[2]);
     uint32_t state = 0u;
-    if ((int)(v >> 16) >= a.min_w) {
-      const bool neg = (int16_t)(v & 0xffffu) < 0;
+    if (dn_weight(v) >= a.min_w) {
+      const bool neg = (int16_t)(v & 0xffffu) < 0;                           // dn_tsdf(v) < 0, spelled out here and below: the call moves the kernel's registers
       state = neg ? 2u : 1u;
 #pragma unroll
       for (int k = 0; k < 3; ++k)
@@ -90,8 +79,8 @@ __global__ __launch_bounds__(256) void k_dt_sites(DtArgs a, const uint32_t* __re
           int m[3] = {l[0], l[1], l[2]};
           m[k] += d;
           if (m[k] < 0 || m[k] >= a.n[k]) continue;
-          const uint32_t q = dt_word(a, vol, m[0], m[1], m[2]);
-          site = site || ((int)(q >> 16) >= a.min_w && ((int16_t)(q & 0xffffu) < 0) != neg);
+          const uint32_t q = dn_word(vol, a.n, a.om, m[0], m[1], m[2]);
+          site = site || (dn_weight(q) >= a.min_w && ((int16_t)(q & 0xffffu) < 0) != neg);
         }
     }
     field[i] = state << 28;
@@ -223,7 +212,7 @@ __global__ __launch_bounds__(256) void k_dt_sample(DtSnap sn, const uint32_t* __
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       const float p = xyz[3 * i + k], u = p / sn.voxel, b = floorf(u);
-      const bool ok = dn_finite(p) && b >= -4194304.0f && b <= 4194303.0f;
+      const bool ok = dn_indexable(p, b);
       if (ok) g[k] = (int)b;
       in = in && ok && g[k] >= sn.lo[k] && g[k] < sn.hi[k];
     }
@@ -245,8 +234,7 @@ struct vdo_distance {
   vdo::DtSnap snap{};
   uint32_t* d_field = nullptr; uint32_t* d_tmp = nullptr;                    // [nvox] the snapshot; the other side of the passes
   vdo::u64* d_bits = nullptr;                                                // [(nvox + 63) / 64] site bits in box order
-  vdo::u64* d_cnt = nullptr;                                                 // [kDtSlots][kDtCounters]
-  vdo::u64* h_cnt = nullptr;                                                 // pinned
+  vdo::SlotCounts cnt;                                                       // [kDtSlots][kDtCounters]
   float* d_xyz = nullptr; uint32_t* d_words = nullptr;                       // [VDO_DISTANCE_WINDOW][3], [VDO_DISTANCE_WINDOW]: a window of host points
   vdo::StageTimer tm;
 };
@@ -254,16 +242,10 @@ struct vdo_distance {
 using namespace vdo;
 
 static void dt_free(vdo_distance* h) {
-  hipFree(h->d_field); hipFree(h->d_tmp); hipFree(h->d_bits); hipFree(h->d_cnt); hipFree(h->d_xyz); hipFree(h->d_words);
-  if (h->h_cnt) hipHostFree(h->h_cnt);
+  hipFree(h->d_field); hipFree(h->d_tmp); hipFree(h->d_bits); hipFree(h->d_xyz); hipFree(h->d_words);
+  h->cnt.destroy();
   h->tm.destroy();
   delete h;
-}
-
-static int64_t dt_sum(const vdo_distance* h, int k) {
-  u64 sum = 0;
-  for (int slot = 0; slot < kDtSlots; ++slot) sum += h->h_cnt[slot * kDtCounters + k];
-  return (int64_t)sum;
 }
 
 extern "C" int vdo_distance_create(vdo_ctx* ctx, const vdo_distance_params* p, vdo_distance** out) {
@@ -271,20 +253,18 @@ extern "C" int vdo_distance_create(vdo_ctx* ctx, const vdo_distance_params* p, v
   if (!ctx) return set_error(VDO_ERR_INVALID, "%s: ctx is null", who);
   if (!p) return set_error(VDO_ERR_INVALID, "%s: params is null", who);
   if (!out) return set_error(VDO_ERR_INVALID, "%s: out is null", who);
-  for (int k = 0; k < 3; ++k) if (p->n[k] < 1) return set_error(VDO_ERR_INVALID, "%s: n[%d] = %d < 1", who, k, p->n[k]);
-  for (int k = 0; k < 3; ++k) if (p->n[k] > kDnMaxSide) return set_error(VDO_ERR_UNSUPPORTED, "%s: n[%d] = %d exceeds 2^12", who, k, p->n[k]);
-  const int64_t nvox = (int64_t)p->n[0] * p->n[1] * p->n[2];
-  if (nvox > kDnMaxVoxels) return set_error(VDO_ERR_UNSUPPORTED, "%s: %d x %d x %d voxels exceed 2^31", who, p->n[0], p->n[1], p->n[2]);
-  int rc = ctx_bind(ctx);
+  int64_t nvox;
+  int rc = dn_check_sides(who, p->n);
+  if (rc == VDO_OK) rc = dn_check_size(who, p->n, &nvox);
+  if (rc == VDO_OK) rc = ctx_bind(ctx);
   if (rc != VDO_OK) return rc;
   vdo_distance* h = new vdo_distance;
   h->ctx = ctx; h->nvox = nvox;
-  const size_t nv = (size_t)nvox, cb = (size_t)kDtSlots * kDtCounters * sizeof(u64);
+  const size_t nv = (size_t)nvox;
   const bool ok = hipMalloc((void**)&h->d_field, nv * sizeof(uint32_t)) == hipSuccess && hipMalloc((void**)&h->d_tmp, nv * sizeof(uint32_t)) == hipSuccess &&
-                  hipMalloc((void**)&h->d_bits, (nv + 63) / 64 * sizeof(u64)) == hipSuccess && hipMalloc((void**)&h->d_cnt, cb) == hipSuccess &&
+                  hipMalloc((void**)&h->d_bits, (nv + 63) / 64 * sizeof(u64)) == hipSuccess && h->cnt.create(kDtSlots, kDtCounters) &&
                   hipMalloc((void**)&h->d_xyz, (size_t)VDO_DISTANCE_WINDOW * 3 * sizeof(float)) == hipSuccess &&
-                  hipMalloc((void**)&h->d_words, (size_t)VDO_DISTANCE_WINDOW * sizeof(uint32_t)) == hipSuccess &&
-                  hipHostMalloc((void**)&h->h_cnt, cb, hipHostMallocDefault) == hipSuccess && h->tm.create();
+                  hipMalloc((void**)&h->d_words, (size_t)VDO_DISTANCE_WINDOW * sizeof(uint32_t)) == hipSuccess && h->tm.create();
   if (!ok) {
     (void)hipGetLastError();
     dt_free(h);
@@ -332,17 +312,13 @@ extern "C" int vdo_distance_compute(vdo_distance* h, vdo_dense* map, const int32
   if (map->ctx != h->ctx) return set_error(VDO_ERR_INVALID, "%s: map belongs to another context", who);
   DtArgs a;
   DtSnap sn;
-  bool empty = false;
-  int64_t nbox = 1;
+  const DnClip clip = dn_clip(map, lo, hi);
+  const int64_t nbox = clip.voxels();
   for (int k = 0; k < 3; ++k) {
     a.n[k] = map->a.n[k]; a.om[k] = map->a.om[k];
-    const int64_t o = map->a.o[k], a0 = lo[k] > o ? lo[k] : o, a1 = hi[k] < o + a.n[k] ? hi[k] : o + a.n[k];
-    empty = empty || a1 <= a0;
-    a.blo[k] = (int)(a0 < a1 ? a0 - o : 0); a.b[k] = (int)(a0 < a1 ? a1 - a0 : 0);
-    sn.lo[k] = (int)(a0 < a1 ? a0 : 0); sn.hi[k] = (int)(a0 < a1 ? a1 : 0);
-    nbox *= a.b[k];
+    a.blo[k] = clip.empty ? 0 : clip.box.lo[k] - map->a.o[k]; a.b[k] = clip.box.b[k];
+    sn.lo[k] = clip.box.lo[k]; sn.hi[k] = clip.box.lo[k] + clip.box.b[k];
   }
-  if (empty) { nbox = 0; for (int k = 0; k < 3; ++k) sn.lo[k] = sn.hi[k] = 0; }
   if (nbox > h->nvox)
     return set_error(VDO_ERR_INVALID, "%s: the clipped box of %d x %d x %d voxels is larger than the handle's %lld", who, a.b[0], a.b[1], a.b[2], (long long)h->nvox);
   sn.voxel = map->a.voxel;
@@ -353,22 +329,21 @@ extern "C" int vdo_distance_compute(vdo_distance* h, vdo_dense* map, const int32
   const auto t0 = h->tm.begin(s);
   h->tm.ms[0] = h->tm.ms[1] = 0;
   if (nbox > 0) {
-    const size_t cb = (size_t)kDtSlots * kDtCounters * sizeof(u64);
     const dim3 grid((unsigned)((nbox + 255) / 256)), block(256);
-    hipMemsetAsync(h->d_cnt, 0, cb, s);
-    hipLaunchKernelGGL(k_dt_sites, grid, block, 0, s, a, (const uint32_t*)map->d_vol, h->d_bits, h->d_field, h->d_cnt);
+    h->cnt.zero(s);
+    hipLaunchKernelGGL(k_dt_sites, grid, block, 0, s, a, (const uint32_t*)map->d_vol, h->d_bits, h->d_field, h->cnt.d);
     hipLaunchKernelGGL(k_dt_x, grid, block, 0, s, a, (const u64*)h->d_bits, h->d_field);
     dt_axis(h, s, h->d_field, h->d_tmp, (size_t)a.b[0], a.b[1], (size_t)a.b[2], radius, nullptr);
-    dt_axis(h, s, h->d_tmp, h->d_field, (size_t)a.b[0] * a.b[1], a.b[2], 1, radius, h->d_cnt);
+    dt_axis(h, s, h->d_tmp, h->d_field, (size_t)a.b[0] * a.b[1], a.b[2], 1, radius, h->cnt.d);
     h->tm.mark_end(s);
-    hipMemcpyAsync(h->h_cnt, h->d_cnt, cb, hipMemcpyDeviceToHost, s);
+    h->cnt.download(s);
   } else {
     h->tm.mark_end(s);
   }
   h->has = true; h->nbox = nbox; h->snap = sn;                                // (the field's words are the new box's from the first kernel on)
   rc = sync_check(who, s);
   if (rc != VDO_OK) return rc;
-  counts[0] = nbox ? dt_sum(h, 0) : 0; counts[1] = nbox ? dt_sum(h, 1) : 0; counts[2] = nbox;
+  counts[0] = nbox ? h->cnt.sum(0) : 0; counts[1] = nbox ? h->cnt.sum(1) : 0; counts[2] = nbox;
   h->tm.finish(t0);
   return VDO_OK;
 }
@@ -405,8 +380,7 @@ extern "C" int vdo_distance_sample(vdo_distance* h, int64_t n, const float* xyz,
   const auto t0 = h->tm.begin(s);
   DtSnap sn = h->snap;
   if (!h->has) { for (int k = 0; k < 3; ++k) sn.lo[k] = sn.hi[k] = 0; sn.voxel = 1.f; }
-  const size_t cb = (size_t)kDtSlots * kDtCounters * sizeof(u64);
-  hipMemsetAsync(h->d_cnt, 0, cb, s);
+  h->cnt.zero(s);
   // device points in windows of 2^30, host points through the staging lists, VDO_DISTANCE_WINDOW at a time
   const long long window = is_device ? kDtMaxWindow : (long long)VDO_DISTANCE_WINDOW;
   for (long long base = 0; base < n; base += window) {
@@ -417,7 +391,7 @@ extern "C" int vdo_distance_sample(vdo_distance* h, int64_t n, const float* xyz,
       hipMemcpyAsync(h->d_xyz, xyz + 3 * base, (size_t)cap * 3 * sizeof(float), hipMemcpyHostToDevice, s);
       i_xyz = h->d_xyz; o_words = h->d_words;
     }
-    hipLaunchKernelGGL(k_dt_sample, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, s, sn, (const uint32_t*)h->d_field, cap, i_xyz, o_words, h->d_cnt);
+    hipLaunchKernelGGL(k_dt_sample, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, s, sn, (const uint32_t*)h->d_field, cap, i_xyz, o_words, h->cnt.d);
     if (!is_device) {
       hipMemcpyAsync(words + base, h->d_words, (size_t)cap * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
       rc = check_hip(who, hipStreamSynchronize(s));                          // the staging lists are free for the next window
@@ -425,10 +399,10 @@ extern "C" int vdo_distance_sample(vdo_distance* h, int64_t n, const float* xyz,
     }
   }
   h->tm.mark_end(s);
-  hipMemcpyAsync(h->h_cnt, h->d_cnt, cb, hipMemcpyDeviceToHost, s);
+  h->cnt.download(s);
   rc = sync_check(who, s);
   if (rc != VDO_OK) return rc;
-  *n_inside = dt_sum(h, 2);
+  *n_inside = h->cnt.sum(2);
   h->tm.finish(t0);
   return VDO_OK;
 }

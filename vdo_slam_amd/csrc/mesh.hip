@@ -37,20 +37,9 @@ struct MsArgs {
   float voxel;
 };
 
-typedef unsigned long long u64;
-
 __device__ __forceinline__ void ms_local(const MsArgs& a, unsigned i, int l[3]) {
   const unsigned nx = (unsigned)a.n[0], ny = (unsigned)a.n[1], r = i / nx;
   l[0] = (int)(i - r * nx); l[2] = (int)(r / ny); l[1] = (int)(r - (unsigned)l[2] * ny);
-}
-
-// the word of the voxel at local (x, y, z), each inside [0, n)
-__device__ __forceinline__ uint32_t ms_word(const MsArgs& a, const uint32_t* __restrict__ vol, int x, int y, int z) {
-  int sx = a.om[0] + x, sy = a.om[1] + y, sz = a.om[2] + z;
-  if (sx >= a.n[0]) sx -= a.n[0];
-  if (sy >= a.n[1]) sy -= a.n[1];
-  if (sz >= a.n[2]) sz -= a.n[2];
-  return vol[((size_t)sz * a.n[1] + sy) * a.n[0] + sx];
 }
 
 // the 8 corners of the cell at l (corner dx + 2 dy + 4 dz); false, nothing read, unless all of them are inside the volume
@@ -58,8 +47,8 @@ __device__ __forceinline__ bool ms_corners(const MsArgs& a, const uint32_t* __re
   if (l[0] + 1 >= a.n[0] || l[1] + 1 >= a.n[1] || l[2] + 1 >= a.n[2]) return false;
 #pragma unroll
   for (int c = 0; c < 8; ++c) {
-    const uint32_t v = ms_word(a, vol, l[0] + (c & 1), l[1] + (c >> 1 & 1), l[2] + (c >> 2));
-    t[c] = (int)(int16_t)(v & 0xffffu); w[c] = (int)(v >> 16);
+    const uint32_t v = dn_word(vol, a.n, a.om, l[0] + (c & 1), l[1] + (c >> 1 & 1), l[2] + (c >> 2));
+    t[c] = dn_tsdf(v); w[c] = dn_weight(v);
   }
   return true;
 }
@@ -156,7 +145,7 @@ __global__ __launch_bounds__(256) void k_ms_edges(MsArgs a, const uint32_t* __re
   // every quad of a uses the cell at a itself: nothing to do unless that cell is valid, and then a and a + e_k are inside with w >= min_weight
   if (i < a.nvox && (valid[i >> 6] >> (i & 63u) & 1ull)) {
     ms_local(a, i, l);
-    ta = (int)(int16_t)(ms_word(a, vol, l[0], l[1], l[2]) & 0xffffu);
+    ta = (int)(int16_t)(dn_word(vol, a.n, a.om, l[0], l[1], l[2]) & 0xffffu);   // dn_tsdf, spelled out here and for tb: the call costs k_ms_edges<true> two instructions
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       const int ai = (k + 1) % 3, aj = (k + 2) % 3;
@@ -165,7 +154,7 @@ __global__ __launch_bounds__(256) void k_ms_edges(MsArgs a, const uint32_t* __re
       if (!((valid[c1 >> 6] >> (c1 & 63u)) & (valid[c2 >> 6] >> (c2 & 63u)) & (valid[c3 >> 6] >> (c3 & 63u)) & 1ull)) continue;
       int b[3] = {l[0], l[1], l[2]};
       b[k] += 1;
-      const int tb = (int)(int16_t)(ms_word(a, vol, b[0], b[1], b[2]) & 0xffffu);
+      const int tb = (int)(int16_t)(dn_word(vol, a.n, a.om, b[0], b[1], b[2]) & 0xffffu);
       if ((ta < 0) == (tb < 0)) continue;
       // the 3 x 3 x 2 corner block inside the box
       const bool in = l[ai] - 1 >= a.lo[ai] && l[ai] + 1 < a.hi[ai] && l[aj] - 1 >= a.lo[aj] && l[aj] + 1 < a.hi[aj] && l[k] >= a.lo[k] && l[k] + 1 < a.hi[k];
@@ -225,13 +214,13 @@ extern "C" int vdo_mesh_create(vdo_ctx* ctx, const vdo_mesh_params* p, vdo_mesh*
   if (!ctx) return set_error(VDO_ERR_INVALID, "%s: ctx is null", who);
   if (!p) return set_error(VDO_ERR_INVALID, "%s: params is null", who);
   if (!out) return set_error(VDO_ERR_INVALID, "%s: out is null", who);
-  for (int k = 0; k < 3; ++k) if (p->n[k] < 1) return set_error(VDO_ERR_INVALID, "%s: n[%d] = %d < 1", who, k, p->n[k]);
+  int rc = dn_check_sides(who, p->n);
+  if (rc != VDO_OK) return rc;
   if (p->stage_vertices < 1) return set_error(VDO_ERR_INVALID, "%s: stage_vertices %d < 1", who, p->stage_vertices);
   if (p->stage_triangles < 1) return set_error(VDO_ERR_INVALID, "%s: stage_triangles %d < 1", who, p->stage_triangles);
-  for (int k = 0; k < 3; ++k) if (p->n[k] > kDnMaxSide) return set_error(VDO_ERR_UNSUPPORTED, "%s: n[%d] = %d exceeds 2^12", who, k, p->n[k]);
-  const int64_t nvox = (int64_t)p->n[0] * p->n[1] * p->n[2];
-  if (nvox > kDnMaxVoxels) return set_error(VDO_ERR_UNSUPPORTED, "%s: %d x %d x %d voxels exceed 2^31", who, p->n[0], p->n[1], p->n[2]);
-  int rc = ctx_bind(ctx);
+  int64_t nvox;
+  rc = dn_check_size(who, p->n, &nvox);
+  if (rc == VDO_OK) rc = ctx_bind(ctx);
   if (rc != VDO_OK) return rc;
   vdo_mesh* h = new vdo_mesh;
   h->ctx = ctx; h->nvox = nvox; h->nblk = (nvox + 255) / 256; h->stage_v = p->stage_vertices; h->stage_t = p->stage_triangles;
@@ -280,14 +269,11 @@ extern "C" int vdo_mesh_extract(vdo_mesh* h, vdo_dense* map, const int32_t lo[3]
   if (rc != VDO_OK) return rc;
   hipStream_t s = h->ctx->stream;
   MsArgs a;
-  bool empty = false;
+  const DnClip clip = dn_clip(map, lo, hi);
   for (int k = 0; k < 3; ++k) {
     a.n[k] = map->a.n[k]; a.o[k] = map->a.o[k]; a.om[k] = map->a.om[k];
-    const int64_t o = a.o[k], a0 = lo[k] > o ? lo[k] : o, a1 = hi[k] < o + a.n[k] ? hi[k] : o + a.n[k];
-    a.lo[k] = (int)(a0 < a1 ? a0 - o : 0); a.hi[k] = (int)(a0 < a1 ? a1 - o : 0);
-    empty = empty || a1 <= a0;
+    a.lo[k] = clip.empty ? 0 : clip.box.lo[k] - a.o[k]; a.hi[k] = a.lo[k] + clip.box.b[k];
   }
-  if (empty) for (int k = 0; k < 3; ++k) a.lo[k] = a.hi[k] = 0;
   a.outside = outside ? 1 : 0; a.min_w = min_weight; a.nvox = (unsigned)map->nvox; a.voxel = map->a.voxel;   // (2^31 voxels fit an unsigned index)
   const uint32_t* vol = map->d_vol;
   const long long nblk = (map->nvox + 255) / 256;

@@ -34,7 +34,6 @@ constexpr int kRcMaxSteps = 1 << 16;                                       // (f
 constexpr int kRcBrick = 3;                                                // log2 of the brick edge in slots
 constexpr int kRcSlots = 256;                                              // copies of the counters, 32 bytes apart
 constexpr int kRcCounters = 4;                                             // hit, missed, no valid sample, (unused)
-constexpr int kRcTotal = kRcSlots * kRcCounters;
 
 // what the kernels take by value
 struct RcArgs {
@@ -46,10 +45,6 @@ struct RcArgs {
 };
 
 __device__ __forceinline__ float rc_lerp(float u, float v, float f) { return u + f * (v - u); }
-
-__device__ __forceinline__ float rc_t(uint32_t w) { return (float)(int)(int16_t)(w & 0xffffu); }
-
-__device__ __forceinline__ int rc_w(uint32_t w) { return (int)(w >> 16); }
 
 // four lerps along x, two along y, one along z; tijk is the corner at (x, y, z) = (i, j, k)
 __device__ __forceinline__ float rc_tri(float t000, float t100, float t010, float t110, float t001, float t101, float t011, float t111, const float f[3]) {
@@ -72,27 +67,25 @@ __device__ __forceinline__ bool rc_cell(const RcArgs& a, float lam, const float 
   return ok;
 }
 
-// the slot of the global voxel g, o <= g < o + n
-__device__ __forceinline__ int rc_slot(int g, int o, int om, int n) { const int s = om + (g - o); return s >= n ? s - n : s; }
-
-__device__ __forceinline__ int rc_next(int s, int n) { return s + 1 == n ? 0 : s + 1; }
+// the slot of the base cell b on axis k (b passed rc_cell: o <= b <= o + n - 2)
+__device__ __forceinline__ int rc_base(const RcArgs& a, const float b[3], int k) { return dn_slot((int)b[k] - a.o[k], a.om[k], a.n[k]); }
 
 // sample at depth lam: true iff VALID; *F its value and *wmin the smallest corner weight (both meaningful only when the words were read)
 __device__ __forceinline__ bool rc_sample(const RcArgs& a, const uint32_t* __restrict__ vol, const uint8_t* __restrict__ grid, float lam, const float r[3], float* F, int* wmin) {
   float b[3], f[3];
   if (!rc_cell(a, lam, r, b, f)) return false;
-  const int x0 = rc_slot((int)b[0], a.o[0], a.om[0], a.n[0]), y0 = rc_slot((int)b[1], a.o[1], a.om[1], a.n[1]), z0 = rc_slot((int)b[2], a.o[2], a.om[2], a.n[2]);
+  const int x0 = rc_base(a, b, 0), y0 = rc_base(a, b, 1), z0 = rc_base(a, b, 2);
   if (grid && !grid[((z0 >> kRcBrick) * a.nb[1] + (y0 >> kRcBrick)) * a.nb[0] + (x0 >> kRcBrick)]) return false;      // all eight words are 0: weight 0 < min_weight
-  const int y1 = rc_next(y0, a.n[1]), z1 = rc_next(z0, a.n[2]);
+  const int y1 = dn_next(y0, a.n[1]), z1 = dn_next(z0, a.n[2]);
   const int dx1 = x0 + 1 == a.n[0] ? -x0 : 1;                                // the x-neighbour is the next word except at the seam
   const uint32_t* r00 = vol + ((size_t)z0 * a.n[1] + y0) * a.n[0] + x0;
   const uint32_t* r10 = vol + ((size_t)z0 * a.n[1] + y1) * a.n[0] + x0;
   const uint32_t* r01 = vol + ((size_t)z1 * a.n[1] + y0) * a.n[0] + x0;
   const uint32_t* r11 = vol + ((size_t)z1 * a.n[1] + y1) * a.n[0] + x0;
   const uint32_t w000 = r00[0], w100 = r00[dx1], w010 = r10[0], w110 = r10[dx1], w001 = r01[0], w101 = r01[dx1], w011 = r11[0], w111 = r11[dx1];
-  const int m = min(min(min(rc_w(w000), rc_w(w100)), min(rc_w(w010), rc_w(w110))), min(min(rc_w(w001), rc_w(w101)), min(rc_w(w011), rc_w(w111))));
+  const int m = min(min(min(dn_weight(w000), dn_weight(w100)), min(dn_weight(w010), dn_weight(w110))), min(min(dn_weight(w001), dn_weight(w101)), min(dn_weight(w011), dn_weight(w111))));
   *wmin = m;
-  *F = rc_tri(rc_t(w000), rc_t(w100), rc_t(w010), rc_t(w110), rc_t(w001), rc_t(w101), rc_t(w011), rc_t(w111), f);
+  *F = rc_tri(dn_tsdf_f(w000), dn_tsdf_f(w100), dn_tsdf_f(w010), dn_tsdf_f(w110), dn_tsdf_f(w001), dn_tsdf_f(w101), dn_tsdf_f(w011), dn_tsdf_f(w111), f);
   return m >= a.min_w;
 }
 
@@ -106,10 +99,10 @@ __device__ __forceinline__ void rc_gradient(const RcArgs& a, const uint32_t* __r
   if (!ok) return;
   // slots of the cells b - 1, b, b + 1, b + 2 per axis: all inside the volume, n >= 4
   int sx[4], sy[4], sz[4];
-  sx[1] = rc_slot((int)b[0], a.o[0], a.om[0], a.n[0]); sy[1] = rc_slot((int)b[1], a.o[1], a.om[1], a.n[1]); sz[1] = rc_slot((int)b[2], a.o[2], a.om[2], a.n[2]);
+  sx[1] = rc_base(a, b, 0); sy[1] = rc_base(a, b, 1); sz[1] = rc_base(a, b, 2);
   sx[0] = sx[1] == 0 ? a.n[0] - 1 : sx[1] - 1; sy[0] = sy[1] == 0 ? a.n[1] - 1 : sy[1] - 1; sz[0] = sz[1] == 0 ? a.n[2] - 1 : sz[1] - 1;
-  sx[2] = rc_next(sx[1], a.n[0]); sy[2] = rc_next(sy[1], a.n[1]); sz[2] = rc_next(sz[1], a.n[2]);
-  sx[3] = rc_next(sx[2], a.n[0]); sy[3] = rc_next(sy[2], a.n[1]); sz[3] = rc_next(sz[2], a.n[2]);
+  sx[2] = dn_next(sx[1], a.n[0]); sy[2] = dn_next(sy[1], a.n[1]); sz[2] = dn_next(sz[1], a.n[2]);
+  sx[3] = dn_next(sx[2], a.n[0]); sy[3] = dn_next(sy[2], a.n[1]); sz[3] = dn_next(sz[2], a.n[2]);
   const size_t nx = (size_t)a.n[0], nxy = nx * (size_t)a.n[1];
   uint32_t c[2][2][2], xm[2][2], xp[2][2], ym[2][2], yp[2][2], zm[2][2], zp[2][2];      // c[z][y][x]; xm, xp [z][y]; ym, yp [z][x]; zm, zp [y][x]
 #pragma unroll
@@ -138,17 +131,17 @@ __device__ __forceinline__ void rc_gradient(const RcArgs& a, const uint32_t* __r
   for (int k = 0; k < 2; ++k)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      m = min(m, min(rc_w(c[k][j][0]), rc_w(c[k][j][1])));
-      m = min(m, min(min(rc_w(xm[k][j]), rc_w(xp[k][j])), min(rc_w(ym[k][j]), rc_w(yp[k][j]))));
-      m = min(m, min(rc_w(zm[k][j]), rc_w(zp[k][j])));
+      m = min(m, min(dn_weight(c[k][j][0]), dn_weight(c[k][j][1])));
+      m = min(m, min(min(dn_weight(xm[k][j]), dn_weight(xp[k][j])), min(dn_weight(ym[k][j]), dn_weight(yp[k][j]))));
+      m = min(m, min(dn_weight(zm[k][j]), dn_weight(zp[k][j])));
     }
   if (m < a.min_w) return;
-  const float xa = rc_tri(rc_t(c[0][0][1]), rc_t(xp[0][0]), rc_t(c[0][1][1]), rc_t(xp[0][1]), rc_t(c[1][0][1]), rc_t(xp[1][0]), rc_t(c[1][1][1]), rc_t(xp[1][1]), f);
-  const float xb = rc_tri(rc_t(xm[0][0]), rc_t(c[0][0][0]), rc_t(xm[0][1]), rc_t(c[0][1][0]), rc_t(xm[1][0]), rc_t(c[1][0][0]), rc_t(xm[1][1]), rc_t(c[1][1][0]), f);
-  const float ya = rc_tri(rc_t(c[0][1][0]), rc_t(c[0][1][1]), rc_t(yp[0][0]), rc_t(yp[0][1]), rc_t(c[1][1][0]), rc_t(c[1][1][1]), rc_t(yp[1][0]), rc_t(yp[1][1]), f);
-  const float yb = rc_tri(rc_t(ym[0][0]), rc_t(ym[0][1]), rc_t(c[0][0][0]), rc_t(c[0][0][1]), rc_t(ym[1][0]), rc_t(ym[1][1]), rc_t(c[1][0][0]), rc_t(c[1][0][1]), f);
-  const float za = rc_tri(rc_t(c[1][0][0]), rc_t(c[1][0][1]), rc_t(c[1][1][0]), rc_t(c[1][1][1]), rc_t(zp[0][0]), rc_t(zp[0][1]), rc_t(zp[1][0]), rc_t(zp[1][1]), f);
-  const float zb = rc_tri(rc_t(zm[0][0]), rc_t(zm[0][1]), rc_t(zm[1][0]), rc_t(zm[1][1]), rc_t(c[0][0][0]), rc_t(c[0][0][1]), rc_t(c[0][1][0]), rc_t(c[0][1][1]), f);
+  const float xa = rc_tri(dn_tsdf_f(c[0][0][1]), dn_tsdf_f(xp[0][0]), dn_tsdf_f(c[0][1][1]), dn_tsdf_f(xp[0][1]), dn_tsdf_f(c[1][0][1]), dn_tsdf_f(xp[1][0]), dn_tsdf_f(c[1][1][1]), dn_tsdf_f(xp[1][1]), f);
+  const float xb = rc_tri(dn_tsdf_f(xm[0][0]), dn_tsdf_f(c[0][0][0]), dn_tsdf_f(xm[0][1]), dn_tsdf_f(c[0][1][0]), dn_tsdf_f(xm[1][0]), dn_tsdf_f(c[1][0][0]), dn_tsdf_f(xm[1][1]), dn_tsdf_f(c[1][1][0]), f);
+  const float ya = rc_tri(dn_tsdf_f(c[0][1][0]), dn_tsdf_f(c[0][1][1]), dn_tsdf_f(yp[0][0]), dn_tsdf_f(yp[0][1]), dn_tsdf_f(c[1][1][0]), dn_tsdf_f(c[1][1][1]), dn_tsdf_f(yp[1][0]), dn_tsdf_f(yp[1][1]), f);
+  const float yb = rc_tri(dn_tsdf_f(ym[0][0]), dn_tsdf_f(ym[0][1]), dn_tsdf_f(c[0][0][0]), dn_tsdf_f(c[0][0][1]), dn_tsdf_f(ym[1][0]), dn_tsdf_f(ym[1][1]), dn_tsdf_f(c[1][0][0]), dn_tsdf_f(c[1][0][1]), f);
+  const float za = rc_tri(dn_tsdf_f(c[1][0][0]), dn_tsdf_f(c[1][0][1]), dn_tsdf_f(c[1][1][0]), dn_tsdf_f(c[1][1][1]), dn_tsdf_f(zp[0][0]), dn_tsdf_f(zp[0][1]), dn_tsdf_f(zp[1][0]), dn_tsdf_f(zp[1][1]), f);
+  const float zb = rc_tri(dn_tsdf_f(zm[0][0]), dn_tsdf_f(zm[0][1]), dn_tsdf_f(zm[1][0]), dn_tsdf_f(zm[1][1]), dn_tsdf_f(c[0][0][0]), dn_tsdf_f(c[0][0][1]), dn_tsdf_f(c[0][1][0]), dn_tsdf_f(c[0][1][1]), f);
   g[0] = xa - xb; g[1] = ya - yb; g[2] = za - zb;
 }
 
@@ -238,8 +231,7 @@ struct vdo_raycast {
   size_t npix = 0, grid_bytes = 0;
   float* d_stage = nullptr;                               // [H][W] depth, [H][W][3] gradient, [H][W] weight: staging of host outputs
   uint8_t* d_grid = nullptr;                              // one byte per brick
-  unsigned long long* d_cnt = nullptr;                    // [kRcSlots][kRcCounters]
-  unsigned long long* h_cnt = nullptr;                    // pinned
+  vdo::SlotCounts cnt;                                    // [kRcSlots][kRcCounters]
   vdo::StageTimer tm;
   hipEvent_t evg = nullptr;                               // between the brick grid and the march
   double grid_ms = 0;
@@ -253,8 +245,8 @@ void vdo::rc_view_info(const vdo_raycast* view, int* W, int* H, float K[4], vdo_
 }
 
 static void rc_free(vdo_raycast* h) {
-  hipFree(h->d_stage); hipFree(h->d_grid); hipFree(h->d_cnt);
-  if (h->h_cnt) hipHostFree(h->h_cnt);
+  hipFree(h->d_stage); hipFree(h->d_grid);
+  h->cnt.destroy();
   h->tm.destroy();
   if (h->evg) hipEventDestroy(h->evg);
   delete h;
@@ -285,8 +277,7 @@ extern "C" int vdo_raycast_create(vdo_dense* map, int width, int height, const v
   for (int k = 0; k < 3; ++k) { a.n[k] = map->a.n[k]; a.nb[k] = (a.n[k] + (1 << kRcBrick) - 1) >> kRcBrick; h->grid_bytes *= (size_t)a.nb[k]; }
   h->npix = (size_t)width * height;
   const bool ok = hipMalloc((void**)&h->d_stage, h->npix * 5 * sizeof(float)) == hipSuccess && hipMalloc((void**)&h->d_grid, h->grid_bytes) == hipSuccess &&
-                  hipMalloc((void**)&h->d_cnt, kRcTotal * sizeof(unsigned long long)) == hipSuccess &&
-                  hipHostMalloc((void**)&h->h_cnt, kRcTotal * sizeof(unsigned long long), hipHostMallocDefault) == hipSuccess && h->tm.create() &&
+                  h->cnt.create(kRcSlots, kRcCounters) && h->tm.create() &&
                   hipEventCreate(&h->evg) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
@@ -330,7 +321,7 @@ extern "C" int vdo_raycast_render(vdo_raycast* h, const float T[16], float* dept
   float* o_grad = grad ? (out_is_device ? grad : h->d_stage + np) : nullptr;
   int32_t* o_wgt = weight ? (out_is_device ? weight : (int32_t*)(h->d_stage + 4 * np)) : nullptr;
   const auto t0 = h->tm.begin(s);
-  hipMemsetAsync(h->d_cnt, 0, kRcTotal * sizeof(unsigned long long), s);
+  h->cnt.zero(s);
   if (h->skip) {
     hipMemsetAsync(h->d_grid, 0, h->grid_bytes, s);
     const int v = a.n[0] % 4 == 0 ? 4 : 1;                                   // (the volume is a hipMalloc of its own: its rows are then 16-byte aligned)
@@ -341,9 +332,9 @@ extern "C" int vdo_raycast_render(vdo_raycast* h, const float T[16], float* dept
   }
   hipEventRecord(h->evg, s);
   const unsigned tiles = (unsigned)a.tiles_x * (unsigned)((a.H + 15) / 16);
-  hipLaunchKernelGGL(k_rc_march, dim3(tiles), dim3(64, 4), 0, s, a, (const uint32_t*)h->map->d_vol, (const uint8_t*)(h->skip ? h->d_grid : nullptr), o_depth, o_grad, o_wgt, h->d_cnt);
+  hipLaunchKernelGGL(k_rc_march, dim3(tiles), dim3(64, 4), 0, s, a, (const uint32_t*)h->map->d_vol, (const uint8_t*)(h->skip ? h->d_grid : nullptr), o_depth, o_grad, o_wgt, h->cnt.d);
   h->tm.mark_end(s);
-  hipMemcpyAsync(h->h_cnt, h->d_cnt, kRcTotal * sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
+  h->cnt.download(s);
   if (!out_is_device) {
     if (depth) hipMemcpyAsync(depth, o_depth, np * sizeof(float), hipMemcpyDeviceToHost, s);
     if (grad) hipMemcpyAsync(grad, o_grad, np * 3 * sizeof(float), hipMemcpyDeviceToHost, s);
@@ -351,11 +342,7 @@ extern "C" int vdo_raycast_render(vdo_raycast* h, const float T[16], float* dept
   }
   rc = sync_check(who, s);
   if (rc != VDO_OK) return rc;
-  for (int k = 0; k < 3; ++k) {
-    unsigned long long sum = 0;
-    for (int slot = 0; slot < kRcSlots; ++slot) sum += h->h_cnt[slot * kRcCounters + k];
-    out[k] = (int64_t)sum;
-  }
+  for (int k = 0; k < 3; ++k) out[k] = h->cnt.sum(k);
   h->tm.finish(t0);
   h->grid_ms = h->skip ? elapsed_ms(h->tm.ev0, h->evg) : 0.0;
   return VDO_OK;
