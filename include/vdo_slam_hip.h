@@ -406,6 +406,20 @@ int vdo_orb_last_timing(vdo_orb* orb, double ms[2]);
  * took the host tree: 1 over the node limit at create (or VDO_ORB_HOST_TREE / VDO_ORB_FUSED_ANGLE), 2 more candidates than
  * the scratch holds, 3 more nodes than N + 3, 4 round limit, 5 a candidate outside the initial strips. */
 int vdo_orb_tree_info(vdo_orb* orb, int level, int* on_device, int* status);
+/* Diagnostic: K5 alone on given candidate lists instead of an image's.  level_count[n_levels]; x, y, resp level-major (level 0's
+ * list first), x, y relative to the level's keypoint region as vdo_orb_get_candidates returns them.  The lists are placed where
+ * the extraction's compaction puts its candidates, then the extraction's own tree launch and per-level resolution run (device
+ * ids where the status is 0, the host tree otherwise; a handle created under VDO_ORB_HOST_TREE=1 runs the host tree);
+ * vdo_orb_tree_info tells where each level ran.  sel: for level 0, 1, ... the indices INTO THAT LEVEL'S LIST of its keypoints,
+ * in the order of the node list; sel_count[n_levels] their numbers.  Refused with VDO_ERR_INVALID, the message naming the
+ * argument, and nothing written: a null argument, a negative count, more candidates in all than the extractor's dense
+ * capacity, a sel_capacity below what the lists can return (per level min(count, max(4 nIni, n_features + 2))), an x or y that
+ * is not an integer-valued float inside the level's region [0, w - 32) x [0, h - 32), a resp that is not an integer-valued
+ * float in [0, 255] - what the compaction guarantees and the device tree relies on.  Afterwards the handle holds no keypoints
+ * (vdo_orb_last_keypoints 0, no descriptors; vdo_orb_get_candidates returns the lists, with angles that mean nothing: no
+ * pyramid stands behind them); the next vdo_orb_extract behaves as on a fresh handle. */
+int vdo_orb_tree_run(vdo_orb* orb, const int32_t* level_count, const float* x, const float* y, const float* resp,
+                     int32_t* sel, int sel_capacity, int32_t* sel_count);
 /* Kernel launches that build the pyramid of one image: 2 (levels 0-4 cascaded in LDS from the image, the rest from level 4;
  * 1 with <= 5 levels) - possible with <= 8 levels whose cascaded source windows fit the LDS buffers - or n_levels (level by
  * level; also forced by the environment variable VDO_ORB_PYRAMID_LAUNCHES). */

@@ -115,7 +115,7 @@ void build_pyramid(const uint8_t* gray, int w, int h, const vdo_orb_params& p, s
 }
 
 // cv::FAST(roi, kps, threshold, true) — TYPE_9_16.  Returns keypoints (x,y,score) in raster order.
-struct Cand { float x, y, resp; };
+struct Cand { float x, y, resp; int id = -1; };   // id: position in the list distribute was given (set there)
 const int RING[16][2] = {{0, 3}, {1, 3}, {2, 2}, {3, 1}, {3, 0}, {3, -1}, {2, -2}, {1, -3}, {0, -3}, {-1, -3}, {-2, -2}, {-3, -1}, {-3, 0}, {-3, 1}, {-2, 2}, {-1, 3}};
 
 int fast_score(const Img& im, int x, int y, int t) {   // 0 = not a corner, else cornerScore (>= t)
@@ -218,8 +218,14 @@ void divide(const Node& n, Node& n1, Node& n2, Node& n3, Node& n4) {
 }
 
 // false: nIni == 0 (a region less than half as wide as it is tall), where the reference indexes an empty vector
-bool distribute(const std::vector<Cand>& in, int minX, int maxX, int minY, int maxY, int N, std::vector<Cand>& out) {
+// sel / trace (both nullable, neither changes what is computed): the list index of every keypoint of `out`; {full rounds run, final
+// passes run, nodes processed in the last final pass, nodes in that pass's sorted list}
+bool distribute(const std::vector<Cand>& in, int minX, int maxX, int minY, int maxY, int N, std::vector<Cand>& out,
+                std::vector<int>* sel = nullptr, int* trace = nullptr) {
   out.clear();
+  if (sel) sel->clear();
+  int tr[4] = {0, 0, 0, 0};
+  if (trace) std::memcpy(trace, tr, sizeof(tr));
   if (in.empty()) return true;
   const int nIni = (int)std::round((float)(maxX - minX) / (maxY - minY));
   if (nIni < 1) return false;
@@ -235,7 +241,7 @@ bool distribute(const std::vector<Cand>& in, int minX, int maxX, int minY, int m
     nodes.push_back(ni);
     ini[i] = &nodes.back();
   }
-  for (const Cand& kp : in) ini[(int)(kp.x / hX)]->keys.push_back(kp);
+  for (size_t k = 0; k < in.size(); ++k) { Cand kp = in[k]; kp.id = (int)k; ini[(int)(kp.x / hX)]->keys.push_back(kp); }
   for (auto it = nodes.begin(); it != nodes.end();) {
     if (it->keys.size() == 1) { it->noMore = true; ++it; }
     else if (it->keys.empty()) it = nodes.erase(it);
@@ -269,6 +275,7 @@ bool distribute(const std::vector<Cand>& in, int minX, int maxX, int minY, int m
       add_children(c, &nToExpand);
       it = nodes.erase(it);
     }
+    ++tr[0];
     if ((int)nodes.size() >= N || (int)nodes.size() == prevSize) finish = true;
     else if ((int)nodes.size() + nToExpand * 3 > N) {
       while (!finish) {
@@ -276,7 +283,9 @@ bool distribute(const std::vector<Cand>& in, int minX, int maxX, int minY, int m
         std::vector<SP> prev = sizeAndNode;
         sizeAndNode.clear();
         std::sort(prev.begin(), prev.end(), sp_less);
+        ++tr[1]; tr[2] = 0; tr[3] = (int)prev.size();
         for (int j = (int)prev.size() - 1; j >= 0; --j) {
+          ++tr[2];
           Node c[4];
           divide(*prev[j].second, c[0], c[1], c[2], c[3]);
           add_children(c, nullptr);
@@ -292,7 +301,9 @@ bool distribute(const std::vector<Cand>& in, int minX, int maxX, int minY, int m
     float mr = best->resp;
     for (size_t k = 1; k < nd.keys.size(); ++k) if (nd.keys[k].resp > mr) { best = &nd.keys[k]; mr = nd.keys[k].resp; }
     out.push_back(*best);
+    if (sel) sel->push_back(best->id);
   }
+  if (trace) std::memcpy(trace, tr, sizeof(tr));
   return true;
 }
 
@@ -492,6 +503,21 @@ extern "C" int vdo_oracle_orb_extract_desc(const uint8_t* gray, int w, int h, co
     }
   }
   return n;
+}
+
+// DistributeOctTree alone on a given candidate list (x, y relative to (minX, minY)): sel = the list index of every keypoint, in the order
+// of the node list.  Returns their number; -1 when cap is too small, -2 where distribute refuses.  trace (nullable): see distribute.
+extern "C" int vdo_oracle_orb_distribute(const float* x, const float* y, const float* resp, int n, int minX, int maxX, int minY, int maxY, int N,
+                                         int32_t* sel, int cap, int32_t trace[4]) {
+  std::vector<Cand> c((size_t)std::max(n, 0)), out;
+  for (int i = 0; i < n; ++i) { c[i].x = x[i]; c[i].y = y[i]; c[i].resp = resp[i]; }
+  std::vector<int> idx;
+  int tr[4];
+  if (!distribute(c, minX, maxX, minY, maxY, N, out, &idx, tr)) return -2;
+  if (trace) for (int k = 0; k < 4; ++k) trace[k] = tr[k];
+  if ((int)idx.size() > cap) return -1;
+  for (size_t k = 0; k < idx.size(); ++k) sel[k] = idx[k];
+  return (int)idx.size();
 }
 
 extern "C" int vdo_oracle_orb_extract(const uint8_t* gray, int w, int h, const vdo_orb_params* p,

@@ -218,6 +218,11 @@ int vdo_oracle_orb_fast_level(const uint8_t* gray, int w, int h, const vdo_orb_p
                               float* x, float* y, float* resp, int cap);
 int vdo_oracle_orb_extract(const uint8_t* gray, int w, int h, const vdo_orb_params* p,
                            float* kx, float* ky, float* kresp, float* kangle, int32_t* koct, float* ksize, int cap);
+/* DistributeOctTree alone on a candidate list (x, y relative to (minX, minY)): sel = the list index of every keypoint, in the order of
+ * the node list; returns their number, -1 when cap is too small, -2 where the tree would start with no node.  trace (nullable):
+ * {full rounds run, final passes run, nodes processed in the last final pass, nodes in that pass's sorted list} */
+int vdo_oracle_orb_distribute(const float* x, const float* y, const float* resp, int n, int minX, int maxX, int minY, int maxY, int N,
+                              int32_t* sel, int cap, int32_t trace[4]);
 /* the same + rotated BRIEF (computeOrbDescriptor, src/ORBextractor.cc:97-136; commented-out call site :1083-1091): desc [cap][32], nullable */
 int vdo_oracle_orb_extract_desc(const uint8_t* gray, int w, int h, const vdo_orb_params* p,
                                 float* kx, float* ky, float* kresp, float* kangle, int32_t* koct, float* ksize, int cap, uint8_t* desc);

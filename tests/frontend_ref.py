@@ -62,6 +62,21 @@ def extract_desc(o, gray, prm=PARAMS, cap=8192):
     return dict(x=a[0][:n], y=a[1][:n], response=a[2][:n], angle=a[3][:n], octave=octv[:n], size=a[4][:n], desc=desc[:n])
 
 
+def distribute(o, x, y, resp, region_w, region_h, N):
+    """DistributeOctTree alone (vdo_oracle_orb_distribute) on a candidate list whose x, y are relative to the region's corner, the region
+    being region_w x region_h.  Returns (sel, trace): the list index of every keypoint in the order of the node list, and
+    [full rounds run, final passes run, nodes processed in the last final pass, nodes in that pass's sorted list]."""
+    x, y, resp = (np.ascontiguousarray(a, dtype=np.float32) for a in (x, y, resp))
+    n = x.size
+    assert y.size == n and resp.size == n
+    cap = max(n, 1)
+    sel = np.zeros(cap, np.int32); trace = np.zeros(4, np.int32)
+    o.vdo_oracle_orb_distribute.argtypes = [K.c_float_p] * 3 + [C.c_int] * 6 + [K.c_int32_p, C.c_int, K.c_int32_p]
+    m = o.vdo_oracle_orb_distribute(_fp(x), _fp(y), _fp(resp), n, 16, 16 + region_w, 16, 16 + region_h, N, _ip(sel), cap, _ip(trace))
+    assert m >= 0, f"vdo_oracle_orb_distribute: {m}"
+    return sel[:m].copy(), trace
+
+
 def blur7(o, img):
     img = np.ascontiguousarray(img)
     out = np.zeros_like(img)

@@ -71,6 +71,27 @@ def test_extract_counts_order_and_angles(oracle, frame):
     assert kp["size"][0] == 31 and kp["size"][-1] == int(31 * np.float32(1.2) ** 7)
 
 
+def test_distribute_hook_selects_the_keypoints_of_extract_on_every_level(oracle, frame):
+    """vdo_oracle_orb_distribute (the tree alone, on a list) fed with vdo_oracle_orb_fast_level's candidates is the tree inside
+    vdo_oracle_orb_extract: the same keypoints in the same order on every level, and a trace that is consistent with them."""
+    gray = frame["gray"]
+    kp = R.extract(oracle, gray)
+    ws, hs, nf = R.level_sizes(oracle, gray.shape[1], gray.shape[0])
+    scale = np.float32(1)
+    for l in range(R.PARAMS.n_levels):
+        x, y, r = R.fast_level(oracle, gray, l)
+        sel, trace = R.distribute(oracle, x, y, r, int(ws[l]) - 32, int(hs[l]) - 32, int(nf[l]))
+        assert sel.size == np.unique(sel).size and (sel.size == 0 or (sel.min() >= 0 and sel.max() < x.size))
+        want = kp["octave"] == l
+        assert sel.size == int(want.sum()) > 0, (l, sel.size, int(want.sum()))
+        ex, ey = x[sel] + np.float32(16), y[sel] + np.float32(16)
+        if l:
+            ex, ey = ex * scale, ey * scale
+        assert np.array_equal(ex, kp["x"][want]) and np.array_equal(ey, kp["y"][want]) and np.array_equal(r[sel], kp["response"][want]), l
+        assert trace[0] >= 1 and (trace[1] == 0 or 1 <= trace[2] <= trace[3]), trace
+        scale = np.float32(scale * np.float32(R.PARAMS.scale_factor))
+
+
 def test_blur_matches_float_gaussian_within_fixed_point_gain(oracle, frame):
     img = frame["gray"][:120, :200].copy()
     out = R.blur7(oracle, img).astype(np.float64)

@@ -1379,6 +1379,41 @@ extern "C" int vdo_orb_create(vdo_ctx* ctx, const vdo_orb_params* prm, int w, in
   return VDO_OK;
 }
 
+// K5 on the device: k_quadtree behind whatever has put the candidate lists of all levels into d_level_cnt / d_x / d_y / d_resp on the extractor's stream
+// (k_compact; vdo_orb_tree_run).  Its counts, status words and ids land in the mapped block behind the four candidate rows and in d_qhdr / d_qsel.
+static void orb_queue_tree(vdo_orb* o) {
+  int* qh = (int*)(o->d_pin + 32 + 4 * (size_t)o->dense_cap);
+  hipLaunchKernelGGL(k_quadtree, dim3(o->prm.n_levels), dim3(kQtThreads), 0, o->ctx->stream, (const QtDesc*)o->d_qtd, (const int*)o->d_level_cnt, (const float*)o->d_x,
+                     (const float*)o->d_y, (const float*)o->d_resp, o->d_qt_i, o->d_qt_p, o->d_qsel, o->d_qhdr, qh + 32, qh);
+}
+
+// K5 of every level once the candidates (o->hx / hy / hresp, o->hlevel_cnt) and, with the device tree, k_quadtree's block are on the host: o->sel[l] = the
+// level's keypoints as ids into its own list, in list order - the device's ids where its status is kQtOk, QuadTree::run otherwise.  on_dev[l] says which;
+// returns whether every level ran on the device.
+static bool orb_resolve_levels(vdo_orb* o, bool on_dev[16]) {
+  const int NL = o->prm.n_levels;
+  int lvl_pos[17];
+  lvl_pos[0] = 0;
+  for (int l = 0; l < NL; ++l) lvl_pos[l + 1] = lvl_pos[l] + o->hlevel_cnt[l];
+  const int minB = kEdge - 3;
+  const int* qh = (const int*)(o->h_pin + 32 + 4 * (size_t)o->dense_cap);     // device tree: [16 counts][16 status][ids]
+  bool all_dev = o->dev_tree;
+  for (int l = 0; l < NL; ++l) { on_dev[l] = o->dev_tree && qh[16 + l] == kQtOk && qh[l] >= 0 && qh[l] <= o->qtd[l].node_cap; all_dev = all_dev && on_dev[l]; }
+  auto level_task = [&](int l) {
+    const LevelDesc& L = o->levels[l];
+    const int pos = lvl_pos[l];
+    if (on_dev[l]) {
+      const int* ids = qh + 32 + o->qtd[l].out_off;
+      o->sel[l].assign(ids, ids + qh[l]);
+      return;
+    }
+    o->qt[l].run(o->hx + pos, o->hy + pos, o->hresp + pos, o->hlevel_cnt[l], minB, L.w - kEdge + 3, minB, L.h - kEdge + 3, o->nfeat[l], o->sel[l]);
+  };
+  if (o->pool) o->pool->run(NL, level_task);
+  else for (int l = 0; l < NL; ++l) level_task(l);
+  return all_dev;
+}
+
 // Device part of operator(): pyramid, blur, FAST cells, compaction + angles.  gray_dev: device, row stride `stride`.
 static int orb_device_stage(vdo_orb* o, const uint8_t* gray_dev, int stride) {
   hipStream_t s = o->ctx->stream;
@@ -1414,8 +1449,7 @@ static int orb_device_stage(vdo_orb* o, const uint8_t* gray_dev, int stride) {
                        (const uint32_t*)o->d_pack, o->ncells, o->cell_cap, o->d_x, o->d_y, o->d_resp, o->d_lvl, (int*)o->d_pin, rows, rows + pitch, rows + 2 * pitch);
     if (o->dev_tree) {
       int* qh = (int*)(rows + 4 * pitch);
-      hipLaunchKernelGGL(k_quadtree, dim3(NL), dim3(kQtThreads), 0, s, (const QtDesc*)o->d_qtd, (const int*)o->d_level_cnt, (const float*)o->d_x, (const float*)o->d_y,
-                         (const float*)o->d_resp, o->d_qt_i, o->d_qt_p, o->d_qsel, o->d_qhdr, qh + 32, qh);
+      orb_queue_tree(o);
       hipLaunchKernelGGL(k_qt_rows, dim3((o->qt_out + 7) / 8), dim3(256), 0, s, (const QtDesc*)o->d_qtd, NL, (const int*)o->d_qhdr, (const int*)o->d_qsel, (const float*)o->d_x,
                          (const float*)o->d_y, (const float*)o->d_resp, (const uint8_t*)o->d_pyr, (const LevelDesc*)o->d_levels, o->um, (float*)(qh + 32 + o->qt_out), o->qt_out);
     }
@@ -1529,22 +1563,9 @@ extern "C" int vdo_orb_extract_end(vdo_orb* o, vdo_keypoints* out) {
   lvl_pos[0] = 0;
   for (int l = 0; l < NL; ++l) lvl_pos[l + 1] = lvl_pos[l] + o->hlevel_cnt[l];
   const int minB = kEdge - 3;
-  const int* qh = (const int*)(rows + 4 * pitch);     // device tree: [16 counts][16 status][ids]
+  const int* qh = (const int*)(rows + 4 * pitch);     // device tree: [16 counts][16 status][ids][rows of the keypoints]
   bool on_dev[16] = {};
-  bool all_dev = o->dev_tree;
-  for (int l = 0; l < NL; ++l) { on_dev[l] = o->dev_tree && qh[16 + l] == kQtOk && qh[l] >= 0 && qh[l] <= o->qtd[l].node_cap; all_dev = all_dev && on_dev[l]; }
-  auto level_task = [&](int l) {
-    const LevelDesc& L = o->levels[l];
-    const int pos = lvl_pos[l];
-    if (on_dev[l]) {
-      const int* ids = qh + 32 + o->qtd[l].out_off;
-      o->sel[l].assign(ids, ids + qh[l]);
-      return;
-    }
-    o->qt[l].run(o->hx + pos, o->hy + pos, o->hresp + pos, o->hlevel_cnt[l], minB, L.w - kEdge + 3, minB, L.h - kEdge + 3, o->nfeat[l], o->sel[l]);
-  };
-  if (o->pool) o->pool->run(NL, level_task);
-  else for (int l = 0; l < NL; ++l) level_task(l);
+  const bool all_dev = orb_resolve_levels(o, on_dev);
   // split path: the angle row was written under the quadtrees (o->hang and vdo_orb_get_candidates are valid from here on)
   // (device tree: k_qt_rows has written the rows of its keypoints, angle included; the angle row of all candidates is waited for only by a level
   //  that took the host tree, and by vdo_orb_get_candidates)
@@ -1674,6 +1695,91 @@ extern "C" int vdo_orb_tree_info(vdo_orb* o, int level, int* on_device, int* sta
   if ((int)o->hlevel_cnt.size() != 16) return set_error(VDO_ERR_INVALID, "vdo_orb_tree_info: nothing extracted yet");
   const int st = o->dev_tree ? ((const int*)(o->h_pin + 32 + 4 * (size_t)o->dense_cap))[16 + level] : (int)kQtHostLevel;
   *on_device = st == kQtOk; *status = st;
+  return VDO_OK;
+}
+
+// K5 alone on given candidate lists (diagnostic: the tests pin k_quadtree on lists no image produces).  The lists go where k_compact puts an image's
+// candidates, then the extraction's own launch (orb_queue_tree) and the extraction's own resolution (orb_resolve_levels) run.  k_qt_rows is not queued: it
+// reads a pyramid.  Everything is checked before anything is written.
+extern "C" int vdo_orb_tree_run(vdo_orb* o, const int32_t* level_count, const float* x, const float* y, const float* resp,
+                                int32_t* sel, int sel_capacity, int32_t* sel_count) {
+  if (!o) return set_error(VDO_ERR_INVALID, "vdo_orb_tree_run: null argument orb");
+  if (!level_count) return set_error(VDO_ERR_INVALID, "vdo_orb_tree_run: null argument level_count");
+  if (!x) return set_error(VDO_ERR_INVALID, "vdo_orb_tree_run: null argument x");
+  if (!y) return set_error(VDO_ERR_INVALID, "vdo_orb_tree_run: null argument y");
+  if (!resp) return set_error(VDO_ERR_INVALID, "vdo_orb_tree_run: null argument resp");
+  if (!sel) return set_error(VDO_ERR_INVALID, "vdo_orb_tree_run: null argument sel");
+  if (!sel_count) return set_error(VDO_ERR_INVALID, "vdo_orb_tree_run: null argument sel_count");
+  if (o->begun) return set_error(VDO_ERR_INVALID, "vdo_orb_tree_run: an extraction is in flight (vdo_orb_extract_begin without _end)");
+  const int NL = o->prm.n_levels;
+  int64_t total = 0, need = 0;
+  for (int l = 0; l < NL; ++l) {
+    if (level_count[l] < 0) return set_error(VDO_ERR_INVALID, "vdo_orb_tree_run: level_count[%d] = %d is negative", l, level_count[l]);
+    total += level_count[l];
+  }
+  if (total > o->dense_cap) return set_error(VDO_ERR_INVALID, "vdo_orb_tree_run: level_count sums to %lld candidates, the extractor's dense capacity is %d", (long long)total, o->dense_cap);
+  std::vector<int> lvl((size_t)total);
+  {
+    int64_t pos = 0;
+    for (int l = 0; l < NL; ++l) {
+      const int n = level_count[l];
+      const int W = o->levels[l].w - 2 * kEdge + 6, H = o->levels[l].h - 2 * kEdge + 6;     // maxX - minX, maxY - minY
+      bool cells = false;
+      for (int c : o->cell_level) cells = cells || c == l;
+      if (n > 0 && !cells) return set_error(VDO_ERR_INVALID, "vdo_orb_tree_run: level_count[%d] = %d, but level %d has no FAST cell and never has a candidate", l, n, l);
+      // what a level can return: a keypoint per node (vdo_orb_create: max(4 nIni, N + 2)) and never more than it has candidates
+      if (cells) need += std::min<int64_t>(n, std::max(4 * o->qtd[l].nIni, o->nfeat[l] + 2));
+      for (int k = 0; k < n; ++k) {
+        const float fx = x[pos + k], fy = y[pos + k], fr = resp[pos + k];
+        if (!(fx >= 0.f && fx < (float)W && fx == std::floor(fx)))
+          return set_error(VDO_ERR_INVALID, "vdo_orb_tree_run: x[%lld] = %g (level %d, key %d) is not an integer in [0, %d)", (long long)(pos + k), (double)fx, l, k, W);
+        if (!(fy >= 0.f && fy < (float)H && fy == std::floor(fy)))
+          return set_error(VDO_ERR_INVALID, "vdo_orb_tree_run: y[%lld] = %g (level %d, key %d) is not an integer in [0, %d)", (long long)(pos + k), (double)fy, l, k, H);
+        if (!(fr >= 0.f && fr <= 255.f && fr == std::floor(fr)))
+          return set_error(VDO_ERR_INVALID, "vdo_orb_tree_run: resp[%lld] = %g (level %d, key %d) is not an integer in [0, 255]", (long long)(pos + k), (double)fr, l, k);
+        lvl[pos + k] = l;
+      }
+      pos += n;
+    }
+  }
+  if (sel_capacity < need) return set_error(VDO_ERR_INVALID, "vdo_orb_tree_run: sel_capacity %d too small, these lists can return %lld keypoints", sel_capacity, (long long)need);
+  int rc = ctx_bind(o->ctx);
+  if (rc != VDO_OK) return rc;
+  hipStream_t s = o->ctx->stream;
+  if (hipStreamSynchronize(s) != hipSuccess) return set_error(VDO_ERR_NO_DEVICE, "vdo_orb_tree_run: %s", hipGetErrorString(hipGetLastError()));   // (the last extraction's blur / angle stages)
+  // the lists where k_compact puts them: header and x / y / resp rows of the mapped block (what the host tree reads), the dense device rows and counts
+  int* hdr = (int*)o->h_pin;
+  float* rows = o->h_pin + 32;
+  const size_t pitch = (size_t)o->dense_cap;
+  for (int q = 0; q < 32; ++q) hdr[q] = 0;
+  for (int l = 0; l < NL; ++l) hdr[l] = level_count[l];
+  hdr[16] = (int)total;
+  if (total) {
+    std::memcpy(rows, x, 4 * (size_t)total); std::memcpy(rows + pitch, y, 4 * (size_t)total); std::memcpy(rows + 2 * pitch, resp, 4 * (size_t)total);
+    hipMemcpyAsync(o->d_x, rows, 4 * (size_t)total, hipMemcpyHostToDevice, s);
+    hipMemcpyAsync(o->d_y, rows + pitch, 4 * (size_t)total, hipMemcpyHostToDevice, s);
+    hipMemcpyAsync(o->d_resp, rows + 2 * pitch, 4 * (size_t)total, hipMemcpyHostToDevice, s);
+    hipMemcpyAsync(o->d_lvl, lvl.data(), 4 * (size_t)total, hipMemcpyHostToDevice, s);
+  }
+  hipMemcpyAsync(o->d_level_cnt, hdr, 4 * 32, hipMemcpyHostToDevice, s);
+  if (o->dev_tree) orb_queue_tree(o);
+  // no keypoints of an image from here on: nothing for the descriptors or the matcher (no pyramid stands behind these lists)
+  o->desc_ready = o->pos_ready = false; o->ang_queued = false;
+  o->sel_dense.clear();
+  o->hlevel_cnt.assign(hdr, hdr + 16);
+  o->n_cand = (int)total;
+  o->hx = rows; o->hy = rows + pitch; o->hresp = rows + 2 * pitch; o->hang = rows + 3 * pitch;
+  if (hipStreamSynchronize(s) != hipSuccess) return set_error(VDO_ERR_NO_DEVICE, "vdo_orb_tree_run: %s", hipGetErrorString(hipGetLastError()));
+  bool on_dev[16] = {};
+  orb_resolve_levels(o, on_dev);
+  int64_t m = 0;
+  for (int l = 0; l < NL; ++l) m += (int64_t)o->sel[l].size();
+  if (m > sel_capacity) return set_error(VDO_ERR_INTERNAL, "vdo_orb_tree_run: %lld keypoints, more than the bound %lld", (long long)m, (long long)need);
+  int n = 0;
+  for (int l = 0; l < NL; ++l) {
+    for (int id : o->sel[l]) sel[n++] = id;
+    sel_count[l] = (int)o->sel[l].size();
+  }
   return VDO_OK;
 }
 

@@ -154,6 +154,33 @@ class ORBextractor:
         K.check(_lib().vdo_orb_get_candidates(self._h, level, _fp(x), _fp(y), _fp(r), _fp(a), cap, C.byref(n)))
         return x[:n.value], y[:n.value], r[:n.value], a[:n.value]
 
+    def tree_info(self):
+        """(on_device, status) of every level in the last extraction or ``tree_run`` (vdo_orb_tree_info)."""
+        L = _lib()
+        L.vdo_orb_tree_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        out = []
+        for l in range(self.nlevels):
+            d, s = C.c_int(), C.c_int()
+            K.check(L.vdo_orb_tree_info(self._h, l, C.byref(d), C.byref(s)))
+            out.append((d.value, s.value))
+        return out
+
+    def tree_run(self, lists, capacity=None):
+        """The extractor's quadtree alone on given candidate lists (vdo_orb_tree_run, diagnostic): ``lists`` holds one ``(x, y, resp)``
+        per level, x and y relative to the level's keypoint region.  Returns per level the indices into its list, in list order."""
+        if len(lists) != self.nlevels:
+            raise ValueError(f"{len(lists)} lists, extractor has {self.nlevels} levels")
+        cnt = np.array([np.asarray(q[0]).size for q in lists], np.int32)
+        x, y, r = (np.ascontiguousarray(np.concatenate([np.asarray(q[k], np.float32).ravel() for q in lists] + [np.zeros(1, np.float32)]))
+                   for k in range(3))
+        cap = int(capacity if capacity is not None else max(self.max_keypoints, 1))
+        sel = np.zeros(max(cap, 1), np.int32); sel_cnt = np.zeros(self.nlevels, np.int32)
+        L = _lib()
+        L.vdo_orb_tree_run.argtypes = [C.c_void_p, K.c_int32_p, K.c_float_p, K.c_float_p, K.c_float_p, K.c_int32_p, C.c_int, K.c_int32_p]
+        K.check(L.vdo_orb_tree_run(self._h, _ip(cnt), _fp(x), _fp(y), _fp(r), _ip(sel), cap, _ip(sel_cnt)))
+        off = np.concatenate([[0], np.cumsum(sel_cnt)])
+        return [sel[off[l]:off[l + 1]].copy() for l in range(self.nlevels)]
+
     def close(self):
         if self._h:
             _lib().vdo_orb_destroy(self._h); self._h = C.c_void_p()
