@@ -1586,6 +1586,127 @@ int vdo_distance_set_method(vdo_distance* h, int method);
 /* The last compute or sample: ms[0] wall time of the call, ms[1] device time from the first command to the end of the last kernel. */
 int vdo_distance_last_timing(vdo_distance* h, double ms[2]);
 
+/* ---- Photometric aligner: an intensity term beside the aligner's point-to-plane ICP, and their joint solve ------------------------------------
+ * New (the reference has no dense pose estimator).  Point-to-plane ICP cannot see a motion that slides along the surface: in front of a road, a
+ * facade or a corridor wall two or three of the six motions leave every residual of the Aligner unchanged.  The texture on the surface can see them.
+ * A vdo_photo compares the grey value of every frame pixel with the bilinear grey value of a MODEL image at the pixel's projection, and gives the
+ * normal equations of that residual in the Aligner's own form - the same twist about the camera, the same 28 sums, the same tree -, so that the two
+ * systems add (vdo_photo_combine) and the Aligner's host step (vdo_align_step) solves their sum.  All per-sample arithmetic is fp32, one rounded
+ * operation per step in the order written, no contraction (/ and floorf correctly rounded); every gathered address is bounded by float compares
+ * made before any conversion to int (a NaN fails them); the 28 terms are exact double products; the sums are in double in ONE fixed tree.  No float
+ * atomics.  No result depends on workgroup shape, on the launch shape or on the schedule; two runs give the same bits.
+ *
+ * Grey image.  The frame's image is uint8, `channels` 1, 3 or 4 (the fourth is ignored) per pixel, rows image_stride_bytes apart, rgb_order 0: R
+ *   first, 1: B first - as vdo_colour_integrate takes it.  Y = (77*R + 150*G + 29*B + 128) >> 8 in integers (77 + 150 + 29 = 256: a grey pixel
+ *   keeps its value, 0 and 255 stay 0 and 255); with 1 channel Y is the value.  Y is stored as a float, which is exact.  The handle owns ONE
+ *   [H][W] float image I of the current frame, written by a pack kernel (vdo_photo_set_image).  An intensity is VALID iff it is finite and >= 0
+ *   (a packed image is valid everywhere; a model's intensity image may hold anything).
+ * Model.  The handle owns ONE packed image [Hm][Wm] of (depth, intensity) float pairs with its intrinsics Km = (fxm, fym, cxm, cym) and its pose
+ *   Tm (world -> camera, as T); nothing is borrowed.  Its size and intrinsics may differ from the frame's; Wm * Hm is at most W * H.  Dm is a
+ *   z-depth.  A model pixel is USABLE iff its depth is finite and > 0 and its intensity is valid.  vdo_photo_set_model packs any two float
+ *   images unchanged.  vdo_photo_keep_as_model makes the current frame the model: the intensity is I, Km = K, Tm = T, and the depth is d where
+ *   d passes the frame's depth test below and the mask is NULL or 0 there, else 0.0f - moving objects are left out of the model.
+ * Inputs of a linearisation.  depth D[H][W], mask, K, T and the samples exactly as the Aligner has them; I as above.
+ * Per sample (i, j), pixel (x, y) = (i*s, j*s):
+ *      d = D(y,x);  iF = I(y,x);   skip[no depth] unless d finite, d > max(min_depth, 0) and d <= max_depth, and iF valid
+ *                                  skip[masked] if mask != NULL and mask(y,x) != 0
+ *      dx, dy, Pc, q, Pw, Xm, Ym, Zm as the Aligner;          skip[no model] unless Zm finite and Zm > FLT_MIN
+ *      u = (fxm*Xm)/Zm + cxm;  v = (fym*Ym)/Zm + cym;  x0 = floorf(u);  y0 = floorf(v)
+ *                                  skip[no model] unless u, v finite, 0 <= x0 <= (float)(Wm-2), 0 <= y0 <= (float)(Hm-2)
+ *                                  (so u = Wm-1 exactly has no model, and a model with Wm < 2 or Hm < 2 skips every sample as no model)
+ *      fa = u - x0;  fb = v - y0
+ *      the model pixels (y0,x0) (y0,x0+1) (y0+1,x0) (y0+1,x0+1): depths d00 d10 d01 d11, intensities i00 i10 i01 i11
+ *                                  skip[no model] unless all four are usable
+ *                                  skip[far] unless fabsf(dk - Zm) <= max_dist for all four (the occlusion gate)
+ *      top = i00 + fa*(i10 - i00);  bot = i01 + fa*(i11 - i01);  im = top + fb*(bot - top)
+ *      gx = (i10 - i00) + fb*((i11 - i01) - (i10 - i00));  gy = bot - top
+ *      e = im - iF;                skip[far] unless fabsf(e) <= max_diff
+ *      iz = 1.0f/Zm;  ax = (fxm*gx)*iz;  ay = (fym*gy)*iz;  az = -(((ax*Xm) + (ay*Ym))*iz)      (the gradient of im by the point in the model's camera)
+ *      gw_a = (Tm0a*ax + Tm1a*ay) + Tm2a*az                                                      (in the world)
+ *      gc_a = (Ta0*gw0 + Ta1*gw1) + Ta2*gw2                                                      (in the frame's camera)
+ *      J = (gc0, gc1, gc2,  Pc1*gc2 - Pc2*gc1,  Pc2*gc0 - Pc0*gc2,  Pc0*gc1 - Pc1*gc0);   w = 1
+ *   e is in grey levels.  With T' = Exp(-xi) * T the residual changes by J . xi to first order, the Aligner's convention.
+ * Terms, 28 per sample, in double and exact: A_ij = (double)J_i * (double)J_j, i <= j, row-major; b_i = (double)J_i * (double)e;
+ *   chi2 = (double)e * (double)e.  A skipped sample contributes +0.0.
+ * The sum: the Aligner's, word for word - 8 x 8 sample tiles, slot ((j/8)*tiles_x + i/8)*64 + (j%8)*8 + (i%8), padded with +0.0 to a power of two,
+ *   the adjacent-pair tree in double.  Counts, int64: used, no depth, masked, no model, far; they add up to Ws*Hs.
+ * Combine (vdo_photo_combine, pure host code).  lam = weight*weight; out[k] = geo[k] + lam*photo[k], two rounded operations in double, no
+ *   contraction; a NULL geo stands for 28 values +0.0.  weight is in metres per grey level: it turns a grey residual into the Aligner's metres.
+ * Solve.  Per round, at the same T: the photometric linearisation, and with a vdo_align its linearisation of the same depth and mask.  Status 1
+ *   (T unchanged, xi = 0) if used_p < min_pixels or (a vdo_align is given and used_g < ITS min_pixels).  Otherwise combine and
+ *   vdo_align_step(out, used_g + used_p, 6, T, ..).  The stop rules are vdo_align_solve's. */
+typedef struct vdo_photo vdo_photo;
+typedef struct vdo_photo_params {
+  float K[4];                       /* fx, fy, cx, cy of the frame; fx, fy > 0, all finite */
+  float min_depth, max_depth;       /* 0 <= min_depth < max_depth, finite, metres */
+  float max_dist;                   /* > 0, finite, metres: the gate on |model depth - Zm| at each of the four model pixels */
+  float max_diff;                   /* > 0, finite, grey levels: the gate on |e|; 255 turns it off */
+  int32_t subsample;                /* 1..8 */
+  int32_t min_pixels;               /* >= 6 */
+  int32_t max_iterations;           /* 1..64 */
+  float eps;                        /* >= 0, finite: a solve stops when every component of xi is at most eps in magnitude */
+  int32_t keep_rows;                /* 0 / 1: keep the row image of the last linearisation (vdo_photo_get_rows) */
+} vdo_photo_params;
+typedef struct vdo_photo_report {
+  int32_t iterations;               /* rounds done */
+  int32_t status;                   /* of the last round: 0, 1, 2 */
+  int64_t used_geo, used_photo;     /* samples used at the last round (used_geo 0 without a vdo_align) */
+  double rms_geo_first, rms_geo_last;       /* sqrt(chi2_geo / used_geo), metres, 0 when used_geo is 0 */
+  double rms_photo_first, rms_photo_last;   /* sqrt(chi2_photo / used_photo), grey levels, 0 when used_photo is 0 */
+  double xi[6];                     /* of the last step (0 unless its status is 0) */
+} vdo_photo_report;
+#define VDO_PHOTO_TRACE_ROW (16 + 28 + 5 + 28 + 5)
+/* A photometric aligner for width x height frames.  ALL device memory is taken here (staging for a host or strided depth and mask, 8 bytes per
+ * pixel, and for a host image, 4; the grey image, 4; the model, 8 per pixel of the FRAME's size; the tile partials, 256 bytes per 8 x 8 sample
+ * tile, and the levels above them; with keep_rows the row image, 32 bytes per sample); the other entries allocate nothing.  Refusals as
+ * vdo_align_create, and max_diff not positive or not finite. */
+int vdo_photo_create(vdo_ctx* ctx, int width, int height, const vdo_photo_params* params, vdo_photo** out);
+int vdo_photo_destroy(vdo_photo* h);
+/* The current frame's image -> I, host-synchronous.  image is a host pointer, or a device pointer when is_device != 0.  VDO_ERR_INVALID, the
+ * message naming the argument, and then nothing changes: a null handle or image; image_stride_bytes smaller than width * channels; channels not
+ * 1, 3 or 4; rgb_order not 0 or 1. */
+int vdo_photo_set_image(vdo_photo* h, const uint8_t* image, int64_t image_stride_bytes, int channels, int rgb_order, int is_device);
+/* The model from two packed float images [Hm][Wm], both host pointers or both device pointers (is_device != 0); they are copied (interleaved)
+ * and not kept.  VDO_ERR_INVALID, the message naming the argument, and then nothing changes: a null pointer, a size < 1, a Km that is not finite
+ * or has fxm, fym <= 0.  VDO_ERR_UNSUPPORTED when Wm * Hm exceeds width * height; the previous model stays.  A non-finite Tm is not refused:
+ * every sample is then skipped. */
+int vdo_photo_set_model(vdo_photo* h, const float* depth, const float* intensity, int model_width, int model_height, const float Km[4], const float Tm[16], int is_device);
+/* The current frame becomes the model (see "Model"): depth, mask, strides and src_is_device as vdo_photo_linearise takes them, I as the last
+ * vdo_photo_set_image left it, Km = K, Tm = T.  VDO_ERR_INVALID, and then nothing changes: a null handle, depth or T; a stride too small; no
+ * image set. */
+int vdo_photo_keep_as_model(vdo_photo* h, const float* depth, int64_t depth_stride_floats, const int32_t* mask, int64_t mask_stride_ints, int src_is_device, const float T[16]);
+/* The same from the resident depth (after K1: metres) and mask of a vdo_frame_images of the handle's size, read where they lie and not written. */
+int vdo_photo_keep_as_model_frame(vdo_photo* h, const vdo_frame_images* frame, const float T[16]);
+/* Inspection.  vdo_photo_get_image: I, [H][W] floats (host).  vdo_photo_get_model: the pairs, [Hm][Wm][2] floats (host, may be NULL), and the
+ * model's size (host, each may be NULL).  VDO_ERR_INVALID for a null handle or grey, and before the first image / model. */
+int vdo_photo_get_image(vdo_photo* h, float* grey);
+int vdo_photo_get_model(vdo_photo* h, float* pairs, int* model_width, int* model_height);
+/* The combine of the contract: pure host code, no device or context.  geo may be NULL; out may be geo or photo.  VDO_ERR_INVALID for a null
+ * photo or out and for a weight that is not positive and finite; nothing is written then. */
+int vdo_photo_combine(const double geo[28], const double photo[28], double weight, double out[28]);
+/* One linearisation at T, host-synchronous on the context's stream.  depth, mask, strides and src_is_device as vdo_align_linearise takes them.
+ * sums (host): the 28 sums.  counts (host): used, no depth, masked, no model, far.  VDO_ERR_INVALID, the message naming the argument, and then
+ * NOTHING is written: a null handle, depth, T, sums or counts; a stride too small; no image set; no model set.  A non-finite T is not refused:
+ * every sample is then skipped. */
+int vdo_photo_linearise(vdo_photo* h, const float* depth, int64_t depth_stride_floats, const int32_t* mask, int64_t mask_stride_ints, int src_is_device, const float T[16],
+                        double sums[28], int64_t counts[5]);
+int vdo_photo_linearise_frame(vdo_photo* h, const vdo_frame_images* frame, const float T[16], double sums[28], int64_t counts[5]);
+/* Up to max_iterations rounds from T_init (see "Solve"); both models stay fixed.  geo: a vdo_align of the same frame size on the same device
+ * with its model set, or NULL for the photometric term alone.  It stops after a round whose status is not 0 (T_out is then the T of that round)
+ * or whose xi is at most eps in every component.  report (host, may be NULL).  trace (host, may be NULL): [max_iterations][VDO_PHOTO_TRACE_ROW]
+ * doubles, per round the T it used, the geometric sums and counts (0 without geo) and the photometric sums and counts; later rows are not
+ * written.  Refusals as vdo_photo_linearise, and: a null T_init or T_out; a weight that is not positive and finite; a geo of another frame
+ * size or device, or without a model. */
+int vdo_photo_solve(vdo_photo* h, vdo_align* geo, const float* depth, int64_t depth_stride_floats, const int32_t* mask, int64_t mask_stride_ints, int src_is_device, double weight,
+                    const float T_init[16], float T_out[16], vdo_photo_report* report, double* trace);
+int vdo_photo_solve_frame(vdo_photo* h, vdo_align* geo, const vdo_frame_images* frame, double weight, const float T_init[16], float T_out[16], vdo_photo_report* report,
+                          double* trace);
+/* With keep_rows: rows (host) [Hs][Ws][8] floats of the last photometric linearisation - J (6), e, w (1 where used), all 0 where the sample was
+ * skipped.  Storing them changes no sum.  VDO_ERR_INVALID without keep_rows, before the first linearisation, or for a null pointer. */
+int vdo_photo_get_rows(vdo_photo* h, float* rows);
+/* The last linearise or solve: ms[0] wall time of the call, ms[1] device time of its PHOTOMETRIC linearisations, first command to last kernel. */
+int vdo_photo_last_timing(vdo_photo* h, double ms[2]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,10 +10,7 @@
 //                    xor-butterfly over masks 1 .. 32 is the first six levels of the tree; it is done TRANSPOSING - at mask m a lane keeps the half
 //                    of its values its bit of m selects and sends the other half, 16 + 8 + 4 + 2 + 1 + 1 = 32 exchanges of a double, not 32 x 6 -,
 //                    which leaves lane l < 32 with the tile's sum of the value whose index is l's five bits reversed.  256 bytes per tile.
-//   k_al_tree        eight levels over 256 consecutive nodes per workgroup: thread (sub, term) pairs 32 nodes of one term in registers (five
-//                    levels), the eight subs meet in LDS (three levels).  Launched until one node is left: 2^20 tiles need three launches, a
-//                    1242 x 375 frame two, the second a single workgroup of eight levels - there is no serial stage.  A node beyond the padded
-//                    count does not exist: its partner passes through unchanged, as the contract's tree over the next power of two has it.
+//   k_al_tree        pt_tree of pair_tree.hpp: eight levels over 256 consecutive nodes per workgroup, launched until one node is left.
 //
 // NO OUT-OF-RANGE ACCESS: the one gathered address of the model comes from float compares against 0 and Wm - 1 / Hm - 1 made before any conversion to
 // int (a NaN fails them); the frame is read at (i * s, j * s) with i < Ws, j < Hs; a partial is written at tile < tiles, a row at a sample of the grid.
@@ -29,12 +26,13 @@
 #include "frame_images.hpp"
 #include "stage.hpp"
 #include "dense.hpp"
+#include "pair_tree.hpp"
 
 namespace vdo {
 
 constexpr int kAlTerms = 28;
-constexpr int kAlVals = 32;                                                // the 28 terms, then used, masked, no model, far as doubles
-constexpr int kAlSpan = 256;                                               // nodes per workgroup of k_al_tree
+constexpr int kAlVals = kPtVals;                                           // the 28 terms, then used, masked, no model, far as doubles
+constexpr int kAlSpan = kPtSpan;                                           // nodes per workgroup of k_al_tree
 
 // what the kernels take by value
 struct AlArgs {
@@ -149,32 +147,8 @@ __global__ __launch_bounds__(256) void k_al_rows(AlArgs a, const float* __restri
 // padded node count (a power of two >= n_real), out [max(P / 256, 1)][32].  A pair whose second node lies beyond P's level does not exist.
 __global__ __launch_bounds__(256) void k_al_tree(const double* __restrict__ in, int n_real, int P, double* __restrict__ out) {
   __shared__ double lds[8][kAlVals];
-  const int term = threadIdx.x & 31, sub = threadIdx.x >> 5;
-  const int n_loc = P < kAlSpan ? P : kAlSpan;
-  const long long base = (long long)blockIdx.x * kAlSpan + sub * 32;
-  double v[32];
-#pragma unroll
-  for (int k = 0; k < 32; ++k) v[k] = base + k < n_real ? in[(size_t)(base + k) * kAlVals + term] : 0.0;
-#pragma unroll
-  for (int L = 0; L < 5; ++L) {
-#pragma unroll
-    for (int k = 0; k < (16 >> L); ++k) v[k] = sub * (32 >> L) + 2 * k + 1 < (n_loc >> L) ? v[2 * k] + v[2 * k + 1] : v[2 * k];
-  }
-  lds[sub][term] = v[0];
-  __syncthreads();
-  if (sub != 0) return;
-  double r[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) r[k] = lds[k][term];
-#pragma unroll
-  for (int L = 5; L < 8; ++L) {
-#pragma unroll
-    for (int k = 0; k < (128 >> L); ++k) r[k] = 2 * k + 1 < (n_loc >> L) ? r[2 * k] + r[2 * k + 1] : r[2 * k];
-  }
-  out[(size_t)blockIdx.x * kAlVals + term] = r[0];
+  pt_tree(in, n_real, P, out, lds);
 }
-
-static int al_pow2(int n) { int p = 1; while (p < n) p <<= 1; return p; }
 
 }  // namespace vdo
 
@@ -198,6 +172,10 @@ struct vdo_align {
 };
 
 using namespace vdo;
+
+void vdo::al_info(const vdo_align* h, int* W, int* H, int* min_pixels, bool* has_model, vdo_ctx** ctx) {
+  *W = h->W; *H = h->H; *min_pixels = h->p.min_pixels; *has_model = h->has_model; *ctx = h->ctx;
+}
 
 static void al_free(vdo_align* h) {
   hipFree(h->d_depth); hipFree(h->d_mask); hipFree(h->d_mdepth); hipFree(h->d_mgrad); hipFree(h->d_part[0]); hipFree(h->d_part[1]); hipFree(h->d_rows);
@@ -234,7 +212,7 @@ extern "C" int vdo_align_create(vdo_ctx* ctx, int width, int height, const vdo_a
   a.min_d = p->min_depth > 0.f ? p->min_depth : 0.f; a.max_d = p->max_depth; a.max_dist2 = p->max_dist * p->max_dist;
   a.W = width; a.s = s; a.Ws = h->Ws; a.Hs = h->Hs; a.tiles_x = (h->Ws + 7) / 8; a.tiles = a.tiles_x * ((h->Hs + 7) / 8);
   h->npix = (size_t)width * height;
-  const size_t n1 = (size_t)(al_pow2(a.tiles) / kAlSpan > 1 ? al_pow2(a.tiles) / kAlSpan : 1);
+  const size_t n1 = (size_t)(pt_pow2(a.tiles) / kAlSpan > 1 ? pt_pow2(a.tiles) / kAlSpan : 1);
   bool ok = hipMalloc((void**)&h->d_depth, h->npix * sizeof(float)) == hipSuccess && hipMalloc((void**)&h->d_mask, h->npix * sizeof(int32_t)) == hipSuccess &&
             hipMalloc((void**)&h->d_mdepth, h->npix * sizeof(float)) == hipSuccess && hipMalloc((void**)&h->d_mgrad, h->npix * 3 * sizeof(float)) == hipSuccess &&
             hipMalloc((void**)&h->d_part[0], (size_t)a.tiles * kAlVals * sizeof(double)) == hipSuccess && hipMalloc((void**)&h->d_part[1], n1 * kAlVals * sizeof(double)) == hipSuccess &&
@@ -331,7 +309,7 @@ static int al_linearise(const char* who, vdo_align* h, AlSrc src, const float T[
   const dim3 grid((unsigned)((a.tiles + 3) / 4)), block(64, 4);
   if (h->d_rows) hipLaunchKernelGGL(k_al_rows<true>, grid, block, 0, s, a, src.depth, src.mask, h->m_depth, h->m_grad, h->d_part[0], h->d_rows);
   else hipLaunchKernelGGL(k_al_rows<false>, grid, block, 0, s, a, src.depth, src.mask, h->m_depth, h->m_grad, h->d_part[0], (float*)nullptr);
-  int n = a.tiles, P = al_pow2(a.tiles), from = 0;
+  int n = a.tiles, P = pt_pow2(a.tiles), from = 0;
   do {
     const int blocks = P / kAlSpan > 1 ? P / kAlSpan : 1;
     hipLaunchKernelGGL(k_al_tree, dim3((unsigned)blocks), dim3(256), 0, s, (const double*)h->d_part[from], n, P, h->d_part[from ^ 1]);

@@ -159,4 +159,7 @@ void dn_queue_move(hipStream_t s, uint32_t* words, const int n[3], int64_t nvox,
 // What another handle needs of a view (raycast.hip): its image size, its intrinsics (fx, fy, cx, cy) and the context of its map
 void rc_view_info(const vdo_raycast* view, int* W, int* H, float K[4], vdo_ctx** ctx);
 
+// What the joint solve needs of an aligner (align.hip): its frame size, its min_pixels, whether a model is set, and its context
+void al_info(const vdo_align* h, int* W, int* H, int* min_pixels, bool* has_model, vdo_ctx** ctx);
+
 }  // namespace vdo

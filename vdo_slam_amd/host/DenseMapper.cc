@@ -50,6 +50,7 @@ DenseMapper::~DenseMapper() {
   vdo_distance_destroy(dist_);
   vdo_colour_destroy(colour_);                            // the colourer borrows the map
   vdo_mesh_destroy(mesher_);
+  vdo_photo_destroy(photo_);
   vdo_align_destroy(align_);
   vdo_raycast_destroy(view_);                             // the view borrows the map
   vdo_dense_destroy(h_);
@@ -81,6 +82,15 @@ std::string DenseMapper::CheckAlign(const Settings& s) {
   if (s.alignMinPixels != 0 && s.alignMinPixels < 6) return "settings: Dense.Align.MinPixels must be at least 6";
   return "";
 }
+
+std::string DenseMapper::CheckAlignPhoto(const Settings& s) {
+  if (!std::isfinite(s.alignPhoto) || !(s.alignPhoto >= 0.f)) return "settings: Dense.Align.Photo must be finite and not negative (0: off)";
+  if (!std::isfinite(s.alignPhotoMaxDiff) || !(s.alignPhotoMaxDiff > 0.f) || !(s.alignPhotoMaxDiff <= 255.f)) return "settings: Dense.Align.Photo.MaxDiff outside (0, 255]";
+  if (s.alignPhotoMinPixels != 0 && s.alignPhotoMinPixels < 6) return "settings: Dense.Align.Photo.MinPixels must be at least 6";
+  return "";
+}
+
+int DenseMapper::AlignPhotoMinPixels(const Settings& s, int width, int height) { return s.alignPhotoMinPixels > 0 ? s.alignPhotoMinPixels : AlignMinPixels(s, width, height); }
 
 std::string DenseMapper::CheckColour(const Settings& s) {
   if (!std::isfinite(s.colourBand) || !(s.colourBand > 0.f)) return "settings: Dense.Colour.Band must be positive";
@@ -170,6 +180,65 @@ void DenseMapper::Align(const cv::Mat& depth, const cv::Mat& mask, const float T
 void DenseMapper::AlignFrame(const vdo_frame_images* frame, const float Tcw_init[16], float Tcw_out[16], vdo_align_report* report) {
   EnsureAligner(Tcw_init);
   if (vdo_align_solve_frame(align_, frame, Tcw_init, Tcw_out, report, nullptr) != VDO_OK) die("vdo_align_solve_frame");
+}
+
+void DenseMapper::EnsurePhoto(const Image& image) {
+  if (!(s_.alignPhoto > 0.f)) throw std::runtime_error("VDO_SLAM::DenseMapper: AlignPhoto without Dense.Align.Photo");
+  if (!image.data) throw std::runtime_error("VDO_SLAM::DenseMapper: AlignPhoto without an image");
+  if (!photo_) {
+    const std::string err = CheckAlignPhoto(s_);
+    if (!err.empty()) throw std::runtime_error("VDO_SLAM::DenseMapper: " + err);
+    const vdo_dense_params& p = s_.params;
+    const vdo_photo_params pp{{p.K[0], p.K[1], p.K[2], p.K[3]}, p.min_depth, p.max_depth, s_.alignMaxDist > 0.f ? s_.alignMaxDist : p.trunc, s_.alignPhotoMaxDiff, s_.alignSubsample,
+                              AlignPhotoMinPixels(s_, w_, h_px_), s_.alignIterations > 0 ? s_.alignIterations : 10, 1e-5f, 0};
+    if (vdo_photo_create(ctx_, w_, h_px_, &pp, &photo_) != VDO_OK) die("vdo_photo_create");
+  }
+  if (vdo_photo_set_image(photo_, image.data, image.step, image.channels, image.bgr ? 1 : 0, image.device ? 1 : 0) != VDO_OK) die("vdo_photo_set_image");
+}
+
+void DenseMapper::SolvePhoto(const vdo_frame_images* frame, const cv::Mat* depth, const cv::Mat* mask, const float Tcw_init[16], float Tcw_out[16], vdo_photo_report* report) {
+  const float* d = frame ? nullptr : (const float*)depth->data;
+  const int64_t ds = frame ? 0 : (int64_t)(depth->step / 4);
+  const int32_t* m = frame || mask->empty() ? nullptr : (const int32_t*)mask->data;
+  const int64_t ms = m ? (int64_t)(mask->step / 4) : 0;
+  vdo_photo_report rep{};
+  bool joint = photoModel_;
+  if (joint) {
+    const int rc = frame ? vdo_photo_solve_frame(photo_, align_, frame, (double)s_.alignPhoto, Tcw_init, Tcw_out, &rep, nullptr)
+                         : vdo_photo_solve(photo_, align_, d, ds, m, ms, 0, (double)s_.alignPhoto, Tcw_init, Tcw_out, &rep, nullptr);
+    if (rc != VDO_OK) die("vdo_photo_solve");
+    joint = rep.status != 1;
+  }
+  if (!joint) {                                            // the geometry alone, as Align does it
+    vdo_align_report a{};
+    const int rc = frame ? vdo_align_solve_frame(align_, frame, Tcw_init, Tcw_out, &a, nullptr) : vdo_align_solve(align_, d, ds, m, ms, 0, Tcw_init, Tcw_out, &a, nullptr);
+    if (rc != VDO_OK) die("vdo_align_solve");
+    rep = vdo_photo_report{};
+    rep.iterations = a.iterations; rep.status = a.status; rep.used_geo = a.used; rep.rms_geo_first = a.rms_first; rep.rms_geo_last = a.rms_last;
+    for (int k = 0; k < 6; ++k) rep.xi[k] = a.xi[k];
+  }
+  if (report) *report = rep;
+}
+
+void DenseMapper::AlignPhoto(const cv::Mat& depth, const cv::Mat& mask, const Image& image, const float Tcw_init[16], float Tcw_out[16], vdo_photo_report* report) {
+  auto img = [&](const cv::Mat& m, int type) { return !m.empty() && m.rows == h_px_ && m.cols == w_ && m.depth() == type && m.channels() == 1 && m.step % 4 == 0; };
+  if (!img(depth, cv::CV_32F)) throw std::runtime_error("VDO_SLAM::DenseMapper: depth must be CV_32FC1 of the mapper's size");
+  if (!mask.empty() && !img(mask, cv::CV_32S)) throw std::runtime_error("VDO_SLAM::DenseMapper: mask must be empty or CV_32SC1 of the mapper's size");
+  EnsurePhoto(image);
+  EnsureAligner(Tcw_init);
+  SolvePhoto(nullptr, &depth, &mask, Tcw_init, Tcw_out, report);
+}
+
+void DenseMapper::AlignPhotoFrame(const vdo_frame_images* frame, const Image& image, const float Tcw_init[16], float Tcw_out[16], vdo_photo_report* report) {
+  EnsurePhoto(image);
+  EnsureAligner(Tcw_init);
+  SolvePhoto(frame, nullptr, nullptr, Tcw_init, Tcw_out, report);
+}
+
+void DenseMapper::KeepPhotoModel(const vdo_frame_images* frame, const float Tcw[16]) {
+  if (!photo_) throw std::runtime_error("VDO_SLAM::DenseMapper: KeepPhotoModel before AlignPhoto");
+  if (vdo_photo_keep_as_model_frame(photo_, frame, Tcw) != VDO_OK) die("vdo_photo_keep_as_model_frame");
+  photoModel_ = true;
 }
 
 void DenseMapper::Render(const float Tcw[16], cv::Mat& depth, cv::Mat& normals, cv::Mat* weight, int64_t counts[3]) {

@@ -24,6 +24,9 @@ class DenseMapper {
     // gate on the distance between a point and its model point in metres (0: params.trunc), the sample stride, the smallest number of used samples
     // (0: a sixteenth of the sample grid, at least 6), and whether System fuses with the aligned pose.
     int alignIterations = 0; float alignMaxDist = 0.f; int alignSubsample = 1, alignMinPixels = 0; bool alignApply = false;
+    // The photometric term beside it (settings keys Dense.Align.Photo*): the weight in metres per grey level (0: off - there is no default weight), the
+    // gate on the grey residual in levels (255 turns it off) and the smallest number of used photometric samples (0: the aligner's).
+    float alignPhoto = 0.f, alignPhotoMaxDiff = 255.f; int alignPhotoMinPixels = 0;
     // Settings key Dense.Mesh (0): a mesher is made, and before the volume moves the quads that will not be wholly inside what stays are kept (Mesh below)
     bool mesh = false;
     // Settings keys Dense.Colour (0), Dense.Colour.Band (params.trunc / 2), Dense.Colour.MaxWeight (params.max_weight), Dense.Colour.MinWeight (1): a
@@ -46,6 +49,11 @@ class DenseMapper {
   static std::string CheckAlign(const Settings& s);
   // The smallest number of used samples Align asks for on width x height images
   static int AlignMinPixels(const Settings& s, int width, int height);
+  // The settings error of the photometric fields ("" when in order): Photo negative or not finite, MaxDiff outside (0, 255], MinPixels below 6 (0
+  // stands for the aligner's)
+  static std::string CheckAlignPhoto(const Settings& s);
+  // The smallest number of used photometric samples AlignPhoto asks for
+  static int AlignPhotoMinPixels(const Settings& s, int width, int height);
   // The defaults of the view from the fields above: Near max(min_depth, voxel); Step trunc / 2 - half the thickness of the valid negative band behind a
   // surface, so that a pair of samples cannot step over that band from the fusing direction; MinWeight minWeight.
   static void ViewDefaults(Settings& s);
@@ -116,6 +124,16 @@ class DenseMapper {
   // the map changes.
   void Align(const cv::Mat& depth, const cv::Mat& mask, const float Tcw_init[16], float Tcw_out[16], vdo_align_report* report = nullptr);
   void AlignFrame(const vdo_frame_images* frame, const float Tcw_init[16], float Tcw_out[16], vdo_align_report* report = nullptr);
+  // Align with the photometric term (vdo_photo_solve: include/vdo_slam_hip.h, "Photometric aligner"; settings().alignPhoto > 0, else it throws): the
+  // frame's image becomes the photometric handle's grey image, and the frame is aligned jointly - the aligner against the map's view rendered at
+  // Tcw_init, the intensity term against the MODEL FRAME KeepPhotoModel last kept - with the weight settings().alignPhoto.  Without a model frame
+  // (the first frame), and whenever the joint solve ends with status 1, the frame is aligned by the geometry alone, exactly as Align does it, and
+  // the report says so: used_photo and both rms_photo are 0.  The handle is made on first use.
+  void AlignPhoto(const cv::Mat& depth, const cv::Mat& mask, const Image& image, const float Tcw_init[16], float Tcw_out[16], vdo_photo_report* report = nullptr);
+  void AlignPhotoFrame(const vdo_frame_images* frame, const Image& image, const float Tcw_init[16], float Tcw_out[16], vdo_photo_report* report = nullptr);
+  // The frame whose image the last AlignPhoto* set becomes the model frame with the pose it was fused with (vdo_photo_keep_as_model_frame: masked
+  // pixels - moving objects - carry no depth and are left out).
+  void KeepPhotoModel(const vdo_frame_images* frame, const float Tcw[16]);
   // The distance field of the box [lo, hi) (global voxels, clipped to the volume; both null: the whole current volume) with the settings' radius and
   // weight (vdo_distance_compute); it becomes the snapshot Clearance samples until the map changes.  counts (optional): sites, voxels within the
   // radius, voxels of the clipped box.  Throws std::runtime_error unless settings().distance.
@@ -140,10 +158,15 @@ class DenseMapper {
   void Colour(Points& p, size_t from);                   // with a colourer: p.rgba of the points from `from` on, sampled from the volume as it is now
   void EnsureView();
   void EnsureAligner(const float Tcw_init[16]);          // and renders the view at Tcw_init into its model
+  void EnsurePhoto(const Image& image);                  // and packs the image into its grey image
+  // the joint solve (frame, or depth and mask when frame is null), or the aligner's alone: see AlignPhoto
+  void SolvePhoto(const vdo_frame_images* frame, const cv::Mat* depth, const cv::Mat* mask, const float Tcw_init[16], float Tcw_out[16], vdo_photo_report* report);
   vdo_ctx* ctx_ = nullptr;
   vdo_dense* h_ = nullptr;
   vdo_raycast* view_ = nullptr;                          // made by the first Render or Align; destroyed before the map
   vdo_align* align_ = nullptr;                           // made by the first Align; destroyed before the view
+  vdo_photo* photo_ = nullptr;                           // made by the first AlignPhoto; destroyed before the view
+  bool photoModel_ = false;                              // KeepPhotoModel has kept a frame
   vdo_mesh* mesher_ = nullptr;                           // only with settings().mesh
   vdo_colour* colour_ = nullptr;                         // only with settings().colour; borrows the map: destroyed before it
   vdo_distance* dist_ = nullptr;                         // only with settings().distance; destroyed before the map

@@ -272,6 +272,20 @@ std::string read_dense_settings(const std::string& path, const TrackingSettings&
   s.alignIterations = (int)al[0]; s.alignSubsample = (int)al[1]; s.alignMinPixels = (int)al[2]; s.alignApply = al[3] == 1; s.alignMaxDist = (float)max_dist;
   const std::string align_err = DenseMapper::CheckAlign(s);
   if (!align_err.empty()) return align_err;
+  // the photometric term beside it, read only when frames are aligned: Dense.Align.Photo (absent or 0: off; no default weight), .MaxDiff, .MinPixels
+  if (s.alignIterations > 0) {
+    for (const char* key : {"Dense.Align.Photo", "Dense.Align.Photo.MaxDiff", "Dense.Align.Photo.MinPixels"})
+      if (lists.count(key)) return std::string("settings: ") + key + " must be a number";
+    const double photo = get(raw, "Dense.Align.Photo", 0), max_diff = get(raw, "Dense.Align.Photo.MaxDiff", 255), photo_px = get(raw, "Dense.Align.Photo.MinPixels", 0);
+    if (!std::isfinite(photo) || !(photo >= 0) || !std::isfinite((float)photo) || (photo > 0 && !((float)photo > 0)))
+      return "settings: Dense.Align.Photo must be 0 (off) or a positive weight in metres per grey level";
+    if (!std::isfinite(max_diff) || !(max_diff > 0) || !(max_diff <= 255) || !((float)max_diff > 0)) return "settings: Dense.Align.Photo.MaxDiff outside (0, 255]";
+    if (!whole(photo_px)) return "settings: Dense.Align.Photo.MinPixels must be a whole number";
+    if (raw.count("Dense.Align.Photo.MinPixels") && photo_px < 6) return "settings: Dense.Align.Photo.MinPixels must be at least 6";
+    s.alignPhoto = (float)photo; s.alignPhotoMaxDiff = (float)max_diff; s.alignPhotoMinPixels = (int)photo_px;
+    const std::string photo_err = DenseMapper::CheckAlignPhoto(s);
+    if (!photo_err.empty()) return photo_err;
+  }
   // Dense.Mesh (0): 1 keeps the surface as triangles too (DenseMapper::Mesh, System::SaveDenseMesh)
   const double mesh = get(raw, "Dense.Mesh", 0);
   if (lists.count("Dense.Mesh") || (mesh != 0 && mesh != 1)) return "settings: Dense.Mesh must be 0 or 1";
@@ -739,12 +753,22 @@ cv::Mat Tracking::FinishFrame(const cv::Mat& mTcw_gt, std::chrono::steady_clock:
     std::memcpy(dense_fused_, pipe_->Tcw_out_, sizeof dense_fused_);
     if (dense_->settings().alignIterations > 0) {
       float aligned[16];
-      dense_->AlignFrame(pipe_->LastImages(), pipe_->Tcw_out_, aligned, &dense_align_);
+      if (dense_->settings().alignPhoto > 0.f) {
+        // Dense.Align.Photo: the frame's image (what the colourer gets) goes to the photometric handle and the solve is the joint one
+        dense_->AlignPhotoFrame(pipe_->LastImages(), colour_src_, pipe_->Tcw_out_, aligned, &dense_photo_);
+        dense_photo_valid_ = true;
+        dense_align_ = vdo_align_report{dense_photo_.iterations, dense_photo_.status, dense_photo_.used_geo, dense_photo_.rms_geo_first, dense_photo_.rms_geo_last, {}};
+        for (int k = 0; k < 6; ++k) dense_align_.xi[k] = dense_photo_.xi[k];
+      } else {
+        dense_->AlignFrame(pipe_->LastImages(), pipe_->Tcw_out_, aligned, &dense_align_);
+      }
       dense_align_valid_ = true;
       ++dense_align_count_;
       if (dense_->settings().alignApply && dense_align_.status == 0) std::memcpy(dense_fused_, aligned, sizeof dense_fused_);
     }
     dense_->FuseFrame(pipe_->LastImages(), dense_fused_, dense_counts_);
+    // the fused frame is the photometric model of the next one, with the pose it was fused with
+    if (dense_->settings().alignIterations > 0 && dense_->settings().alignPhoto > 0.f) dense_->KeepPhotoModel(pipe_->LastImages(), dense_fused_);
     // the colour of the same frame, with the pose its geometry was fused with (Dense.Colour: 1)
     if (dense_->settings().colour) dense_->FuseColour(colour_src_, dense_fused_, colour_counts_);
     // the object models: the same images and pose, and the motions of the step that made them (FramePipeline::FinishObjects: mod_label, the label in
@@ -1064,6 +1088,31 @@ bool System::LastDenseAlignment(vdo_align_report& report) const {
   return true;
 }
 
+bool System::AlignDenseViewPhoto(const cv::Mat& Tcw, const cv::Mat& imD, const cv::Mat& mask, const cv::Mat& image, cv::Mat& Tcw_out) {
+  DenseMapper* d = mpTracker->dense();
+  if (!d || !(d->settings().alignPhoto > 0.f)) return false;
+  if (Tcw.rows != 4 || Tcw.cols != 4 || Tcw.type() != cv::CV_32FC1) throw std::runtime_error("VDO_SLAM::System::AlignDenseViewPhoto: Tcw must be a 4 x 4 CV_32F matrix");
+  if (image.empty() || image.rows != d->height() || image.cols != d->width() || image.depth() != cv::CV_8U || (image.channels() != 1 && image.channels() != 3 && image.channels() != 4))
+    throw std::runtime_error("VDO_SLAM::System::AlignDenseViewPhoto: image must be CV_8U with 1, 3 or 4 channels of the camera's image size");
+  float T[16], Tn[16];
+  for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) T[4 * r + c] = Tcw.at<float>(r, c);
+  const DenseMapper::Image img{image.data, (int64_t)image.step, image.channels(), !mpTracker->rgb_order(), false};
+  d->AlignPhoto(imD, mask, img, T, Tn, &view_photo_);
+  view_photo_valid_ = true;
+  view_photo_at_ = mpTracker->dense_alignments();
+  Tcw_out.create(4, 4, cv::CV_32FC1);
+  std::memcpy(Tcw_out.data, Tn, sizeof Tn);
+  return true;
+}
+
+bool System::LastDensePhotoAlignment(vdo_photo_report& report) const {
+  if (view_photo_valid_ && view_photo_at_ == mpTracker->dense_alignments()) { report = view_photo_; return true; }      // no frame has been aligned since
+  const vdo_photo_report* r = mpTracker->dense_photo_alignment();
+  if (!r) return false;
+  report = *r;
+  return true;
+}
+
 // The Map (reference format) is materialised from the pipeline's flat store when somebody looks at it.
 Map* System::map() { mpTracker->pipeline()->SyncMap(); return mpMap; }
 
@@ -1358,6 +1407,23 @@ int host_settings_check_dense_align(const char* path, char* msg, int cap, double
   }
   return err.empty() ? 0 : 1;
 }
+// the Dense.Align.Photo* keys as Tracking::Tracking reads them, without a GPU: 0 in order, 1 a settings error (text in msg), -2 no file.  out4 (may be
+// null): present (0 / 1: Dense.VoxelSize is in the file AND Dense.Align.Iterations > 0; the rest only then), Photo (the weight; 0: off), MaxDiff,
+// MinPixels as DenseMapper::AlignPhoto will use it
+int host_settings_check_dense_photo(const char* path, char* msg, int cap, double* out4) {
+  VDO_SLAM::TrackingSettings t{};
+  std::map<std::string, double> raw;
+  if (!VDO_SLAM::read_tracking_settings(path, t, &raw)) return -2;
+  VDO_SLAM::DenseSettings ds;
+  const std::string err = VDO_SLAM::read_dense_settings(path, t, raw, ds);
+  if (msg && cap > 0) std::snprintf(msg, (size_t)cap, "%s", err.c_str());
+  if (out4 && err.empty()) {
+    const bool present = ds.present && ds.s.alignIterations > 0;
+    out4[0] = present ? 1 : 0;
+    if (present) { out4[1] = ds.s.alignPhoto; out4[2] = ds.s.alignPhotoMaxDiff; out4[3] = VDO_SLAM::DenseMapper::AlignPhotoMinPixels(ds.s, t.width, t.height); }
+  }
+  return err.empty() ? 0 : 1;
+}
 // the Dense.Objects.* keys as Tracking::Tracking reads them, without a GPU: 0 in order, 1 a settings error (text in msg), -2 no file.  out13 (may be null):
 // present (0 / 1: Dense.VoxelSize AND Dense.Objects.VoxelSize are in the file; the rest only then), VoxelSize, nx, ny, nz, Truncation, MinDepth, MaxDepth,
 // MaxWeight, MaxObjects, MinPixels, MinFrames, MinWeight
@@ -1459,6 +1525,51 @@ int host_system_align_dense_view(VDO_SLAM::System* s, const float* Tcw, const fl
     report11[0] = r.iterations; report11[1] = r.status; report11[2] = (double)r.used; report11[3] = r.rms_first; report11[4] = r.rms_last;
     for (int k = 0; k < 6; ++k) report11[5 + k] = r.xi[k];
   } catch (const std::exception& e) { std::fprintf(stderr, "host_system_align_dense_view: %s\n", e.what()); return -1; }
+  return 0;
+}
+static void photo_report14(const vdo_photo_report& r, double* out) {
+  out[0] = r.iterations; out[1] = r.status; out[2] = (double)r.used_geo; out[3] = (double)r.used_photo; out[4] = r.rms_geo_first; out[5] = r.rms_geo_last;
+  out[6] = r.rms_photo_first; out[7] = r.rms_photo_last;
+  for (int k = 0; k < 6; ++k) out[8 + k] = r.xi[k];
+}
+// The joint alignment of the last frame of a System with Dense.Align.Photo (Tracking::dense_photo_alignment): report14 = iterations, status, used_geo,
+// used_photo, rms_geo first and last, rms_photo first and last, xi (6); fused16 (may be null): the pose the frame was fused with.  0, 1 when there is
+// none (nothing is written), -1 on a failure.
+int host_system_dense_photo_alignment(VDO_SLAM::System* s, double* report14, float* fused16) {
+  try {
+    const vdo_photo_report* r = s->tracker()->dense_photo_alignment();
+    if (!r) return 1;
+    photo_report14(*r, report14);
+    if (fused16) std::memcpy(fused16, s->tracker()->dense_fused_pose(), 16 * sizeof(float));
+  } catch (const std::exception& e) { std::fprintf(stderr, "host_system_dense_photo_alignment: %s\n", e.what()); return -1; }
+  return 0;
+}
+// System::LastDensePhotoAlignment alone: report14 as above.  0, 1 when there has been none (nothing is written), -1 on a failure.
+int host_system_last_dense_photo_alignment(VDO_SLAM::System* s, double* report14) {
+  try {
+    vdo_photo_report r{};
+    if (!s->LastDensePhotoAlignment(r)) return 1;
+    photo_report14(r, report14);
+  } catch (const std::exception& e) { std::fprintf(stderr, "host_system_last_dense_photo_alignment: %s\n", e.what()); return -1; }
+  return 0;
+}
+// System::AlignDenseViewPhoto + System::LastDensePhotoAlignment: as host_system_align_dense_view, with image [Camera.height][Camera.width][channels]
+// uint8.  0, 1 without a mapper or without Dense.Align.Photo (nothing is written), -1 on a failure.
+int host_system_align_dense_view_photo(VDO_SLAM::System* s, const float* Tcw, const float* depth, const int* mask, const unsigned char* image, int channels, float* Tcw_out,
+                                       double* report14) {
+  try {
+    VDO_SLAM::DenseMapper* d = s->tracker()->dense();
+    if (!d || !(d->settings().alignPhoto > 0.f)) return 1;
+    const int w = d->width(), h = d->height();
+    cv::Mat T(4, 4, cv::CV_32FC1, (void*)Tcw), D(h, w, cv::CV_32FC1, (void*)depth), M, To;
+    if (mask) M = cv::Mat(h, w, cv::CV_32SC1, (void*)mask);
+    cv::Mat I(h, w, channels == 1 ? cv::CV_8UC1 : channels == 3 ? cv::CV_8UC3 : cv::CV_8UC4, (void*)image);
+    if (!s->AlignDenseViewPhoto(T, D, M, I, To)) return 1;
+    std::memcpy(Tcw_out, To.data, 16 * sizeof(float));
+    vdo_photo_report r{};
+    if (!s->LastDensePhotoAlignment(r)) return -1;
+    photo_report14(r, report14);
+  } catch (const std::exception& e) { std::fprintf(stderr, "host_system_align_dense_view_photo: %s\n", e.what()); return -1; }
   return 0;
 }
 // System::RenderDenseView: Tcw [16] world -> camera; depth [Camera.height][Camera.width], normals [Camera.height][Camera.width][3]; wh2 (may be null)

@@ -76,6 +76,9 @@ class Tracking {
   // (null otherwise, and before the first frame), and the pose the frame was fused with
   const vdo_align_report* dense_alignment() const { return dense_align_valid_ ? &dense_align_ : nullptr; }
   long long dense_alignments() const { return dense_align_count_; }      // frames aligned so far
+  // With Dense.Align.Photo as well: the joint report of the same alignment (null otherwise).  dense_alignment() then carries its geometric half.
+  const vdo_photo_report* dense_photo_alignment() const { return dense_photo_valid_ ? &dense_photo_ : nullptr; }
+  bool rgb_order() const { return mbRGB; }               // Camera.RGB: the order of a colour image handed in
   const float* dense_fused_pose() const { return dense_fused_; }
   // The object mapper (settings keys Dense.Objects.*, System::SaveObjectMaps below): null without Dense.VoxelSize and Dense.Objects.VoxelSize.
   // FinishFrame runs its frame right after the static map's, on the same context, with the pose that map was fused with and the step's motions.
@@ -143,6 +146,8 @@ class Tracking {
   int64_t colour_counts_[3] = {0, 0, 0};                 // voxels coloured, skipped by the mask, skipped as outside the band in the last frame
   vdo_align_report dense_align_{};                       // Dense.Align.Iterations > 0: the last frame against the map
   bool dense_align_valid_ = false;
+  vdo_photo_report dense_photo_{};                       // Dense.Align.Photo > 0: the joint report of the last frame
+  bool dense_photo_valid_ = false;
   long long dense_align_count_ = 0;
   float dense_fused_[16] = {0};                          // the pose the last frame was fused with
   std::unique_ptr<MotionSegmenter> motion_;              // made by the first GrabImageStereoVideo from motion_p_
@@ -262,6 +267,15 @@ class System {
   // The report of the last alignment - of AlignDenseView, or of the last frame with Dense.Align.Iterations > 0, whichever came later.  False when
   // there has been none.
   bool LastDenseAlignment(vdo_align_report& report) const;
+  // AlignDenseView with the photometric term (DenseMapper::AlignPhoto, vdo_photo_solve): image (CV_8U, 1, 3 or 4 channels, in the order of Camera.RGB)
+  // is the frame's image; the intensity term compares it with the last frame the tracker kept as its model frame.  False without a mapper or without
+  // Dense.Align.Photo.  Settings keys, read only with Dense.VoxelSize and Dense.Align.Iterations > 0: Dense.Align.Photo (0 or absent: off; a positive
+  // value: the weight of a grey level in metres - every Track* entry then aligns its frame jointly and keeps the fused frame as the next model frame;
+  // there is no default weight), Dense.Align.Photo.MaxDiff (255; (0, 255]), Dense.Align.Photo.MinPixels (Dense.Align.MinPixels).  The first frame,
+  // and a frame whose joint solve ends with status 1, is aligned by the geometry alone.  Dense.Align.Apply keeps its meaning.
+  bool AlignDenseViewPhoto(const cv::Mat& Tcw, const cv::Mat& imD, const cv::Mat& mask, const cv::Mat& image, cv::Mat& Tcw_out);
+  // The joint report of the last alignment with the photometric term - of AlignDenseViewPhoto or of the last frame, whichever came later.
+  bool LastDensePhotoAlignment(vdo_photo_report& report) const;
   // A dense model per tracked object (ObjectMapper).  Settings keys, read only with Dense.VoxelSize; the object mapper exists only if
   // Dense.Objects.VoxelSize (the voxel edge in metres) is present as well, and without it nothing changes: Dense.Objects.Size [nx, ny, nz] ([96, 64, 96]),
   // Dense.Objects.Truncation (4 x voxel), Dense.Objects.MaxDepth (ThDepthOBJ; above Dense.MinDepth, which is the objects' too), Dense.Objects.MaxObjects
@@ -296,6 +310,9 @@ class System {
   vdo_align_report view_align_{};      // of the last AlignDenseView
   bool view_align_valid_ = false;
   long long view_align_at_ = 0;        // the frames the tracker had aligned when AlignDenseView ran: a later frame's report is the newer one
+  vdo_photo_report view_photo_{};      // of the last AlignDenseViewPhoto
+  bool view_photo_valid_ = false;
+  long long view_photo_at_ = 0;
 };
 
 }  // namespace VDO_SLAM

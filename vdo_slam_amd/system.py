@@ -405,6 +405,56 @@ class System:
             raise K.VdoError("System.align_dense_view failed")
         return out.reshape(4, 4), self._align_report(r)
 
+    @staticmethod
+    def _photo_report(r):
+        return dict(iterations=int(r[0]), status=int(r[1]), used_geo=int(r[2]), used_photo=int(r[3]), rms_geo_first=float(r[4]), rms_geo_last=float(r[5]), rms_photo_first=float(r[6]),
+                    rms_photo_last=float(r[7]), xi=r[8:14].copy())
+
+    def dense_photo_alignment(self):
+        """With Dense.Align.Photo: (joint report dict of the last frame's alignment - iterations, status, used_geo, used_photo, rms_geo_first / last in
+        metres, rms_photo_first / last in grey levels, xi -, the pose [4, 4] f32 the frame was fused with), or None when there has been none."""
+        L = self._L
+        L.host_system_dense_photo_alignment.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        r = np.zeros(14, np.float64); fused = np.zeros(16, np.float32)
+        rc = L.host_system_dense_photo_alignment(self._h, _ptr(r), _ptr(fused))
+        if rc == 1:
+            return None
+        if rc != 0:
+            raise K.VdoError("System.dense_photo_alignment failed")
+        return self._photo_report(r), fused.reshape(4, 4)
+
+    def last_dense_photo_alignment(self):
+        """System::LastDensePhotoAlignment: the joint report dict of AlignDenseViewPhoto or of the last frame, whichever came later; None when there has been none."""
+        L = self._L
+        L.host_system_last_dense_photo_alignment.argtypes = [C.c_void_p, C.c_void_p]
+        r = np.zeros(14, np.float64)
+        rc = L.host_system_last_dense_photo_alignment(self._h, _ptr(r))
+        if rc == 1:
+            return None
+        if rc != 0:
+            raise K.VdoError("System.last_dense_photo_alignment failed")
+        return self._photo_report(r)
+
+    def align_dense_view_photo(self, T, depth, mask, image):
+        """System::AlignDenseViewPhoto + LastDensePhotoAlignment: as align_dense_view, with the frame's image uint8 [h, w] or [h, w, 1 | 3 | 4] (in the order
+        of Camera.RGB) for the photometric term against the tracker's model frame: (refined T [4, 4] f32, joint report dict), or None without a mapper
+        or without Dense.Align.Photo."""
+        L = self._L
+        L.host_system_align_dense_view_photo.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_void_p]
+        Tc = np.ascontiguousarray(np.asarray(T, np.float32).reshape(16))
+        d = np.ascontiguousarray(depth, np.float32); m = np.ascontiguousarray(mask, np.int32) if mask is not None else None
+        img = np.ascontiguousarray(image, np.uint8)
+        channels = 1 if img.ndim == 2 else img.shape[2]
+        if channels not in (1, 3, 4) or img.shape[:2] != d.shape:
+            raise ValueError(f"image: {img.shape}, depth {d.shape}")
+        out = np.zeros(16, np.float32); r = np.zeros(14, np.float64)
+        rc = L.host_system_align_dense_view_photo(self._h, _ptr(Tc), _ptr(d), _ptr(m) if m is not None else None, _ptr(img), channels, _ptr(out), _ptr(r))
+        if rc == 1:
+            return None
+        if rc != 0:
+            raise K.VdoError("System.align_dense_view_photo failed")
+        return out.reshape(4, 4), self._photo_report(r)
+
     def object_motions(self, cap=64):
         """The motions of the last frame as the object mapper takes them (host_system_object_motions): [(mod_label, sem_label, n_inliers, H [4, 4] f32)]
         in the tracker's order - mod_label the tracking id, sem_label the label the object's pixels carry in the frame's mask, H the world-frame motion
